@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the path_mis hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--strong]
+    python bench.py --gpus N --steps K --warmup W [--strong] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[3], "C4"): 1 M random triangles + 8 mesh lights in a closed diffuse room,
@@ -169,6 +169,30 @@ def film_crc(rgbw_film, border, x0=928, y0=508, n=64):
     return "%08x" % (zlib.crc32(c.tobytes()) & 0xFFFFFFFF)
 
 
+DUMP_BYTES = 64 * 10**6        # --dump-outputs: at most this much in all
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BYTES):
+    """DIR/<name>.npy for every (H, W, C) array, as float32. Whole arrays when all of them fit the budget (C4: film + rgb, 58 MB); otherwise (C5) each keeps
+    an equal share as a fixed sample of its pixels - the same pixels in every run (seeded, sorted) - written as (n, C) beside DIR/<name>_pixels.npy, the
+    pixels' row-major indices (float64). Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    whole = sum(a.nbytes for a in arrays.values()) <= budget
+    shapes = {}
+    for name, a in arrays.items():
+        if not whole:
+            px = a.reshape(a.shape[0] * a.shape[1], -1)
+            keep = min(px.shape[0], ((budget - 4096) // len(arrays)) // (px.shape[1] * 4 + 8))      # (4096: the .npy headers)
+            idx = np.sort(np.random.default_rng(1).choice(px.shape[0], keep, replace=False))
+            np.save(os.path.join(directory, name + "_pixels.npy"), idx.astype(np.float64))
+            a = px[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 # film_crc of the parity render below (C4, sample indices [0, 64), crop 64 x 64 at (928, 508)) on ONE GPU: the value every N must reproduce.
 # (measured at N = 1 on the GPU box in round 6, profiles/r06a_film/bench_n1.json; tests/test_gpu_multi.py::test_bench_parity_crc_is_independent_of_the_cut
 # reproduces it through 2, 4 and 8 aliased replicas and through two ranks)
@@ -235,6 +259,9 @@ def main():
     ap.add_argument("--no-ext-scenes", action="store_true", help="N = 1: skip the EXT-kernel scenes and C1 / C2 / C3 at their BASELINE sizes (each beside the oracle's CPU time) that ride in the same JSON line")
     ap.add_argument("--profile-pass", action="store_true", help="(scripts/profile_bench.sh) every step asks for ONE pass of 2^30 items explicitly instead of earning it call by call: "
                                                                 "the counter runs profile the first step of a process, and the pass they see must be the steady state's")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed - the film (rgb * w, w per texel) and the rgb image a caller "
+                                                                        "downloads - as DIR/<name>.npy (float32, at most 64 MB in all); the last timed step then starts from a "
+                                                                        "cleared film, so that the files hold its samples alone and are the same in every run of the same arguments")
     args = ap.parse_args()
     if args.cold_job:
         return cold_job(args.cold_job, args.tris)
@@ -242,6 +269,8 @@ def main():
         args.steps = 1 if args.strong else 6
     if args.warmup is None:
         args.warmup = 0 if args.strong else 4          # (the default pass size is earned call by call: 2^27 items, then doubling - the fourth call runs passes of 2^30)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     commit = os.environ.get("GRAFT_HEAD") or git_head()          # before torch / HIP are loaded: no fork from a process that has initialised the GPU
     cold = None
     if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.strong and not args.no_cold_job:
@@ -361,7 +390,8 @@ def main():
     barrier()
     t_start = time.perf_counter()
     for k in range(args.steps):
-        step(args.warmup + k)
+        # (--dump-outputs: the film otherwise holds every step since the warm-up began, and how many settling steps that was depends on timing)
+        step(args.warmup + k, accumulate=not (args.dump_outputs and k == args.steps - 1))
     barrier()
     elapsed = time.perf_counter() - t_start
     kernel_ms_last = scene.last_kernel_ms()      # hipEvents on the launch stream around the last call / its passes
@@ -383,6 +413,10 @@ def main():
     log("rank %d/%d: device %d (%s), %d tiles = %d px, %.3f s for %d steps, passes %s, free %.1f of %.1f GB, download %.1f MB in %.1f ms, gather %.1f ms"
         % (rank, world, device_index, torch.cuda.get_device_name(device_index), len(tiles), my_pixels, elapsed, args.steps, info, free_b / 2**30, total_b / 2**30,
            packed.nbytes / 1e6, 1e3 * (t_d - t_g), 1e3 * gather_s))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"film": film_np, "rgb": scene.rgb(film_np)})
+        log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, json.dumps(dumped)))
 
     # ---- parity render (every rank; outside the timed region): sample indices [0, 64) of the frame, tiles dealt as above, gathered on rank 0. The film does not
     # depend on N, on the dealing or on the pass size (round 6: per-pixel running tap sums, rects merged in tile order), so the crc32 of a fixed crop is the same at
@@ -523,6 +557,8 @@ def main():
                           "first_call_ms": first_call_ms, "first_call": "the first (warm-up) step: beam lists of every pixel (kz_wf_beam, once per pixel and replica), the pass context "
                                                                         "growing (its memory is mapped on a side thread while the first passes run), then the step itself; a timed step is ms_per_step"},
                "roofline": roofline, "cpu_baseline": cpu, "cold_job": cold, "parity": parity}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
     # ---- side jobs. The headline record above is complete: a failure below lands in the sub-record as {"error": ...} and never costs the measurement
     # (ADVICE r04). A collective side job is entered only when EVERY rank is fit for it, and every step of it checks the ranks' status first.
     if world > 1 and not args.strong and not args.no_strong_c5:

@@ -31,6 +31,7 @@ struct FakeDevice { std::vector<KzTile> rendered; int uploads = 0; };
 static FakeDevice g_dev[64];
 static std::atomic<int> g_failDevice{-1};
 static std::atomic<int> g_renderCalls{0};
+static std::atomic<int> g_takersIn{0};                 // fake devices that have reached the dealer in the current call (main resets it)
 
 static void jitter(int device, int salt) {
     static thread_local std::mt19937 rng((unsigned)std::chrono::steady_clock::now().time_since_epoch().count() ^ (unsigned)(device * 7919 + salt));
@@ -56,6 +57,13 @@ int kz_render_tiles(KzScene *scene, const KzRenderOpts *opts, const KzTile *tile
     FakeDevice &d = g_dev[device];
     d.rendered.clear();
     if (opts && opts->dealer) {
+        // (a thread that starts late - ThreadSanitizer slows thread start-up - could find every batch taken: a taker waits, 1 s at most, until a second one
+        //  has arrived, so that the dealing is exercised between threads that run side by side). The counter is an ordering point between the device threads: a
+        //  race between what one device thread does BEFORE kz_render_tiles and what another does after it would no longer be reported. Today that prologue
+        //  (kz_multi.cpp, the device thread's start) writes only its own job entry and its own copy of the options, and the options and tile list it reads
+        //  are not written while the threads run; a change that makes it write shared state needs a check of its own.
+        ++g_takersIn;
+        for (int i = 0; i < 20000 && opts->dealer->takers > 1 && g_takersIn.load() < 2; ++i) std::this_thread::sleep_for(std::chrono::microseconds(50));
         // as renderOn does: the planner resolves the batch size from the list, the sample range and `takers`; the takers agree; batches come from the counter
         std::vector<uint32_t> offs(nTiles + 1, 0);
         for (uint32_t t = 0; t < nTiles; ++t) offs[t + 1] = offs[t] + (uint32_t)(tiles[t].w * tiles[t].h);
@@ -127,6 +135,7 @@ int main() {
                 o.tileDealing = dynamic;
                 std::vector<float> ms(n, -1.f);
                 std::fill(film.begin(), film.end(), -7.f);
+                g_takersIn.store(0);
                 const int rc = kz_render_multi(&scene, &o, devs.data(), (uint32_t)n, T, film.data(), nFloats, ms.data());
                 if (rc) std::fprintf(stderr, "kz_render_multi: %s\n", kz_last_error());
                 CHECK(rc == KZ_OK);

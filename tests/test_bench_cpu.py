@@ -46,3 +46,22 @@ def test_profile_facts_are_stamped_with_the_live_sources():
     if facts["source_sha16"] != bench.source_hash():                       # (not a failure of the product: bench.py then withholds the counter facts and says why)
         pytest.skip("kernel or ABI sources changed after the profile was taken: run scripts/profile_bench.sh + scripts/summarize_profile.py")
     assert os.path.isdir(os.path.join(ROOT, facts["profile"])) and "kz_wf_trace<0>" in facts["kernels"]
+
+
+def test_dump_outputs_are_whole_or_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: the C4 film + image are written whole; larger outputs (C5) as the same seeded sample of pixels in every run, the files within the budget."""
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(2)
+    film, rgb = rng.random((1084, 1924, 4), dtype=np.float32), rng.random((1080, 1920, 3), dtype=np.float32)
+    assert bench.dump_outputs(str(tmp_path / "c4"), {"film": film, "rgb": rgb}) == {"film": [1084, 1924, 4], "rgb": [1080, 1920, 3]}
+    for name, a in (("film", film), ("rgb", rgb)):
+        b = np.load(tmp_path / "c4" / (name + ".npy"))
+        assert b.dtype == np.float32 and np.array_equal(b, a), name
+    film5, rgb5 = rng.random((2164, 3844, 4), dtype=np.float32), rng.random((2160, 3840, 3), dtype=np.float32)
+    for run in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / run), {"film": film5, "rgb": rgb5})
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= bench.DUMP_BYTES
+    for f in ("film.npy", "film_pixels.npy", "rgb.npy", "rgb_pixels.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    idx = np.load(tmp_path / "a" / "rgb_pixels.npy").astype(np.int64)
+    assert shapes["rgb"] == [len(idx), 3] and np.array_equal(np.load(tmp_path / "a" / "rgb.npy"), rgb5.reshape(-1, 3)[idx])

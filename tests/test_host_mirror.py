@@ -231,10 +231,9 @@ def test_cpp_xml_render_equals_python_render(exe, kz, gpu_lib, tmp_path, name, s
     assert rgb.mean() > 0.01 and np.array_equal(sc.rgb().view(np.uint32), rgb.view(np.uint32)), float(np.abs(sc.rgb() - rgb).max())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/scene/2022_q1"), reason="the reference checkout is only present in the build container")
 @pytest.mark.parametrize("rel", ["parameters/default_m0_r0.5.xml", "parameters/m1_r0.xml", "WarmStudio/WarmStudio.xml"])
-def test_cpp_xml_loader_on_reference_scene_files(exe, kz, rel):
-    path = os.path.join("/root/reference/scene/2022_q1", rel)
+def test_cpp_xml_loader_on_reference_scene_files(exe, kz, q1_scene_dir, rel):
+    path = os.path.join(q1_scene_dir, rel)                 # (files equivalent to the reference's scene files, written by the conftest from the committed fixtures)
     d = json.loads(subprocess.check_output([exe, "--xml", path]).decode())
     assert "error" not in d, d
     py = kz.xmlscene.load_xml(path)

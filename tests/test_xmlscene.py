@@ -6,7 +6,8 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 MINI = os.path.join(HERE, "golden", "xml", "mini.xml")
-REF = "/root/reference/scene/2022_q1/parameters"
+REF = "/root/reference/scene/2022_q1/parameters"          # (where the reference checkout is present, the fixtures below are checked against its files)
+PINS = os.path.join(HERE, "golden", "q1_published_pngs.npz")
 
 
 def test_mini_scene_parses_like_the_reference_loader(kz):
@@ -127,9 +128,8 @@ PIN_IMAGES = ["default_m0_r0.5", "m0.0_r0", "m0.0_r0.5", "m0.0_r1", "m0_r0_spec0
 PUBLISHED_LIGHT_FACTORS = (0.976, 1.135, 1.034)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is only present in the build container")
 @pytest.mark.parametrize("name", PIN_IMAGES)
-def test_reference_scene_files_match_their_published_pngs(kz, O, name):
+def test_reference_scene_files_match_their_published_pngs(kz, O, q1_scene_dir, name):
     """ALL 22 scene/2022_q1/parameters/*.xml (36 378 triangles, SURVEY 8d C1 geometry; a kiss parameter sweep over metallic,
     roughness, specular, specularTint, clearcoat, sheen) loaded through the adapter and rendered by the oracle at 240x135x64 against the
     reference's own 4096-spp PNG (doc/2022_q1/img/param/) - the only image-level pin the reference offers ('usable only as a
@@ -141,9 +141,11 @@ def test_reference_scene_files_match_their_published_pngs(kz, O, name):
     (PUBLISHED_LIGHT_FACTORS), reproduce the mean linear radiance of EVERY one of the 22 pictures to +-0.5 % and the mean of the 16x9 sRGB grid to
     0.004 - whatever the object's BSDF parameters are. A transport or BSDF error in the restatement would show as a dependence on those
     parameters, which is what the bound excludes; that the published renders used other light intensities than the checked-in XML stays a
-    hypothesis about the reference's data (profiles/pin/README.md), not about its code."""
-    from PIL import Image
-    d = kz.xmlscene.load_xml(os.path.join(REF, name + ".xml"), {"camera": {"width": 240, "height": 135}, "sampler": {"sampleCount": 64}})
+    hypothesis about the reference's data (profiles/pin/README.md), not about its code.
+
+    The scene files are the conftest's q1_scene_dir (equivalent files written from the committed fixtures), the pictures' block statistics tests/golden/q1_published_pngs.npz
+    (tests/golden/make_q1_files.py)."""
+    d = kz.xmlscene.load_xml(os.path.join(q1_scene_dir, "parameters", name + ".xml"), {"camera": {"width": 240, "height": 135}, "sampler": {"sampleCount": 64}})
     assert d.n_tris() == 36378
     lights = [m["light"] for m in d.meshes if m["light"]]
     assert [l["intensity"] for l in lights] == [1.0, 1.5, 4.0]                                       # what the scene files say
@@ -151,10 +153,10 @@ def test_reference_scene_files_match_their_published_pngs(kz, O, name):
         l["intensity"] *= f
     o = O.OracleScene(d)
     rgb = o.rgb(o.render(threads=0)).astype(np.float64)
-    png = np.asarray(Image.open("/root/reference/doc/2022_q1/img/param/%s.png" % name).convert("RGB"), np.float64) / 255
-    lin_png = np.where(png <= 0.04045, png / 12.92, np.power((png + 0.055) / 1.055, 2.4))            # common.cpp:368-382
-    clipped = (png >= 1.0).any(axis=2).reshape(27, 40, 48, 40).any(axis=(1, 3))
-    lp = lin_png.mean(axis=2).reshape(27, 40, 48, 40).mean(axis=(1, 3))
+    pins = np.load(PINS)
+    i = list(pins["names"]).index(name)
+    clipped = pins["clipped"][i]                                                                     # 40 x 40-pixel blocks of the 1920 x 1080 picture
+    lp = pins["lin_blocks"][i]                                                                       # (sRGB decoded as common.cpp:368-382, channels averaged)
     lo = rgb.mean(axis=2).reshape(27, 5, 48, 5).mean(axis=(1, 3))
     ok = ~clipped & (lp > 0.02)
     assert ok.sum() >= 1000
@@ -163,19 +165,18 @@ def test_reference_scene_files_match_their_published_pngs(kz, O, name):
     assert ratio.std() < 0.055                                                                       # the low-frequency shape no light factor removes (0.045-0.049)
     x = np.clip(rgb, 0, 1)
     srgb = np.where(x <= 0.0031308, 12.92 * x, 1.055 * np.power(x, 1 / 2.4) - 0.055)                 # common.cpp:352-366
-    ok9 = ~(png >= 1.0).any(axis=2).reshape(9, 120, 16, 120).any(axis=(1, 3))
-    ref9, mine9 = png.reshape(9, 120, 16, 120, 3).mean(axis=(1, 3)), srgb.reshape(9, 15, 16, 15, 3).mean(axis=(1, 3))
+    ok9 = ~pins["clipped9"][i]                                                                       # 120 x 120-pixel blocks
+    ref9, mine9 = pins["srgb_blocks"][i], srgb.reshape(9, 15, 16, 15, 3).mean(axis=(1, 3))
     assert ok9.sum() >= 120
     # (the worst single block and channel: 0.028-0.032 for the rough objects, up to 0.057 next to the mirror-like objects' highlights at 64 spp)
     assert np.abs(mine9 - ref9)[ok9].max() < 0.06 and abs(mine9[ok9].mean() - ref9[ok9].mean()) < 0.004
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is only present in the build container")
-def test_every_reference_scene_file_loads(kz):
-    """All checked-in scene XMLs of the reference (scene/2022_q1/**) stay inside the hot path's plugin set: they load through
-    xmlscene.load_xml unchanged and pass kz_scene_create's validation on the host (no GPU needed)."""
+def test_every_reference_scene_file_loads(kz, q1_scene_dir):
+    """All checked-in scene XMLs of the reference (scene/2022_q1/**: the equivalent files the conftest's q1_scene_dir writes from the committed fixtures) stay inside the hot
+    path's plugin set: they load through xmlscene.load_xml unchanged and pass kz_scene_create's validation on the host (no GPU needed)."""
     import glob
-    files = sorted(glob.glob("/root/reference/scene/2022_q1/**/*.xml", recursive=True))
+    files = sorted(glob.glob(os.path.join(q1_scene_dir, "**", "*.xml"), recursive=True))
     assert len(files) >= 23
     for f in files:
         d = kz.xmlscene.load_xml(f, {"camera": {"width": 32, "height": 18}, "sampler": {"sampleCount": 1}})

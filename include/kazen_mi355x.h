@@ -64,7 +64,10 @@ enum { KZ_SAMPLER_INDEPENDENT = 0 /* "independent"   src/kazen/sampler.cpp:18-71
        KZ_SAMPLER_CORRELATED = 3  /* "correlated"    src/kazen/sampler.cpp:176-269 */ };
 enum { KZ_CAMERA_PERSPECTIVE = 0  /* "perspective"   src/kazen/camera.cpp:14-131   */,
        KZ_CAMERA_THINLENS = 1     /* "thinlens"      src/kazen/camera.cpp:133-270  */ };
-enum { KZ_INTEGRATOR_PATH_MIS = 0 /* "path_mis"      src/kazen/integrator.cpp:185-355 */ };
+enum { KZ_INTEGRATOR_PATH_MIS = 0 /* "path_mis"      src/kazen/integrator.cpp:185-355 */,
+       KZ_INTEGRATOR_NORMALS = 1  /* "normals"       src/kazen/integrator.cpp:11-34    */,
+       KZ_INTEGRATOR_AO = 2       /* "ao"            src/kazen/integrator.cpp:37-71    */,
+       KZ_INTEGRATOR_PATH_MATS = 3 /* "path_mats"    src/kazen/integrator.cpp:137-181  */ };
 enum { KZ_FILTER_GAUSSIAN = 0     /* "gaussian"      src/kazen/rfilter.cpp:10-31   */,
        KZ_FILTER_MITCHELL = 1     /* "mitchell"      src/kazen/rfilter.cpp:39-70   */,
        KZ_FILTER_TENT = 2         /* "tent"          src/kazen/rfilter.cpp:73-88   */,
@@ -203,9 +206,11 @@ typedef struct KzSampler {
     const uint16_t *blueNoise;      /* [48][128][128], indexed [tex][x][y], pmj02bn only */
 } KzSampler;
 
-/* "path_mis" (src/kazen/integrator.cpp:187-193). */
+/* "path_mis" (src/kazen/integrator.cpp:187-193) reads every field. "normals", "ao" and "path_mats" read only `type`: their
+   constructors take no properties (integrator.cpp:13, :40, :139), so the other fields are ignored. path_mats has no depth property
+   in the reference; its paths end by roulette, a miss or a zero BSDF weight, and at the latest after 512 bounces (LAB_NOTES H15). */
 typedef struct KzIntegrator {
-    int32_t type;               /* KZ_INTEGRATOR_PATH_MIS                              */
+    int32_t type;               /* KZ_INTEGRATOR_*                                     */
     int32_t maxDepth;           /* default 5, capped at 512                            */
     float traceBias;            /* default 1e-3                                        */
     int32_t regularization;     /* default 0                                           */

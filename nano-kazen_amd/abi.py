@@ -18,7 +18,7 @@ KZ_PIXEL_U8, KZ_PIXEL_F32 = 0, 1
 KZ_TEX_MAX_DEPTH = 8
 KZ_SAMPLER_INDEPENDENT, KZ_SAMPLER_PMJ02BN, KZ_SAMPLER_STRATIFIED, KZ_SAMPLER_CORRELATED = 0, 1, 2, 3
 KZ_CAMERA_PERSPECTIVE, KZ_CAMERA_THINLENS = 0, 1
-KZ_INTEGRATOR_PATH_MIS = 0
+KZ_INTEGRATOR_PATH_MIS, KZ_INTEGRATOR_NORMALS, KZ_INTEGRATOR_AO, KZ_INTEGRATOR_PATH_MATS = 0, 1, 2, 3
 KZ_FILTER_GAUSSIAN, KZ_FILTER_MITCHELL, KZ_FILTER_TENT, KZ_FILTER_BOX = 0, 1, 2, 3
 KZ_FILTER_RESOLUTION = 32
 KZ_PMJ02BN_SETS, KZ_PMJ02BN_SAMPLES = 5, 65536

@@ -201,7 +201,9 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
     if (d->abiVersion != KZ_ABI_VERSION) return kz_fail(KZ_ERR_INVALID_ARG, "ABI version %u, library is %u", d->abiVersion, KZ_ABI_VERSION);
     // plugin types outside the hot path are an error, never a silent fallback
     if (d->camera.type != KZ_CAMERA_PERSPECTIVE && d->camera.type != KZ_CAMERA_THINLENS) return kz_fail(KZ_ERR_UNSUPPORTED, "camera type %d is not supported (\"perspective\", \"thinlens\")", d->camera.type);
-    if (d->integrator.type != KZ_INTEGRATOR_PATH_MIS) return kz_fail(KZ_ERR_UNSUPPORTED, "integrator type %d is not on the hot path (only \"path_mis\")", d->integrator.type);
+    const int32_t integ = d->integrator.type;
+    if (integ != KZ_INTEGRATOR_PATH_MIS && integ != KZ_INTEGRATOR_NORMALS && integ != KZ_INTEGRATOR_AO && integ != KZ_INTEGRATOR_PATH_MATS)
+        return kz_fail(KZ_ERR_UNSUPPORTED, "integrator type %d is not on the hot path (\"path_mis\", \"normals\", \"ao\", \"path_mats\")", integ);
     if (d->sampler.type < KZ_SAMPLER_INDEPENDENT || d->sampler.type > KZ_SAMPLER_CORRELATED)
         return kz_fail(KZ_ERR_UNSUPPORTED, "sampler type %d is not supported (\"independent\", \"pmj02bn\", \"stratified\", \"correlated\")", d->sampler.type);
     if (d->sampler.type == KZ_SAMPLER_STRATIFIED && (d->sampler.resolution < 1 || d->sampler.resolution > 256)) return kz_fail(KZ_ERR_INVALID_ARG, "stratified resolution %d", d->sampler.resolution);
@@ -225,6 +227,10 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
         const bool rough = b.type == KZ_BSDF_ROUGHCONDUCTOR || b.type == KZ_BSDF_ROUGHPLASTIC || b.type == KZ_BSDF_ROUGHDIELECTRIC;
         if ((b.alphaResolved != 0 && b.alphaResolved != 1) || (b.alphaResolved && !rough))
             return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u (type %d): alphaResolved = %d (0 or 1, and only roughconductor / roughplastic / roughdielectric rows have a resolved alpha)", i, b.type, b.alphaResolved);
+        // path_mats hands the BSDF a record whose intersection is default-constructed (integrator.cpp:168-170): a normal map would read a frame that
+        // was never set (LAB_NOTES H16)
+        if (b.type == KZ_BSDF_NORMALMAP && integ == KZ_INTEGRATOR_PATH_MATS)
+            return kz_fail(KZ_ERR_UNSUPPORTED, "bsdf %u is a normalmap: path_mats does not support normal maps (its BSDF record carries no intersection frame)", i);
         if (b.type == KZ_BSDF_NORMALMAP) {                  // bsdf.cpp:391-404: one texture child + one nested BSDF
             if (b.normalTex == 0) return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u: normalmap without a normal texture", i);
             if (b.nested < 0 || b.nested >= (int32_t)d->nBsdfs || d->bsdfs[b.nested].type == KZ_BSDF_NORMALMAP)
@@ -407,11 +413,18 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
     p.tapLo = (int)std::floor(-rf.radius - 0.5f) + 1;
     p.tapHi = (int)std::floor(rf.radius + 0.5f);
     if (p.tapHi - p.tapLo + 1 > KZ_MAX_FILTER_TAPS) { delete sc; return kz_fail(KZ_ERR_UNSUPPORTED, "filter radius %g needs too many taps", rf.radius); }
-    // ---- integrator (integrator.cpp:187-193)
-    p.maxDepth = std::min(512, d->integrator.maxDepth);
-    p.traceBias = d->integrator.traceBias;
-    p.regularization = d->integrator.regularization ? 1 : 0;
-    p.accumulatedRoughness = d->integrator.accumulatedRoughness;
+    // ---- integrator (integrator.cpp:187-193). normals / ao / path_mats read no properties (integrator.cpp:13, :40, :139): maxDepth is then 1 for
+    // normals and ao (the camera ray is traced) and the 512-bounce cap of path_mats (LAB_NOTES H15); traceBias is unused by them
+    p.integrator = integ;
+    if (integ == KZ_INTEGRATOR_PATH_MIS) {
+        p.maxDepth = std::min(512, d->integrator.maxDepth);
+        p.traceBias = d->integrator.traceBias;
+        p.regularization = d->integrator.regularization ? 1 : 0;
+        p.accumulatedRoughness = d->integrator.accumulatedRoughness;
+    } else {
+        p.maxDepth = integ == KZ_INTEGRATOR_PATH_MATS ? KZ_PATH_MATS_MAX_DEPTH : 1;
+        p.traceBias = 1e-5f; p.regularization = 0; p.accumulatedRoughness = 0.f;
+    }
     // ---- lights / background (scene.h:45-56, texture.cpp:121-126)
     p.nLights = (uint32_t)sc->lightRows.size();
     p.lightPickPdf = p.nLights ? 1.f / (float)p.nLights : 0.f;

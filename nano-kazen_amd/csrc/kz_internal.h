@@ -10,6 +10,7 @@
 #define KZ_STACK_DEPTH 32        // per-lane traversal stack entries (LDS); the builder caps the tree depth to this
 #define KZ_MAX_LEAF 4            // triangles per leaf
 #define KZ_MAX_FILTER_TAPS 9     // candidates per axis the film kernel supports (filter radius <= 4)
+#define KZ_PATH_MATS_MAX_DEPTH 512   // bounces of a path_mats path at most (the reference has no cap: LAB_NOTES H15)
 
 // ---- device formats (DESIGN.md "data layout in HBM") ---------------------------------------------
 // BVH2 node, 64 B, four 16-B quads -> four global_load_dwordx4 per lane:
@@ -101,7 +102,8 @@ struct KzParams {
     float lightPickScale;                // nLights when that is a power of two (x / lightPickPdf == x * nLights bit for bit), else 0
     int32_t bgPresent; float bgRadiance[3];          // constant background: intensity * colour
     int32_t bgImage; float bgIntensity;             // environment map: row of `images` (-1: none) and the intensity it is scaled by
-    int32_t bgFilter; int32_t bgPad_;               // KZ_TEXFILTER_* of that lookup (the nested texture's `filter`)
+    int32_t bgFilter;                               // KZ_TEXFILTER_* of that lookup (the nested texture's `filter`)
+    int32_t integrator;                             // KZ_INTEGRATOR_* (in what was this row's padding word: the path_mis kernels' arguments keep their layout)
     // film (block.cpp:13-21)
     float filterRadius, lookupFactor; int32_t tapLo, tapHi;
     uint32_t rootRef;

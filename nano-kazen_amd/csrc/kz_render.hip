@@ -12,6 +12,7 @@
 #include "kz_internal.h"
 #include "kz_devfn.h"
 #include "kz_wavefront.h"
+#include "kz_integrators.h"
 #include "kz_plan.h"
 #ifdef KZ_EXPERIMENTS
 #include "variants/experiments/kz_experiments.h"
@@ -648,9 +649,90 @@ static int ensureOverflow(KzScene *scene, KzDeviceState *ds, PassCtx &c, const K
 #define KZ_BESIDE_ITEMS_IN_FLIGHT (1u << 24)      // ... with passes in flight or a dealer (renderOn)
 #endif
 
+// One pass of the wavefront pipeline for normals / ao / path_mats (kz_integrators.h). The camera stage is path_mis's (generate, beams + list kernel, packet
+// or per-lane traversal) run with a copy of the parameters that names no invisible light: none of the three walks through a light (H6 is path_mis's alone),
+// so a first hit on such a light is kept and an occlusion ray is blocked by it. Then:
+//   normals    kz_wf_normals                                                    (no bounce state)
+//   ao         kz_wf_ao -> kz_wf_trace<4> on the occlusion rays                 (any hit, every triangle blocks)
+//   path_mats  { kz_wf_mats(iter) -> kz_wf_trace<0> } until the path queue is empty or 512 bounces are done; the host reads the survivor count back
+//              after every 4th bounce (one stream synchronisation per 4 bounces), so a pass launches 2 + 2 x (bounces rounded up to 4) kernels after the camera's.
+static int wfPassIntegrator(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t stream, const uint32_t *pixList, uint32_t sBegin, uint32_t Sp, uint32_t items,
+                            KzTune tune, bool beams) {
+    KzParams P = scene->prm;
+    P.anyInvisibleLight = 0; P.nIlTris = 0; P.shadowFast = 1;
+    KzWf W = c.wf;
+    W.outJx = c.plane[0]; W.outJy = c.plane[1]; W.outR = c.plane[2]; W.outG = c.plane[3]; W.outB = c.plane[4]; W.stats = ds->stats;
+    const bool st = ds->statsOn;
+    const dim3 blk(KZ_BLOCK);
+    const dim3 gTrav((unsigned)(ds->numCU * tune.travBlocksPerCU)), gShade((unsigned)(ds->numCU * (tune.shadeBlocksPerCU > 0 ? tune.shadeBlocksPerCU : 8)));
+    const dim3 gPacket((unsigned)(ds->numCU * 8));
+    const int stackBound = std::max(tune.wide ? P.stackBound4 : P.stackDepth, 2);
+    tune.ldsStack = std::max(2, std::min(tune.ldsStack, stackBound));
+    const size_t traceLds = (size_t)(tune.ldsStack + 1) * KZ_BLOCK * sizeof(uint32_t);
+    { const int rc_ = ensureOverflow(scene, ds, c, tune, stream); if (rc_) return rc_; tune.ovf = c.ovf; tune.ovfStride = (uint32_t)((size_t)gTrav.x * KZ_BLOCK); }
+    c.stageUsed = 0;
+    HIP_TRY(hipMemsetAsync(W.counts, 0, 8 * 520 * sizeof(uint32_t), stream));
+    { int rc_ = stageMark(c, stream, -1); if (rc_) return rc_; }
+    hipLaunchKernelGGL(kz_wf_generate, dim3((items + KZ_BLOCK - 1) / KZ_BLOCK), blk, 0, stream, P, ds->T, W, pixList, items, Sp, sBegin);
+    { int rc_ = stageMark(c, stream, 0); if (rc_) return rc_; }
+    auto trace = [&](int mode, const uint32_t *q, const uint32_t *cptr, uint32_t cimm, uint32_t *head) {
+        KzTune t = tune;
+        if (t.batch <= 0) t.batch = 128;
+        if (t.refill <= 0) t.refill = mode == 4 ? 32 : 40;
+        hipLaunchKernelGGL(traceFn(mode, st), gTrav, blk, traceLds, stream, P, ds->T, W, q, cptr, cimm, head, t, (uint32_t *)nullptr, (uint32_t *)nullptr);
+    };
+    const bool packet = tune.packet != 1 && P.stackBound4 <= 128;
+    if (packet && beams) {
+        uint32_t *fbQ = W.queue[0], *fbCount = W.counts + 8 * 520 - 8, *fbHead = fbCount + 1;
+        const dim3 gList((items + KZ_BLOCK - 1) / KZ_BLOCK);
+        if (st) hipLaunchKernelGGL((kz_wf_trace_list<true, false>), gList, blk, 0, stream, P, ds->T, W, pixList, items, Sp, (const uint2 *)ds->beamEntries, (const uint2 *)ds->beamCount, fbQ, fbCount, W.queue[2], W.counts + 0);
+        else hipLaunchKernelGGL((kz_wf_trace_list<false, false>), gList, blk, 0, stream, P, ds->T, W, pixList, items, Sp, (const uint2 *)ds->beamEntries, (const uint2 *)ds->beamCount, fbQ, fbCount, W.queue[2], W.counts + 0);
+        if (st) hipLaunchKernelGGL((kz_wf_trace_packet<true, false>), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)fbQ, (const uint32_t *)fbCount, 0u, fbHead, 8, W.queue[2], W.counts + 0);
+        else hipLaunchKernelGGL((kz_wf_trace_packet<false, false>), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)fbQ, (const uint32_t *)fbCount, 0u, fbHead, 8, W.queue[2], W.counts + 0);
+    } else if (packet) {
+        if (st) hipLaunchKernelGGL((kz_wf_trace_packet<true, false>), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)nullptr, (const uint32_t *)nullptr, items, W.counts + 2, 8, W.queue[2], W.counts + 0);
+        else hipLaunchKernelGGL((kz_wf_trace_packet<false, false>), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)nullptr, (const uint32_t *)nullptr, items, W.counts + 2, 8, W.queue[2], W.counts + 0);
+    } else trace(0, nullptr, nullptr, items, W.counts + 2);
+    { int rc_ = stageMark(c, stream, 5); if (rc_) return rc_; }
+    if (P.integrator == KZ_INTEGRATOR_NORMALS) {
+        hipLaunchKernelGGL(kz_wf_normals, gShade, blk, 0, stream, P, ds->T, W, items);
+        { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
+    } else if (P.integrator == KZ_INTEGRATOR_AO) {
+        uint32_t *shQ = W.queue[2], *shCount = W.counts + 5;
+        hipLaunchKernelGGL(kz_wf_ao, gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, items, shQ, shCount);
+        { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
+        trace(4, shQ, shCount, 0u, W.counts + 7);
+        { int rc_ = stageMark(c, stream, 3); if (rc_) return rc_; }
+    } else {
+        const int xsel = P.bsdfExt == 0 ? 0 : (P.bsdfExt == KZ_X_MODELS ? KZ_X_MODELS : KZ_X_MATS);
+        const uint32_t *cur = nullptr, *curCount = nullptr;
+        for (int iter = 0; iter < P.maxDepth; ++iter) {
+            uint32_t *nextQ = W.queue[iter & 1], *nextCount = W.counts + 4 * (iter + 1);
+#define KZ_MATS(EX) hipLaunchKernelGGL((kz_wf_mats<EX>), gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, iter, cur, curCount, cur ? 0u : items, nextQ, nextCount)
+            if (xsel == KZ_X_MATS) KZ_MATS(KZ_X_MATS); else if (xsel) KZ_MATS(KZ_X_MODELS); else KZ_MATS(0);
+#undef KZ_MATS
+            { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
+            if (iter == P.maxDepth - 1) break;                    // (the ray of the last bounce is not traced: H15)
+            if ((iter & 3) == 3) {                                // the queue runs dry long before the cap: stop launching when it has
+                uint32_t left = 0;
+                HIP_TRY(hipMemcpyAsync(&left, nextCount, sizeof left, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                if (left == 0) break;
+            }
+            trace(0, nextQ, nextCount, 0u, nextCount + 2);
+            { int rc_ = stageMark(c, stream, 1); if (rc_) return rc_; }
+            cur = nextQ; curCount = nextCount;
+        }
+    }
+    if (st) hipLaunchKernelGGL(kz_wf_count, dim3((items + KZ_BLOCK - 1) / KZ_BLOCK), blk, 0, stream, W, items);
+    HIP_TRY(hipGetLastError());
+    return KZ_OK;
+}
+
 // One pass of the wavefront pipeline over `items` = nPixPass x Sp (pixel, sample) items: pixels pixList[0 .. nPixPass), sample indices
 // [sBegin, sBegin + Sp). Every launch goes to `stream`; queue counts stay on the device.
 static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t stream, const uint32_t *pixList, uint32_t p0, uint32_t nPixPass, uint32_t sBegin, uint32_t Sp, uint32_t items, KzTune tune, bool beams, int shadowBeside) {
+    if (scene->prm.integrator != KZ_INTEGRATOR_PATH_MIS) return wfPassIntegrator(scene, ds, c, stream, pixList, sBegin, Sp, items, tune, beams);
     const KzParams &P = scene->prm;
     KzWf W = c.wf;
     W.outJx = c.plane[0]; W.outJy = c.plane[1]; W.outR = c.plane[2]; W.outG = c.plane[3]; W.outB = c.plane[4]; W.stats = ds->stats;
@@ -1008,7 +1090,8 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
         // scene what was fastest per item - "one stream" unless something beat it by 3 %. (Such a wait is nothing new: a call already stays one pass ahead of a context that still grows.)
         int sb = opts->shadowBeside, probe = -1;
         bool halves = opts->passHalves == 2;
-        if (pipeline == 2 && opts->shadowBeside == 0 && opts->passHalves == 0 && items > KZ_BESIDE_ITEMS) {
+        // (normals / ao / path_mats have no shadow rays of a bounce to put beside anything: no mode is timed for them)
+        if (pipeline == 2 && opts->shadowBeside == 0 && opts->passHalves == 0 && items > KZ_BESIDE_ITEMS && P.integrator == KZ_INTEGRATOR_PATH_MIS) {
             if (multi || dealer || ds->statsOn || expTune) sb = 1;
             else {
                 if (ds->largeMode < 0 && ds->probeLaunched == 4) {
@@ -1087,8 +1170,14 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
                 float *sJx = c.plane[0], *sJy = c.plane[1], *sR = c.plane[2], *sG = c.plane[3], *sB = c.plane[4];
 #define KZ_MEGA(ST, EX) hipLaunchKernelGGL((kz_path_megakernel<ST, EX>), grid, dim3(KZ_BLOCK), 0, pst, P, ds->T, pixList, (uint32_t)items, Sp, s, \
                                        (const uint32_t *)nullptr, sJx, sJy, sR, sG, sB, ds->stats)
-                if (ds->statsOn) { if (P.bsdfExt) KZ_MEGA(true, KZ_X_ALL); else KZ_MEGA(true, 0); }
+#define KZ_IMEGA(IN, EX) hipLaunchKernelGGL((kz_integrator_megakernel<IN, EX>), grid, dim3(KZ_BLOCK), 0, pst, P, ds->T, pixList, (uint32_t)items, Sp, s, \
+                                        (const uint32_t *)nullptr, sJx, sJy, sR, sG, sB)
+                if (P.integrator == KZ_INTEGRATOR_NORMALS) KZ_IMEGA(KZ_INTEGRATOR_NORMALS, 0);
+                else if (P.integrator == KZ_INTEGRATOR_AO) KZ_IMEGA(KZ_INTEGRATOR_AO, 0);
+                else if (P.integrator == KZ_INTEGRATOR_PATH_MATS) { if (P.bsdfExt) KZ_IMEGA(KZ_INTEGRATOR_PATH_MATS, KZ_X_MATS); else KZ_IMEGA(KZ_INTEGRATOR_PATH_MATS, 0); }
+                else if (ds->statsOn) { if (P.bsdfExt) KZ_MEGA(true, KZ_X_ALL); else KZ_MEGA(true, 0); }
                 else { if (P.bsdfExt) KZ_MEGA(false, KZ_X_ALL); else KZ_MEGA(false, 0); }
+#undef KZ_IMEGA
 #undef KZ_MEGA
             }
             HIP_TRY(hipEventRecord(ep.b, pst));
@@ -1310,8 +1399,15 @@ int kz_render_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint
     KZ_ALLOC(&dP.p, (size_t)n * 4); KZ_ALLOC(&dI.p, (size_t)n * 4); KZ_ALLOC(&dOut.p, (size_t)n * 20);
     float *dO = dOut.as<float>();
     HIP_TRY(hipMemcpy(dP.p, pl.data(), (size_t)n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dI.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL((kz_path_megakernel<false, KZ_X_ALL>), dim3((n + KZ_BLOCK - 1) / KZ_BLOCK), dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.as<uint32_t>(), n, 1u, 0u, dI.as<uint32_t>(),
-                       dO, dO + n, dO + 2 * (size_t)n, dO + 3 * (size_t)n, dO + 4 * (size_t)n, ds->stats);
+    const dim3 gS((n + KZ_BLOCK - 1) / KZ_BLOCK);
+#define KZ_IMEGA(IN) hipLaunchKernelGGL((kz_integrator_megakernel<IN, KZ_X_MATS>), gS, dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.as<uint32_t>(), n, 1u, 0u, dI.as<uint32_t>(), \
+                                    dO, dO + n, dO + 2 * (size_t)n, dO + 3 * (size_t)n, dO + 4 * (size_t)n)
+    if (P.integrator == KZ_INTEGRATOR_NORMALS) KZ_IMEGA(KZ_INTEGRATOR_NORMALS);      // (normals / ao read no BSDF row; path_mats has no normal maps)
+    else if (P.integrator == KZ_INTEGRATOR_AO) KZ_IMEGA(KZ_INTEGRATOR_AO);
+    else if (P.integrator == KZ_INTEGRATOR_PATH_MATS) KZ_IMEGA(KZ_INTEGRATOR_PATH_MATS);
+    else hipLaunchKernelGGL((kz_path_megakernel<false, KZ_X_ALL>), gS, dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.as<uint32_t>(), n, 1u, 0u, dI.as<uint32_t>(),
+                            dO, dO + n, dO + 2 * (size_t)n, dO + 3 * (size_t)n, dO + 4 * (size_t)n, ds->stats);
+#undef KZ_IMEGA
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     std::vector<float> h((size_t)n * 5);

@@ -104,7 +104,7 @@ DeviceScene::DeviceScene(const Scene *scene) {
     }
     if (!scene->getCamera()->describe(m_desc.camera)) throw Exception("Camera {} is not on the MI355X path", scene->getCamera()->toString());
     if (!scene->getSampler()->describe(m_desc.sampler)) throw Exception("Sampler {} is not on the MI355X path", scene->getSampler()->toString());
-    if (!scene->getIntegrator()->describe(m_desc.integrator)) throw Exception("Integrator {} is not on the MI355X path (path_mis)", scene->getIntegrator()->toString());
+    if (!scene->getIntegrator()->describe(m_desc.integrator)) throw Exception("Integrator {} is not on the MI355X path (path_mis, normals, ao, path_mats)", scene->getIntegrator()->toString());
     if (scene->getBackground() && !scene->getBackground()->describeBackground(m_desc.background, m_rows))
         throw Exception("Scene background {} is not on the MI355X path", scene->getBackground()->toString());
     m_desc.abiVersion = KZ_ABI_VERSION;

@@ -5,7 +5,7 @@
 //   ObjectFactory::createInstance(name, PropertyList)        include/kazen/object.h:133-138, KAZEN_REGISTER_CLASS :144-152
 //   Object::addChild / activate / getClassType               include/kazen/object.h:40-75
 //   Scene, Mesh, PerspectiveCamera("perspective"), Independent("independent"), PMJ02BN("pmj02bn"),
-//   PathMisIntegrator("path_mis"), Diffuse("diffuse"), KazenStandardSurface("kazenstandard"), AreaLight("area"),
+//   PathMisIntegrator("path_mis"), NormalIntegrator("normals"), AmbientOcclusionIntegrator("ao"), PathMatsIntegrator("path_mats"), Diffuse("diffuse"), KazenStandardSurface("kazenstandard"), AreaLight("area"),
 //   ConstantTexture("constanttexture"), BackgroundTexture("background"), GaussianFilter("gaussian"),
 //   MitchellNetravaliFilter("mitchell"), TentFilter("tent"), BoxFilter("box")
 //   renderer::render(Scene*, ...)                              include/kazen/renderer.h:10, src/kazen/renderer.cpp:72-153
@@ -583,7 +583,7 @@ class Integrator : public Object {                   // include/kazen/integrator
 public:
     EClassType getClassType() const override { return EIntegrator; }
     virtual void preprocess(const class Scene *) {}
-    /// ADDED: the integrator's parameters for KzSceneDesc.integrator; false = not on the MI355X path (only path_mis is)
+    /// ADDED: the integrator's parameters for KzSceneDesc.integrator; false = not on the MI355X path (path_mis, normals, ao, path_mats are)
     virtual bool describe(KzIntegrator &) const { return false; }
 };
 class PathMisIntegrator : public Integrator {        // src/kazen/integrator.cpp:185-355
@@ -596,6 +596,26 @@ public:
     std::string toString() const override { return "PathMisIntegrator[]"; }
 private:
     int m_maxDepth; float m_rayEpsilon; bool m_regularization; float m_accumulatedRoughness;
+};
+// The three integrators that take no properties (their constructors read none): describe() fills the type and leaves the other fields at 0, which
+// the library ignores for them (include/kazen_mi355x.h KzIntegrator)
+class NormalIntegrator : public Integrator {         // src/kazen/integrator.cpp:11-34
+public:
+    explicit NormalIntegrator(const PropertyList &) {}
+    bool describe(KzIntegrator &row) const override { row = KzIntegrator{}; row.type = KZ_INTEGRATOR_NORMALS; return true; }
+    std::string toString() const override { return "NormalIntegrator[]"; }
+};
+class AmbientOcclusionIntegrator : public Integrator {   // src/kazen/integrator.cpp:37-71
+public:
+    explicit AmbientOcclusionIntegrator(const PropertyList &) {}
+    bool describe(KzIntegrator &row) const override { row = KzIntegrator{}; row.type = KZ_INTEGRATOR_AO; return true; }
+    std::string toString() const override { return "AmbientOcculusionIntegrator[]"; }      // (the reference's spelling, integrator.cpp:65)
+};
+class PathMatsIntegrator : public Integrator {       // src/kazen/integrator.cpp:137-181
+public:
+    explicit PathMatsIntegrator(const PropertyList &) {}
+    bool describe(KzIntegrator &row) const override { row = KzIntegrator{}; row.type = KZ_INTEGRATOR_PATH_MATS; return true; }
+    std::string toString() const override { return "PathMatsIntegrator[]"; }
 };
 class Camera : public Object {                       // include/kazen/camera.h:16-56 + the virtual INTEGRATION.md adds
 public:
@@ -797,6 +817,9 @@ KAZEN_MI355X_REGISTER(Correlated, "correlated");
 KAZEN_MI355X_REGISTER(ThinlensCamera, "thinlens");
 KAZEN_MI355X_REGISTER(PMJ02BN, "pmj02bn");
 KAZEN_MI355X_REGISTER(PathMisIntegrator, "path_mis");
+KAZEN_MI355X_REGISTER(NormalIntegrator, "normals");
+KAZEN_MI355X_REGISTER(AmbientOcclusionIntegrator, "ao");
+KAZEN_MI355X_REGISTER(PathMatsIntegrator, "path_mats");
 
 // ---- Bitmap (include/kazen/bitmap.h, src/kazen/bitmap.cpp:23-64): the renderer's output files ----------------------------
 // The reference writes through OpenImageIO; these writers are self-contained: an 8-bit RGB PNG (stored deflate blocks) and the

@@ -150,6 +150,9 @@ def look_at(origin, target, up):
     return m.astype(np.float32)
 
 
+# KzIntegrator.type of each integrator the library renders (include/kazen_mi355x.h KZ_INTEGRATOR_*)
+INTEGRATOR_TAGS = {"path_mis": 0, "normals": 1, "ao": 2, "path_mats": 3}
+
 class SceneDescription:
     """meshes: list of dicts {V (nV,3) f32, N (nV,3)|None, UV (nV,2)|None, F (nF,3) u32, bsdf: dict|None, light: dict|None}"""
 
@@ -331,7 +334,7 @@ class SceneDescription:
             d.sampler.pmj02bnSamples = pmj.ctypes.data_as(abi.u32p)
             d.sampler.blueNoise = bn.ctypes.data_as(abi.u16p)
         it = self.integrator
-        d.integrator.type = 0 if it["type"] == "path_mis" else 99
+        d.integrator.type = INTEGRATOR_TAGS.get(it["type"], 99)            # whitted and anything unknown: refused by kz_scene_create
         d.integrator.maxDepth = it["maxDepth"]
         d.integrator.traceBias = it["traceBias"]
         d.integrator.regularization = 1 if it["regularization"] else 0

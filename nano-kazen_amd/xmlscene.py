@@ -305,10 +305,11 @@ def load_xml(path, overrides=None):
             continue
         t = node.get("type")
         if node.tag == "integrator":
-            if t != "path_mis":
-                raise ValueError("integrator \"%s\" is not on the hot path (only path_mis)" % t)
-            p = _props(node)
-            s.integrator = {"type": "path_mis", "maxDepth": min(512, p.get("maxDepth", 5)), "traceBias": p.get("traceBias", 0.001),
+            if t not in S.INTEGRATOR_TAGS:
+                raise ValueError("integrator \"%s\" is not on the hot path (path_mis, normals, ao, path_mats)" % t)
+            # normals / ao / path_mats take no properties (integrator.cpp:13, :40, :139): theirs are ignored, the keys keep the defaults
+            p = _props(node) if t == "path_mis" else {}
+            s.integrator = {"type": t, "maxDepth": min(512, p.get("maxDepth", 5)), "traceBias": p.get("traceBias", 0.001),
                             "regularization": p.get("regularization", False), "accumulatedRoughness": p.get("accumulatedRoughness", 0.5)}
             have_integrator = True
         elif node.tag == "sampler":

@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the path_mis hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--strong] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--strong] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the record: `value`, `ms_per_step`, `end_to_end` and
+`config`. --full adds everything else, before and after that: the cold jobs, the parity render, the roofline, the CPU baseline, and the side
+jobs (N = 1: the reference's scene, the EXT scenes and C1-C3; N > 1: the C5 strong-scaling job). The --no-* options leave parts of it out.
 
 Workload (BASELINE.json configs[3], "C4"): 1 M random triangles + 8 mesh lights in a closed diffuse room,
 1920x1080, pmj02bn sampler (1024 spp), path_mis maxDepth 5. A "step" is one kz_render call over one batch: a 128-spp
@@ -22,11 +26,11 @@ in HBM before the timed region starts.
 --strong: BASELINE.json configs[4], "C5" - the SAME scene at 3840x2160 x 4096 spp as ONE fixed job: a step is the whole frame, every rank
 renders all 4096 spp of its tiles (scaling "strong": the work per GPU shrinks with N). Not the default: at N = 1 the driver's run must be C4.
 
-`cold_job` (N = 1): the reference renders ONE frame per process (renderer.cpp:72-153). Before this process touches the GPU, two CHILD
+`cold_job` (N = 1, --full): the reference renders ONE frame per process (renderer.cpp:72-153). Before this process touches the GPU, two CHILD
 processes each do exactly that job and report its wall time - kz_scene_upload of a freshly built scene, the WHOLE frame (C4: 1920x1080 x 1024 spp; the
 reference's own scene file default_m0_r0.5 at its 4096 spp), kz_film_download - every allocation, the beam lists and the growth of the pass context included.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` and `cpu_baseline`.
+Prints ONE JSON line on stdout on rank 0 (every log line goes to stderr); with --full it also carries `roofline`, `cpu_baseline`, `cold_job` and `parity`.
 """
 import argparse
 import importlib
@@ -245,6 +249,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--tris", type=int, default=NTRIS)
     ap.add_argument("--strong", action="store_true", help="C5: 3840x2160 x 4096 spp as one fixed job split over the ranks (a step = the frame)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the cold jobs, the parity render, the roofline (a pass alone, "
+                                                        "counters, a copy stream), the CPU baseline and the side jobs; the --no-* options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-strong-c5", action="store_true", help="N > 1: skip the bounded C5 strong-scaling job that rides in the same JSON line")
     ap.add_argument("--strong-spp", type=int, default=256, help="samples per pixel of that job (sample indices [0, n) of the 4096-spp table)")
@@ -273,7 +279,7 @@ def main():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     commit = os.environ.get("GRAFT_HEAD") or git_head()          # before torch / HIP are loaded: no fork from a process that has initialised the GPU
     cold = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.strong and not args.no_cold_job:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.strong and not args.no_cold_job:
         if profiler_attached():
             cold = {"skipped": "a profiler is attached (ROCPROFILER_* / ROCP_* in the environment or a rocprofiler preload): its library has initialised the GPU before "
                                "bench.py started, and a process that holds the GPU must not start child processes - pass --no-cold-job"}
@@ -422,7 +428,7 @@ def main():
     # depend on N, on the dealing or on the pass size (round 6: per-pixel running tap sums, rects merged in tile order), so the crc32 of a fixed crop is the same at
     # every N - the scaling run carries its own parity check.
     parity = None
-    if not args.strong and not args.no_parity:
+    if args.full and not args.strong and not args.no_parity:
         # (weak scaling lengthens the sampler table from N = 4 on: those ranks build the 1024-entry scene for this render - outside every clock)
         psc = scene if spp_table == PARITY_SPP_TABLE else kz.Scene(kz.scenes.random_triangles(args.tris, Wd, Hd, PARITY_SPP_TABLE, sampler="pmj02bn", seed=1), device=device_index)
         psc.render(0, 64, tiles=render_tiles, accumulate=False, stream=stream, **kw)
@@ -447,7 +453,7 @@ def main():
     total_samples = float(px.item()) * spp_step * args.steps
     value = total_samples / elapsed / 1e6
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- one pass run alone: per-stage device times (with two passes in flight the stage events of a pass overlap the other's)
         pass_spp = info["sppPerPass"]
         scene.render(0, pass_spp, tiles=render_tiles, accumulate=True, stream=stream, **dict(kw, shadow_beside=1))      # (one stream: the stage clock shows the shadow and the closest-hit kernels apart)
@@ -537,6 +543,7 @@ def main():
                                  "counters_per_sample_executed": {k: round(v / max(1, st_exec["samples"]), 3) for k, v in st_exec.items() if k != "samples"},
                                  "note": "algorithmic bytes are served by L1/L2/Infinity Cache, so this ratio is not a fraction of anything physical; "
                                          "the physical HBM figure is traffic_frac_of_peak"}
+    if rank == 0:
         rgb = scene.rgb(film_np)
         name = "C5" if args.strong else "C4"
         out = {"metric": "Msamples/s (w*h*spp/s) at %dx%d, 1 M-tri scene" % (Wd, Hd), "value": round(value, 3), "unit": "Msamples/s",
@@ -555,13 +562,14 @@ def main():
                           "how_the_last_timed_pass_ran": ("one stream", "its shadow rays beside its closest-hit rays", "as two halves side by side")[info["shadowBeside"]],
                           "large_passes_measured_by_the_replica": scene.pass_mode_info(), "warmup_steps_until_settled": settle, "warmup_wait_for_context_s": round(grow_wait_s, 2),
                           "first_call_ms": first_call_ms, "first_call": "the first (warm-up) step: beam lists of every pixel (kz_wf_beam, once per pixel and replica), the pass context "
-                                                                        "growing (its memory is mapped on a side thread while the first passes run), then the step itself; a timed step is ms_per_step"},
-               "roofline": roofline, "cpu_baseline": cpu, "cold_job": cold, "parity": parity}
+                                                                        "growing (its memory is mapped on a side thread while the first passes run), then the step itself; a timed step is ms_per_step"}}
+        if args.full:
+            out.update(roofline=roofline, cpu_baseline=cpu, cold_job=cold, parity=parity)
         if dumped is not None:
             out["dumped_outputs"] = dumped
-    # ---- side jobs. The headline record above is complete: a failure below lands in the sub-record as {"error": ...} and never costs the measurement
+    # ---- side jobs (--full). The headline record above is complete: a failure below lands in the sub-record as {"error": ...} and never costs the measurement
     # (ADVICE r04). A collective side job is entered only when EVERY rank is fit for it, and every step of it checks the ranks' status first.
-    if world > 1 and not args.strong and not args.no_strong_c5:
+    if args.full and world > 1 and not args.strong and not args.no_strong_c5:
         # the same launch also carries the strong-scaling job (collective: every rank); this rank's C4 replica goes first - its pass contexts stay in the
         # device's pool and the C5 replica renders in them
         try:
@@ -572,15 +580,15 @@ def main():
             log("rank %d: strong_c5 failed: %r" % (rank, e))
         if rank == 0:
             out["strong_c5"] = sc5
-    if world == 1 and not args.strong and not (args.no_asset_scene and args.no_ext_scenes):
+    if args.full and world == 1 and not args.strong and not (args.no_asset_scene and args.no_ext_scenes):
         scene.close()                                          # (its pass contexts go to the device's pool: the scenes below render in them - until round 6 the reference's
                                                                #  scene ran BESIDE the benched one's 175 GB of path state, in passes a quarter of the size it would otherwise earn)
-    if world == 1 and not args.strong and not args.no_asset_scene:
+    if args.full and world == 1 and not args.strong and not args.no_asset_scene:
         try:
             out["reference_scene"] = reference_scene(kz, device_index, args.asset_spp)
         except Exception as e:                                 # noqa: BLE001
             out["reference_scene"] = {"error": repr(e)}
-    if world == 1 and not args.strong and not args.no_ext_scenes:
+    if args.full and world == 1 and not args.strong and not args.no_ext_scenes:
         try:
             out["ext_scenes"] = ext_scenes(kz, device_index, cpu=not args.no_cpu_baseline)
         except Exception as e:                                 # noqa: BLE001

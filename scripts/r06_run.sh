@@ -9,7 +9,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -q ${KZ_TESTSEL:+-k "$KZ_TESTSEL
 tail -15 $OUT/tests.log
 [ $RC -eq 0 ] || exit $RC
 shift
-timeout -k 10 700 python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.log; RC=$?
+timeout -k 10 700 python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.log; RC=$?
 tail -5 $OUT/bench.log
 python3 -c "
 import json,sys

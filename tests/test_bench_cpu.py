@@ -65,3 +65,27 @@ def test_dump_outputs_are_whole_or_a_fixed_sample_within_the_budget(tmp_path):
         assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
     idx = np.load(tmp_path / "a" / "rgb_pixels.npy").astype(np.int64)
     assert shapes["rgb"] == [len(idx), 3] and np.array_equal(np.load(tmp_path / "a" / "rgb.npy"), rgb5.reshape(-1, 3)[idx])
+
+
+def test_only_a_full_run_starts_the_cold_jobs(monkeypatch):
+    """A plain run goes straight to the headline figure: the cold jobs (child processes, before the GPU is touched) run with --full only. Without a GPU both runs
+    then stop at the GPU check."""
+    import pytest
+    import torch
+    bench = importlib.import_module("bench")
+    started = []
+    monkeypatch.setattr(bench, "run_cold_jobs", lambda tris: started.append(tris) or {})
+    monkeypatch.setattr(bench, "profiler_attached", lambda: False)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    saved = os.dup(1)                                                     # (main() points file descriptor 1 at stderr: the record goes to a copy of the original)
+    try:
+        for extra, cold in (([], []), (["--full"], [bench.NTRIS])):
+            started.clear()
+            monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "1", "--warmup", "0"] + extra)
+            with pytest.raises(SystemExit, match="needs a GPU"):
+                bench.main()
+            assert started == cold, extra
+    finally:
+        os.dup2(saved, 1)
+        os.close(saved)

@@ -159,6 +159,10 @@ class KzHit(C.Structure):
                 ("sh_n", C.c_float * 3), ("geo_n", C.c_float * 3)]
 
 
+class KzVertexUpdate(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("nV", C.c_uint32), ("V", f32p), ("N", f32p)]
+
+
 class KzBvhInfo(C.Structure):
     _fields_ = [("nNodes", C.c_uint32), ("nLeaves", C.c_uint32), ("nTris", C.c_uint32), ("maxDepth", C.c_uint32),
                 ("maxLeafSize", C.c_uint32), ("sahCost", C.c_float), ("buildSeconds", C.c_double)]
@@ -175,7 +179,10 @@ EXPORTS = ["kz_scene_create", "kz_scene_destroy", "kz_scene_bvh_info", "kz_scene
            "kz_scene_evict", "kz_scene_devices", "kz_render_tiles", "kz_render_multi", "kz_deal_tiles", "kz_film_merge", "kz_film_download_on",
            "kz_film_clear_on", "kz_sync_on", "kz_last_pass_info", "kz_device_mem_info", "kz_camera_rays", "kz_light_query", "kz_kat_exact_math", "kz_kat_permute", "kz_kat_fresnel", "kz_kat_math", "kz_build_flags",
            "kz_tiles_packed_floats", "kz_film_download_tiles", "kz_film_merge_tiles", "kz_film_merge_rects", "kz_device_trim", "kz_kat_dpdf", "kz_kat_pow4", "kz_last_grow_note",
-           "kz_plan_passes", "kz_plan_schedule", "kz_pass_mode_info"]
+           "kz_plan_passes", "kz_plan_schedule", "kz_pass_mode_info", "kz_scene_table"]
+# what include/kazen_mi355x_edit.h declares (checked by tests/test_scene_edit_cpu.py): editing a scene that already exists
+EDIT_EXPORTS = ["kz_scene_set_camera", "kz_scene_set_vertices"]
+KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS = range(8)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices"]
 
@@ -259,6 +266,10 @@ def load_library(path=None):
         lib.kz_plan_passes.argtypes = [C.POINTER(KzPlanQuery), C.POINTER(KzPlanAnswer)]
         lib.kz_plan_schedule.argtypes = [C.POINTER(KzPlanQuery), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32, u32p]
     lib.kz_kat_dpdf.argtypes = [C.c_uint32, f32p, f32p, f32p]
+    if hasattr(lib, "kz_scene_set_vertices"):     # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(KzCamera)]
+        lib.kz_scene_set_vertices.argtypes = [C.c_void_p, C.POINTER(KzVertexUpdate), C.c_uint32]
+        lib.kz_scene_table.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

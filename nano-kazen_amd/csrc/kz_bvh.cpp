@@ -8,6 +8,7 @@
 // The tree depth is capped at KZ_STACK_DEPTH-2 (median splits take over when the SAH tree gets too
 // deep) because the traversal kernels keep a fixed per-lane stack in LDS.
 #include "kz_internal.h"
+#include "kz_refit.h"
 
 #include <algorithm>
 #include <atomic>
@@ -311,11 +312,12 @@ int kz_build_bvh(const std::vector<KzBuildTri> &in, std::vector<KzNode> &nodes, 
 // opening the inner child with the largest surface area until four slots are used. Nodes are numbered breadth-first.
 // ------------------------------------------------------------------------------------------------------------------
 namespace {
-struct ChildBox { float lo[3], hi[3]; uint32_t ref; };
+struct ChildBox { float lo[3], hi[3]; uint32_t ref; uint32_t src; };     // src = 2 x BVH2 node + child: the BVH2 box the slot is quantised from
 
 void childBoxesOf(const std::vector<KzNode> &nodes, uint32_t n, ChildBox out[2]) {
     const KzNode &nd = nodes[n];
     out[0].ref = nd.child[0]; out[1].ref = nd.child[1];
+    out[0].src = 2 * n; out[1].src = 2 * n + 1;
     out[0].lo[0] = nd.q[0]; out[0].lo[1] = nd.q[1]; out[0].lo[2] = nd.q[2]; out[0].hi[0] = nd.q[3]; out[0].hi[1] = nd.q[4]; out[0].hi[2] = nd.q[5];
     out[1].lo[0] = nd.q[6]; out[1].lo[1] = nd.q[7]; out[1].lo[2] = nd.q[8]; out[1].hi[0] = nd.q[9]; out[1].hi[1] = nd.q[10]; out[1].hi[2] = nd.q[11];
 }
@@ -323,12 +325,12 @@ float boxArea(const ChildBox &c) {
     float dx = c.hi[0] - c.lo[0], dy = c.hi[1] - c.lo[1], dz = c.hi[2] - c.lo[2];
     return 2.f * (dx * dy + dy * dz + dz * dx);
 }
-// the kernel's dequantisation, evaluated identically on the host (no contraction: q * s is exact, one rounding in the add)
-inline float deq(float p, uint32_t q, float s) { volatile float prod = (float)q * s; return p + prod; }
 }
 
-int kz_collapse_bvh4(const std::vector<KzNode> &nodes, uint32_t rootRef, std::vector<KzNode4> &out, uint32_t &rootRef4, int &stackBound) {
+int kz_collapse_bvh4(const std::vector<KzNode> &nodes, uint32_t rootRef, std::vector<KzNode4> &out, uint32_t &rootRef4, int &stackBound,
+                     std::vector<uint32_t> *slotSrc) {
     out.clear(); stackBound = 1;
+    if (slotSrc) slotSrc->clear();
     rootRef4 = rootRef;                      // empty scene or single-leaf root: same reference
     if (rootRef == 0xFFFFFFFFu || (rootRef & 0x80000000u)) return KZ_OK;
     struct Item { uint32_t bvh2; };
@@ -435,39 +437,18 @@ int kz_collapse_bvh4(const std::vector<KzNode> &nodes, uint32_t rootRef, std::ve
     }
     if (order.size() >= (1u << 31)) return KZ_ERR_UNSUPPORTED;
     out.resize(order.size());
+    if (slotSrc) slotSrc->assign(4 * order.size(), 0xFFFFFFFFu);
     for (size_t h = 0; h < order.size(); ++h) {
+        // (the quantisation is kz_refit.h's, which a refit repeats from the slots' BVH2 boxes: slotSrc)
         KzNode4 &nd = out[h]; std::memset(&nd, 0, sizeof nd);
         const int n = nk[h]; const auto &cb = kids[h];
-        float lo[3] = {kInf, kInf, kInf}, hi[3] = {-kInf, -kInf, -kInf};
-        for (int i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], cb[i].lo[a]); hi[a] = std::max(hi[a], cb[i].hi[a]); }
-        uint32_t exps = 0; float scale[3];
-        for (int a = 0; a < 3; ++a) {
-            nd.p[a] = lo[a];
-            float ext = hi[a] - lo[a];
-            int e = 0;
-            if (ext > 0.f) { std::frexp(ext / 255.0f, &e); }            // ext/255 = m * 2^e, m in [0.5,1) -> 2^e >= ext/255
-            else e = -126;
-            e = std::max(-126, std::min(127, e));
-            // make sure 255 steps reach hi even after the rounding of p + 255*s
-            while (e < 127 && deq(lo[a], 255u, std::ldexp(1.0f, e)) < hi[a]) ++e;
-            scale[a] = std::ldexp(1.0f, e);
-            exps |= (uint32_t)(e + 127) << (8 * a);
-        }
-        (void)exps; nd.scaleX = scale[0]; nd.scaleY = scale[1]; nd.scaleZ = scale[2];
-        for (int i = 0; i < 4; ++i) {
-            if (i >= n) { for (int a = 0; a < 3; ++a) { nd.qlo[a] |= 255u << (8 * i); } nd.child[i] = 0; continue; }     // qhi = 0: inverted, never hit
+        KzBox bx[4];
+        for (int i = 0; i < n; ++i) {
+            for (int a = 0; a < 3; ++a) { bx[i].lo[a] = cb[i].lo[a]; bx[i].hi[a] = cb[i].hi[a]; }
             nd.child[i] = cb[i].ref;
-            for (int a = 0; a < 3; ++a) {
-                int ql = (int)std::floor((cb[i].lo[a] - lo[a]) / scale[a]);
-                ql = std::max(0, std::min(255, ql));
-                while (ql > 0 && deq(lo[a], (uint32_t)ql, scale[a]) > cb[i].lo[a]) --ql;
-                int qh = (int)std::ceil((cb[i].hi[a] - lo[a]) / scale[a]);
-                qh = std::max(0, std::min(255, qh));
-                while (qh < 255 && deq(lo[a], (uint32_t)qh, scale[a]) < cb[i].hi[a]) ++qh;
-                nd.qlo[a] |= (uint32_t)ql << (8 * i);
-                nd.qhi[a] |= (uint32_t)qh << (8 * i);
-            }
+            if (slotSrc) (*slotSrc)[4 * h + i] = cb[i].src;
         }
+        kzQuantiseNode4(nd, bx, n);
     }
     // worst-case stack depth of the traversal: a node pushes (children - 1) entries before descending
     std::vector<int> need(out.size(), 0);

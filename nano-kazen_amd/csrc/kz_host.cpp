@@ -167,6 +167,100 @@ static int flattenTextures(const KzSceneDesc *d, KzScene *sc) {
 
 } // namespace
 
+// ---- the parts of kz_scene_create that an edit repeats (kazen_mi355x_edit.h, kz_edit.cpp) ----------------------------------------------
+// A light mesh's area CDF: DiscretePDF::append of every triangle's area, then normalize (scene.cpp:42-46, mesh.cpp:24-53, dpdf.h:35-37,77-89)
+void kzLightCdf(const KzTriShade *shade, uint32_t nF, std::vector<float> &t, float &normalization) {
+    t.assign(1, 0.0f);
+    for (uint32_t f = 0; f < nF; ++f) {
+        const KzTriShade &s = shade[f];
+        float e1[3], e2[3];
+        for (int a = 0; a < 3; ++a) { e1[a] = s.p[3 + a] - s.p[a]; e2[a] = s.p[6 + a] - s.p[a]; }
+        float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+        float area = 0.5f * std::sqrt(cx * cx + cy * cy + cz * cz);          // mesh.cpp:47-53
+        t.push_back(t.back() + area);
+    }
+    normalization = dpdfNormalize(t, 0, nullptr);
+}
+
+// invisible-light triangles for the exact any-hit shadow test
+void kzInvisibleLights(KzScene *sc) {
+    KzParams &p = sc->prm;
+    sc->ilTris.clear();
+    p.shadowFast = 1; p.nIlTris = 0; p.anyInvisibleLight = 0;
+    uint32_t ilGidLo = 0xFFFFFFFFu, ilGidHi = 0;
+    for (int a = 0; a < 3; ++a) { p.ilLo[a] = INFINITY; p.ilHi[a] = -INFINITY; }
+    for (const KzLightRow &lr : sc->lightRows) {
+        if (lr.primaryVisibility) continue;
+        p.anyInvisibleLight = 1;
+        if (lr.nF) { ilGidLo = std::min(ilGidLo, lr.triOffset); ilGidHi = std::max(ilGidHi, lr.triOffset + lr.nF - 1); }
+        for (uint32_t f = 0; f < lr.nF; ++f) {
+            const KzTriShade &s = sc->shade[lr.triOffset + f];
+            KzTri t; std::memset(&t, 0, sizeof t);
+            for (int a = 0; a < 3; ++a) {
+                t.p0[a] = s.p[a]; t.e1[a] = s.p[3 + a] - s.p[a]; t.e2[a] = s.p[6 + a] - s.p[a];
+                for (int v = 0; v < 3; ++v) { p.ilLo[a] = std::min(p.ilLo[a], s.p[3 * v + a]); p.ilHi[a] = std::max(p.ilHi[a], s.p[3 * v + a]); }
+            }
+            t.mesh = lr.mesh; t.prim = f; t.gid = lr.triOffset + f;
+            sc->ilTris.push_back(t);
+        }
+    }
+    if (sc->ilTris.size() > 64) { p.shadowFast = 0; sc->ilTris.clear(); }      // big emissive meshes: literal closest-hit loop
+    p.nIlTris = (uint32_t)sc->ilTris.size();
+    p.ilGidLo = ilGidLo <= ilGidHi ? ilGidLo : 1u; p.ilGidSpan = ilGidLo <= ilGidHi ? ilGidHi - ilGidLo : 0u;
+    for (int a = 0; a < 3; ++a) {        // same padding as BVH boxes
+        float m = std::max(std::fabs(p.ilLo[a]), std::fabs(p.ilHi[a]));
+        if (std::isfinite(m)) { float e = m * 4e-7f + 1e-30f; p.ilLo[a] -= e; p.ilHi[a] += e; }
+    }
+}
+
+// ---- camera (camera.cpp:35-68). Eigen is not available: the 4x4 product and inverse are formed in
+// double and narrowed once, unless the caller hands over Eigen's own m_sampleToCamera.
+int kzCameraParams(const KzCamera &c, KzParams &p) {
+    if (c.type != KZ_CAMERA_PERSPECTIVE && c.type != KZ_CAMERA_THINLENS) return kz_fail(KZ_ERR_UNSUPPORTED, "camera type %d is not supported (\"perspective\", \"thinlens\")", c.type);
+    p.width = c.width; p.height = c.height;
+    p.invW = 1.0f / (float)c.width; p.invH = 1.0f / (float)c.height;
+    p.nearClip = c.nearClip; p.farClip = c.farClip;
+    std::memcpy(p.c2w, c.toWorld, sizeof p.c2w);
+    if (c.sampleToCamera) std::memcpy(p.s2c, c.sampleToCamera, sizeof p.s2c);
+    else {
+        float aspect = c.width / (float)c.height;
+        float recip = 1.0f / (c.farClip - c.nearClip);
+        float cot = 1.0f / std::tan((c.fov / 2.0f) * (3.14159265358979323846f / 180.0f));      // common.h:222 degToRad; M_PI is the float literal of common.h:33
+        double P[16] = {cot, 0, 0, 0, 0, cot, 0, 0, 0, 0, (double)(c.farClip * recip), (double)(-c.nearClip * c.farClip * recip), 0, 0, 1, 0};
+        double T[16] = {1, 0, 0, -1, 0, 1, 0, (double)(-1.0f / aspect), 0, 0, 1, 0, 0, 0, 0, 1};
+        double D[16] = {-0.5, 0, 0, 0, 0, (double)(-0.5f * aspect), 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        double TP[16], M[16], Mi[16];
+        mat4mul(T, P, TP); mat4mul(D, TP, M);
+        if (!mat4inv(M, Mi)) return kz_fail(KZ_ERR_INVALID_ARG, "singular projection (fov %g, clip %g..%g)", c.fov, c.nearClip, c.farClip);
+        for (int i = 0; i < 16; ++i) p.s2c[i] = (float)Mi[i];
+    }
+    {   // pixel beams (kz_wf_beam): only for a pinhole camera whose homogeneous divide does not depend on the sample position and an affine c2w
+        const float *m = p.s2c, *w = p.c2w;
+        p.beamOk = 0;
+        for (int r = 0; r < 3; ++r) p.beamO[r] = p.beamA[r] = p.beamU[r] = p.beamV[r] = 0.f;      // (a camera without beams carries zeros: an edit leaves no stale ones)
+        const float tiny = 1e-9f * std::fabs(m[15]);          // (a numerically formed inverse leaves 1e-17s where the zeros are: far inside the beams' margins)
+        if (c.type != KZ_CAMERA_THINLENS && std::fabs(m[12]) <= tiny && std::fabs(m[13]) <= tiny && m[15] != 0.f && w[12] == 0.f && w[13] == 0.f && w[14] == 0.f && w[15] != 0.f) {
+            const double rw = m[15];
+            const double A[3] = {m[3] / rw, m[7] / rw, m[11] / rw}, U[3] = {m[0] * (double)p.invW / rw, m[4] * (double)p.invW / rw, m[8] * (double)p.invW / rw},
+                         V[3] = {m[1] * (double)p.invH / rw, m[5] * (double)p.invH / rw, m[9] * (double)p.invH / rw};
+            bool fin = true;
+            for (int r = 0; r < 3; ++r) {
+                p.beamA[r] = (float)(w[4 * r] * A[0] + w[4 * r + 1] * A[1] + w[4 * r + 2] * A[2]);
+                p.beamU[r] = (float)(w[4 * r] * U[0] + w[4 * r + 1] * U[1] + w[4 * r + 2] * U[2]);
+                p.beamV[r] = (float)(w[4 * r] * V[0] + w[4 * r + 1] * V[1] + w[4 * r + 2] * V[2]);
+                p.beamO[r] = w[4 * r + 3] / w[15];
+                fin = fin && std::isfinite(p.beamA[r]) && std::isfinite(p.beamU[r]) && std::isfinite(p.beamV[r]) && std::isfinite(p.beamO[r]);
+            }
+            p.beamOk = fin ? 1 : 0;
+        }
+    }
+    p.cameraType = c.type; p.apertureRadius = c.apertureRadius; p.focusDistance = c.focusDistance;
+    return KZ_OK;
+}
+
+namespace {
+} // namespace
+
 extern "C" {
 
 const char *kz_last_error(void) { return g_err; }
@@ -256,7 +350,7 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
     size_t totalF = 0;
     for (uint32_t m = 0; m < d->nMeshes; ++m) totalF += d->meshes[m].nF;
     if (totalF >= (1ull << 28)) { delete sc; return kz_fail(KZ_ERR_UNSUPPORTED, "%zu triangles (limit 2^28)", totalF); }
-    bt.reserve(totalF); sc->shade.reserve(totalF);
+    bt.reserve(totalF); sc->shade.reserve(totalF); sc->triVtx.reserve(3 * totalF);
     uint32_t gid = 0;
     for (uint32_t m = 0; m < d->nMeshes; ++m) {
         const KzMesh &km = d->meshes[m];
@@ -290,6 +384,7 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
                 if (km.UV) { s.uv[2 * v] = km.UV[2 * (size_t)idx[v]]; s.uv[2 * v + 1] = km.UV[2 * (size_t)idx[v] + 1]; }
             }
             bt.push_back(t); sc->shade.push_back(s);
+            sc->triVtx.insert(sc->triVtx.end(), idx, idx + 3);
         }
         // ---- light rows + area CDF (scene.cpp:42-46, mesh.cpp:24-45, dpdf.h:35-37,77-89)
         if (km.light >= 0) {
@@ -299,21 +394,14 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
             lr.primaryVisibility = kl.primaryVisibility ? 1 : 0;
             while (sc->cdf.size() & 3u) sc->cdf.push_back(2.0f);            // every light's table starts on a 16-B boundary (cdfSample reads short tables as float4s)
             lr.mesh = m; lr.triOffset = row.triOffset; lr.nF = km.nF; lr.cdfOffset = (uint32_t)sc->cdf.size(); lr.hasN = km.N ? 1u : 0u;
-            size_t base = sc->cdf.size();
-            sc->cdf.push_back(0.0f);
-            for (uint32_t f = 0; f < km.nF; ++f) {
-                const KzTriShade &s = sc->shade[row.triOffset + f];
-                float e1[3], e2[3];
-                for (int a = 0; a < 3; ++a) { e1[a] = s.p[3 + a] - s.p[a]; e2[a] = s.p[6 + a] - s.p[a]; }
-                float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-                float area = 0.5f * std::sqrt(cx * cx + cy * cy + cz * cz);          // mesh.cpp:47-53
-                sc->cdf.push_back(sc->cdf.back() + area);
-            }
-            lr.normalization = dpdfNormalize(sc->cdf, base, nullptr);
+            std::vector<float> t;
+            kzLightCdf(&sc->shade[row.triOffset], km.nF, t, lr.normalization);
+            sc->cdf.insert(sc->cdf.end(), t.begin(), t.end());
             row.light = (int32_t)sc->lightRows.size();
             sc->lightRows.push_back(lr);
         }
         sc->meshRows.push_back(row);
+        sc->meshNV.push_back(km.nV);
     }
     sc->cdf.insert(sc->cdf.end(), 8, 2.0f);          // padding: the device reads eight entries of a short table at once (cdfSample)
     std::string berr;
@@ -324,7 +412,7 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
     KzParams &p = sc->prm;
     p.rootRef = rootRef;
     { int sb = 1; uint32_t r4 = rootRef;
-      rc = kz_collapse_bvh4(sc->nodes, rootRef, sc->nodes4, r4, sb);
+      rc = kz_collapse_bvh4(sc->nodes, rootRef, sc->nodes4, r4, sb, &sc->slotSrc);
       if (rc != KZ_OK) { delete sc; return kz_fail(rc, "BVH4 collapse failed"); }
       // (the kernels address a packet as table base + a 32-bit byte offset, kz_devfn.h kzNode4Ptr)
       if (sc->nodes4.size() > (size_t(1) << 26)) { delete sc; return kz_fail(KZ_ERR_UNSUPPORTED, "scene too large: %zu BVH4 packets (limit 2^26 = 4 GB of packets)", sc->nodes4.size()); }
@@ -337,71 +425,10 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
         else if (b.type > KZ_BSDF_KAZENSTANDARD) p.bsdfExt |= 1;
         if (b.albedoTex || b.roughnessTex || b.metallicTex) p.bsdfExt |= 2;
     }
-    // invisible-light triangles for the exact any-hit shadow test
-    p.shadowFast = 1; p.nIlTris = 0; p.anyInvisibleLight = 0;
-    uint32_t ilGidLo = 0xFFFFFFFFu, ilGidHi = 0;
-    for (int a = 0; a < 3; ++a) { p.ilLo[a] = INFINITY; p.ilHi[a] = -INFINITY; }
-    for (const KzLightRow &lr : sc->lightRows) {
-        if (lr.primaryVisibility) continue;
-        p.anyInvisibleLight = 1;
-        if (lr.nF) { ilGidLo = std::min(ilGidLo, lr.triOffset); ilGidHi = std::max(ilGidHi, lr.triOffset + lr.nF - 1); }
-        for (uint32_t f = 0; f < lr.nF; ++f) {
-            const KzTriShade &s = sc->shade[lr.triOffset + f];
-            KzTri t; std::memset(&t, 0, sizeof t);
-            for (int a = 0; a < 3; ++a) {
-                t.p0[a] = s.p[a]; t.e1[a] = s.p[3 + a] - s.p[a]; t.e2[a] = s.p[6 + a] - s.p[a];
-                for (int v = 0; v < 3; ++v) { p.ilLo[a] = std::min(p.ilLo[a], s.p[3 * v + a]); p.ilHi[a] = std::max(p.ilHi[a], s.p[3 * v + a]); }
-            }
-            t.mesh = lr.mesh; t.prim = f; t.gid = lr.triOffset + f;
-            sc->ilTris.push_back(t);
-        }
-    }
-    if (sc->ilTris.size() > 64) { p.shadowFast = 0; sc->ilTris.clear(); }      // big emissive meshes: literal closest-hit loop
-    p.nIlTris = (uint32_t)sc->ilTris.size();
-    p.ilGidLo = ilGidLo <= ilGidHi ? ilGidLo : 1u; p.ilGidSpan = ilGidLo <= ilGidHi ? ilGidHi - ilGidLo : 0u;
-    for (int a = 0; a < 3; ++a) {        // same padding as BVH boxes
-        float m = std::max(std::fabs(p.ilLo[a]), std::fabs(p.ilHi[a]));
-        if (std::isfinite(m)) { float e = m * 4e-7f + 1e-30f; p.ilLo[a] -= e; p.ilHi[a] += e; }
-    }
-    // ---- camera (camera.cpp:35-68). Eigen is not available: the 4x4 product and inverse are formed in
-    // double and narrowed once, unless the caller hands over Eigen's own m_sampleToCamera.
+    kzInvisibleLights(sc);
     const KzCamera &c = d->camera;
-    p.width = c.width; p.height = c.height;
-    p.invW = 1.0f / (float)c.width; p.invH = 1.0f / (float)c.height;
-    p.nearClip = c.nearClip; p.farClip = c.farClip;
-    std::memcpy(p.c2w, c.toWorld, sizeof p.c2w);
-    if (c.sampleToCamera) std::memcpy(p.s2c, c.sampleToCamera, sizeof p.s2c);
-    else {
-        float aspect = c.width / (float)c.height;
-        float recip = 1.0f / (c.farClip - c.nearClip);
-        float cot = 1.0f / std::tan((c.fov / 2.0f) * (3.14159265358979323846f / 180.0f));      // common.h:222 degToRad; M_PI is the float literal of common.h:33
-        double P[16] = {cot, 0, 0, 0, 0, cot, 0, 0, 0, 0, (double)(c.farClip * recip), (double)(-c.nearClip * c.farClip * recip), 0, 0, 1, 0};
-        double T[16] = {1, 0, 0, -1, 0, 1, 0, (double)(-1.0f / aspect), 0, 0, 1, 0, 0, 0, 0, 1};
-        double D[16] = {-0.5, 0, 0, 0, 0, (double)(-0.5f * aspect), 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        double TP[16], M[16], Mi[16];
-        mat4mul(T, P, TP); mat4mul(D, TP, M);
-        if (!mat4inv(M, Mi)) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "singular projection (fov %g, clip %g..%g)", c.fov, c.nearClip, c.farClip); }
-        for (int i = 0; i < 16; ++i) p.s2c[i] = (float)Mi[i];
-    }
-    {   // pixel beams (kz_wf_beam): only for a pinhole camera whose homogeneous divide does not depend on the sample position and an affine c2w
-        const float *m = p.s2c, *w = p.c2w;
-        p.beamOk = 0;
-        const float tiny = 1e-9f * std::fabs(m[15]);          // (a numerically formed inverse leaves 1e-17s where the zeros are: far inside the beams' margins)
-        if (c.type != KZ_CAMERA_THINLENS && std::fabs(m[12]) <= tiny && std::fabs(m[13]) <= tiny && m[15] != 0.f && w[12] == 0.f && w[13] == 0.f && w[14] == 0.f && w[15] != 0.f) {
-            const double rw = m[15];
-            const double A[3] = {m[3] / rw, m[7] / rw, m[11] / rw}, U[3] = {m[0] * (double)p.invW / rw, m[4] * (double)p.invW / rw, m[8] * (double)p.invW / rw},
-                         V[3] = {m[1] * (double)p.invH / rw, m[5] * (double)p.invH / rw, m[9] * (double)p.invH / rw};
-            bool fin = true;
-            for (int r = 0; r < 3; ++r) {
-                p.beamA[r] = (float)(w[4 * r] * A[0] + w[4 * r + 1] * A[1] + w[4 * r + 2] * A[2]);
-                p.beamU[r] = (float)(w[4 * r] * U[0] + w[4 * r + 1] * U[1] + w[4 * r + 2] * U[2]);
-                p.beamV[r] = (float)(w[4 * r] * V[0] + w[4 * r + 1] * V[1] + w[4 * r + 2] * V[2]);
-                p.beamO[r] = w[4 * r + 3] / w[15];
-                fin = fin && std::isfinite(p.beamA[r]) && std::isfinite(p.beamU[r]) && std::isfinite(p.beamV[r]) && std::isfinite(p.beamO[r]);
-            }
-            p.beamOk = fin ? 1 : 0;
-        }
-    }
+    if ((rc = kzCameraParams(c, p)) != KZ_OK) { delete sc; return rc; }
+    sc->rfilter = c.rfilter;
     // ---- film filter table (block.cpp:13-21)
     const KzFilter &rf = c.rfilter;
     p.filterRadius = rf.radius;
@@ -453,7 +480,6 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
     p.seed = d->sampler.seed;
     p.sampleCount = d->sampler.sampleCount;
     p.resX = p.resY = 1;
-    p.cameraType = d->camera.type; p.apertureRadius = d->camera.apertureRadius; p.focusDistance = d->camera.focusDistance;
     if (d->sampler.type == KZ_SAMPLER_STRATIFIED) {                       // Stratified ctor, sampler.cpp:84-92
         int res = d->sampler.resolution;
         while ((uint32_t)(res * res) < p.sampleCount) res++;
@@ -521,6 +547,7 @@ void kz_scene_destroy(KzScene *scene) {
 
 int kz_scene_bvh_info(const KzScene *scene, KzBvhInfo *out) {
     if (!scene || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null argument");
+    kzHostSync(const_cast<KzScene *>(scene));           // (sahCost of the refit tree after an edit)
     *out = scene->bvh;
     return KZ_OK;
 }

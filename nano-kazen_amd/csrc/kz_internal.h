@@ -2,8 +2,10 @@
 // Not part of the ABI (that is include/kazen_mi355x.h).
 #pragma once
 #include "../../include/kazen_mi355x_dev.h"
+#include "../../include/kazen_mi355x_edit.h"
 
 #include <cstdint>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -166,6 +168,15 @@ struct KzScene {
     KzParams prm;
     uint32_t texPow2 = 1;               // every image of the scene has power-of-two sides
     KzBvhInfo bvh;
+    // editing (include/kazen_mi355x_edit.h, kz_edit.cpp): what a refit needs beyond the flat tables, and how far the host tables lag behind the last edit
+    KzFilter rfilter;                   // the film's filter as created (an edited camera must keep it)
+    std::vector<uint32_t> triVtx;       // 3 per gid: the face's vertex indices within its mesh
+    std::vector<uint32_t> meshNV;       // vertex count of every mesh at creation
+    std::vector<uint32_t> slotSrc;      // 4 per BVH4 packet: 2 x BVH2 node + child of the box each slot is quantised from (0xFFFFFFFF: empty slot)
+    std::vector<uint32_t> levelStart;   // the BVH2 nodes of depth d are [levelStart[d], levelStart[d + 1]) (breadth-first numbering; filled by the first edit)
+    std::vector<std::vector<float>> pendV, pendN;   // per mesh: positions / normals an edit has set that the host's shading records do not hold yet
+    bool hostStale = false;             // tris, nodes, nodes4 and bvh.sahCost do not follow the last edit yet (kzHostSync brings them up to date)
+    std::mutex editMutex;               // guards the lazy host refit (kzHostSync may be reached from several device threads of kz_render_multi)
     // device replicas, one per GPU the scene is resident on (KzReplicaSet, owned by kz_render.hip; created with the scene)
     void *dev = nullptr;
 };
@@ -174,10 +185,22 @@ struct KzScene {
 struct KzBuildTri { float v[3][3]; uint32_t mesh, prim, gid; };
 int kz_build_bvh(const std::vector<KzBuildTri> &in, std::vector<KzNode> &nodes, std::vector<KzTri> &tris,
                  uint32_t &rootRef, KzBvhInfo &info, std::string &err);
-int kz_collapse_bvh4(const std::vector<KzNode> &nodes, uint32_t rootRef, std::vector<KzNode4> &out, uint32_t &rootRef4, int &stackBound);
+int kz_collapse_bvh4(const std::vector<KzNode> &nodes, uint32_t rootRef, std::vector<KzNode4> &out, uint32_t &rootRef4, int &stackBound,
+                     std::vector<uint32_t> *slotSrc = nullptr);
 
 // kz_host.cpp
 int kz_fail(int code, const char *fmt, ...);
+int kzCameraParams(const KzCamera &c, KzParams &p);                     // the camera part of KzParams (pixel beams included)
+void kzLightCdf(const KzTriShade *shade, uint32_t nF, std::vector<float> &t, float &normalization);   // a light mesh's area CDF (t[0] = 0, nF + 1 entries)
+void kzInvisibleLights(KzScene *sc);                                    // ilTris, ilLo / ilHi, ilGid* and shadowFast from the shading records
+
+// kz_edit.cpp: the host tables follow every edit before anything reads them (uploads, BVH2 paths, kz_scene_bvh_info, kz_scene_table)
+void kzHostSync(KzScene *scene);
+// kz_refit.hip: the device side of an edit, on every replica of the scene
+int kzEditWait(KzScene *scene);                                        // the work earlier calls enqueued has finished
+int kzEditPrepare(KzScene *scene);                                     // BVH2, triangle vertex indices and slot map resident (once per replica)
+int kzEditBeamsUnbuilt(KzScene *scene);                                // every replica's pixel-beam lists marked unbuilt
+int kzEditVertices(KzScene *scene, const KzVertexUpdate *u, uint32_t n, const std::vector<uint32_t> &lightRows);   // upload + refit + derived rows
 
 // kz_render.hip
 void kz_device_init(KzScene *scene);          // empty replica set

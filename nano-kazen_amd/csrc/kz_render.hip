@@ -110,7 +110,7 @@ static void releaseReplica(KzDeviceState *ds) {
     (void)hipSetDevice(ds->hipDevice);
     (void)hipDeviceSynchronize();
     for (void *p : ds->allocs) (void)hipFree(p);
-    for (void *p : {(void *)ds->film, (void *)ds->tapSums, (void *)ds->srgb, (void *)ds->pixList, (void *)ds->stats, (void *)ds->packDev, (void *)ds->rectsDev, (void *)ds->beamEntries, (void *)ds->beamCount, (void *)ds->tileDev}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)ds->film, (void *)ds->tapSums, (void *)ds->srgb, (void *)ds->pixList, (void *)ds->stats, (void *)ds->packDev, (void *)ds->rectsDev, (void *)ds->beamEntries, (void *)ds->beamCount, (void *)ds->tileDev, (void *)ds->editStage}) if (p) (void)hipFree(p);
     if (ds->tileHost) (void)hipHostFree(ds->tileHost);
     if (ds->evTiles) (void)hipEventDestroy(ds->evTiles);
     if (ds->evBeam) (void)hipEventDestroy(ds->evBeam);
@@ -251,6 +251,7 @@ static int uploadReplica(KzScene *scene, KzDeviceState *ds) {
 // The BVH2 table of a replica, on first use (see uploadReplica). The caller has made the replica's device current.
 int kzEnsureBvh2(KzScene *scene, KzDeviceState *ds) {
     if (ds->bvh2Resident || scene->nodes.empty()) return KZ_OK;
+    kzHostSync(scene);                                  // (the host BVH2 follows the last edit before it goes up)
     void *p = nullptr;
     const size_t bytes = scene->nodes.size() * sizeof(KzNode);
     KZ_ALLOC(&p, bytes);
@@ -294,6 +295,7 @@ int kz_scene_upload(KzScene *scene, int device) {
     KZ_TRACE("kz_scene_upload(%d)", device);
     HIP_TRY(hipSetDevice(kzPhysicalDevice(device)));
     KZ_TRACE("upload: hipSetDevice done");
+    kzHostSync(scene);                                  // (the tables follow the last edit before they go up)
     KzDeviceState *ds = new KzDeviceState();
     ds->device = device; ds->hipDevice = kzPhysicalDevice(device);
     const int rc = uploadReplica(scene, ds);

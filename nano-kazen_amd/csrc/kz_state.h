@@ -216,6 +216,9 @@ struct KzDeviceState {
     size_t beamBytes() const { return beamCap * (KZ_BEAM_CAP + 1) * sizeof(uint2); }
     size_t ctxBytes() const { size_t b = 0; for (const PassCtx *c : ctx) if (c) b += c->bytes(); return b; }
     KzPassInfo lastInfo{}; std::string growNote;
+    // Edits (kz_refit.hip): the triangles' vertex indices and the BVH4 slot map, uploaded on the replica's first kz_scene_set_vertices (with the BVH2, which the
+    // refit keeps resident), a staging area for the vertex data of a batch, and the refit's absolute box padding. editBytes: what they hold.
+    uint32_t *editTriVtx = nullptr, *editSlotSrc = nullptr; float *editPad = nullptr; float *editStage = nullptr; size_t editStageCap = 0; size_t editBytes = 0;
 };
 struct KzReplicaSet { std::mutex m; std::vector<KzDeviceState *> v; };
 

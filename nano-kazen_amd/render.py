@@ -1,4 +1,4 @@
-"""Thin handle around a KzScene* (the library's immutable scene + device tables + device film)."""
+"""Thin handle around a KzScene* (the library's scene + device tables + device film; its camera and vertex data can be edited in place)."""
 import ctypes as C
 
 import numpy as np
@@ -41,6 +41,41 @@ class Scene:
         info = abi.KzBvhInfo()
         abi.check(self.lib, self.lib.kz_scene_bvh_info(self.h, C.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def set_camera(self, camera):
+        """kz_scene_set_camera (include/kazen_mi355x_edit.h): `camera` holds keys of SceneDescription.camera; the others keep their values.
+        width, height and rfilter must stay the scene's. Scene.desc.camera follows."""
+        from .scenes import camera_to_c
+        cam = dict(self.desc.camera)
+        cam.update(camera)
+        if "toWorld" in camera:
+            cam["toWorld"] = np.array(camera["toWorld"], np.float32)
+        c = camera_to_c(cam, abi.KzCamera())
+        abi.check(self.lib, self.lib.kz_scene_set_camera(self.h, C.byref(c)))
+        self.desc.camera = cam
+
+    def set_vertices(self, updates):
+        """kz_scene_set_vertices (include/kazen_mi355x_edit.h) for a batch {mesh: V} or {mesh: (V, N)}: V / N (nV, 3) float32 from host memory, N exactly when
+        the mesh has normals. Scene.desc's meshes follow (new arrays: the old ones are not written)."""
+        rows, keep = [], []
+        for m, x in updates.items():
+            V, N = (x if isinstance(x, tuple) else (x, None))
+            V = np.ascontiguousarray(V, np.float32).reshape(-1, 3)
+            N = None if N is None else np.ascontiguousarray(N, np.float32).reshape(-1, 3)
+            keep.append((int(m), V, N))
+            rows.append(abi.KzVertexUpdate(int(m) if int(m) >= 0 else 0xFFFFFFFF, V.shape[0], V.ctypes.data_as(abi.f32p), N.ctypes.data_as(abi.f32p) if N is not None else None))
+        arr = (abi.KzVertexUpdate * max(1, len(rows)))(*rows)
+        abi.check(self.lib, self.lib.kz_scene_set_vertices(self.h, arr, len(rows)))
+        for m, V, N in keep:
+            self.desc.meshes[m] = dict(self.desc.meshes[m], V=V.copy(), N=None if N is None else N.copy())
+
+    def table(self, table, device=-1):
+        """kz_scene_table: a flat table of the scene as raw bytes (numpy uint8): device -1 = the host copy, else that replica's (abi.KZ_TABLE_*)."""
+        n = C.c_size_t()
+        abi.check(self.lib, self.lib.kz_scene_table(self.h, int(device), int(table), None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        abi.check(self.lib, self.lib.kz_scene_table(self.h, int(device), int(table), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)))
+        return out
 
     def upload(self, device=0):
         """Adds a replica on `device` (the first one uploaded is the primary, which the calls without a device address)."""

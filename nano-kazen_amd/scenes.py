@@ -153,6 +153,25 @@ def look_at(origin, target, up):
 # KzIntegrator.type of each integrator the library renders (include/kazen_mi355x.h KZ_INTEGRATOR_*)
 INTEGRATOR_TAGS = {"path_mis": 0, "normals": 1, "ao": 2, "path_mats": 3}
 
+def camera_to_c(cam, out):
+    """SceneDescription.camera (dict) -> the KzCamera `out` (kz_scene_create's and kz_scene_set_camera's input)."""
+    out.type = {"perspective": abi.KZ_CAMERA_PERSPECTIVE, "thinlens": abi.KZ_CAMERA_THINLENS}.get(cam["type"], 99)
+    out.apertureRadius = cam.get("apertureRadius", 1.0)
+    out.focusDistance = cam.get("focusDistance", 0.0)
+    out.width, out.height = cam["width"], cam["height"]
+    tw = np.ascontiguousarray(cam["toWorld"], np.float32).reshape(16)
+    out.toWorld[:] = tw.tolist()
+    out.fov, out.nearClip, out.farClip = cam["fov"], cam["nearClip"], cam["farClip"]
+    out.sampleToCamera = None
+    rf = cam["rfilter"]
+    out.rfilter.type = {"gaussian": 0, "mitchell": 1, "tent": 2, "box": 3}[rf["type"]]
+    out.rfilter.radius = {"gaussian": rf.get("radius", 2.0), "mitchell": rf.get("radius", 2.0),
+                          "tent": 1.0, "box": 0.5}[rf["type"]]
+    out.rfilter.stddev = rf.get("stddev", 0.5)
+    out.rfilter.B, out.rfilter.C = rf.get("B", 1 / 3.0), rf.get("C", 1 / 3.0)
+    return out
+
+
 class SceneDescription:
     """meshes: list of dicts {V (nV,3) f32, N (nV,3)|None, UV (nV,2)|None, F (nF,3) u32, bsdf: dict|None, light: dict|None}"""
 
@@ -306,21 +325,7 @@ class SceneDescription:
         d.lights, d.nLights = cl, len(lights)
         d.textures, d.nTextures = ct, len(textures)
         d.images, d.nImages = ci, len(images)
-        cam = self.camera
-        d.camera.type = {"perspective": abi.KZ_CAMERA_PERSPECTIVE, "thinlens": abi.KZ_CAMERA_THINLENS}.get(cam["type"], 99)
-        d.camera.apertureRadius = cam.get("apertureRadius", 1.0)
-        d.camera.focusDistance = cam.get("focusDistance", 0.0)
-        d.camera.width, d.camera.height = cam["width"], cam["height"]
-        tw = np.ascontiguousarray(cam["toWorld"], np.float32).reshape(16)
-        d.camera.toWorld[:] = tw.tolist()
-        d.camera.fov, d.camera.nearClip, d.camera.farClip = cam["fov"], cam["nearClip"], cam["farClip"]
-        d.camera.sampleToCamera = None
-        rf = cam["rfilter"]
-        d.camera.rfilter.type = {"gaussian": 0, "mitchell": 1, "tent": 2, "box": 3}[rf["type"]]
-        d.camera.rfilter.radius = {"gaussian": rf.get("radius", 2.0), "mitchell": rf.get("radius", 2.0),
-                                   "tent": 1.0, "box": 0.5}[rf["type"]]
-        d.camera.rfilter.stddev = rf.get("stddev", 0.5)
-        d.camera.rfilter.B, d.camera.rfilter.C = rf.get("B", 1 / 3.0), rf.get("C", 1 / 3.0)
+        camera_to_c(self.camera, d.camera)
         s = self.sampler
         d.sampler.type = {"independent": 0, "pmj02bn": 1, "stratified": 2, "correlated": 3}.get(s["type"], 99)
         d.sampler.resolution = s.get("resolution", 4)

@@ -256,8 +256,8 @@ typedef struct KzTile { int32_t x0, y0, w, h; } KzTile;
 
 /* Knobs of the persistent kernels. Zero = the library default, which is what the measured numbers use. They are part
  * of the ABI so that nothing behind it depends on process-global state: the library reads no environment variable.
- * The dev* words keep the ABI v4 layout: they select kernels of rejected experiments in development builds of the library
- * (named in kazen_mi355x_dev.h); the product library answers a non-zero value with KZ_ERR_UNSUPPORTED. Leave them 0. */
+ * The dev* words keep the ABI v4 layout. They once selected kernels of rejected experiments, which are gone: every build of the library
+ * answers the values that did (dev0 != 0, dev1 / dev2 / dev4 / dev5 > 0, dev3 > 1) with KZ_ERR_UNSUPPORTED. Leave them 0. */
 typedef struct KzTuning {
     int32_t refill;             /* a wave refills idle lanes once fewer than this many are busy (default 40; shadow rays 32) */
     int32_t postpone;           /* node phase goes on while at least this many lanes hold inner nodes (default 24)  */

@@ -3,7 +3,7 @@
  * scripts use: per-replica forms of the product calls, counters and stage timings, function-level query kernels (the very
  * device functions the path kernels call, on caller-supplied inputs), known-answer self-checks (kz_kat_*: stateless, in the product
  * library, so that what they check IS the product's code), the pass planner as a pure function, and - in development builds of the library only - the hooks that
- * are process-global state (failure injection, growth delay, trace, device aliasing) and the KzTuning words that select kernels of rejected experiments. */
+ * are process-global state (failure injection, growth delay, trace, device aliasing). */
 #ifndef KAZEN_MI355X_DEV_H
 #define KAZEN_MI355X_DEV_H
 #include "kazen_mi355x.h"
@@ -11,14 +11,8 @@
 extern "C" {
 #endif
 
-/* KzTuning.dev*: honoured only by a library built with -DKZ_EXPERIMENTS (kz_build_flags() & KZ_BUILD_EXPERIMENTS); the product
- * library answers a non-zero value with KZ_ERR_UNSUPPORTED (nano-kazen_amd/csrc/variants/experiments/kz_experiments.h holds the kernels). */
-#define KZ_TUNE_BVH2         dev0   /* 1 = per-lane traversal of the BVH2 instead of the quantised BVH4 */
-#define KZ_TUNE_KEY_STACK    dev1   /* 1 = packet kernel without per-lane entry distances, 2 = per-lane kernel with them */
-#define KZ_TUNE_LDS_TOP      dev2   /* n = that many BVH4 packets of the top of the tree staged in LDS (<= 1536) */
-#define KZ_TUNE_LEAF_QUEUE   dev3   /* 2 = bounce / shadow traversal with a decoupled leaf phase (kz_wf_trace_dq) */
-#define KZ_TUNE_LEGACY_TRACE dev4   /* 1 = the non-persistent round-1 traversal launches (kz_wf_extend / kz_wf_shadow) */
-#define KZ_TUNE_MIXED_LAUNCH dev5   /* 1 = one launch for the shadow rays of a bounce and the closest-hit rays of the next */
+/* KzTuning.dev0 .. dev5 are reserved words: the kernels of rejected experiments they selected have been removed (LAB_NOTES 4), and every
+ * build of the library answers the values that selected one with KZ_ERR_UNSUPPORTED (kazen_mi355x.h). */
 
 /* Counters the kernels keep (all optional; zero unless requested with kz_set_stats). */
 typedef struct KzStats {
@@ -177,7 +171,7 @@ int kz_kat_pow4(int32_t spp, int32_t *out4);
 enum { KZ_TABLE_NODES = 0, KZ_TABLE_NODES4 = 1, KZ_TABLE_TRIS = 2, KZ_TABLE_SHADE = 3, KZ_TABLE_CDF = 4, KZ_TABLE_LIGHTS = 5, KZ_TABLE_IL_TRIS = 6, KZ_TABLE_PARAMS = 7 };
 int kz_scene_table(KzScene *scene, int device, int table, void *out, size_t cap, size_t *bytes);
 
-/* How the library was built: bit 0 (KZ_BUILD_EXPERIMENTS) = it contains the kernels of kz_experiments.h. */
+/* How the library was built: bit 0 (KZ_BUILD_EXPERIMENTS) = it is the development variant (-DKZ_EXPERIMENTS), which exports the kz_debug_* hooks. */
 #define KZ_BUILD_EXPERIMENTS 1
 int kz_build_flags(void);
 /* hipMemGetInfo of `device` (what the default state budget of kz_render is derived from). */

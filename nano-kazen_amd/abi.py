@@ -98,10 +98,11 @@ class KzTile(C.Structure):
 
 
 class KzTuning(C.Structure):
+    # dev0 .. dev5: reserved words (kazen_mi355x.h); the values that once selected kernels of rejected experiments are refused with KZ_ERR_UNSUPPORTED
     _fields_ = [("refill", C.c_int32), ("postpone", C.c_int32), ("batch", C.c_int32), ("traceBlocksPerCU", C.c_int32),
-                ("shadeBlocksPerCU", C.c_int32), ("ldsStack", C.c_int32), ("bvh2", C.c_int32), ("packetPrimary", C.c_int32),
-                ("keyStack", C.c_int32), ("ldsTop", C.c_int32), ("filmGather", C.c_int32), ("leafQueue", C.c_int32), ("sppPerPass", C.c_int32), ("legacyTrace", C.c_int32),
-                ("mixedLaunch", C.c_int32), ("streamPriority", C.c_int32)]
+                ("shadeBlocksPerCU", C.c_int32), ("ldsStack", C.c_int32), ("dev0", C.c_int32), ("packetPrimary", C.c_int32),
+                ("dev1", C.c_int32), ("dev2", C.c_int32), ("filmGather", C.c_int32), ("dev3", C.c_int32), ("sppPerPass", C.c_int32), ("dev4", C.c_int32),
+                ("dev5", C.c_int32), ("streamPriority", C.c_int32)]
 
 
 class KzTileDealer(C.Structure):
@@ -200,8 +201,8 @@ class KzError(RuntimeError):
 
 
 def load_dev_library():
-    """The development variant of the library (-DKZ_EXPERIMENTS: the same sources plus the kernels of rejected experiments and the hooks that are process-global
-    state - kz_debug_fail_alloc / grow_delay / trace / alias_devices). Only tests load it; a second copy of the library in one process is a separate world
+    """The development variant of the library (-DKZ_EXPERIMENTS: the same sources plus the hooks that are process-global state - kz_debug_fail_alloc /
+    fail_device / grow_delay / trace / alias_devices). Only tests load it; a second copy of the library in one process is a separate world
     (its own device pools, its own replicas)."""
     return load_library(DEV_LIB_PATH)
 

@@ -14,9 +14,6 @@
 #include "kz_wavefront.h"
 #include "kz_integrators.h"
 #include "kz_plan.h"
-#ifdef KZ_EXPERIMENTS
-#include "variants/experiments/kz_experiments.h"
-#endif
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -134,8 +131,8 @@ void kz_device_release(KzScene *scene) {
 }
 
 // KzTuning -> the kernels' KzTune. Zero = the library default. (The KZ_* environment overrides of ABI v2 / v3 are gone: nothing in the
-// library reads the environment.) Fields that select a kernel of kz_experiments.h are honoured only by a -DKZ_EXPERIMENTS build; the
-// default library refuses them loudly instead of ignoring them.
+// library reads the environment.) dev0 .. dev5 selected the kernels of rejected experiments, which are gone: the values that did are
+// refused loudly instead of ignored.
 static int resolveTune(const KzTuning &t, KzTune &r) {
     auto pick = [](int a, int d) { return a > 0 ? a : d; };
     r = KzTune{};
@@ -143,16 +140,8 @@ static int resolveTune(const KzTuning &t, KzTune &r) {
     r.travBlocksPerCU = std::min(8, pick(t.traceBlocksPerCU, KZ_TRACE_WAVES)); r.shadeBlocksPerCU = std::min(16, pick(t.shadeBlocksPerCU, 0));
     r.ldsStack = pick(t.ldsStack, 16);
     r.packet = pick(t.packetPrimary, 0); r.filmGather = pick(t.filmGather, 0);
-#if defined(KZ_EXPERIMENTS) && defined(KZ_SHADE_SPLIT)
-    r.shadeSplit = KZ_SHADE_SPLIT;          // (development builds only: -DKZ_EXPERIMENTS -DKZ_SHADE_SPLIT=1, profiles/r04b_shade_split)
-#endif
-    r.wide = t.KZ_TUNE_BVH2 ? 0 : 1; r.keyStack = pick(t.KZ_TUNE_KEY_STACK, 0); r.ldsTop = pick(t.KZ_TUNE_LDS_TOP, 0); r.leafQueue = pick(t.KZ_TUNE_LEAF_QUEUE, 0);
-    r.legacyTrace = pick(t.KZ_TUNE_LEGACY_TRACE, 0); r.mixed = pick(t.KZ_TUNE_MIXED_LAUNCH, 0);
-#ifndef KZ_EXPERIMENTS
     if (t.dev0 || t.dev1 > 0 || t.dev2 > 0 || t.dev3 > 1 || t.dev4 > 0 || t.dev5 > 0)
-        return kz_fail(KZ_ERR_UNSUPPORTED, "KzTuning.dev0 .. dev5 (kazen_mi355x_dev.h: bvh2 / keyStack / ldsTop / leafQueue / legacyTrace / mixedLaunch) select kernels of rejected experiments: "
-                                           "this library was built without -DKZ_EXPERIMENTS (kz_build_flags)");
-#endif
+        return kz_fail(KZ_ERR_UNSUPPORTED, "KzTuning.dev0 .. dev5 are reserved: the kernels of rejected experiments they selected (LAB_NOTES 4) have been removed");
     r.ovf = nullptr; r.ovfStride = 0;
     return KZ_OK;
 }
@@ -465,9 +454,6 @@ static int ctxEnsure(PassCtx &c, size_t want, size_t minItems, double graceMs, h
 #endif
     if (rc) return rc;
     KzWf W{};
-    if (KZ_STATE_AOS) {                                             // (development build: two 64-B records per slot laid over arrays 0-3 and 4-7 - not supported by the arena's SoA ranges)
-        return kz_fail(KZ_ERR_UNSUPPORTED, "-DKZ_STATE_AOS=1 predates the growing pass context (round 5): build a revision before it to repeat profiles/r03h_state_layout");
-    }
     W.rayA.p = A.array<float4>(0); W.rayB.p = A.array<float4>(1); W.hit.p = A.array<float4>(2); W.thr.p = A.array<float4>(3);
     W.misc.p = A.array<float4>(4); W.shA.p = A.array<float4>(5); W.shB.p = A.array<float4>(6); W.shL.p = A.array<float4>(7);
     W.smp = A.array<uint4>(8);
@@ -479,112 +465,6 @@ static int ctxEnsure(PassCtx &c, size_t want, size_t minItems, double graceMs, h
     return KZ_OK;
 }
 
-#ifdef KZ_EXPERIMENTS
-// Launch code of the kernels of kz_experiments.h (development builds only): takes over a traversal launch of wfPass when the caller's
-// KzTuning selects one of the rejected experiments. The films stay bit-identical to the product kernels' (tests/test_gpu_configs.py).
-struct KzExpLaunch {
-    KzScene *scene; KzDeviceState *ds; PassCtx *c; hipStream_t stream; KzWf W; KzTune tune; dim3 gTrav; size_t traceLds; int stackBound; bool st; uint32_t items;
-    bool keys = false, dq = false, any = false; size_t ldsX = 0, dqLds = 0, stackBytes = 0; KzTune tuneDq{};
-    int prepare() {
-        const KzParams &P = scene->prm;
-        keys = tune.wide && tune.keyStack == 2;
-        dq = tune.wide && tune.leafQueue == 2;
-        tune.ldsTop = tune.wide ? (int)std::min<size_t>((size_t)std::max(0, tune.ldsTop), std::min<size_t>(scene->nodes4.size(), 1536)) : 0;
-        any = !tune.wide || keys || tune.ldsTop > 0 || dq || tune.legacyTrace || tune.mixed;
-        if (!any) return KZ_OK;
-        stackBytes = (size_t)P.stackDepth * KZ_BLOCK * sizeof(uint32_t);
-        ldsX = (size_t)(tune.ldsStack + 1) * KZ_BLOCK * sizeof(uint32_t) * (keys ? 2 : 1) + (size_t)tune.ldsTop * sizeof(KzNode4);
-        if (ldsX > 64 * 1024) {
-            HIP_TRY(hipFuncSetAttribute((const void *)kz_wf_trace_x<0, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIP_TRY(hipFuncSetAttribute((const void *)kz_wf_trace_x<2, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        }
-        if (dq) {
-            const int dqLS = std::max(2, std::min(tune.ldsStack, std::min(stackBound, 9)));             // 9 rows + queue + results = 19.4 KB per workgroup: 8 per CU
-            dqLds = (size_t)4 * ((size_t)(dqLS + 1) * 64 + 128 + 192 + 2 * KZ_DQ_JOBS) * sizeof(uint32_t);
-            tuneDq = tune; tuneDq.ldsStack = dqLS;
-            const size_t stride = (size_t)gTrav.x * KZ_BLOCK, needOvf = stride * (size_t)std::max(1, stackBound - dqLS);
-            if (needOvf > c->ovfCap) {
-                HIP_TRY(hipStreamSynchronize(stream));
-                if (c->ovf) (void)hipFree(c->ovf);
-                c->ovf = nullptr; c->ovfCap = 0;
-                KZ_ALLOC(&c->ovf, needOvf * sizeof(uint32_t));
-                c->ovfCap = needOvf;
-                tune.ovf = c->ovf;
-            }
-            tuneDq.ovf = c->ovf; tuneDq.ovfStride = (uint32_t)stride;
-            if (items > c->litCap) {
-                HIP_TRY(hipStreamSynchronize(stream));
-                if (c->litQueue) (void)hipFree(c->litQueue);
-                c->litQueue = nullptr; c->litCap = 0;
-                KZ_ALLOC(&c->litQueue, (size_t)items * sizeof(uint32_t));
-                c->litCap = items;
-            }
-        }
-        return KZ_OK;
-    }
-    bool allowsPacket() const { return tune.wide && !tune.legacyTrace; }
-    // the round-2 kernel with its options; MODE 0, 1, 2, 3
-    template <int MODE> void traceX(const uint32_t *q, const uint32_t *cptr, uint32_t cimm, uint32_t *head, const uint32_t *qb, const uint32_t *cb) {
-        const KzParams &P = scene->prm; const dim3 blk(KZ_BLOCK);
-        constexpr int M = MODE;
-        if (tune.wide && tune.ldsTop > 0 && !st && (M == 0 || M == 2)) hipLaunchKernelGGL((kz_wf_trace_x<(M == 0 || M == 2) ? M : 0, false, true, false, true>), gTrav, blk, ldsX, stream, P, ds->T, W, q, cptr, cimm, head, tune, qb, cb);
-        else if (tune.wide && keys && (M == 0 || M == 1)) {
-            if (st) hipLaunchKernelGGL((kz_wf_trace_x<(M == 0 || M == 1) ? M : 0, true, true, true>), gTrav, blk, ldsX, stream, P, ds->T, W, q, cptr, cimm, head, tune, qb, cb);
-            else hipLaunchKernelGGL((kz_wf_trace_x<(M == 0 || M == 1) ? M : 0, false, true, true>), gTrav, blk, ldsX, stream, P, ds->T, W, q, cptr, cimm, head, tune, qb, cb);
-        } else if (tune.wide) {
-            if (st) hipLaunchKernelGGL((kz_wf_trace_x<M, true, true>), gTrav, blk, traceLds, stream, P, ds->T, W, q, cptr, cimm, head, tune, qb, cb);
-            else hipLaunchKernelGGL((kz_wf_trace_x<M, false, true>), gTrav, blk, traceLds, stream, P, ds->T, W, q, cptr, cimm, head, tune, qb, cb);
-        } else {
-            if (st) hipLaunchKernelGGL((kz_wf_trace_x<M, true, false>), gTrav, blk, traceLds, stream, P, ds->T, W, q, cptr, cimm, head, tune, qb, cb);
-            else hipLaunchKernelGGL((kz_wf_trace_x<M, false, false>), gTrav, blk, traceLds, stream, P, ds->T, W, q, cptr, cimm, head, tune, qb, cb);
-        }
-    }
-    // closest-hit launches outside the bounce loop (camera rays, first-hit walk-through) and the lit-ray walk-through
-    bool trace(int mode, const uint32_t *q, const uint32_t *cptr, uint32_t cimm, uint32_t *head, uint32_t *qb, uint32_t *cb) {
-        if (!any) return false;
-        const KzParams &P = scene->prm; const dim3 blk(KZ_BLOCK);
-        if (tune.legacyTrace && (mode == 0 || mode == 1)) {
-            if (mode == 0) { if (st) hipLaunchKernelGGL((kz_wf_extend<true, false>), gTrav, blk, stackBytes, stream, P, ds->T, W, q, cptr, cimm); else hipLaunchKernelGGL((kz_wf_extend<false, false>), gTrav, blk, stackBytes, stream, P, ds->T, W, q, cptr, cimm); }
-            else { if (st) hipLaunchKernelGGL((kz_wf_extend<true, true>), gTrav, blk, stackBytes, stream, P, ds->T, W, q, cptr, cimm); else hipLaunchKernelGGL((kz_wf_extend<false, true>), gTrav, blk, stackBytes, stream, P, ds->T, W, q, cptr, cimm); }
-            return true;
-        }
-        if (mode == 0) { traceX<0>(q, cptr, cimm, head, qb, cb); return true; }
-        if (mode == 1) { traceX<1>(q, cptr, cimm, head, qb, cb); return true; }
-        if (mode == 2) { traceX<2>(q, cptr, cimm, head, qb, cb); return true; }
-        return false;
-    }
-    // the traversal launches of one bounce (shadow rays of this bounce, closest-hit rays of the next)
-    bool bounce(int iter, bool needExtend, uint32_t *nextQ, uint32_t *nextCount, uint32_t *shQ, uint32_t *shCount) {
-        if (!any) return false;
-        const KzParams &P = scene->prm; const dim3 blk(KZ_BLOCK);
-        if (!tune.legacyTrace && tune.mixed && P.nLights > 0 && needExtend) {
-            traceX<3>(nextQ, nextCount, 0u, nextCount + 2, shQ, shCount);
-            (void)stageMark(*c, stream, 1);
-            return true;
-        }
-        if (P.nLights > 0) {
-            if (dq && P.shadowFast) {
-                uint32_t *litCount = W.counts + 4 * 520 + 2 * (iter + 1), *litHead = litCount + 1;
-                if (st) hipLaunchKernelGGL((kz_wf_trace_dq<2, true>), gTrav, blk, dqLds, stream, P, ds->T, W, (const uint32_t *)shQ, (const uint32_t *)shCount, 0u, nextCount + 3, tuneDq, c->litQueue, litCount);
-                else hipLaunchKernelGGL((kz_wf_trace_dq<2, false>), gTrav, blk, dqLds, stream, P, ds->T, W, (const uint32_t *)shQ, (const uint32_t *)shCount, 0u, nextCount + 3, tuneDq, c->litQueue, litCount);
-                traceX<2>(c->litQueue, litCount, 0u, litHead, nullptr, nullptr);      // the few rays that cross an invisible light
-            } else if (tune.legacyTrace) {
-                if (st) hipLaunchKernelGGL(kz_wf_shadow<true>, gTrav, blk, stackBytes, stream, P, ds->T, W, (const uint32_t *)shQ, (const uint32_t *)shCount);
-                else hipLaunchKernelGGL(kz_wf_shadow<false>, gTrav, blk, stackBytes, stream, P, ds->T, W, (const uint32_t *)shQ, (const uint32_t *)shCount);
-            } else traceX<2>(shQ, shCount, 0u, nextCount + 3, nullptr, nullptr);
-        }
-        (void)stageMark(*c, stream, 3);
-        if (needExtend) {
-            if (dq && st) hipLaunchKernelGGL((kz_wf_trace_dq<0, true>), gTrav, blk, dqLds, stream, P, ds->T, W, (const uint32_t *)nextQ, (const uint32_t *)nextCount, 0u, nextCount + 2, tuneDq, (uint32_t *)nullptr, (uint32_t *)nullptr);
-            else if (dq) hipLaunchKernelGGL((kz_wf_trace_dq<0, false>), gTrav, blk, dqLds, stream, P, ds->T, W, (const uint32_t *)nextQ, (const uint32_t *)nextCount, 0u, nextCount + 2, tuneDq, (uint32_t *)nullptr, (uint32_t *)nullptr);
-            else trace(0, nextQ, nextCount, 0u, nextCount + 2, nullptr, nullptr);
-            (void)stageMark(*c, stream, 1);
-        }
-        return true;
-    }
-};
-#endif
-
 // kz_wf_trace instantiations by (mode, stats): the launch code picks from this table instead of a ladder of macros
 typedef void (*KzTraceFn)(KzParams, KzDevTables, KzWf, const uint32_t *, const uint32_t *, uint32_t, uint32_t *, KzTune, uint32_t *, uint32_t *);
 static KzTraceFn traceFn(int mode, bool stats) {
@@ -592,7 +472,17 @@ static KzTraceFn traceFn(int mode, bool stats) {
                                         {kz_wf_trace<2, false>, kz_wf_trace<2, true>}, {nullptr, nullptr}, {kz_wf_trace<4, false>, kz_wf_trace<4, true>}};
     return tab[mode][stats ? 1 : 0];
 }
-
+// ... and the camera-ray kernels by (stats, fix): FIX = the scene has an invisible light, whose first hits are queued for the walk-through
+typedef void (*KzListFn)(KzParams, KzDevTables, KzWf, const uint32_t *, uint32_t, uint32_t, const uint2 *, const uint2 *, uint32_t *, uint32_t *, uint32_t *, uint32_t *);
+static KzListFn listFn(bool stats, bool fix) {
+    static const KzListFn tab[2][2] = {{kz_wf_trace_list<false, false>, kz_wf_trace_list<false, true>}, {kz_wf_trace_list<true, false>, kz_wf_trace_list<true, true>}};
+    return tab[stats ? 1 : 0][fix ? 1 : 0];
+}
+typedef void (*KzPacketFn)(KzParams, KzDevTables, KzWf, const uint32_t *, const uint32_t *, uint32_t, uint32_t *, int, uint32_t *, uint32_t *);
+static KzPacketFn packetFn(bool stats, bool fix) {
+    static const KzPacketFn tab[2][2] = {{kz_wf_trace_packet<false, false>, kz_wf_trace_packet<false, true>}, {kz_wf_trace_packet<true, false>, kz_wf_trace_packet<true, true>}};
+    return tab[stats ? 1 : 0][fix ? 1 : 0];
+}
 
 // Beam lists for pixels [p0, p0 + n) of the current pixel list: launched on `stream` (the call's stream) unless that range of this list has been
 // handed to the kernel before; the kernel itself skips pixels that already have a list (from another tile set or chunk). evBeam / beamSeq tell the
@@ -630,9 +520,9 @@ static int ensureBeams(KzScene *scene, KzDeviceState *ds, hipStream_t stream, ui
 // The global overflow area of the traversal stacks (entries beyond tune.ldsStack per lane, sized from the builder's worst-case bound) of one pass context.
 static int ensureOverflow(KzScene *scene, KzDeviceState *ds, PassCtx &c, const KzTune &tune, hipStream_t stream) {
     const KzParams &P = scene->prm;
-    const int stackBound = std::max(tune.wide ? P.stackBound4 : P.stackDepth, 2);
+    const int stackBound = std::max(P.stackBound4, 2);
     const int ldsStack = std::max(2, std::min(tune.ldsStack, stackBound));
-    const size_t stride = (size_t)(ds->numCU * tune.travBlocksPerCU) * KZ_BLOCK, needOvf = stride * (size_t)std::max(1, stackBound - ldsStack) * 3;      // (x 3: the key stack of kz_experiments.h; the shadow kernels of a small pass on the side stream, wfPass)
+    const size_t stride = (size_t)(ds->numCU * tune.travBlocksPerCU) * KZ_BLOCK, needOvf = stride * (size_t)std::max(1, stackBound - ldsStack) * 3;      // (x 3: part 0 the pass's own stream, part 1 spare, part 2 the shadow kernels of a small pass on the side stream, wfPass)
     if (needOvf > c.ovfCap) {
         HIP_TRY(hipStreamSynchronize(stream));
         if (c.ovf) (void)hipFree(c.ovf);
@@ -651,91 +541,15 @@ static int ensureOverflow(KzScene *scene, KzDeviceState *ds, PassCtx &c, const K
 #define KZ_BESIDE_ITEMS_IN_FLIGHT (1u << 24)      // ... with passes in flight or a dealer (renderOn)
 #endif
 
-// One pass of the wavefront pipeline for normals / ao / path_mats (kz_integrators.h). The camera stage is path_mis's (generate, beams + list kernel, packet
-// or per-lane traversal) run with a copy of the parameters that names no invisible light: none of the three walks through a light (H6 is path_mis's alone),
-// so a first hit on such a light is kept and an occlusion ray is blocked by it. Then:
-//   normals    kz_wf_normals                                                    (no bounce state)
-//   ao         kz_wf_ao -> kz_wf_trace<4> on the occlusion rays                 (any hit, every triangle blocks)
-//   path_mats  { kz_wf_mats(iter) -> kz_wf_trace<0> } until the path queue is empty or 512 bounces are done; the host reads the survivor count back
-//              after every 4th bounce (one stream synchronisation per 4 bounces), so a pass launches 2 + 2 x (bounces rounded up to 4) kernels after the camera's.
-static int wfPassIntegrator(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t stream, const uint32_t *pixList, uint32_t sBegin, uint32_t Sp, uint32_t items,
-                            KzTune tune, bool beams) {
-    KzParams P = scene->prm;
-    P.anyInvisibleLight = 0; P.nIlTris = 0; P.shadowFast = 1;
-    KzWf W = c.wf;
-    W.outJx = c.plane[0]; W.outJy = c.plane[1]; W.outR = c.plane[2]; W.outG = c.plane[3]; W.outB = c.plane[4]; W.stats = ds->stats;
-    const bool st = ds->statsOn;
-    const dim3 blk(KZ_BLOCK);
-    const dim3 gTrav((unsigned)(ds->numCU * tune.travBlocksPerCU)), gShade((unsigned)(ds->numCU * (tune.shadeBlocksPerCU > 0 ? tune.shadeBlocksPerCU : 8)));
-    const dim3 gPacket((unsigned)(ds->numCU * 8));
-    const int stackBound = std::max(tune.wide ? P.stackBound4 : P.stackDepth, 2);
-    tune.ldsStack = std::max(2, std::min(tune.ldsStack, stackBound));
-    const size_t traceLds = (size_t)(tune.ldsStack + 1) * KZ_BLOCK * sizeof(uint32_t);
-    { const int rc_ = ensureOverflow(scene, ds, c, tune, stream); if (rc_) return rc_; tune.ovf = c.ovf; tune.ovfStride = (uint32_t)((size_t)gTrav.x * KZ_BLOCK); }
-    c.stageUsed = 0;
-    HIP_TRY(hipMemsetAsync(W.counts, 0, 8 * 520 * sizeof(uint32_t), stream));
-    { int rc_ = stageMark(c, stream, -1); if (rc_) return rc_; }
-    hipLaunchKernelGGL(kz_wf_generate, dim3((items + KZ_BLOCK - 1) / KZ_BLOCK), blk, 0, stream, P, ds->T, W, pixList, items, Sp, sBegin);
-    { int rc_ = stageMark(c, stream, 0); if (rc_) return rc_; }
-    auto trace = [&](int mode, const uint32_t *q, const uint32_t *cptr, uint32_t cimm, uint32_t *head) {
-        KzTune t = tune;
-        if (t.batch <= 0) t.batch = 128;
-        if (t.refill <= 0) t.refill = mode == 4 ? 32 : 40;
-        hipLaunchKernelGGL(traceFn(mode, st), gTrav, blk, traceLds, stream, P, ds->T, W, q, cptr, cimm, head, t, (uint32_t *)nullptr, (uint32_t *)nullptr);
-    };
-    const bool packet = tune.packet != 1 && P.stackBound4 <= 128;
-    if (packet && beams) {
-        uint32_t *fbQ = W.queue[0], *fbCount = W.counts + 8 * 520 - 8, *fbHead = fbCount + 1;
-        const dim3 gList((items + KZ_BLOCK - 1) / KZ_BLOCK);
-        if (st) hipLaunchKernelGGL((kz_wf_trace_list<true, false>), gList, blk, 0, stream, P, ds->T, W, pixList, items, Sp, (const uint2 *)ds->beamEntries, (const uint2 *)ds->beamCount, fbQ, fbCount, W.queue[2], W.counts + 0);
-        else hipLaunchKernelGGL((kz_wf_trace_list<false, false>), gList, blk, 0, stream, P, ds->T, W, pixList, items, Sp, (const uint2 *)ds->beamEntries, (const uint2 *)ds->beamCount, fbQ, fbCount, W.queue[2], W.counts + 0);
-        if (st) hipLaunchKernelGGL((kz_wf_trace_packet<true, false>), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)fbQ, (const uint32_t *)fbCount, 0u, fbHead, 8, W.queue[2], W.counts + 0);
-        else hipLaunchKernelGGL((kz_wf_trace_packet<false, false>), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)fbQ, (const uint32_t *)fbCount, 0u, fbHead, 8, W.queue[2], W.counts + 0);
-    } else if (packet) {
-        if (st) hipLaunchKernelGGL((kz_wf_trace_packet<true, false>), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)nullptr, (const uint32_t *)nullptr, items, W.counts + 2, 8, W.queue[2], W.counts + 0);
-        else hipLaunchKernelGGL((kz_wf_trace_packet<false, false>), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)nullptr, (const uint32_t *)nullptr, items, W.counts + 2, 8, W.queue[2], W.counts + 0);
-    } else trace(0, nullptr, nullptr, items, W.counts + 2);
-    { int rc_ = stageMark(c, stream, 5); if (rc_) return rc_; }
-    if (P.integrator == KZ_INTEGRATOR_NORMALS) {
-        hipLaunchKernelGGL(kz_wf_normals, gShade, blk, 0, stream, P, ds->T, W, items);
-        { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
-    } else if (P.integrator == KZ_INTEGRATOR_AO) {
-        uint32_t *shQ = W.queue[2], *shCount = W.counts + 5;
-        hipLaunchKernelGGL(kz_wf_ao, gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, items, shQ, shCount);
-        { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
-        trace(4, shQ, shCount, 0u, W.counts + 7);
-        { int rc_ = stageMark(c, stream, 3); if (rc_) return rc_; }
-    } else {
-        const int xsel = P.bsdfExt == 0 ? 0 : (P.bsdfExt == KZ_X_MODELS ? KZ_X_MODELS : KZ_X_MATS);
-        const uint32_t *cur = nullptr, *curCount = nullptr;
-        for (int iter = 0; iter < P.maxDepth; ++iter) {
-            uint32_t *nextQ = W.queue[iter & 1], *nextCount = W.counts + 4 * (iter + 1);
-#define KZ_MATS(EX) hipLaunchKernelGGL((kz_wf_mats<EX>), gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, iter, cur, curCount, cur ? 0u : items, nextQ, nextCount)
-            if (xsel == KZ_X_MATS) KZ_MATS(KZ_X_MATS); else if (xsel) KZ_MATS(KZ_X_MODELS); else KZ_MATS(0);
-#undef KZ_MATS
-            { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
-            if (iter == P.maxDepth - 1) break;                    // (the ray of the last bounce is not traced: H15)
-            if ((iter & 3) == 3) {                                // the queue runs dry long before the cap: stop launching when it has
-                uint32_t left = 0;
-                HIP_TRY(hipMemcpyAsync(&left, nextCount, sizeof left, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                if (left == 0) break;
-            }
-            trace(0, nextQ, nextCount, 0u, nextCount + 2);
-            { int rc_ = stageMark(c, stream, 1); if (rc_) return rc_; }
-            cur = nextQ; curCount = nextCount;
-        }
-    }
-    if (st) hipLaunchKernelGGL(kz_wf_count, dim3((items + KZ_BLOCK - 1) / KZ_BLOCK), blk, 0, stream, W, items);
-    HIP_TRY(hipGetLastError());
-    return KZ_OK;
-}
-
 // One pass of the wavefront pipeline over `items` = nPixPass x Sp (pixel, sample) items: pixels pixList[0 .. nPixPass), sample indices
-// [sBegin, sBegin + Sp). Every launch goes to `stream`; queue counts stay on the device.
+// [sBegin, sBegin + Sp). Every launch goes to `stream`; queue counts stay on the device. All four integrators share the camera stage (generate, beams + list
+// kernel, packet or per-lane traversal, first-hit walk-through); then path_mis runs its bounce loop and normals / ao / path_mats their tail (kz_integrators.h).
+// The three others see a copy of the parameters that names no invisible light: none of them walks through a light (H6 is path_mis's alone), so a first hit
+// on such a light is kept and an occlusion ray is blocked by it.
 static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t stream, const uint32_t *pixList, uint32_t p0, uint32_t nPixPass, uint32_t sBegin, uint32_t Sp, uint32_t items, KzTune tune, bool beams, int shadowBeside) {
-    if (scene->prm.integrator != KZ_INTEGRATOR_PATH_MIS) return wfPassIntegrator(scene, ds, c, stream, pixList, sBegin, Sp, items, tune, beams);
-    const KzParams &P = scene->prm;
+    const bool mis = scene->prm.integrator == KZ_INTEGRATOR_PATH_MIS;
+    KzParams P = scene->prm;
+    if (!mis) { P.anyInvisibleLight = 0; P.nIlTris = 0; P.shadowFast = 1; }
     KzWf W = c.wf;
     W.outJx = c.plane[0]; W.outJy = c.plane[1]; W.outR = c.plane[2]; W.outG = c.plane[3]; W.outB = c.plane[4]; W.stats = ds->stats;
     const bool st = ds->statsOn;
@@ -743,12 +557,13 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
     // shade: the lean variant runs 4 workgroups per CU at once (its launch bounds), so the default grid is exactly those, each looping over
     // its share: with 6 per CU the kernel ran 1.5 rounds, the second with half the CUs idle (same-call sweep, profiles/r02h_shade: shade alone
     // 24.1 ms at 6, 23.0 at 4, 22.6 at 8, 22.3 at 12 - and with two passes in flight the small grid leaves the most room for the other pass:
-    // 1246 Msamples/s at 4 against 1214-1218 at 6 / 8 / 12). The EXT variant (3 resident) shows no preference on C3 and stays at 6.
-    const int shadeBlocks = tune.shadeBlocksPerCU > 0 ? tune.shadeBlocksPerCU : (P.bsdfExt ? 6 : KZ_SHADE_WAVES);
+    // 1246 Msamples/s at 4 against 1214-1218 at 6 / 8 / 12). The EXT variant (3 resident) shows no preference on C3 and stays at 6. The kernels of the
+    // other integrators run 8 per CU.
+    const int shadeBlocks = tune.shadeBlocksPerCU > 0 ? tune.shadeBlocksPerCU : !mis ? 8 : (P.bsdfExt ? 6 : KZ_SHADE_WAVES);
     const dim3 gTrav((unsigned)(ds->numCU * tune.travBlocksPerCU)), gShade((unsigned)(ds->numCU * shadeBlocks));
     const dim3 gPacket((unsigned)(ds->numCU * 8));                  // the packet kernel is compiled for 8 waves per SIMD whatever KZ_TRACE_WAVES is
     // stack: tune.ldsStack entries per lane in LDS, the rest of the worst case (known from the builder) in a global overflow area
-    const int stackBound = std::max(tune.wide ? P.stackBound4 : P.stackDepth, 2);
+    const int stackBound = std::max(P.stackBound4, 2);
     tune.ldsStack = std::max(2, std::min(tune.ldsStack, stackBound));
     const size_t traceLds = (size_t)(tune.ldsStack + 1) * KZ_BLOCK * sizeof(uint32_t);      // + one scratch slot per lane (branch-free pushes)
     {
@@ -762,18 +577,10 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
     { int rc_ = stageMark(c, stream, -1); if (rc_) return rc_; }
     hipLaunchKernelGGL(kz_wf_generate, dim3((items + KZ_BLOCK - 1) / KZ_BLOCK), blk, 0, stream, P, ds->T, W, pixList, items, Sp, sBegin);
     { int rc_ = stageMark(c, stream, 0); if (rc_) return rc_; }
-    if (maxDepth <= 0) return KZ_OK;           // Li returns 0 before the loop contributes anything
-#ifdef KZ_EXPERIMENTS
-    KzTune tuneX = tune; if (tuneX.batch <= 0) tuneX.batch = 128; if (tuneX.refill <= 0) tuneX.refill = 40;
-    KzExpLaunch X{scene, ds, &c, stream, W, tuneX, gTrav, traceLds, stackBound, st, items};
-    if (int rc_ = X.prepare()) return rc_;
-#endif
+    if (mis && maxDepth <= 0) return KZ_OK;           // Li returns 0 before the loop contributes anything
     // mode 0 / 1 / 2 / 4 of kz_wf_trace on queue q (nullptr: identity) of *cptr (nullptr: cimm) entries
     const size_t ovfPart = (size_t)tune.ovfStride * (size_t)std::max(1, stackBound - tune.ldsStack);
     auto trace = [&](int mode, const uint32_t *q, const uint32_t *cptr, uint32_t cimm, uint32_t *head, uint32_t *qb, uint32_t *cb, hipStream_t on = nullptr) {
-#ifdef KZ_EXPERIMENTS
-        if (X.trace(mode, q, cptr, cimm, head, qb, cb)) return;
-#endif
         KzTune t = tune;
         const bool side = on != nullptr;                 // (a launch beside the pass's own stream walks its own part of the overflow area)
         if (side) t.ovf = tune.ovf + 2 * ovfPart; else on = stream;
@@ -786,133 +593,111 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
     };
     // camera rays: pixel beams + per-sample triangle tests (kz_wf_beam / kz_wf_trace_list), the wave-level packet traversal
     // (kz_wf_trace_packet) for what the beams cannot take, or the per-lane kernel on request
-    bool packet = tune.packet != 1 && P.stackBound4 <= 128;
-#ifdef KZ_EXPERIMENTS
-    if (!X.allowsPacket()) packet = false;
-#endif
-#define KZ_PACKET(ST, FX, q, cptr, cimm, headp) hipLaunchKernelGGL((kz_wf_trace_packet<ST, FX>), gPacket, blk, 0, stream, P, ds->T, W, q, cptr, cimm, headp, 8, W.queue[2], W.counts + 0)
-#define KZ_PACKET4(q, cptr, cimm, headp) do { if (P.anyInvisibleLight) { if (st) KZ_PACKET(true, true, q, cptr, cimm, headp); else KZ_PACKET(false, true, q, cptr, cimm, headp); } \
-                                              else { if (st) KZ_PACKET(true, false, q, cptr, cimm, headp); else KZ_PACKET(false, false, q, cptr, cimm, headp); } } while (0)
+    const bool packet = tune.packet != 1 && P.stackBound4 <= 128, fix = P.anyInvisibleLight != 0;
     if (packet && beams) {
         // (the lists of this pass's pixels were handed to kz_wf_beam on the call's stream - ensureBeams - and this stream has waited for it)
-        const uint2 *lstEntries = ds->beamEntries, *lstHeads = ds->beamCount;
         uint32_t *fbQ = W.queue[0], *fbCount = W.counts + 8 * 520 - 8, *fbHead = fbCount + 1;      // rays of pixels whose list overflowed: the packet kernel's
-        const dim3 gList((items + KZ_BLOCK - 1) / KZ_BLOCK);
-#define KZ_LIST(ST, FX) hipLaunchKernelGGL((kz_wf_trace_list<ST, FX>), gList, blk, 0, stream, P, ds->T, W, pixList, items, Sp, lstEntries, lstHeads, fbQ, fbCount, W.queue[2], W.counts + 0)
-        if (P.anyInvisibleLight) { if (st) KZ_LIST(true, true); else KZ_LIST(false, true); }
-        else { if (st) KZ_LIST(true, false); else KZ_LIST(false, false); }
-#undef KZ_LIST
-        KZ_PACKET4((const uint32_t *)fbQ, (const uint32_t *)fbCount, 0u, fbHead);
+        hipLaunchKernelGGL(listFn(st, fix), dim3((items + KZ_BLOCK - 1) / KZ_BLOCK), blk, 0, stream, P, ds->T, W, pixList, items, Sp, (const uint2 *)ds->beamEntries, (const uint2 *)ds->beamCount,
+                           fbQ, fbCount, W.queue[2], W.counts + 0);
+        hipLaunchKernelGGL(packetFn(st, fix), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)fbQ, (const uint32_t *)fbCount, 0u, fbHead, 8, W.queue[2], W.counts + 0);
     } else if (packet) {
         // (scenes with an invisible light: the epilogue queues the first hits on such a light for the walk-through launch below)
-        KZ_PACKET4((const uint32_t *)nullptr, (const uint32_t *)nullptr, items, W.counts + 2);
+        hipLaunchKernelGGL(packetFn(st, fix), gPacket, blk, 0, stream, P, ds->T, W, (const uint32_t *)nullptr, (const uint32_t *)nullptr, items, W.counts + 2, 8, W.queue[2], W.counts + 0);
     } else {
         trace(0, nullptr, nullptr, items, W.counts + 2, nullptr, nullptr);
-        if (P.anyInvisibleLight) hipLaunchKernelGGL(kz_wf_primary_fix, gShade, blk, 0, stream, P, ds->T, W, items, W.queue[2], W.counts + 0);
+        if (fix) hipLaunchKernelGGL(kz_wf_primary_fix, gShade, blk, 0, stream, P, ds->T, W, items, W.queue[2], W.counts + 0);
     }
-#undef KZ_PACKET4
-#undef KZ_PACKET
-    if (P.anyInvisibleLight) trace(1, W.queue[2], W.counts + 0, 0u, W.counts + 3, nullptr, nullptr);      // H6 walk-through of the first hit
+    if (fix) trace(1, W.queue[2], W.counts + 0, 0u, W.counts + 3, nullptr, nullptr);      // H6 walk-through of the first hit
     { int rc_ = stageMark(c, stream, 5); if (rc_) return rc_; }
     const uint32_t *cur = nullptr, *curCount = nullptr;
-#ifdef KZ_SHADE_CONST_ARGS
-    int shadeArgSlot = 0;
-    for (int i = 0; i < KZ_MAX_PASSES_IN_FLIGHT; ++i) if (ds->ctx[i] == &c) shadeArgSlot = i;
-    { KzShadeArgs a{P, ds->T, W}; HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_kzShadeArgs), &a, sizeof a, (size_t)shadeArgSlot * sizeof a, hipMemcpyHostToDevice, stream)); }
-#endif
-    const bool split = tune.shadeSplit != 0;
-    const dim3 gClassify((unsigned)(ds->numCU * 8));
-    // A pass of a small job (C1: 1 M items on a chip of 524 288 lanes) is a chain of ~25 dependent launches, each of which lasts as long as its slowest ray
-    // whatever the number of rays: there the shadow rays of a bounce run BESIDE its closest-hit rays (the context's side stream) instead of in front of them
-    // (C1 2.47 -> 2.03 ms; the gain fades with the pass size: -4 .. -6 % at 2^22 - 2^23 items of C3 / C4-like scenes, -1 % at 2^25, nothing either way at 2^27 - where the q1 asset still gains 7 %, so the rule ends there: profiles/r06v_shadow_beside).
-    // A LARGE pass is another matter: on C4 each kernel saturates the VALUs by itself and sharing the chip costs 1 % (bench 1 798 / 1 812 one stream, 1 788 / 1 782
-    // beside) - but a scene whose shadow rays are short-lived (the reference's own q1 asset: an object on a backdrop under three lights, shadow kernel at 0.67 VALU
-    // busy) gains 6 - 10 % at EVERY pass size, all 22 scene files of the reference do. Nothing known at upload tells the two kinds apart, so renderOn MEASURES it
-    // (one large pass each way per replica) and passes 1 or 2 down here; 0 reaches this function for small passes only. The film is the same bits either way.
-    bool beside = !split && P.nLights > 0 && maxDepth > 1 && (shadowBeside == 2 || (shadowBeside == 0 && items <= KZ_BESIDE_ITEMS));
-#ifdef KZ_EXPERIMENTS
-    if (X.any) beside = false;              // (an experiment kernel of kz_experiments.h is selected: one stream)
-#endif
-    ds->lastInfo.shadowBeside = beside ? 1u : 0u;      // (what the last pass did: kz_last_pass_info)
-    if (beside && !c.side) {
-        HIP_TRY(hipStreamCreateWithFlags(&c.side, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&c.evFork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c.evJoin, hipEventDisableTiming));
-    }
-    for (int iter = 0; iter < maxDepth; ++iter) {
-        // One kernel per bounce: the path queues ping-pong (W.queue[iter & 1] is written, the other one read). Two kernels (tune.shadeSplit): kz_wf_classify
-        // reads the path queue and writes the survivors to W.queue[0]; kz_wf_shade_b reads those and writes the next path queue to W.queue[1], which
-        // the classification has finished reading by then (one stream).
-        uint32_t *nextQ = split ? W.queue[1] : W.queue[iter & 1], *nextCount = W.counts + 4 * (iter + 1), *shQ = W.queue[2], *shCount = W.counts + 4 * (iter + 1) + 1;
-#ifdef KZ_EXPERIMENTS
-        if (split) {
-            uint32_t *svQ = W.queue[0], *svCount = W.counts + 6 * 520 + (iter + 1);
-#define KZ_SHADE2(ST, EX) do { hipLaunchKernelGGL((kz_wf_classify<ST, EX>), gClassify, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, iter, cur, curCount, items, svQ, svCount); \
-                               hipLaunchKernelGGL((kz_wf_shade_b<ST, EX>), gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, iter, (const uint32_t *)svQ, (const uint32_t *)svCount, nextQ, nextCount, shQ, shCount); } while (0)
-            if (st) { if (P.bsdfExt) KZ_SHADE2(true, KZ_X_ALL); else KZ_SHADE2(true, 0); }
-            else { if (P.bsdfExt) KZ_SHADE2(false, KZ_X_ALL); else KZ_SHADE2(false, 0); }
-#undef KZ_SHADE2
-        } else
-#endif
-        {
-#ifdef KZ_SHADE_CONST_ARGS
-#define KZ_SHADE(ST, EX) hipLaunchKernelGGL((kz_wf_shade<ST, EX>), gShade, blk, 0, stream, shadeArgSlot, pixList, Sp, sBegin, iter, cur, curCount, items, nextQ, nextCount, shQ, shCount)
-#else
+    if (P.integrator == KZ_INTEGRATOR_NORMALS) {
+        //   normals    kz_wf_normals                                                    (no bounce state)
+        hipLaunchKernelGGL(kz_wf_normals, gShade, blk, 0, stream, P, ds->T, W, items);
+        { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
+    } else if (P.integrator == KZ_INTEGRATOR_AO) {
+        //   ao         kz_wf_ao -> kz_wf_trace<4> on the occlusion rays                 (any hit, every triangle blocks)
+        uint32_t *shQ = W.queue[2], *shCount = W.counts + 5;
+        hipLaunchKernelGGL(kz_wf_ao, gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, items, shQ, shCount);
+        { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
+        trace(4, shQ, shCount, 0u, W.counts + 7, nullptr, nullptr);
+        { int rc_ = stageMark(c, stream, 3); if (rc_) return rc_; }
+    } else if (!mis) {
+        //   path_mats  { kz_wf_mats(iter) -> kz_wf_trace<0> } until the path queue is empty or 512 bounces are done; the host reads the survivor count back
+        //              after every 4th bounce (one stream synchronisation per 4 bounces), so a pass launches 2 + 2 x (bounces rounded up to 4) kernels after the camera's.
+        const int xsel = P.bsdfExt == 0 ? 0 : (P.bsdfExt == KZ_X_MODELS ? KZ_X_MODELS : KZ_X_MATS);
+        for (int iter = 0; iter < maxDepth; ++iter) {
+            uint32_t *nextQ = W.queue[iter & 1], *nextCount = W.counts + 4 * (iter + 1);
+#define KZ_MATS(EX) hipLaunchKernelGGL((kz_wf_mats<EX>), gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, iter, cur, curCount, cur ? 0u : items, nextQ, nextCount)
+            if (xsel == KZ_X_MATS) KZ_MATS(KZ_X_MATS); else if (xsel) KZ_MATS(KZ_X_MODELS); else KZ_MATS(0);
+#undef KZ_MATS
+            { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
+            if (iter == maxDepth - 1) break;                      // (the ray of the last bounce is not traced: H15)
+            if ((iter & 3) == 3) {                                // the queue runs dry long before the cap: stop launching when it has
+                uint32_t left = 0;
+                HIP_TRY(hipMemcpyAsync(&left, nextCount, sizeof left, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                if (left == 0) break;
+            }
+            trace(0, nextQ, nextCount, 0u, nextCount + 2, nullptr, nullptr);
+            { int rc_ = stageMark(c, stream, 1); if (rc_) return rc_; }
+            cur = nextQ; curCount = nextCount;
+        }
+    } else {
+        // A pass of a small job (C1: 1 M items on a chip of 524 288 lanes) is a chain of ~25 dependent launches, each of which lasts as long as its slowest ray
+        // whatever the number of rays: there the shadow rays of a bounce run BESIDE its closest-hit rays (the context's side stream) instead of in front of them
+        // (C1 2.47 -> 2.03 ms; the gain fades with the pass size: -4 .. -6 % at 2^22 - 2^23 items of C3 / C4-like scenes, -1 % at 2^25, nothing either way at 2^27 - where the q1 asset still gains 7 %, so the rule ends there: profiles/r06v_shadow_beside).
+        // A LARGE pass is another matter: on C4 each kernel saturates the VALUs by itself and sharing the chip costs 1 % (bench 1 798 / 1 812 one stream, 1 788 / 1 782
+        // beside) - but a scene whose shadow rays are short-lived (the reference's own q1 asset: an object on a backdrop under three lights, shadow kernel at 0.67 VALU
+        // busy) gains 6 - 10 % at EVERY pass size, all 22 scene files of the reference do. Nothing known at upload tells the two kinds apart, so renderOn MEASURES it
+        // (one large pass each way per replica) and passes 1 or 2 down here; 0 reaches this function for small passes only. The film is the same bits either way.
+        const bool beside = P.nLights > 0 && maxDepth > 1 && (shadowBeside == 2 || (shadowBeside == 0 && items <= KZ_BESIDE_ITEMS));
+        ds->lastInfo.shadowBeside = beside ? 1u : 0u;      // (what the last pass did: kz_last_pass_info)
+        if (beside && !c.side) {
+            HIP_TRY(hipStreamCreateWithFlags(&c.side, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&c.evFork, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&c.evJoin, hipEventDisableTiming));
+        }
+        for (int iter = 0; iter < maxDepth; ++iter) {
+            // one kernel per bounce: the path queues ping-pong (W.queue[iter & 1] is written, the other one read)
+            uint32_t *nextQ = W.queue[iter & 1], *nextCount = W.counts + 4 * (iter + 1), *shQ = W.queue[2], *shCount = W.counts + 4 * (iter + 1) + 1;
 #define KZ_SHADE(ST, EX) hipLaunchKernelGGL((kz_wf_shade<ST, EX>), gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, iter, cur, curCount, items, nextQ, nextCount, shQ, shCount)
-#endif
             // the kernel compiled for what the scene's BSDF rows need (KzParams::bsdfExt): nothing beyond diffuse / kiss; other models only (four workgroups per CU,
             // no texture machinery); everything (textures, normal maps)
             const int xsel = P.bsdfExt == 0 ? 0 : (P.bsdfExt == KZ_X_MODELS ? KZ_X_MODELS : KZ_X_ALL);
             if (st) { if (xsel == KZ_X_ALL) KZ_SHADE(true, KZ_X_ALL); else if (xsel) KZ_SHADE(true, KZ_X_MODELS); else KZ_SHADE(true, 0); }
             else { if (xsel == KZ_X_ALL) KZ_SHADE(false, KZ_X_ALL); else if (xsel) KZ_SHADE(false, KZ_X_MODELS); else KZ_SHADE(false, 0); }
 #undef KZ_SHADE
+            const bool needExtend = iter < maxDepth - 1 || P.bgPresent;
+            { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
+            // `beside` (above): this bounce's shadow rays go to the context's side stream and run beside its closest-hit rays; the next shade
+            // waits for both. (What the two kernels write is disjoint: the shadow kernels add to the sample sums and use the path queue the shade has just
+            // consumed; the closest-hit kernel stores hit records and reads the other path queue.)
+            hipStream_t shOn = nullptr;
+            if (beside && needExtend) {
+                HIP_TRY(hipEventRecord(c.evFork, stream));
+                HIP_TRY(hipStreamWaitEvent(c.side, c.evFork, 0));
+                shOn = c.side;
+            }
+            if (P.nLights > 0) {
+                if (P.shadowFast) {
+                    // any-hit kernel without the walk-through machinery; the (rare) rays whose segment crosses an invisible-light triangle go to a
+                    // queue - the ping-pong path queue this bounce's shade has just consumed - and are walked through by the general kernel
+                    uint32_t *litQ = W.queue[(iter & 1) ^ 1], *litCount = W.counts + 4 * 520 + 2 * (iter + 1), *litHead = litCount + 1;
+                    trace(4, shQ, shCount, 0u, nextCount + 3, litQ, litCount, shOn);
+                    if (P.anyInvisibleLight) trace(2, litQ, litCount, 0u, litHead, nullptr, nullptr, shOn);
+                } else trace(2, shQ, shCount, 0u, nextCount + 3, nullptr, nullptr, shOn);
+            }
+            if (shOn) HIP_TRY(hipEventRecord(c.evJoin, c.side));
+            { int rc_ = stageMark(c, stream, 3); if (rc_) return rc_; }
+            if (needExtend) {
+                trace(0, nextQ, nextCount, 0u, nextCount + 2, nullptr, nullptr);
+                if (shOn) HIP_TRY(hipStreamWaitEvent(stream, c.evJoin, 0));          // (the stage clock then shows the pair under "trace_bounce" and nothing under "trace_shadow")
+                int rc_ = stageMark(c, stream, 1); if (rc_) return rc_;
+            }
+            cur = nextQ; curCount = nextCount;
         }
-        const bool lastIter = iter == maxDepth - 1;
-        const bool needExtend = !lastIter || P.bgPresent;
-#ifdef KZ_SORT_EXPERIMENT
-        const uint32_t *trQ = nextQ, *trShQ = shQ;            // what the traversal launches read
-        if (g_sortExp.on) {
-            if (int rc_ = g_sortExp.ensure(scene, c.wfCap)) return rc_;
-            uint32_t nB = 0, nS = 0;
-            if (needExtend) { if (int rc_ = g_sortExp.sort(stream, W, 0, nextQ, nextCount, 0, &nB)) return rc_; trQ = g_sortExp.qOut[0]; }
-            if (P.nLights > 0) { if (int rc_ = g_sortExp.sort(stream, W, 1, shQ, shCount, 1, &nS)) return rc_; trShQ = g_sortExp.qOut[1]; }
-            if (iter == maxDepth - 1) { std::fprintf(stderr, "sortexp: bits %d dir %d: sorts of this pass %.3f ms\n", g_sortExp.bits, g_sortExp.useDir, g_sortExp.sortMs); g_sortExp.sortMs = 0; }
-        }
-#else
-        const uint32_t *trQ = nextQ, *trShQ = shQ;
-#endif
-        { int rc_ = stageMark(c, stream, 2); if (rc_) return rc_; }
-#ifdef KZ_EXPERIMENTS
-        if (X.bounce(iter, needExtend, nextQ, nextCount, shQ, shCount)) { cur = nextQ; curCount = nextCount; continue; }
-#endif
-        // `beside` (above): this bounce's shadow rays go to the context's side stream and run beside its closest-hit rays; the next shade
-        // waits for both. (What the two kernels write is disjoint: the shadow kernels add to the sample sums and use the path queue the shade has just
-        // consumed; the closest-hit kernel stores hit records and reads the other path queue.)
-        hipStream_t shOn = nullptr;
-        if (beside && needExtend) {
-            HIP_TRY(hipEventRecord(c.evFork, stream));
-            HIP_TRY(hipStreamWaitEvent(c.side, c.evFork, 0));
-            shOn = c.side;
-        }
-        if (P.nLights > 0) {
-            if (P.shadowFast) {
-                // any-hit kernel without the walk-through machinery; the (rare) rays whose segment crosses an invisible-light triangle go to a
-                // queue - the ping-pong path queue this bounce's shade has just consumed - and are walked through by the general kernel
-                uint32_t *litQ = split ? W.queue[0] : W.queue[(iter & 1) ^ 1], *litCount = W.counts + 4 * 520 + 2 * (iter + 1), *litHead = litCount + 1;
-                trace(4, trShQ, shCount, 0u, nextCount + 3, litQ, litCount, shOn);
-                if (P.anyInvisibleLight) trace(2, litQ, litCount, 0u, litHead, nullptr, nullptr, shOn);
-            } else trace(2, trShQ, shCount, 0u, nextCount + 3, nullptr, nullptr, shOn);
-        }
-        if (shOn) HIP_TRY(hipEventRecord(c.evJoin, c.side));
-        { int rc_ = stageMark(c, stream, 3); if (rc_) return rc_; }
-        if (needExtend) {
-            trace(0, trQ, nextCount, 0u, nextCount + 2, nullptr, nullptr);
-            if (shOn) HIP_TRY(hipStreamWaitEvent(stream, c.evJoin, 0));          // (the stage clock then shows the pair under "trace_bounce" and nothing under "trace_shadow")
-            int rc_ = stageMark(c, stream, 1); if (rc_) return rc_;
-        }
-        cur = nextQ; curCount = nextCount;
+        if (P.bgPresent) hipLaunchKernelGGL(kz_wf_final, gShade, blk, 0, stream, P, ds->T, W, cur, curCount);
     }
-    if (P.bgPresent) hipLaunchKernelGGL(kz_wf_final, gShade, blk, 0, stream, P, ds->T, W, cur, curCount);
     if (st) hipLaunchKernelGGL(kz_wf_count, dim3((items + KZ_BLOCK - 1) / KZ_BLOCK), blk, 0, stream, W, items);
     HIP_TRY(hipGetLastError());
     return KZ_OK;
@@ -928,11 +713,7 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     if (opts->shadowBeside < 0 || opts->shadowBeside > 2) return kz_fail(KZ_ERR_INVALID_ARG, "shadowBeside %d (0 = default, 1 = never, 2 = always)", opts->shadowBeside);
     if (opts->passHalves < 0 || opts->passHalves > 2) return kz_fail(KZ_ERR_INVALID_ARG, "passHalves %d (0 = default, 1 = never, 2 = always)", opts->passHalves);
     const int pipeline = opts->pipeline ? opts->pipeline : 2;
-#ifdef KZ_EXPERIMENTS
-    if ((rc = kzEnsureBvh2(scene, ds))) return rc;          // (development builds: several experiment kernels walk the BVH2)
-#else
     if (pipeline == 1 && (rc = kzEnsureBvh2(scene, ds))) return rc;
-#endif
     uint32_t s0 = opts->sampleBegin, s1 = opts->sampleEnd;
     if (s0 == 0 && s1 == 0) s1 = P.sampleCount;
     if (s0 >= s1 || s1 > P.sampleCount) return kz_fail(KZ_ERR_INVALID_ARG, "sample range [%u,%u) outside [0,%u)", s0, s1, P.sampleCount);
@@ -943,8 +724,6 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     ds->lastStream = stream;
     KzTune tune;
     if ((rc = resolveTune(opts->tune, tune))) return rc;
-    // (a development build asked for one of kz_experiments.h's kernels: such a call runs its passes plainly)
-    const bool expTune = !tune.wide || tune.keyStack || tune.ldsTop || tune.leafQueue || tune.legacyTrace || tune.mixed || tune.shadeSplit;
     if (tune.filmGather != 0 && tune.filmGather != 3) return kz_fail(KZ_ERR_UNSUPPORTED, "KzTuning.filmGather %d: the staged gather kernel of round 1 is gone (round 6: the film is resolved from running tap sums for every filter); 0 = default, 3 = one lane per pixel", tune.filmGather);
     if ((rc = prepareTiles(scene, ds, opts->tiles, opts->nTiles, stream))) return rc;
     // the film: running tap sums of the frame's pixels (kz_film.hip), part of the replica like the film itself - cleared unless the call accumulates
@@ -1094,7 +873,7 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
         bool halves = opts->passHalves == 2;
         // (normals / ao / path_mats have no shadow rays of a bounce to put beside anything: no mode is timed for them)
         if (pipeline == 2 && opts->shadowBeside == 0 && opts->passHalves == 0 && items > KZ_BESIDE_ITEMS && P.integrator == KZ_INTEGRATOR_PATH_MIS) {
-            if (multi || dealer || ds->statsOn || expTune) sb = 1;
+            if (multi || dealer || ds->statsOn) sb = 1;
             else {
                 if (ds->largeMode < 0 && ds->probeLaunched == 4) {
                     HIP_TRY(hipEventSynchronize(ds->evProbe[3][1]));
@@ -1115,7 +894,7 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
                 sb = mode == 1 ? 2 : 1; halves = mode == 2;                   // (a remainder pass of another size: one stream, not comparable)
             }
         }
-        if (halves && (pipeline != 2 || multi || dealer || expTune || nPixPass < 256)) halves = false;      // (passes in flight and dealt batches overlap already)
+        if (halves && (pipeline != 2 || multi || dealer || nPixPass < 256)) halves = false;      // (passes in flight and dealt batches overlap already)
         // ... and for the same reason the small-pass rule ends earlier under them: two passes of 2^22 items in flight still gain from "beside" (+1.5 .. +11 %), at
         // 2^24 - 2^25 C3 / C4 are neutral, from 2^26 they lose 2 - 3 % (the q1 asset gains at every size: whoever renders such scenes that way says 2)
         if (sb == 0 && (multi || dealer) && items > KZ_BESIDE_ITEMS_IN_FLIGHT) sb = 1;

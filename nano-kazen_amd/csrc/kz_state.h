@@ -16,17 +16,11 @@
 #include <thread>
 #include <vector>
 
-// Path state in HBM: one array per field (SoA; 16-B records, coalesced for the stages that sweep all slots). -DKZ_STATE_AOS=1 builds the
-// alternative that round 3 measured and rejected (profiles/r03h_state_layout): one 64-B line per path for (ray origin | direction | hit |
-// throughput) and one for (shadow origin | direction | pending radiance | misc). It was meant to cut the lines fetched per path once the
-// queues hold a thinning, scattered subset of the slots; shade did not move (19.3 -> 19.4 ms: it is not bound by the bytes of these
-// arrays) and the stages that sweep every slot lost (generate 1.5 -> 4.0 ms, camera rays 5.8 -> 6.9): C4 1533-1562 -> 1464-1470 Msamples/s.
-#ifndef KZ_STATE_AOS
-#define KZ_STATE_AOS 0
-#endif
+// Path state in HBM: one array per field (SoA; 16-B records, coalesced for the stages that sweep all slots). Round 3 measured one 64-B line per
+// path instead and rejected it (profiles/r03h_state_layout): the stages that sweep every slot lost, shade did not move.
 template <class Tp> struct KzField {
     Tp *p;
-    __device__ __forceinline__ Tp &operator[](uint32_t i) const { return p[KZ_STATE_AOS ? (size_t)i * 4u : (size_t)i]; }
+    __device__ __forceinline__ Tp &operator[](uint32_t i) const { return p[(size_t)i]; }
 };
 struct KzWf {
     KzField<float4> rayA, rayB;    // o.xyz tmin | d.xyz tmax
@@ -41,8 +35,7 @@ struct KzWf {
     unsigned long long *stats;
 };
 
-struct KzTune { int refill, postpone, batch, travBlocksPerCU, shadeBlocksPerCU, ldsStack, packet, filmGather, shadeSplit;
-                int wide, keyStack, ldsTop, leafQueue, legacyTrace, mixed;      // kz_experiments.h only
+struct KzTune { int refill, postpone, batch, travBlocksPerCU, shadeBlocksPerCU, ldsStack, packet, filmGather;
                 uint32_t *ovf; uint32_t ovfStride; };
 
 
@@ -131,7 +124,6 @@ struct PassCtx {
     KzWf wf{};                                                   // (pointers into the arena, set by ctxEnsure)
     float *plane[5] = {};                                        // the five sample planes jx | jy | r | g | b (each its own range of the arena)
     uint32_t *counts = nullptr;                                  // queue counters of a pass (8 x 520 words)
-    uint32_t *litQueue = nullptr; size_t litCap = 0;             // kz_wf_trace_dq<2>: shadow rays that need the literal walk-through
     uint32_t *ovf = nullptr; size_t ovfCap = 0;
     hipStream_t side = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr;      // small passes: the shadow rays of a bounce beside its closest-hit rays (wfPass)
     // A pass run as two HALVES of its pixels side by side (renderOn: KzRenderOpts::passHalves): two views of this context's arrays - the first and the second part
@@ -141,19 +133,17 @@ struct PassCtx {
     uint64_t beamSeen = 0;                                       // the last beam-list build (KzDeviceState::beamSeq) this context's stream has waited for
     std::vector<hipEvent_t> stageEv; std::vector<int> stageKind; size_t stageUsed = 0;
     size_t items() const { return arena ? arena->mapped.load() : 0; }
-    size_t bytes() const { return (arena ? arena->bytes() : 0) + ovfCap * sizeof(uint32_t) + litCap * 4 + (view[0] ? view[0]->bytes() : 0) + (view[1] ? view[1]->bytes() : 0); }
+    size_t bytes() const { return (arena ? arena->bytes() : 0) + ovfCap * sizeof(uint32_t) + (view[0] ? view[0]->bytes() : 0) + (view[1] ? view[1]->bytes() : 0); }
     // gives the memory back (the context stays usable: it grows again on demand); the caller has synchronised the device
     void release() {
         if (arena) arena->shrinkTo(0);
         wf = KzWf{}; for (float *&q : plane) q = nullptr; wanted = 0;
         if (ovf) (void)hipFree(ovf); ovf = nullptr; ovfCap = 0;
-        if (litQueue) (void)hipFree(litQueue); litQueue = nullptr; litCap = 0;
         for (PassCtx *v : view) if (v) v->release();
     }
     // buffers sized for another frame (a pooled context): given back when a call is short of memory (the caller has synchronised the device)
     void trimAux() {
         if (ovf) { (void)hipFree(ovf); ovf = nullptr; ovfCap = 0; }
-        if (litQueue) { (void)hipFree(litQueue); litQueue = nullptr; litCap = 0; }
         for (PassCtx *v : view) if (v) v->trimAux();
     }
     void destroy() {

@@ -263,85 +263,6 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
     return survivor;
 }
 
-// -DKZ_SHADE_LATE_POST=1 (the variant DESIGN 9.1 named): pass A classifies on the INTERPOLATED NORMAL alone - the three vertex
-// normals and the flag word of the shading record (64 B of its 112) instead of the whole post-intersection - the survivors travel through LDS as the
-// 20-B hit record (slot, t, u, v, triangle), and the whole post-intersection (terminator offset, frames, uv) runs in pass B on full waves, where the exact
-// back-face test of wfClassify is repeated. Conservative: pass A ends a path only when dot(-d, sum b_i n_i) is negative beyond any rounding of the
-// normalisation that the exact test applies afterwards (the sign of a dot product with n / |n| is the sign with n, up to a few ulps of the sum of the
-// terms' magnitudes); an emitter hit does the full post-intersection at once (it needs the hit point and the normal, and ends the path).
-#ifndef KZ_SHADE_LATE_POST
-#define KZ_SHADE_LATE_POST 0
-#endif
-template <int EXT>
-__device__ __forceinline__ bool wfClassifyLight(const KzParams &P, const KzDevTables &T, const KzWf &W, const uint32_t *__restrict__ pixList, uint32_t S, uint32_t sampleBegin,
-                                                int iter, bool compact, uint32_t slot, float4 &hitOut, KzSst &sst) {
-    const float4 h = kzLoadStream(&W.hit[slot]);
-    const float4 rb = kzLoadStream(&W.rayB[slot]);
-    const V3 rd = mk(rb.x, rb.y, rb.z);
-    hitOut = h;
-    if (!(h.x < KZ_INF)) {
-        if (iter > 0 && P.bgPresent) {
-            const float4 th = kzLoadStream(&W.thr[slot]);
-            const V3 c = mk(th.x, th.y, th.z) * backgroundRadiance(P, T, rd);
-            unsafeAtomicAdd(W.outR + slot, c.x); unsafeAtomicAdd(W.outG + slot, c.y); unsafeAtomicAdd(W.outB + slot, c.z);
-        }
-        return false;
-    }
-    const float4 *sp = reinterpret_cast<const float4 *>(T.shade + __float_as_uint(h.w));
-    const float4 s6 = sp[6];
-    const uint32_t lf = __float_as_uint(s6.w);
-    if ((int32_t)(lf >> 2) - 1 >= 0) {                                            // an emitter: integrator.cpp:226-231, 322-327, exactly as wfClassify does it
-        RawHit rh; rh.t = h.x; rh.u = h.y; rh.v = h.z; rh.tri = 0; rh.gid = __float_as_uint(h.w);
-        Its its; postIntersect<false>(T, rh, its);
-        const KzLightRow &lr = T.lights[its.light];
-        const float4 ra = kzLoadStream(&W.rayA[slot]);
-        const float4 th = iter == 0 ? make_float4(1.f, 1.f, 1.f, 1.f) : kzLoadStream(&W.thr[slot]);
-        const float4 mi = iter == 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : (compact ? make_float4(th.w, 0.f, 0.f, 0.f) : kzLoadStream(&W.misc[slot]));
-        const V3 ro = mk(ra.x, ra.y, ra.z);
-        const V3 wi = normalized(its.p - ro);
-        float bsdfWeight = 1.f;
-        if (iter > 0 && mi.z == 0.f) bsdfWeight = powerHeuristic(mi.x, lightPdfSolidAngle(lr.normalization, its.sh.n, wi, its.p, ro));
-        if (dot(its.sh.n, -wi) > 0.f) {
-            const V3 c = (bsdfWeight * mk(th.x, th.y, th.z)) * mk(lr.radiance[0], lr.radiance[1], lr.radiance[2]);
-            unsafeAtomicAdd(W.outR + slot, c.x); unsafeAtomicAdd(W.outG + slot, c.y); unsafeAtomicAdd(W.outB + slot, c.z);
-        }
-        return false;
-    }
-    bool twoSided = false;
-    if (EXT) { const int bt = T.bsdfs[__float_as_uint(s6.z)].type; twoSided = bt == KZ_BSDF_DIELECTRIC || bt == KZ_BSDF_ROUGHDIELECTRIC || bt == KZ_BSDF_NORMALMAP; }
-    bool survivor = true;
-    if (!twoSided) {
-        V3 n;
-        if (lf & 1u) {                                                            // vertex normals: the direction of the shading normal is sum b_i n_i (accel.cpp:177-229)
-            const float4 s2 = sp[2], s3 = sp[3], s4 = sp[4];
-            const float bx = 1 - (h.y + h.z);
-            n = bx * mk(s2.y, s2.z, s2.w) + h.y * mk(s3.x, s3.y, s3.z) + h.z * mk(s3.w, s4.x, s4.y);
-        } else {                                                                  // none: the geometric frame (accel.cpp:231-233)
-            const float4 s0 = sp[0], s1 = sp[1], s2 = sp[2];
-            const V3 p0 = mk(s0.x, s0.y, s0.z);
-            n = cross(mk(s0.w, s1.x, s1.y) - p0, mk(s1.z, s1.w, s2.x) - p0);
-        }
-        const float wzA = -(rd.x * n.x + rd.y * n.y + rd.z * n.z), mag = fabsf(rd.x * n.x) + fabsf(rd.y * n.y) + fabsf(rd.z * n.z);
-        if (wzA < -1e-5f * mag) survivor = false;                                 // certainly below the horizon (NaN compares false: survives, as in wfClassify)
-    }
-    if (survivor && iter >= 3) {                                                  // Russian roulette in front of the compaction, as in wfClassify
-        const uint32_t pl = slot / S; const uint32_t pxy = pixList[pl];
-        Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, wfPmjDim(P, iter));
-        const float4 th = kzLoadStream(&W.thr[slot]);
-        V3 throughput = mk(th.x, th.y, th.z);
-        const float etaA = compact ? 1.f : th.w;
-        const float probability = fminf(maxCoeff(throughput) * etaA * etaA, 0.95f);
-        if (probability <= smp.next1D(P, T)) survivor = false;
-        else {
-            throughput = throughput / probability;
-            kzStoreStream(&W.thr[slot], make_float4(throughput.x, throughput.y, throughput.z, th.w));
-            wfStoreSampler(P, W, slot, smp);
-        }
-    }
-    sst.mark(0);
-    return survivor;
-}
-
 // Pass B of shade(iter) for one surviving path: light sample + BSDF eval / pdf + MIS weight -> pending radiance and shadow ray
 // (integrator.cpp:247-295), BSDF sample -> throughput and next ray (:297-313). (The roulette of integrator.cpp:237-244 was played in pass A.)
 template <bool STATS, int EXT>
@@ -440,41 +361,25 @@ struct WfQueuePair {
     }
 };
 
-// ONE kernel per bounce (KzTune.shadeSplit == 0). Two passes per round of 256 queue entries, because on many scenes about half of the hits end
+// ONE kernel per bounce. Two passes per round of 256 queue entries, because on many scenes about half of the hits end
 // the path before any shading happens (a one-sided BSDF seen from behind, an emitter, a miss): pass A rebuilds the intersection record and classifies;
 // the entries that still need the light sample and the BSDF sample are compacted through LDS (record = slot + frame + uv),
 // and pass B — which carries ~85 % of the kernel's instructions — only ever runs on full waves.
 #define KZ_SV_CAP (2 * KZ_BLOCK)
-#ifndef KZ_MODEL_SORT
-#define KZ_MODEL_SORT 1            // (0: pass B of the EXT variants takes its records in arrival order - the A/B of profiles/r06c_ext)
-#endif
-// -DKZ_SHADE_CONST_ARGS (development build): the three argument structs of the shade kernel (KzParams 300 B, KzDevTables, KzWf) in
-// __constant__ memory, one slot per pass context, instead of in the kernel-argument segment - measured in profiles/r05c_shade_args.
-#ifdef KZ_SHADE_CONST_ARGS
-struct KzShadeArgs { KzParams P; KzDevTables T; KzWf W; };
-__constant__ KzShadeArgs g_kzShadeArgs[KZ_MAX_PASSES_IN_FLIGHT];
-#define KZ_SHADE_PARAMS int argSlot
-#define KZ_SHADE_BIND const KzParams &P = g_kzShadeArgs[argSlot].P; const KzDevTables &T = g_kzShadeArgs[argSlot].T; const KzWf &W = g_kzShadeArgs[argSlot].W;
-#else
-#define KZ_SHADE_PARAMS KzParams P, KzDevTables T, KzWf W
-#define KZ_SHADE_BIND
-#endif
 template <bool STATS, int EXT>
-__global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_SHADE_WAVES)) void kz_wf_shade(KZ_SHADE_PARAMS, const uint32_t *__restrict__ pixList, uint32_t S,
+__global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_SHADE_WAVES)) void kz_wf_shade(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__ pixList, uint32_t S,
                                                         uint32_t sampleBegin, int iter, const uint32_t *__restrict__ queue,
                                                         const uint32_t *__restrict__ countPtr, uint32_t countImm,
                                                         uint32_t *__restrict__ nextQueue, uint32_t *__restrict__ nextCount,
                                                         uint32_t *__restrict__ shadowQueue, uint32_t *__restrict__ shadowCount) {
-    KZ_SHADE_BIND
-    constexpr bool LATE = KZ_SHADE_LATE_POST && !STATS;      // (the counting variant keeps the exact classification in pass A: its counters follow the reference's order of events)
     constexpr bool NMAPX = (EXT & KZ_X_NMAP) != 0;
-    constexpr int SVW = LATE ? 5 : (NMAPX ? 19 : 16);        // words per survivor: slot, p, s, t, n, uv, bsdf row | model key << 24 (+ dpdu: normal maps) | LATE: slot + the hit record
+    constexpr int SVW = NMAPX ? 19 : 16;                     // words per survivor: slot, p, s, t, n, uv, bsdf row | model key << 24 (+ dpdu: normal maps)
     constexpr uint32_t QCAP = (uint32_t)KZ_WF_QCAP;
     __shared__ uint32_t s_bufN[QCAP], s_bufS[QCAP]; __shared__ uint32_t s_nN, s_nS, s_gbN, s_gbS;
     // The full variant (textures, normal maps) deals the 256 records of pass B to the lanes BY MODEL (a counting sort over 16 keys through LDS: a normal map sorts
     // by the model it wraps, + 8): worth 2.5 % of the kernel on the textured scene, nothing on the scene of eleven constant-parameter models - the items of a pass
     // are pixel-major and a queue keeps that order, so a batch already holds mostly ONE object's hits (profiles/r04q_ext_sorted, r06c_ext/ab_sort_vs_nosort.txt)
-    constexpr bool SORT = KZ_MODEL_SORT && NMAPX && !LATE;
+    constexpr bool SORT = NMAPX;
     __shared__ uint32_t s_hist[SORT ? 16 : 1]; __shared__ uint16_t s_perm[SORT ? KZ_BLOCK : 1];
     // The survivor table is a stack; its fill count is double-buffered by round (s_svCnt[round & 1]) so that the count for the NEXT round can
     // be written while this round's is still being read: a round then needs two workgroup barriers (records written | records read, output
@@ -502,12 +407,10 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
         uint32_t slot = 0;
         Its its;
         uint32_t modelKey = 0;
-        float4 hrec = make_float4(0.f, 0.f, 0.f, 0.f);
         if (more && base + threadIdx.x < count) {
             const uint32_t qi = base + threadIdx.x;
             slot = queue ? queue[qi] : qi;
-            if (LATE) survivor = wfClassifyLight<EXT>(P, T, W, pixList, S, sampleBegin, iter, compact, slot, hrec, sst);
-            else survivor = wfClassify<STATS, EXT>(P, T, W, pixList, S, sampleBegin, iter, compact, slot, its, modelKey, cn, sst);
+            survivor = wfClassify<STATS, EXT>(P, T, W, pixList, S, sampleBegin, iter, compact, slot, its, modelKey, cn, sst);
         }
         sst.mark(0);                                        // pass A
         {   // compaction of the survivors onto the LDS record stack
@@ -518,15 +421,12 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
             if (survivor) {
                 const uint32_t e = b + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                 uint32_t *r = s_sv + e;
-                if (LATE) { r[0] = slot; r[KZ_SV_CAP] = __float_as_uint(hrec.x); r[2 * KZ_SV_CAP] = __float_as_uint(hrec.y); r[3 * KZ_SV_CAP] = __float_as_uint(hrec.z); r[4 * KZ_SV_CAP] = __float_as_uint(hrec.w); }
-                else {
                 r[0] = slot; r[KZ_SV_CAP] = __float_as_uint(its.p.x); r[2 * KZ_SV_CAP] = __float_as_uint(its.p.y); r[3 * KZ_SV_CAP] = __float_as_uint(its.p.z);
                 r[4 * KZ_SV_CAP] = __float_as_uint(its.sh.s.x); r[5 * KZ_SV_CAP] = __float_as_uint(its.sh.s.y); r[6 * KZ_SV_CAP] = __float_as_uint(its.sh.s.z);
                 r[7 * KZ_SV_CAP] = __float_as_uint(its.sh.t.x); r[8 * KZ_SV_CAP] = __float_as_uint(its.sh.t.y); r[9 * KZ_SV_CAP] = __float_as_uint(its.sh.t.z);
                 r[10 * KZ_SV_CAP] = __float_as_uint(its.sh.n.x); r[11 * KZ_SV_CAP] = __float_as_uint(its.sh.n.y); r[12 * KZ_SV_CAP] = __float_as_uint(its.sh.n.z);
                 r[13 * KZ_SV_CAP] = __float_as_uint(its.uvx); r[14 * KZ_SV_CAP] = __float_as_uint(its.uvy); r[15 * KZ_SV_CAP] = EXT ? (its.bsdf | (modelKey << 24)) : its.bsdf;      // (kz_scene_create: < 2^24 rows)
                 if (NMAPX) { r[16 * KZ_SV_CAP] = __float_as_uint(its.dpdu.x); r[17 * KZ_SV_CAP] = __float_as_uint(its.dpdu.y); r[18 * KZ_SV_CAP] = __float_as_uint(its.dpdu.z); }
-                }
             }
         }
         __syncthreads();
@@ -554,25 +454,13 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
         if (threadIdx.x < take) {
             const uint32_t *r = s_sv + (n0 - take) + mine;
             slot = r[0];
-            bool alive = true;
-            if (LATE) {
-                // the whole post-intersection on a full wave, then wfClassify's exact test (pass A kept every hit it could not rule out)
-                RawHit rh; rh.t = __uint_as_float(r[KZ_SV_CAP]); rh.u = __uint_as_float(r[2 * KZ_SV_CAP]); rh.v = __uint_as_float(r[3 * KZ_SV_CAP]); rh.tri = 0; rh.gid = r[4 * KZ_SV_CAP];
-                postIntersect<false>(T, rh, its);
-                const float4 rb = kzLoadStream(&W.rayB[slot]);
-                const float wz = dot(-mk(rb.x, rb.y, rb.z), its.sh.n);
-                bool twoSided = false;
-                if (EXT) { const int bt = T.bsdfs[its.bsdf].type; twoSided = bt == KZ_BSDF_DIELECTRIC || bt == KZ_BSDF_ROUGHDIELECTRIC || bt == KZ_BSDF_NORMALMAP; }
-                alive = (wz > 0.f) || twoSided || isnan(wz);
-            } else {
             its.p = mk(__uint_as_float(r[KZ_SV_CAP]), __uint_as_float(r[2 * KZ_SV_CAP]), __uint_as_float(r[3 * KZ_SV_CAP]));
             its.sh.s = mk(__uint_as_float(r[4 * KZ_SV_CAP]), __uint_as_float(r[5 * KZ_SV_CAP]), __uint_as_float(r[6 * KZ_SV_CAP]));
             its.sh.t = mk(__uint_as_float(r[7 * KZ_SV_CAP]), __uint_as_float(r[8 * KZ_SV_CAP]), __uint_as_float(r[9 * KZ_SV_CAP]));
             its.sh.n = mk(__uint_as_float(r[10 * KZ_SV_CAP]), __uint_as_float(r[11 * KZ_SV_CAP]), __uint_as_float(r[12 * KZ_SV_CAP]));
             its.uvx = __uint_as_float(r[13 * KZ_SV_CAP]); its.uvy = __uint_as_float(r[14 * KZ_SV_CAP]); its.bsdf = EXT ? (r[15 * KZ_SV_CAP] & 0xFFFFFFu) : r[15 * KZ_SV_CAP];
             if (NMAPX) its.dpdu = mk(__uint_as_float(r[16 * KZ_SV_CAP]), __uint_as_float(r[17 * KZ_SV_CAP]), __uint_as_float(r[18 * KZ_SV_CAP]));
-            }
-            if (alive) wfShadeSurvivor<STATS, EXT>(P, T, W, pixList, S, sampleBegin, iter, compact, slot, its, pushNext, pushShadow, cn, sst);
+            wfShadeSurvivor<STATS, EXT>(P, T, W, pixList, S, sampleBegin, iter, compact, slot, its, pushNext, pushShadow, cn, sst);
         }
         sst.mark(7);                                        // next-ray stores (and, for lanes without a survivor, nothing)
         apN.push(pushNext, slot); apS.push(pushShadow, slot);
@@ -606,7 +494,7 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
 // constant false the closest-hit bookkeeping of the shadow lanes (hit distance, barycentrics, triangle ids) disappears from that
 // instantiation: 57 VGPRs and no spills instead of 64 with 9 spilled.
 // Shadow test (exact, see kz_devfn.h shadowOccluded): any-hit unless an invisible-light triangle lies on the segment.
-// (The BVH2 form, the per-lane key stack, the LDS top-of-tree and the mixed launches of round 2 live in kz_experiments.h.)
+// (Round 2 measured and rejected a BVH2 form, a per-lane key stack, an LDS top-of-tree and mixed launches: LAB_NOTES 4.)
 #ifndef KZ_TRACE_WAVES
 #define KZ_TRACE_WAVES 8            // waves per SIMD the per-lane traversal is compiled for (64 VGPRs); 7 = 72 VGPRs measured in r02i
 #endif
@@ -617,7 +505,7 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
                                                         uint32_t *__restrict__ queueB, uint32_t *__restrict__ countPtrB) {
     extern __shared__ uint32_t s_stack[];
     const uint32_t count = countPtr ? *countPtr : countImm;
-    constexpr bool SHADOW = MODE == 2 || MODE == 4;
+    [[maybe_unused]] constexpr bool SHADOW = MODE == 2 || MODE == 4;      // (read by the counters of the -DKZ_LANESTAT / -DKZ_TRACESTAT builds)
     constexpr int kind = MODE == 4 ? 2 : MODE;                        // ray kind: 0 closest hit, 1 closest hit on the walk-through ray, 2 shadow
     const int lane = threadIdx.x & 63;
     // The lane's stack is a column of the [entry][lane] LDS array (+ one scratch row). Its state is `top`, the LDS BYTE ADDRESS of the next
@@ -796,30 +684,18 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
                 // hit children in slot order altogether until the pushes got cheap (round 3): in dense geometry the nearest child is where
                 // the occluder is, and the selection now costs less than the visits it saves. Pushes are branch-free (below).
                 uint32_t key[4]; uint4 refs;
-                bool p0, p1, p2, p3;                                          // child i goes on the stack
-                uint32_t nxt; bool any;
-#ifndef KZ_SHADOW_ORDERED
-#define KZ_SHADOW_ORDERED 1             // any-hit rays descend into the nearest hit child first too: 0 = the slot order of round 2 (C4 shadow stage 21.2 ms, C3 21.4; 1: 20.3, 21.6)
-#endif
-                constexpr bool SLOTORDER = SHADOW && !KZ_SHADOW_ORDERED;
-                node4Keys<!SLOTORDER>(T, cur, o, rx, ry, rz, tmin, tmax, key, refs);
-                if (SLOTORDER) {
-                    const bool h0 = key[0] != 0xFFFFFFFFu, h1 = key[1] != 0xFFFFFFFFu, h2 = key[2] != 0xFFFFFFFFu, h3 = key[3] != 0xFFFFFFFFu;
-                    any = h0 || h1 || h2 || h3;
-                    nxt = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : refs.w));
-                    p0 = false; p1 = h1 && h0; p2 = h2 && (h0 || h1); p3 = h3 && (h0 || h1 || h2);
-                } else {
-                    const uint32_t kmin = min(min(key[0], key[1]), min(key[2], key[3]));
-                    any = kmin != 0xFFFFFFFFu;
-                    nxt = pick4b(refs, kmin);
-                    p0 = key[0] != 0xFFFFFFFFu && key[0] != kmin; p1 = key[1] != 0xFFFFFFFFu && key[1] != kmin;
-                    p2 = key[2] != 0xFFFFFFFFu && key[2] != kmin; p3 = key[3] != 0xFFFFFFFFu && key[3] != kmin;
-                }
+                node4Keys(T, cur, o, rx, ry, rz, tmin, tmax, key, refs);
+                const uint32_t kmin = min(min(key[0], key[1]), min(key[2], key[3]));
+                const bool any = kmin != 0xFFFFFFFFu;
+                const uint32_t nxt = pick4b(refs, kmin);
+                // child i goes on the stack
+                const bool p0 = key[0] != 0xFFFFFFFFu && key[0] != kmin, p1 = key[1] != 0xFFFFFFFFu && key[1] != kmin;
+                const bool p2 = key[2] != 0xFFFFFFFFu && key[2] != kmin, p3 = key[3] != 0xFFFFFFFFu && key[3] != kmin;
                 if (top - stkBase + 3u * rowB <= ldsRows) {                      // common case: everything stays in LDS
                     // every child is written at the running top, which advances only past the children that stay: one that does not is
                     // overwritten by the next store or left above the top (the last row it can reach is the scratch row). No address selects.
                     uint32_t a = top;
-                    if (!SLOTORDER) { kzLdsPut(a, refs.x); a += p0 ? rowB : 0u; }
+                    kzLdsPut(a, refs.x); a += p0 ? rowB : 0u;
                     kzLdsPut(a, refs.y); a += p1 ? rowB : 0u;
                     kzLdsPut(a, refs.z); a += p2 ? rowB : 0u;
                     kzLdsPut(a, refs.w); a += p3 ? rowB : 0u;

@@ -5,6 +5,8 @@ import numpy as np
 
 from . import abi
 
+_TUNING_FIELDS = frozenset(name for name, _ in abi.KzTuning._fields_)
+
 
 class Scene:
     """kz_scene_create -> [kz_scene_upload] -> kz_render* -> kz_film_download."""
@@ -112,6 +114,10 @@ class Scene:
         o.shadowBeside = int(shadow_beside)
         o.passHalves = int(pass_halves)
         for k, v in (tune or {}).items():
+            # a name KzTuning does not have is refused, not dropped: ctypes would keep it as a plain attribute the library never sees (a typo, or
+            # one of the names the reserved dev0 .. dev5 words had - bvh2, ... - whose values the library refuses)
+            if k not in _TUNING_FIELDS:
+                raise abi.KzError(abi.KZ_ERR_UNSUPPORTED, "KzTuning has no field %r (its fields: %s)" % (k, ", ".join(sorted(_TUNING_FIELDS))))
             setattr(o.tune, k, int(v))
         return o, keep
 

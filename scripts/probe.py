@@ -5,7 +5,7 @@
                                                          per-stage device times of one pass + Msamples/s of a full call
     python scripts/probe.py sweep --knob refill --values 24,32,40,48,56 [--scene c4]
                                                          the same for a list of values of one KzTuning field (or pass_items / passes_in_flight)
-    python scripts/probe.py counters --values 'keyStack=1;keyStack=2'
+    python scripts/probe.py counters --values 'ldsStack=8;ldsStack=16'
                                                          executed node visits / triangle tests / rays per sample for each tuning
     python scripts/probe.py ab --variants tree,NAME[,NAME2...] [--scenes c4,c3] [--reps 2] [--spp 256] [--tune ...] [--out DIR]
                                                          same-call A/B: `stages` in a child process per (repetition, build, scene); NAME = a build made by
@@ -100,7 +100,7 @@ def cmd_sweep(a):
 
 
 def cmd_counters(a):
-    """executed work per sample (node visits, triangle tests, rays) for a list of tunings: --values 'keyStack=1;keyStack=2'"""
+    """executed work per sample (node visits, triangle tests, rays) for a list of tunings: --values 'ldsStack=8;ldsStack=16'"""
     sc = kz.Scene(scene(a.scene), device=0)
     sc.set_stats(True)
     spp = a.spp or 16

@@ -62,6 +62,17 @@ def test_render_opts_layout_v5(kz):
     assert C.sizeof(kz.abi.KzTuning) == 64 and o.tileDealing.offset == 128 and o.packedOutput.offset == 132 and o.dealer.offset == 136 and o.shadowBeside.offset == 144 and o.passHalves.offset == 148 and C.sizeof(o) == 152
 
 
+def test_unknown_tuning_names_are_refused(kz):
+    """A name KzTuning does not have (a typo, or one of the names the reserved dev0 .. dev5 words had) is refused before the call, never dropped: ctypes
+    would keep it as a plain attribute that the library never sees."""
+    sc = kz.Scene(kz.scenes.cornell_box(16, 16, 1))
+    for name in ("bvh2", "refil"):
+        with pytest.raises(kz.abi.KzError) as e:
+            sc.render(tune={name: 1})
+        assert e.value.code == kz.abi.KZ_ERR_UNSUPPORTED and repr(name) in str(e.value), name
+    sc.close()
+
+
 @pytest.mark.parametrize("w,h,tile,parts", [(1920, 1080, 64, 8), (3840, 2160, 64, 8), (1920, 1080, 128, 3), (100, 70, 32, 5), (64, 64, 64, 4)])
 def test_deal_tiles_partitions_the_image_by_area(kz, w, h, tile, parts):
     """kz_deal_tiles: every pixel in exactly one part, tiles on the 32-px block grid, areas balanced to one tile."""

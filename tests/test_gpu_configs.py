@@ -9,8 +9,6 @@
 """
 import ctypes as C
 import os
-import subprocess
-import sys
 import time
 
 import numpy as np
@@ -19,7 +17,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 L2_TOL = 1e-3
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXPERIMENTS_LIB = os.path.join(ROOT, "nano-kazen_amd", "csrc", "variants", "experiments", "libkazen_mi355x.so")
 
 
 def l2(a, b):
@@ -385,39 +382,10 @@ def test_state_budget_and_pass_options(gpu_lib, kz, O):
     ora = O.OracleScene(desc)
     assert l2(sc.rgb(one_at_a_time), ora.rgb(ora.render(threads=0))) < L2_TOL
     # the kernels of rejected experiments are not in the default library: asking for one is an error, never a silent default
-    if not (gpu_lib.kz_build_flags() & 1):
-        for t in ({"bvh2": 1}, {"keyStack": 2}, {"ldsTop": 5}, {"leafQueue": 2}, {"legacyTrace": 1}, {"mixedLaunch": 1}):
-            with pytest.raises(kz.abi.KzError) as e:
-                sc.render(tune=t)
-            assert e.value.code == kz.abi.KZ_ERR_UNSUPPORTED, t
-
-
-@pytest.mark.skipif(not os.path.exists(EXPERIMENTS_LIB), reason="development variant not built (scripts/build_variant.sh experiments -DKZ_EXPERIMENTS)")
-def test_experiment_kernels_stay_bit_identical():
-    """The rejected experiments (kz_experiments.h: BVH2 per-lane traversal, per-lane key stack, LDS top-of-tree, decoupled leaf queue,
-    mixed launches, the non-persistent round-1 launches) live in a -DKZ_EXPERIMENTS build only. It is run in a child process (one
-    library per process) and every variant must reproduce the product kernels' film bit for bit."""
-    env = {k: v for k, v in os.environ.items() if not k.startswith("KZ_BVH_")}      # (the development build reads its builder sweeps from KZ_BVH_*: build the product's tree)
-    env["KZ_LIB_PATH"] = EXPERIMENTS_LIB
-    code = r"""
-import importlib, sys, numpy as np
-sys.path.insert(0, %r)
-kz = importlib.import_module("nano-kazen_amd")
-assert kz.abi.load_library().kz_build_flags() & 1
-desc = kz.scenes.cornell_box(96, 80, 24, sampler="pmj02bn")
-sc = kz.Scene(desc, device=0)
-npx = 96 * 80
-sc.render(pass_items=npx * 4, passes_in_flight=1)
-ref = sc.film()
-for t in ({"bvh2": 1}, {"keyStack": 2, "ldsStack": 3}, {"ldsTop": 5}, {"leafQueue": 2}, {"leafQueue": 2, "ldsStack": 2, "refill": 64, "batch": 64},
-          {"ldsTop": 1000, "ldsStack": 6, "keyStack": 2}, {"legacyTrace": 1}, {"mixedLaunch": 1}, {"bvh2": 1, "mixedLaunch": 1}):
-    sc.render(pass_items=npx * 4, tune=t)
-    f = sc.film()
-    assert (np.array_equal(f, ref) if not t.get("bvh2") else np.allclose(f, ref, rtol=2e-5, atol=1e-5)), t
-print("ok")
-""" % ROOT
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    for t in ({"dev0": 1}, {"dev1": 2}, {"dev2": 5}, {"dev3": 2}, {"dev4": 1}, {"dev5": 1}):
+        with pytest.raises(kz.abi.KzError) as e:
+            sc.render(tune=t)
+        assert e.value.code == kz.abi.KZ_ERR_UNSUPPORTED, t
 
 
 def test_product_library_has_no_process_global_hooks(gpu_lib, dev_lib, kz):
@@ -426,6 +394,13 @@ def test_product_library_has_no_process_global_hooks(gpu_lib, dev_lib, kz):
         assert not hasattr(gpu_lib, hook), hook
         assert hasattr(dev_lib, hook), hook
     assert gpu_lib.kz_build_flags() == 0
+    # ... and it refuses the same tunings as the product: the kernels of rejected experiments are in neither
+    sc = kz.Scene(kz.scenes.cornell_box(32, 32, 4), device=0, lib=dev_lib)
+    for t in ({"dev0": 1}, {"dev1": 2}, {"dev2": 5}, {"dev3": 2}, {"dev4": 1}, {"dev5": 1}):
+        with pytest.raises(kz.abi.KzError) as e:
+            sc.render(tune=t)
+        assert e.value.code == kz.abi.KZ_ERR_UNSUPPORTED, t
+    sc.close()
 
 
 def test_failed_calls_release_their_device_memory(dev_lib, kz):

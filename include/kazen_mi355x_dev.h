@@ -168,7 +168,8 @@ int kz_kat_pow4(int32_t spp, int32_t *out4);
 /* A copy of one flat table of the scene, for the tests of kazen_mi355x_edit.h: device -1 = the host copy (brought up to date first), else that
  * replica's table. *bytes = the table's size; at most `cap` bytes are copied to `out` (out may be NULL to ask for the size). A replica's BVH2 table
  * (KZ_TABLE_NODES) is there once a BVH2 path or an edit has used it (else KZ_ERR_STATE); KZ_TABLE_PARAMS is host-only (the render constants). */
-enum { KZ_TABLE_NODES = 0, KZ_TABLE_NODES4 = 1, KZ_TABLE_TRIS = 2, KZ_TABLE_SHADE = 3, KZ_TABLE_CDF = 4, KZ_TABLE_LIGHTS = 5, KZ_TABLE_IL_TRIS = 6, KZ_TABLE_PARAMS = 7 };
+enum { KZ_TABLE_NODES = 0, KZ_TABLE_NODES4 = 1, KZ_TABLE_TRIS = 2, KZ_TABLE_SHADE = 3, KZ_TABLE_CDF = 4, KZ_TABLE_LIGHTS = 5, KZ_TABLE_IL_TRIS = 6, KZ_TABLE_PARAMS = 7,
+       KZ_TABLE_BSDFS = 8 /* the resolved BSDF rows (the default diffuse row behind the description's, when a mesh has no BSDF) */ };
 int kz_scene_table(KzScene *scene, int device, int table, void *out, size_t cap, size_t *bytes);
 
 /* How the library was built: bit 0 (KZ_BUILD_EXPERIMENTS) = it is the development variant (-DKZ_EXPERIMENTS), which exports the kz_debug_* hooks. */

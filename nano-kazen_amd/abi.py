@@ -164,6 +164,18 @@ class KzVertexUpdate(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("nV", C.c_uint32), ("V", f32p), ("N", f32p)]
 
 
+class KzBsdfUpdate(C.Structure):
+    _fields_ = [("row", C.c_uint32), ("bsdf", KzBSDF)]
+
+
+class KzLightUpdate(C.Structure):
+    _fields_ = [("light", C.c_uint32), ("value", KzLight)]
+
+
+class KzTransformUpdate(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("toWorld", C.c_float * 16)]
+
+
 class KzBvhInfo(C.Structure):
     _fields_ = [("nNodes", C.c_uint32), ("nLeaves", C.c_uint32), ("nTris", C.c_uint32), ("maxDepth", C.c_uint32),
                 ("maxLeafSize", C.c_uint32), ("sahCost", C.c_float), ("buildSeconds", C.c_double)]
@@ -182,8 +194,8 @@ EXPORTS = ["kz_scene_create", "kz_scene_destroy", "kz_scene_bvh_info", "kz_scene
            "kz_tiles_packed_floats", "kz_film_download_tiles", "kz_film_merge_tiles", "kz_film_merge_rects", "kz_device_trim", "kz_kat_dpdf", "kz_kat_pow4", "kz_last_grow_note",
            "kz_plan_passes", "kz_plan_schedule", "kz_pass_mode_info", "kz_scene_table"]
 # what include/kazen_mi355x_edit.h declares (checked by tests/test_scene_edit_cpu.py): editing a scene that already exists
-EDIT_EXPORTS = ["kz_scene_set_camera", "kz_scene_set_vertices"]
-KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS = range(8)
+EDIT_EXPORTS = ["kz_scene_set_camera", "kz_scene_set_vertices", "kz_scene_set_bsdfs", "kz_scene_set_lights", "kz_scene_set_transforms"]
+KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS = range(9)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices"]
 
@@ -271,6 +283,10 @@ def load_library(path=None):
         lib.kz_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(KzCamera)]
         lib.kz_scene_set_vertices.argtypes = [C.c_void_p, C.POINTER(KzVertexUpdate), C.c_uint32]
         lib.kz_scene_table.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(lib, "kz_scene_set_transforms"):
+        lib.kz_scene_set_bsdfs.argtypes = [C.c_void_p, C.POINTER(KzBsdfUpdate), C.c_uint32]
+        lib.kz_scene_set_lights.argtypes = [C.c_void_p, C.POINTER(KzLightUpdate), C.c_uint32]
+        lib.kz_scene_set_transforms.argtypes = [C.c_void_p, C.POINTER(KzTransformUpdate), C.c_uint32]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

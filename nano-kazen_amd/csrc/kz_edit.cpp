@@ -10,6 +10,7 @@
 // formed on the host at once: they are few, and the light CDF is a sequential float sum.
 #include "kz_internal.h"
 #include "kz_refit.h"
+#include "kz_xform.h"
 
 #include <algorithm>
 #include <cmath>
@@ -44,6 +45,47 @@ void computeLevels(KzScene *sc) {
     sc->levelStart.push_back((uint32_t)sc->nodes.size());
 }
 
+// A mesh's base data for its first transform: what an edit has set and the shading records do not hold yet (pendV / pendN), else a copy out of the shading
+// records through the faces' vertex indices (exact; a vertex no face names is never read again and stays 0). The caller holds editMutex.
+void captureBase(KzScene *sc, uint32_t m) {
+    const size_t nMeshes = sc->meshRows.size();
+    if (sc->baseV.size() != nMeshes) { sc->baseV.resize(nMeshes); sc->baseN.resize(nMeshes); sc->pendX.resize(nMeshes); sc->pendXOn.assign(nMeshes, 0); }
+    if (sc->pendV.size() != nMeshes) { sc->pendV.resize(nMeshes); sc->pendN.resize(nMeshes); }
+    if (!sc->baseV[m].empty() || !sc->meshNV[m]) return;
+    const KzMeshRow &row = sc->meshRows[m];
+    const bool hasN = (row.flags & 1u) != 0;
+    if (!sc->pendV[m].empty()) { sc->baseV[m] = sc->pendV[m]; sc->baseN[m] = sc->pendN[m]; return; }
+    sc->baseV[m].assign(3 * (size_t)sc->meshNV[m], 0.f);
+    if (hasN) sc->baseN[m].assign(3 * (size_t)sc->meshNV[m], 0.f);
+    for (uint32_t f = 0; f < row.nF; ++f) {
+        const uint32_t g = row.triOffset + f;
+        const KzTriShade &t = sc->shade[g];
+        for (int v = 0; v < 3; ++v) {
+            const size_t i = sc->triVtx[3 * (size_t)g + v];
+            for (int a = 0; a < 3; ++a) { sc->baseV[m][3 * i + a] = t.p[3 * v + a]; if (hasN) sc->baseN[m][3 * i + a] = t.n[3 * v + a]; }
+        }
+    }
+}
+
+// base data of mesh m under x (kz_xform.h); false when a transformed coordinate is not finite
+bool transformMesh(const KzScene *sc, uint32_t m, const KzXform &x, std::vector<float> &V, std::vector<float> &N) {
+    const std::vector<float> &bV = sc->baseV[m], &bN = sc->baseN[m];
+    V.resize(bV.size()); N.resize(bN.size());
+    bool fin = true;
+    for (size_t i = 0; i < bV.size(); i += 3) { kzXfPoint(x, &bV[i], &V[i]); fin = fin && kzFinite(V[i]) && kzFinite(V[i + 1]) && kzFinite(V[i + 2]); }
+    for (size_t i = 0; i < bN.size(); i += 3) kzXfNormal(x, &bN[i], &N[i]);
+    return fin;
+}
+
+// the rows a light mesh's new positions move: its shading records, its CDF (the caller re-forms the invisible-light rows once per batch)
+void applyLightMesh(KzScene *sc, uint32_t m, const float *V, const float *N) {
+    applyMesh(sc, m, V, N);
+    KzLightRow &lr = sc->lightRows[(size_t)sc->meshRows[m].light];
+    std::vector<float> t;
+    kzLightCdf(&sc->shade[lr.triOffset], lr.nF, t, lr.normalization);
+    std::copy(t.begin(), t.end(), sc->cdf.begin() + lr.cdfOffset);
+}
+
 } // namespace
 
 // The host refit: the same arithmetic, node by node, as the device's (kz_refit.hip) and the build's (kz_bvh.cpp).
@@ -54,6 +96,13 @@ void kzHostSync(KzScene *sc) {
         if (sc->pendV[m].empty()) continue;
         applyMesh(sc, (uint32_t)m, sc->pendV[m].data(), sc->pendN[m].empty() ? nullptr : sc->pendN[m].data());
         std::vector<float>().swap(sc->pendV[m]); std::vector<float>().swap(sc->pendN[m]);
+    }
+    for (size_t m = 0; m < sc->pendXOn.size(); ++m) {   // (kz_scene_set_transforms of a mesh that is no light: its base data under the matrix, by the arithmetic the replicas used)
+        if (!sc->pendXOn[m]) continue;
+        std::vector<float> V, N;
+        transformMesh(sc, (uint32_t)m, sc->pendX[m], V, N);
+        applyMesh(sc, (uint32_t)m, V.data(), N.empty() ? nullptr : N.data());
+        sc->pendXOn[m] = 0;
     }
     for (KzTri &t : sc->tris) {                         // p0, e1 = v1 - v0, e2 = v2 - v0 (kz_bvh.cpp: the leaf triangles)
         const float *p = sc->shade[t.gid].p;
@@ -136,23 +185,126 @@ int kz_scene_set_vertices(KzScene *sc, const KzVertexUpdate *u, uint32_t n) {
         for (uint32_t i = 0; i < n; ++i) {
             const KzVertexUpdate &x = u[i];
             const int32_t light = sc->meshRows[x.mesh].light;
+            if (!sc->baseV.empty()) {                   // new base data: the host's copy is taken again by the mesh's next transform (every replica's follows in kzEditVertices), its transform goes
+                std::vector<float>().swap(sc->baseV[x.mesh]); std::vector<float>().swap(sc->baseN[x.mesh]); sc->pendXOn[x.mesh] = 0;
+            }
             if (light < 0) {
                 sc->pendV[x.mesh].assign(x.V, x.V + 3 * (size_t)x.nV);
                 if (x.N) sc->pendN[x.mesh].assign(x.N, x.N + 3 * (size_t)x.nV); else sc->pendN[x.mesh].clear();
                 continue;
             }
             std::vector<float>().swap(sc->pendV[x.mesh]); std::vector<float>().swap(sc->pendN[x.mesh]);
-            applyMesh(sc, x.mesh, x.V, x.N);
-            KzLightRow &lr = sc->lightRows[(size_t)light];
-            std::vector<float> t;
-            kzLightCdf(&sc->shade[lr.triOffset], lr.nF, t, lr.normalization);
-            std::copy(t.begin(), t.end(), sc->cdf.begin() + lr.cdfOffset);
+            applyLightMesh(sc, x.mesh, x.V, x.N);
             lightRows.push_back((uint32_t)light);
         }
         if (!lightRows.empty()) kzInvisibleLights(sc);
         sc->hostStale = true;
     }
     return kzEditVertices(sc, u, n, lightRows);
+}
+
+int kz_scene_set_bsdfs(KzScene *sc, const KzBsdfUpdate *u, uint32_t n) {
+    if (!sc || (n && !u)) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_bsdfs: null argument");
+    std::vector<KzBSDF> table(sc->bsdfs.begin(), sc->bsdfs.begin() + sc->nDescBsdfs);      // the addressable rows (a default diffuse row may follow them)
+    std::vector<uint8_t> seen(sc->nDescBsdfs, 0);
+    std::vector<uint32_t> rows;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (u[i].row >= sc->nDescBsdfs) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_bsdfs: update %u names row %u, the scene was created with %u BSDF rows", i, u[i].row, sc->nDescBsdfs);
+        if (seen[u[i].row]) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_bsdfs: row %u is listed twice in one batch", u[i].row);
+        seen[u[i].row] = 1;
+        table[u[i].row] = u[i].bsdf;
+        rows.push_back(u[i].row);
+    }
+    int rc = kzCheckBsdfs("kz_scene_set_bsdfs: ", table.data(), sc->nDescBsdfs, (uint32_t)sc->texProgs.size(), sc->prm.integrator);
+    if (rc != KZ_OK) return rc;
+    if (!n) return KZ_OK;
+    if ((rc = kzEditWait(sc)) != KZ_OK) return rc;
+    for (uint32_t r : rows) { kzResolveBsdf(table[r]); sc->bsdfs[r] = table[r]; }
+    const int32_t ext = kzBsdfExt(sc->bsdfs);           // over the whole table, default row included: a render picks its kernel variants from it per launch
+    const bool extChanged = ext != sc->prm.bsdfExt;
+    sc->prm.bsdfExt = ext;
+    return kzEditBsdfRows(sc, rows.data(), (uint32_t)rows.size(), extChanged);
+}
+
+int kz_scene_set_lights(KzScene *sc, const KzLightUpdate *u, uint32_t n) {
+    if (!sc || (n && !u)) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_lights: null argument");
+    std::vector<int32_t> which(sc->nDescLights, -1);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (u[i].light >= sc->nDescLights) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_lights: update %u names light %u, the scene was created with %u lights", i, u[i].light, sc->nDescLights);
+        if (which[u[i].light] >= 0) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_lights: light %u is listed twice in one batch", u[i].light);
+        which[u[i].light] = (int32_t)i;
+    }
+    if (!n) return KZ_OK;
+    int rc;
+    if ((rc = kzEditWait(sc)) != KZ_OK) return rc;
+    {
+        std::lock_guard<std::mutex> g(sc->editMutex);
+        for (size_t l = 0; l < sc->lightRows.size(); ++l) {
+            const int32_t i = which[sc->lightDesc[l]];
+            if (i < 0) continue;
+            const KzLight &kl = u[i].value;
+            KzLightRow &lr = sc->lightRows[l];
+            for (int a = 0; a < 3; ++a) lr.radiance[a] = kl.intensity * kl.color[a];
+            lr.primaryVisibility = kl.primaryVisibility ? 1 : 0;
+        }
+        kzInvisibleLights(sc);                           // (the shading records of light meshes follow every edit at once: nothing to sync first)
+    }
+    return kzEditLightRows(sc);
+}
+
+int kz_scene_set_transforms(KzScene *sc, const KzTransformUpdate *u, uint32_t n) {
+    if (!sc || (n && !u)) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: null argument");
+    const uint32_t nMeshes = (uint32_t)sc->meshRows.size();
+    std::vector<uint8_t> seen(nMeshes, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (u[i].mesh >= nMeshes) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: update %u names mesh %u, the scene has %u meshes", i, u[i].mesh, nMeshes);
+        if (seen[u[i].mesh]) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: mesh %u is listed twice in one batch", u[i].mesh);
+        seen[u[i].mesh] = 1;
+        for (int k = 0; k < 16; ++k)
+            if (!kzFinite(u[i].toWorld[k])) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: mesh %u: matrix entry %d is not finite (%g)", u[i].mesh, k, u[i].toWorld[k]);
+    }
+    if (!n) return KZ_OK;
+    int rc;
+    if ((rc = kzEditWait(sc)) != KZ_OK) return rc;
+    std::vector<KzXform> xf(n);
+    std::vector<KzXformJob> jobs(n);
+    for (uint32_t i = 0; i < n; ++i) { kzXformFromMatrix(u[i].toWorld, xf[i]); jobs[i] = KzXformJob{u[i].mesh, &xf[i]}; }
+    // ---- nothing below changes a table before every check has passed: the host checks the light meshes (and, for a scene no replica holds, all of them),
+    // every replica's kz_edit_xform the rest
+    const bool resident = kzEditReplicaCount(sc) > 0;
+    std::vector<std::vector<float>> lightV(n), lightN(n);
+    {
+        std::lock_guard<std::mutex> g(sc->editMutex);
+        for (uint32_t i = 0; i < n; ++i) captureBase(sc, u[i].mesh);
+        for (uint32_t i = 0; i < n; ++i) {
+            const bool light = sc->meshRows[u[i].mesh].light >= 0;
+            if (!light && resident) continue;
+            std::vector<float> V, N;
+            if (!transformMesh(sc, u[i].mesh, xf[i], V, N))
+                return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: mesh %u: a transformed position is not finite (the matrix maps a vertex to w = 0 or overflows)", u[i].mesh);
+            if (light) { lightV[i].swap(V); lightN[i].swap(N); }
+        }
+    }
+    int32_t bad = -1;
+    if ((rc = kzEditXformStage(sc, jobs.data(), n, &bad)) != KZ_OK) return rc;
+    if (bad >= 0) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: mesh %u: a transformed position is not finite (the matrix maps a vertex to w = 0 or overflows)", u[bad].mesh);
+    computeLevels(sc);
+    if ((rc = kzEditPrepare(sc)) != KZ_OK) return rc;          // (as kz_scene_set_vertices: the BVH2, the vertex indices and the slot map, once per replica)
+    std::vector<uint32_t> lightRows;
+    {
+        std::lock_guard<std::mutex> g(sc->editMutex);
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t m = u[i].mesh;
+            std::vector<float>().swap(sc->pendV[m]); std::vector<float>().swap(sc->pendN[m]);
+            if (sc->meshRows[m].light < 0) { sc->pendX[m] = xf[i]; sc->pendXOn[m] = 1; continue; }
+            sc->pendXOn[m] = 0;
+            applyLightMesh(sc, m, lightV[i].data(), lightN[i].empty() ? nullptr : lightN[i].data());
+            lightRows.push_back((uint32_t)sc->meshRows[m].light);
+        }
+        if (!lightRows.empty()) kzInvisibleLights(sc);
+        sc->hostStale = true;
+    }
+    return kzEditXformCommit(sc, jobs.data(), n, lightRows);
 }
 
 } // extern "C"

@@ -213,6 +213,53 @@ void kzInvisibleLights(KzScene *sc) {
     }
 }
 
+// The checks of a whole BSDF row table (kz_scene_create: the description's rows; kz_scene_set_bsdfs: the scene's rows with a batch applied). `who` is put in
+// front of every message ("" or "kz_scene_set_bsdfs: ").
+int kzCheckBsdfs(const char *who, const KzBSDF *rows, uint32_t n, uint32_t nTextures, int32_t integ) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const KzBSDF &b = rows[i];
+        if (b.type < KZ_BSDF_DIFFUSE || b.type > KZ_BSDF_NORMALMAP)
+            return kz_fail(KZ_ERR_UNSUPPORTED, "%sbsdf %u has type %d (supported: diffuse, kazenstandard, mirror, dielectric, ggx, roughconductor, roughplastic, roughdielectric, normalmap)", who, i, b.type);
+        const int32_t ids[4] = {b.albedoTex, b.roughnessTex, b.metallicTex, b.normalTex};
+        for (int32_t id : ids) if (id < 0 || id > (int32_t)nTextures) return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u: texture id %d out of range (0 = constant, 1..%u)", who, i, id, nTextures);
+        // which rows read a Texture child: diffuse/lambertian + ggx "albedo" (bsdf.cpp:259-262, :672-675), kiss (bsdf.cpp:1375-1390)
+        const bool takesAlbedo = b.type == KZ_BSDF_DIFFUSE || b.type == KZ_BSDF_GGX || b.type == KZ_BSDF_KAZENSTANDARD;
+        if ((b.albedoTex && !takesAlbedo) || ((b.roughnessTex || b.metallicTex) && b.type != KZ_BSDF_KAZENSTANDARD) || (b.normalTex && b.type != KZ_BSDF_NORMALMAP))
+            return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u (type %d): a texture id is set on a parameter this model does not read through a texture", who, i, b.type);
+        const bool rough = b.type == KZ_BSDF_ROUGHCONDUCTOR || b.type == KZ_BSDF_ROUGHPLASTIC || b.type == KZ_BSDF_ROUGHDIELECTRIC;
+        if ((b.alphaResolved != 0 && b.alphaResolved != 1) || (b.alphaResolved && !rough))
+            return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u (type %d): alphaResolved = %d (0 or 1, and only roughconductor / roughplastic / roughdielectric rows have a resolved alpha)", who, i, b.type, b.alphaResolved);
+        // path_mats hands the BSDF a record whose intersection is default-constructed (integrator.cpp:168-170): a normal map would read a frame that
+        // was never set (LAB_NOTES H16)
+        if (b.type == KZ_BSDF_NORMALMAP && integ == KZ_INTEGRATOR_PATH_MATS)
+            return kz_fail(KZ_ERR_UNSUPPORTED, "%sbsdf %u is a normalmap: path_mats does not support normal maps (its BSDF record carries no intersection frame)", who, i);
+        if (b.type == KZ_BSDF_NORMALMAP) {                  // bsdf.cpp:391-404: one texture child + one nested BSDF
+            if (b.normalTex == 0) return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u: normalmap without a normal texture", who, i);
+            if (b.nested < 0 || b.nested >= (int32_t)n || rows[b.nested].type == KZ_BSDF_NORMALMAP)
+                return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u: normalmap needs a nested BSDF row that is not itself a normalmap (got %d)", who, i, b.nested);
+        }
+    }
+    return KZ_OK;
+}
+// the rough BSDFs' constructors keep m_alpha = max(MIN_ALPHA, sqr(roughness)) (bsdf.cpp:696-700, :818-822, :956-959): formed once, in float, as they
+// form it (rows that arrive with alphaResolved = 1 carry it already); the kernels read the row's alpha as it is
+void kzResolveBsdf(KzBSDF &b) {
+    if ((b.type == KZ_BSDF_ROUGHCONDUCTOR || b.type == KZ_BSDF_ROUGHPLASTIC || b.type == KZ_BSDF_ROUGHDIELECTRIC) && !b.alphaResolved) {
+        const float MIN_ALPHA = 0.001f, a2 = b.alpha * b.alpha;
+        b.alpha = std::max(MIN_ALPHA, a2); b.alphaResolved = 1;
+    }
+}
+// what the scene's BSDF rows need beyond constant diffuse / kazenstandard (kz_devfn.h KZ_X_*): 1 = other models, 2 = texture-backed parameters, 4 = normal maps
+int32_t kzBsdfExt(const std::vector<KzBSDF> &rows) {
+    int32_t ext = 0;
+    for (const KzBSDF &b : rows) {
+        if (b.type == KZ_BSDF_NORMALMAP) ext |= 4 | 2;
+        else if (b.type > KZ_BSDF_KAZENSTANDARD) ext |= 1;
+        if (b.albedoTex || b.roughnessTex || b.metallicTex) ext |= 2;
+    }
+    return ext;
+}
+
 // ---- camera (camera.cpp:35-68). Eigen is not available: the 4x4 product and inverse are formed in
 // double and narrowed once, unless the caller hands over Eigen's own m_sampleToCamera.
 int kzCameraParams(const KzCamera &c, KzParams &p) {
@@ -308,40 +355,13 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
     if (!(d->camera.rfilter.radius > 0.f) || d->camera.rfilter.radius > 4.0f) return kz_fail(KZ_ERR_UNSUPPORTED, "filter radius %g (supported: (0, 4])", d->camera.rfilter.radius);
     if ((d->nMeshes && !d->meshes) || (d->nBsdfs && !d->bsdfs) || (d->nLights && !d->lights)) return kz_fail(KZ_ERR_INVALID_ARG, "null table with non-zero count");
     if ((d->nTextures && !d->textures) || (d->nImages && !d->images)) return kz_fail(KZ_ERR_INVALID_ARG, "null texture/image table with non-zero count");
-    for (uint32_t i = 0; i < d->nBsdfs; ++i) {
-        const KzBSDF &b = d->bsdfs[i];
-        if (b.type < KZ_BSDF_DIFFUSE || b.type > KZ_BSDF_NORMALMAP)
-            return kz_fail(KZ_ERR_UNSUPPORTED, "bsdf %u has type %d (supported: diffuse, kazenstandard, mirror, dielectric, ggx, roughconductor, roughplastic, roughdielectric, normalmap)", i, b.type);
-        const int32_t ids[4] = {b.albedoTex, b.roughnessTex, b.metallicTex, b.normalTex};
-        for (int32_t id : ids) if (id < 0 || id > (int32_t)d->nTextures) return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u: texture id %d out of range (0 = constant, 1..%u)", i, id, d->nTextures);
-        // which rows read a Texture child: diffuse/lambertian + ggx "albedo" (bsdf.cpp:259-262, :672-675), kiss (bsdf.cpp:1375-1390)
-        const bool takesAlbedo = b.type == KZ_BSDF_DIFFUSE || b.type == KZ_BSDF_GGX || b.type == KZ_BSDF_KAZENSTANDARD;
-        if ((b.albedoTex && !takesAlbedo) || ((b.roughnessTex || b.metallicTex) && b.type != KZ_BSDF_KAZENSTANDARD) || (b.normalTex && b.type != KZ_BSDF_NORMALMAP))
-            return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u (type %d): a texture id is set on a parameter this model does not read through a texture", i, b.type);
-        const bool rough = b.type == KZ_BSDF_ROUGHCONDUCTOR || b.type == KZ_BSDF_ROUGHPLASTIC || b.type == KZ_BSDF_ROUGHDIELECTRIC;
-        if ((b.alphaResolved != 0 && b.alphaResolved != 1) || (b.alphaResolved && !rough))
-            return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u (type %d): alphaResolved = %d (0 or 1, and only roughconductor / roughplastic / roughdielectric rows have a resolved alpha)", i, b.type, b.alphaResolved);
-        // path_mats hands the BSDF a record whose intersection is default-constructed (integrator.cpp:168-170): a normal map would read a frame that
-        // was never set (LAB_NOTES H16)
-        if (b.type == KZ_BSDF_NORMALMAP && integ == KZ_INTEGRATOR_PATH_MATS)
-            return kz_fail(KZ_ERR_UNSUPPORTED, "bsdf %u is a normalmap: path_mats does not support normal maps (its BSDF record carries no intersection frame)", i);
-        if (b.type == KZ_BSDF_NORMALMAP) {                  // bsdf.cpp:391-404: one texture child + one nested BSDF
-            if (b.normalTex == 0) return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u: normalmap without a normal texture", i);
-            if (b.nested < 0 || b.nested >= (int32_t)d->nBsdfs || d->bsdfs[b.nested].type == KZ_BSDF_NORMALMAP)
-                return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u: normalmap needs a nested BSDF row that is not itself a normalmap (got %d)", i, b.nested);
-        }
-    }
+    { const int brc = kzCheckBsdfs("", d->bsdfs, d->nBsdfs, d->nTextures, integ); if (brc != KZ_OK) return brc; }
 
     KzScene *sc = new KzScene();
     std::memset(&sc->prm, 0, sizeof sc->prm);
     sc->bsdfs.assign(d->bsdfs, d->bsdfs + d->nBsdfs);
-    // the rough BSDFs' constructors keep m_alpha = max(MIN_ALPHA, sqr(roughness)) (bsdf.cpp:696-700, :818-822, :956-959): formed here once, in float, as they
-    // form it (rows that arrive with alphaResolved = 1 carry it already); the kernels read the row's alpha as it is
-    for (KzBSDF &b : sc->bsdfs)
-        if ((b.type == KZ_BSDF_ROUGHCONDUCTOR || b.type == KZ_BSDF_ROUGHPLASTIC || b.type == KZ_BSDF_ROUGHDIELECTRIC) && !b.alphaResolved) {
-            const float MIN_ALPHA = 0.001f, a2 = b.alpha * b.alpha;
-            b.alpha = std::max(MIN_ALPHA, a2); b.alphaResolved = 1;
-        }
+    for (KzBSDF &b : sc->bsdfs) kzResolveBsdf(b);         // (the rough models' alpha, formed once)
+    sc->nDescBsdfs = d->nBsdfs; sc->nDescLights = d->nLights;
     { int trc = flattenTextures(d, sc); if (trc != KZ_OK) { delete sc; return trc; } }
     int defaultBsdf = -1;
 
@@ -399,6 +419,7 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
             sc->cdf.insert(sc->cdf.end(), t.begin(), t.end());
             row.light = (int32_t)sc->lightRows.size();
             sc->lightRows.push_back(lr);
+            sc->lightDesc.push_back((uint32_t)km.light);
         }
         sc->meshRows.push_back(row);
         sc->meshNV.push_back(km.nV);
@@ -418,13 +439,7 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
       if (sc->nodes4.size() > (size_t(1) << 26)) { delete sc; return kz_fail(KZ_ERR_UNSUPPORTED, "scene too large: %zu BVH4 packets (limit 2^26 = 4 GB of packets)", sc->nodes4.size()); }
       p.rootRef4 = r4; p.stackBound4 = sb; }
     p.stackDepth = (int32_t)std::max<uint32_t>(2u, sc->bvh.maxDepth + 1);
-    // what the scene's BSDF rows need beyond constant diffuse / kazenstandard (kz_devfn.h KZ_X_*): 1 = other models, 2 = texture-backed parameters, 4 = normal maps
-    p.bsdfExt = 0;
-    for (const KzBSDF &b : sc->bsdfs) {
-        if (b.type == KZ_BSDF_NORMALMAP) p.bsdfExt |= 4 | 2;
-        else if (b.type > KZ_BSDF_KAZENSTANDARD) p.bsdfExt |= 1;
-        if (b.albedoTex || b.roughnessTex || b.metallicTex) p.bsdfExt |= 2;
-    }
+    p.bsdfExt = kzBsdfExt(sc->bsdfs);
     kzInvisibleLights(sc);
     const KzCamera &c = d->camera;
     if ((rc = kzCameraParams(c, p)) != KZ_OK) { delete sc; return rc; }

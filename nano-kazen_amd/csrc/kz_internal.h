@@ -145,6 +145,14 @@ struct KzDevTables {
     uint32_t texPow2;           // every image has power-of-two sides: the periodic wrap of a texel coordinate is a mask (kz_scene_create)
 };
 
+// A mesh's object-to-world matrix as kz_scene_set_transforms applies it (kz_xform.h): the matrix (row-major) and, formed once on the host in double, the nine
+// cofactors of the 4x4 that make up the upper 3x3 of its inverse (before the division by the determinant) and the determinant.
+struct KzXform {
+    float m[16];
+    double c[9];            // inv[0] inv[4] inv[8] | inv[1] inv[5] inv[9] | inv[2] inv[6] inv[10] of the cofactor inverse
+    double det;
+};
+
 struct KzScene {
     // flattened host tables
     std::vector<KzNode> nodes;
@@ -175,6 +183,12 @@ struct KzScene {
     std::vector<uint32_t> slotSrc;      // 4 per BVH4 packet: 2 x BVH2 node + child of the box each slot is quantised from (0xFFFFFFFF: empty slot)
     std::vector<uint32_t> levelStart;   // the BVH2 nodes of depth d are [levelStart[d], levelStart[d + 1]) (breadth-first numbering; filled by the first edit)
     std::vector<std::vector<float>> pendV, pendN;   // per mesh: positions / normals an edit has set that the host's shading records do not hold yet
+    // what kz_scene_set_bsdfs / _lights / _transforms need (kz_edit.cpp)
+    uint32_t nDescBsdfs = 0, nDescLights = 0;       // rows of KzSceneDesc.bsdfs / .lights as given (bsdfs may hold the default diffuse row behind them)
+    std::vector<uint32_t> lightDesc;    // per light row: the index into KzSceneDesc.lights its mesh named
+    std::vector<std::vector<float>> baseV, baseN;   // per mesh: its base data (the V / N of creation or of the last kz_scene_set_vertices), held from its first transform on
+    std::vector<KzXform> pendX;         // per mesh: the transform the host's shading records do not follow yet (pendXOn[m]); applied to baseV / baseN by kzHostSync
+    std::vector<uint8_t> pendXOn;
     bool hostStale = false;             // tris, nodes, nodes4 and bvh.sahCost do not follow the last edit yet (kzHostSync brings them up to date)
     std::mutex editMutex;               // guards the lazy host refit (kzHostSync may be reached from several device threads of kz_render_multi)
     // device replicas, one per GPU the scene is resident on (KzReplicaSet, owned by kz_render.hip; created with the scene)
@@ -193,6 +207,9 @@ int kz_fail(int code, const char *fmt, ...);
 int kzCameraParams(const KzCamera &c, KzParams &p);                     // the camera part of KzParams (pixel beams included)
 void kzLightCdf(const KzTriShade *shade, uint32_t nF, std::vector<float> &t, float &normalization);   // a light mesh's area CDF (t[0] = 0, nF + 1 entries)
 void kzInvisibleLights(KzScene *sc);                                    // ilTris, ilLo / ilHi, ilGid* and shadowFast from the shading records
+int kzCheckBsdfs(const char *who, const KzBSDF *rows, uint32_t n, uint32_t nTextures, int32_t integrator);   // the checks of a whole BSDF row table (kz_scene_create, kz_scene_set_bsdfs)
+void kzResolveBsdf(KzBSDF &b);                                          // a row as the kernels read it (the rough models' alpha)
+int32_t kzBsdfExt(const std::vector<KzBSDF> &rows);                     // KzParams::bsdfExt of a row table
 
 // kz_edit.cpp: the host tables follow every edit before anything reads them (uploads, BVH2 paths, kz_scene_bvh_info, kz_scene_table)
 void kzHostSync(KzScene *scene);
@@ -201,6 +218,12 @@ int kzEditWait(KzScene *scene);                                        // the wo
 int kzEditPrepare(KzScene *scene);                                     // BVH2, triangle vertex indices and slot map resident (once per replica)
 int kzEditBeamsUnbuilt(KzScene *scene);                                // every replica's pixel-beam lists marked unbuilt
 int kzEditVertices(KzScene *scene, const KzVertexUpdate *u, uint32_t n, const std::vector<uint32_t> &lightRows);   // upload + refit + derived rows
+int kzEditBsdfRows(KzScene *scene, const uint32_t *rows, uint32_t n, bool extChanged);   // the listed rows of scene->bsdfs go up; the large-pass probe starts over when bsdfExt changed
+int kzEditLightRows(KzScene *scene);                                   // light rows + invisible-light triangles go up
+struct KzXformJob { uint32_t mesh; const KzXform *x; };
+int kzEditReplicaCount(KzScene *scene);
+int kzEditXformStage(KzScene *scene, const KzXformJob *jobs, uint32_t n, int32_t *bad);   // base data resident, kz_edit_xform into the staging area; *bad = the first job whose non-finite flag a replica raised, or -1
+int kzEditXformCommit(KzScene *scene, const KzXformJob *jobs, uint32_t n, const std::vector<uint32_t> &lightRows);   // refit from the staging area + derived rows
 
 // kz_render.hip
 void kz_device_init(KzScene *scene);          // empty replica set

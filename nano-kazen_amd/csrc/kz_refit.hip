@@ -15,6 +15,7 @@
 
 #include "kz_state.h"
 #include "kz_refit.h"
+#include "kz_xform.h"
 
 #include <algorithm>
 #include <cstring>
@@ -34,6 +35,27 @@ __global__ __launch_bounds__(KZ_EDIT_BLOCK) void kz_edit_shade(KzTriShade *__res
             s.p[3 * v + a] = V[3 * i + a];
             if (N) s.n[3 * v + a] = N[3 * i + a];
         }
+    }
+}
+
+// kz_scene_set_transforms, one lane per vertex: the replica's base V / N of one mesh under its matrix (kz_xform.h) into the staging area, where kz_edit_shade reads them as it
+// reads uploaded vertices. A lane whose position is not finite raises the job's flag with a plain store of 1 (every writer stores the same value: no atomic); the host
+// reads the flags before anything is written to a table.
+__global__ __launch_bounds__(KZ_EDIT_BLOCK) void kz_edit_xform(const float *__restrict__ baseV, const float *__restrict__ baseN, float *__restrict__ outV, float *__restrict__ outN,
+                                                               uint32_t nV, KzXform x, uint32_t *__restrict__ flag) {
+    const uint32_t i = blockIdx.x * KZ_EDIT_BLOCK + threadIdx.x;
+    if (i >= nV) return;                                   // (base and staging hold nV x 3 floats each: kzEditXformStage)
+    const size_t o = 3 * (size_t)i;
+    const float p[3] = {baseV[o], baseV[o + 1], baseV[o + 2]};
+    float q[3];
+    kzXfPoint(x, p, q);
+    outV[o] = q[0]; outV[o + 1] = q[1]; outV[o + 2] = q[2];
+    if (!kzFinite(q[0]) || !kzFinite(q[1]) || !kzFinite(q[2])) flag[0] = 1u;
+    if (baseN) {
+        const float n[3] = {baseN[o], baseN[o + 1], baseN[o + 2]};
+        float r[3];
+        kzXfNormal(x, n, r);
+        outN[o] = r[0]; outN[o + 1] = r[1]; outN[o + 2] = r[2];
     }
 }
 
@@ -136,15 +158,50 @@ int kzEditPrepare(KzScene *scene) {
     });
 }
 
+static int stageRoom(KzDeviceState *ds, size_t floats) {
+    if (ds->editStageCap >= floats) return KZ_OK;
+    if (ds->editStage) { (void)hipFree(ds->editStage); ds->editBytes -= ds->editStageCap * sizeof(float); ds->editStage = nullptr; ds->editStageCap = 0; }
+    KZ_ALLOC(&ds->editStage, floats * sizeof(float));
+    ds->editStageCap = floats; ds->editBytes += floats * sizeof(float);
+    return KZ_OK;
+}
+
+// The refit of one replica behind kz_edit_shade (launched by the caller for every mesh of the batch): triangles, BVH2 levels, padding, BVH4 packets; then the rows the
+// host formed for the light meshes of the batch; the pixel-beam lists are marked unbuilt. Ends with the device idle.
+static int refitChain(KzScene *scene, KzDeviceState *ds, const std::vector<uint32_t> &lightRows) {
+    KzTri *tris = const_cast<KzTri *>(ds->T.tris);
+    KzNode *nodes = const_cast<KzNode *>(ds->T.nodes);
+    if (!scene->tris.empty()) hipLaunchKernelGGL(kz_edit_tris, editGrid(scene->tris.size()), dim3(KZ_EDIT_BLOCK), 0, 0, tris, ds->T.shade, (uint32_t)scene->tris.size());
+    if (!scene->nodes.empty()) {
+        const std::vector<uint32_t> &L = scene->levelStart;
+        for (size_t d = L.size() - 1; d-- > 0;)
+            hipLaunchKernelGGL(kz_edit_level, editGrid(L[d + 1] - L[d]), dim3(KZ_EDIT_BLOCK), 0, 0, nodes, (const KzTri *)tris, ds->T.shade, L[d], L[d + 1] - L[d], ds->editPad);
+        hipLaunchKernelGGL(kz_edit_pad, editGrid(scene->nodes.size()), dim3(KZ_EDIT_BLOCK), 0, 0, nodes, (uint32_t)scene->nodes.size(), (const float *)ds->editPad);
+        if (!scene->nodes4.empty())
+            hipLaunchKernelGGL(kz_edit_quant, editGrid(scene->nodes4.size()), dim3(KZ_EDIT_BLOCK), 0, 0, const_cast<KzNode4 *>(ds->T.nodes4), (uint32_t)scene->nodes4.size(),
+                               (const KzNode *)nodes, (const uint32_t *)ds->editSlotSrc);
+    }
+    HIP_TRY(hipGetLastError());
+    // the light rows, their CDFs and the invisible-light triangles (formed on the host: kz_edit.cpp)
+    for (uint32_t l : lightRows) {
+        const KzLightRow &lr = scene->lightRows[l];
+        HIP_TRY(hipMemcpy(const_cast<float *>(ds->T.cdf) + lr.cdfOffset, scene->cdf.data() + lr.cdfOffset, (lr.nF + 1) * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (!lightRows.empty()) {
+        HIP_TRY(hipMemcpy(const_cast<KzLightRow *>(ds->T.lights), scene->lightRows.data(), scene->lightRows.size() * sizeof(KzLightRow), hipMemcpyHostToDevice));
+        if (!scene->ilTris.empty()) HIP_TRY(hipMemcpy(const_cast<KzTri *>(ds->T.ilTris), scene->ilTris.data(), scene->ilTris.size() * sizeof(KzTri), hipMemcpyHostToDevice));
+    }
+    const int rc = beamsUnbuilt(ds); if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return KZ_OK;
+}
+
 int kzEditVertices(KzScene *scene, const KzVertexUpdate *u, uint32_t n, const std::vector<uint32_t> &lightRows) {
     size_t floats = 0;
     for (uint32_t i = 0; i < n; ++i) floats += 3 * (size_t)u[i].nV * (u[i].N ? 2 : 1);
     return forEachReplica(scene, [&](KzDeviceState *ds) -> int {
-        if (ds->editStageCap < floats) {
-            if (ds->editStage) { (void)hipFree(ds->editStage); ds->editBytes -= ds->editStageCap * sizeof(float); ds->editStage = nullptr; ds->editStageCap = 0; }
-            KZ_ALLOC(&ds->editStage, floats * sizeof(float));
-            ds->editStageCap = floats; ds->editBytes += floats * sizeof(float);
-        }
+        int rc;
+        if ((rc = stageRoom(ds, floats))) return rc;
         KzTriShade *shade = const_cast<KzTriShade *>(ds->T.shade);
         size_t off = 0;
         for (uint32_t i = 0; i < n; ++i) {
@@ -155,40 +212,114 @@ int kzEditVertices(KzScene *scene, const KzVertexUpdate *u, uint32_t n, const st
             HIP_TRY(hipMemcpy(V, x.V, k * sizeof(float), hipMemcpyHostToDevice));
             if (N) HIP_TRY(hipMemcpy(N, x.N, k * sizeof(float), hipMemcpyHostToDevice));
             off += N ? 2 * k : k;
+            // (new base data: a replica that holds the mesh's base V / N for its transforms keeps it current, device to device)
+            if (x.mesh < ds->editBase.size() && ds->editBase[x.mesh]) HIP_TRY(hipMemcpy(ds->editBase[x.mesh], V, (N ? 2 * k : k) * sizeof(float), hipMemcpyDeviceToDevice));
             const KzMeshRow &row = scene->meshRows[x.mesh];
             if (row.nF) hipLaunchKernelGGL(kz_edit_shade, editGrid(row.nF), dim3(KZ_EDIT_BLOCK), 0, 0, shade, (const uint32_t *)ds->editTriVtx, row.triOffset, row.nF, (const float *)V, (const float *)N);
         }
-        KzTri *tris = const_cast<KzTri *>(ds->T.tris);
-        KzNode *nodes = const_cast<KzNode *>(ds->T.nodes);
-        if (!scene->tris.empty()) hipLaunchKernelGGL(kz_edit_tris, editGrid(scene->tris.size()), dim3(KZ_EDIT_BLOCK), 0, 0, tris, ds->T.shade, (uint32_t)scene->tris.size());
-        if (!scene->nodes.empty()) {
-            const std::vector<uint32_t> &L = scene->levelStart;
-            for (size_t d = L.size() - 1; d-- > 0;)
-                hipLaunchKernelGGL(kz_edit_level, editGrid(L[d + 1] - L[d]), dim3(KZ_EDIT_BLOCK), 0, 0, nodes, (const KzTri *)tris, ds->T.shade, L[d], L[d + 1] - L[d], ds->editPad);
-            hipLaunchKernelGGL(kz_edit_pad, editGrid(scene->nodes.size()), dim3(KZ_EDIT_BLOCK), 0, 0, nodes, (uint32_t)scene->nodes.size(), (const float *)ds->editPad);
-            if (!scene->nodes4.empty())
-                hipLaunchKernelGGL(kz_edit_quant, editGrid(scene->nodes4.size()), dim3(KZ_EDIT_BLOCK), 0, 0, const_cast<KzNode4 *>(ds->T.nodes4), (uint32_t)scene->nodes4.size(),
-                                   (const KzNode *)nodes, (const uint32_t *)ds->editSlotSrc);
-        }
-        HIP_TRY(hipGetLastError());
-        // the light rows, their CDFs and the invisible-light triangles (formed on the host: kz_edit.cpp)
-        for (uint32_t l : lightRows) {
-            const KzLightRow &lr = scene->lightRows[l];
-            HIP_TRY(hipMemcpy(const_cast<float *>(ds->T.cdf) + lr.cdfOffset, scene->cdf.data() + lr.cdfOffset, (lr.nF + 1) * sizeof(float), hipMemcpyHostToDevice));
-        }
-        if (!lightRows.empty()) {
-            HIP_TRY(hipMemcpy(const_cast<KzLightRow *>(ds->T.lights), scene->lightRows.data(), scene->lightRows.size() * sizeof(KzLightRow), hipMemcpyHostToDevice));
-            if (!scene->ilTris.empty()) HIP_TRY(hipMemcpy(const_cast<KzTri *>(ds->T.ilTris), scene->ilTris.data(), scene->ilTris.size() * sizeof(KzTri), hipMemcpyHostToDevice));
-        }
-        const int rc = beamsUnbuilt(ds); if (rc) return rc;
+        return refitChain(scene, ds, lightRows);
+    });
+}
+
+int kzEditReplicaCount(KzScene *scene) {
+    KzReplicaSet *rs = replicaSet(scene);
+    std::lock_guard<std::mutex> g(rs->m);
+    return (int)rs->v.size();
+}
+
+int kzEditBsdfRows(KzScene *scene, const uint32_t *rows, uint32_t n, bool extChanged) {
+    return forEachReplica(scene, [&](KzDeviceState *ds) -> int {
+        for (uint32_t i = 0; i < n; ++i)                       // (rows < the table's size: kz_scene_set_bsdfs checked them against the rows of creation)
+            HIP_TRY(hipMemcpy(const_cast<KzBSDF *>(ds->T.bsdfs) + rows[i], &scene->bsdfs[rows[i]], sizeof(KzBSDF), hipMemcpyHostToDevice));
+        // the large-pass probe timed another shade kernel: it starts over (films are the same bits in every mode)
+        if (extChanged) { ds->largeMode = -1; ds->probeLaunched = 0; }
         HIP_TRY(hipDeviceSynchronize());
         return KZ_OK;
     });
 }
 
+int kzEditLightRows(KzScene *scene) {
+    return forEachReplica(scene, [&](KzDeviceState *ds) -> int {
+        if (!ds->ilTrisRoomy) {                                 // a visibility toggle changes the length of the invisible-light list: room for the 64 rows it may have
+            void *p = nullptr;
+            KZ_ALLOC(&p, 64 * sizeof(KzTri));
+            ds->allocs.push_back(p);
+            HIP_TRY(hipMemset(p, 0, 64 * sizeof(KzTri)));
+            ds->T.ilTris = (const KzTri *)p; ds->ilTrisRoomy = true; ds->editBytes += 64 * sizeof(KzTri);
+        }
+        if (!scene->lightRows.empty()) HIP_TRY(hipMemcpy(const_cast<KzLightRow *>(ds->T.lights), scene->lightRows.data(), scene->lightRows.size() * sizeof(KzLightRow), hipMemcpyHostToDevice));
+        if (!scene->ilTris.empty()) HIP_TRY(hipMemcpy(const_cast<KzTri *>(ds->T.ilTris), scene->ilTris.data(), scene->ilTris.size() * sizeof(KzTri), hipMemcpyHostToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        return KZ_OK;
+    });
+}
+
+// floats a job's mesh takes in the staging area (and in its base data): V, then N when the mesh has normals
+static size_t xformFloats(const KzScene *scene, uint32_t mesh) { return 3 * (size_t)scene->meshNV[mesh] * ((scene->meshRows[mesh].flags & 1u) ? 2 : 1); }
+
+int kzEditXformStage(KzScene *scene, const KzXformJob *jobs, uint32_t n, int32_t *bad) {
+    *bad = -1;
+    size_t floats = 0;
+    for (uint32_t i = 0; i < n; ++i) floats += xformFloats(scene, jobs[i].mesh);
+    std::vector<uint32_t> flags(n);
+    return forEachReplica(scene, [&](KzDeviceState *ds) -> int {
+        int rc;
+        if ((rc = stageRoom(ds, floats))) return rc;
+        if (ds->editBase.size() != scene->meshRows.size()) ds->editBase.assign(scene->meshRows.size(), nullptr);
+        if (!ds->editFlag) {
+            void *p = nullptr;
+            KZ_ALLOC(&p, 4096 * sizeof(uint32_t));
+            ds->allocs.push_back(p); ds->editFlag = (uint32_t *)p; ds->editBytes += 4096 * sizeof(uint32_t);
+        }
+        size_t off = 0;
+        for (uint32_t first = 0; first < n; first += 4096) {       // (4096 flags: a longer batch is staged in pieces; nothing but the staging area is written)
+            const uint32_t cnt = std::min<uint32_t>(4096, n - first);
+            HIP_TRY(hipMemset(ds->editFlag, 0, cnt * sizeof(uint32_t)));
+            for (uint32_t j = 0; j < cnt; ++j) {
+                const uint32_t m = jobs[first + j].mesh, nV = scene->meshNV[m];
+                const size_t k = 3 * (size_t)nV, all = xformFloats(scene, m);
+                if (!k) continue;
+                if (!ds->editBase[m]) {                            // this replica's first transform of the mesh: its base V / N go up once (the host holds them: kz_edit.cpp captureBase)
+                    void *p = nullptr;
+                    KZ_ALLOC(&p, all * sizeof(float));
+                    ds->allocs.push_back(p); ds->editBytes += all * sizeof(float);
+                    HIP_TRY(hipMemcpy(p, scene->baseV[m].data(), k * sizeof(float), hipMemcpyHostToDevice));
+                    if (all > k) HIP_TRY(hipMemcpy((float *)p + k, scene->baseN[m].data(), k * sizeof(float), hipMemcpyHostToDevice));
+                    ds->editBase[m] = (float *)p;
+                }
+                const float *bV = ds->editBase[m], *bN = all > k ? bV + k : nullptr;
+                float *V = ds->editStage + off, *N = bN ? V + k : nullptr;
+                off += all;
+                hipLaunchKernelGGL(kz_edit_xform, editGrid(nV), dim3(KZ_EDIT_BLOCK), 0, 0, bV, bN, V, N, nV, *jobs[first + j].x, ds->editFlag + j);
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(flags.data() + first, ds->editFlag, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));      // (blocking: behind the kernels above)
+        }
+        for (uint32_t i = 0; i < n; ++i) if (flags[i] && *bad < 0) *bad = (int32_t)i;
+        return KZ_OK;
+    });
+}
+
+int kzEditXformCommit(KzScene *scene, const KzXformJob *jobs, uint32_t n, const std::vector<uint32_t> &lightRows) {
+    return forEachReplica(scene, [&](KzDeviceState *ds) -> int {
+        KzTriShade *shade = const_cast<KzTriShade *>(ds->T.shade);
+        size_t off = 0;
+        for (uint32_t i = 0; i < n; ++i) {                         // (the staging area as kzEditXformStage laid it out)
+            const uint32_t m = jobs[i].mesh;
+            const size_t k = 3 * (size_t)scene->meshNV[m], all = xformFloats(scene, m);
+            if (!k) continue;
+            const float *V = ds->editStage + off, *N = all > k ? V + k : nullptr;
+            off += all;
+            const KzMeshRow &row = scene->meshRows[m];
+            if (row.nF) hipLaunchKernelGGL(kz_edit_shade, editGrid(row.nF), dim3(KZ_EDIT_BLOCK), 0, 0, shade, (const uint32_t *)ds->editTriVtx, row.triOffset, row.nF, V, N);
+        }
+        return refitChain(scene, ds, lightRows);
+    });
+}
+
 extern "C" int kz_scene_table(KzScene *scene, int device, int table, void *out, size_t cap, size_t *bytes) {
     if (!scene || !bytes) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_table: null argument");
-    if (table < KZ_TABLE_NODES || table > KZ_TABLE_PARAMS) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_table: table %d (KZ_TABLE_NODES .. KZ_TABLE_PARAMS)", table);
+    if (table < KZ_TABLE_NODES || table > KZ_TABLE_BSDFS) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_table: table %d (KZ_TABLE_NODES .. KZ_TABLE_BSDFS)", table);
     if (device >= 0 && table == KZ_TABLE_PARAMS) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_table: the render constants (KZ_TABLE_PARAMS) are a host table: device must be -1");
     kzHostSync(scene);
     const void *host = nullptr; size_t n = 0;
@@ -200,6 +331,7 @@ extern "C" int kz_scene_table(KzScene *scene, int device, int table, void *out, 
     case KZ_TABLE_CDF: host = scene->cdf.data(); n = scene->cdf.size() * sizeof(float); break;
     case KZ_TABLE_LIGHTS: host = scene->lightRows.data(); n = scene->lightRows.size() * sizeof(KzLightRow); break;
     case KZ_TABLE_IL_TRIS: host = scene->ilTris.data(); n = scene->ilTris.size() * sizeof(KzTri); break;
+    case KZ_TABLE_BSDFS: host = scene->bsdfs.data(); n = scene->bsdfs.size() * sizeof(KzBSDF); break;
     default: host = &scene->prm; n = sizeof(KzParams); break;
     }
     *bytes = n;
@@ -218,6 +350,7 @@ extern "C" int kz_scene_table(KzScene *scene, int device, int table, void *out, 
     case KZ_TABLE_SHADE: src = ds->T.shade; break;
     case KZ_TABLE_CDF: src = ds->T.cdf; break;
     case KZ_TABLE_LIGHTS: src = ds->T.lights; break;
+    case KZ_TABLE_BSDFS: src = ds->T.bsdfs; break;
     default: src = ds->T.ilTris; break;
     }
     HIP_TRY(hipDeviceSynchronize());

@@ -209,6 +209,9 @@ struct KzDeviceState {
     // Edits (kz_refit.hip): the triangles' vertex indices and the BVH4 slot map, uploaded on the replica's first kz_scene_set_vertices (with the BVH2, which the
     // refit keeps resident), a staging area for the vertex data of a batch, and the refit's absolute box padding. editBytes: what they hold.
     uint32_t *editTriVtx = nullptr, *editSlotSrc = nullptr; float *editPad = nullptr; float *editStage = nullptr; size_t editStageCap = 0; size_t editBytes = 0;
+    // kz_scene_set_transforms: per mesh its base V (then N) on this replica, there from the replica's first transform of the mesh (kz_scene_set_vertices keeps it current);
+    // the flag kz_edit_xform raises for a non-finite position. kz_scene_set_lights: T.ilTris re-allocated once to hold the 64 rows a visibility toggle may need.
+    std::vector<float *> editBase; uint32_t *editFlag = nullptr; bool ilTrisRoomy = false;
 };
 struct KzReplicaSet { std::mutex m; std::vector<KzDeviceState *> v; };
 

@@ -1,4 +1,4 @@
-"""Thin handle around a KzScene* (the library's scene + device tables + device film; its camera and vertex data can be edited in place)."""
+"""Thin handle around a KzScene* (the library's scene + device tables + device film; its camera, vertex data, materials, lights and mesh transforms can be edited in place)."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +14,7 @@ class Scene:
     def __init__(self, desc, device=None, lib=None):
         self.lib = lib or abi.load_library()      # (lib: a development build of the library, abi.load_dev_library() - tests only)
         self.desc = desc
+        self._base = {}                                      # mesh -> (V, N) base data of the meshes a transform has placed (set_transforms)
         cdesc = desc.to_c()
         h = C.c_void_p()
         abi.check(self.lib, self.lib.kz_scene_create(C.byref(cdesc), C.byref(h)))
@@ -70,6 +71,74 @@ class Scene:
         abi.check(self.lib, self.lib.kz_scene_set_vertices(self.h, arr, len(rows)))
         for m, V, N in keep:
             self.desc.meshes[m] = dict(self.desc.meshes[m], V=V.copy(), N=None if N is None else N.copy())
+            self._base.pop(m, None)                          # new base data: the mesh's transform is gone
+
+    def set_bsdfs(self, updates):
+        """kz_scene_set_bsdfs (include/kazen_mi355x_edit.h) for {mesh: bsdf dict}: the edited description is flattened as kz_scene_create's input is and the BSDF rows
+        that differ are sent. ValueError unless the texture and image tables, the mesh -> row assignment and the row count come out as before (create a new scene
+        for those). Scene.desc follows."""
+        import copy
+        old, new = copy.copy(self.desc), copy.copy(self.desc)
+        new.meshes = list(self.desc.meshes)
+        for m, b in updates.items():
+            if new.meshes[int(m)]["bsdf"] is None or b is None:
+                raise ValueError("mesh %d: a mesh without a BSDF keeps the default row, and a mesh with one keeps a row: create a new scene" % int(m))
+            new.meshes[int(m)] = dict(new.meshes[int(m)], bsdf=b)
+        co = old.to_c()
+        new._tex_seed = old._tex_list                        # the scene's textures keep their ids; a texture it does not have would be appended (refused below)
+        cn = new.to_c()
+        io, im = old._keep[-1], new._keep[-1]
+        same = (co.nBsdfs == cn.nBsdfs and co.nTextures == cn.nTextures and co.nImages == cn.nImages
+                and all(co.meshes[i].bsdf == cn.meshes[i].bsdf for i in range(co.nMeshes))
+                and all(bytes(co.textures[i]) == bytes(cn.textures[i]) for i in range(co.nTextures))
+                and all(a is b or (a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b)) for a, b in zip(io, im)))
+        if not same:
+            raise ValueError("set_bsdfs: the edit changes the texture table, the image table, the mesh -> row assignment or the row count: create a new scene")
+        rows = [abi.KzBsdfUpdate(i, cn.bsdfs[i]) for i in range(cn.nBsdfs) if bytes(co.bsdfs[i]) != bytes(cn.bsdfs[i])]
+        arr = (abi.KzBsdfUpdate * max(1, len(rows)))(*rows)
+        abi.check(self.lib, self.lib.kz_scene_set_bsdfs(self.h, arr, len(rows)))
+        self.desc.meshes, self.desc._tex_seed = new.meshes, new._tex_seed
+
+    def set_lights(self, updates):
+        """kz_scene_set_lights for {mesh: light dict (scenes.area)}: colour, intensity and lightPrimaryVisibility of meshes that emit already. Scene.desc follows."""
+        lights = [i for i, m in enumerate(self.desc.meshes) if m["light"] is not None]
+        rows = []
+        for m, l in updates.items():
+            if int(m) not in lights or l is None:
+                raise ValueError("mesh %d: which meshes emit does not change: create a new scene" % int(m))
+            k = abi.KzLight()
+            k.color[:] = l["color"]
+            k.intensity = l["intensity"]
+            k.primaryVisibility = 1 if l["lightPrimaryVisibility"] else 0
+            rows.append(abi.KzLightUpdate(lights.index(int(m)), k))
+        arr = (abi.KzLightUpdate * max(1, len(rows)))(*rows)
+        abi.check(self.lib, self.lib.kz_scene_set_lights(self.h, arr, len(rows)))
+        meshes = list(self.desc.meshes)
+        for m, l in updates.items():
+            meshes[int(m)] = dict(meshes[int(m)], light=dict(l))
+        self.desc.meshes = meshes
+
+    def set_transforms(self, updates):
+        """kz_scene_set_transforms for {mesh: 4x4 (row-major, as camera toWorld)}: the mesh's BASE data (its V / N at creation or from its last set_vertices) under
+        the matrix; transforms of one mesh do not compose. Scene.desc holds the transformed arrays afterwards (scenes.transform_vertices states the arithmetic)."""
+        from .scenes import transform_vertices
+        rows, mats = [], {}
+        for m, M in updates.items():
+            M = np.ascontiguousarray(M, np.float32).reshape(4, 4)
+            mats[int(m)] = M
+            k = abi.KzTransformUpdate()
+            k.mesh = int(m) if int(m) >= 0 else 0xFFFFFFFF
+            k.toWorld[:] = M.reshape(16).tolist()
+            rows.append(k)
+        arr = (abi.KzTransformUpdate * max(1, len(rows)))(*rows)
+        abi.check(self.lib, self.lib.kz_scene_set_transforms(self.h, arr, len(rows)))
+        meshes = list(self.desc.meshes)
+        for m, M in mats.items():
+            if m not in self._base:
+                self._base[m] = (meshes[m]["V"], meshes[m]["N"])
+            V, N = transform_vertices(M, *self._base[m])
+            meshes[m] = dict(meshes[m], V=V, N=N)
+        self.desc.meshes = meshes
 
     def table(self, table, device=-1):
         """kz_scene_table: a flat table of the scene as raw bytes (numpy uint8): device -1 = the host copy, else that replica's (abi.KZ_TABLE_*)."""

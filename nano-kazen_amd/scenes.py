@@ -150,6 +150,44 @@ def look_at(origin, target, up):
     return m.astype(np.float32)
 
 
+def transform_vertices(M, V, N=None):
+    """A mesh's base V / N under the 4x4 M (row-major), operation for operation what kz_scene_set_transforms computes (csrc/kz_xform.h) and what the loaders
+    compute at load (xmlscene.py xf_point / xf_normal): a point is four float32 dot products ((m0 x + m1 y) + m2 z) + m3 and three float32 divisions by w; a
+    normal is the inverse transpose of the upper 3x3 from the float64 cofactor inverse (unchanged when the determinant is 0), narrowed once, then normalised in
+    float32 when its squared length is > 0. Returns (V', N') as float32 arrays (N' None when N is)."""
+    M = np.ascontiguousarray(M, np.float32).reshape(4, 4)
+    V = np.ascontiguousarray(V, np.float32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        q = [((M[i, 0] * V[:, 0] + M[i, 1] * V[:, 1]) + M[i, 2] * V[:, 2]) + M[i, 3] for i in range(4)]
+        Vt = np.stack([q[0] / q[3], q[1] / q[3], q[2] / q[3]], 1).astype(np.float32)
+        if N is None:
+            return Vt, None
+        a = [float(v) for v in M.reshape(-1)]
+        c = [[a[5]*a[10]*a[15]-a[5]*a[11]*a[14]-a[9]*a[6]*a[15]+a[9]*a[7]*a[14]+a[13]*a[6]*a[11]-a[13]*a[7]*a[10],
+              -a[4]*a[10]*a[15]+a[4]*a[11]*a[14]+a[8]*a[6]*a[15]-a[8]*a[7]*a[14]-a[12]*a[6]*a[11]+a[12]*a[7]*a[10],
+              a[4]*a[9]*a[15]-a[4]*a[11]*a[13]-a[8]*a[5]*a[15]+a[8]*a[7]*a[13]+a[12]*a[5]*a[11]-a[12]*a[7]*a[9]],
+             [-a[1]*a[10]*a[15]+a[1]*a[11]*a[14]+a[9]*a[2]*a[15]-a[9]*a[3]*a[14]-a[13]*a[2]*a[11]+a[13]*a[3]*a[10],
+              a[0]*a[10]*a[15]-a[0]*a[11]*a[14]-a[8]*a[2]*a[15]+a[8]*a[3]*a[14]+a[12]*a[2]*a[11]-a[12]*a[3]*a[10],
+              -a[0]*a[9]*a[15]+a[0]*a[11]*a[13]+a[8]*a[1]*a[15]-a[8]*a[3]*a[13]-a[12]*a[1]*a[11]+a[12]*a[3]*a[9]],
+             [a[1]*a[6]*a[15]-a[1]*a[7]*a[14]-a[5]*a[2]*a[15]+a[5]*a[3]*a[14]+a[13]*a[2]*a[7]-a[13]*a[3]*a[6],
+              -a[0]*a[6]*a[15]+a[0]*a[7]*a[14]+a[4]*a[2]*a[15]-a[4]*a[3]*a[14]-a[12]*a[2]*a[7]+a[12]*a[3]*a[6],
+              a[0]*a[5]*a[15]-a[0]*a[7]*a[13]-a[4]*a[1]*a[15]+a[4]*a[3]*a[13]+a[12]*a[1]*a[7]-a[12]*a[3]*a[5]]]
+        i12 = -a[4]*a[9]*a[14]+a[4]*a[10]*a[13]+a[8]*a[5]*a[14]-a[8]*a[6]*a[13]-a[12]*a[5]*a[10]+a[12]*a[6]*a[9]
+        det = a[0] * c[0][0] + a[1] * c[0][1] + a[2] * c[0][2] + a[3] * i12
+        N = np.ascontiguousarray(N, np.float32).reshape(-1, 3)
+        if det == 0.0:
+            r = N.copy()
+        else:
+            n = N.astype(np.float64)
+            r = np.stack([((c[i][0] * n[:, 0] + c[i][1] * n[:, 1]) + c[i][2] * n[:, 2]) / det for i in range(3)], 1).astype(np.float32)
+        l2 = (r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2]
+        ln = np.sqrt(l2)
+        pos = l2 > 0
+        Nt = r.copy()
+        Nt[pos] = (r[pos] / ln[pos, None]).astype(np.float32)
+    return Vt, Nt
+
+
 # KzIntegrator.type of each integrator the library renders (include/kazen_mi355x.h KZ_INTEGRATOR_*)
 INTEGRATOR_TAGS = {"path_mis": 0, "normals": 1, "ao": 2, "path_mats": 3}
 
@@ -253,6 +291,10 @@ class SceneDescription:
             else:
                 getattr(k, field)[:] = v
 
+        # (Scene.set_bsdfs: the textures of the scene as created keep their ids, whatever order the edited rows name them in)
+        for t in getattr(self, "_tex_seed", ()):
+            tex_id(t)
+
         cb = (abi.KzBSDF * max(1, len(bsdfs)))()
         for i, b in enumerate(bsdfs):
             k = cb[i]
@@ -313,6 +355,7 @@ class SceneDescription:
             ci[i].height, ci[i].width, ci[i].channels = a.shape
             ci[i].format = abi.KZ_PIXEL_U8 if a.dtype == np.uint8 else abi.KZ_PIXEL_F32
         self.n_bsdf_rows, self.n_textures = len(bsdfs), len(textures)
+        self._tex_list = [row["t"] for row in textures]
         cl = (abi.KzLight * max(1, len(lights)))()
         for i, l in enumerate(lights):
             cl[i].color[:] = l["color"]

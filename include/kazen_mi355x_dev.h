@@ -112,7 +112,7 @@ int kz_pass_mode_info(KzScene *scene, int device, KzPassModeInfo *out);
 int kz_last_grow_note(KzScene *scene, char *buf, size_t cap);
 
 /* ---- DEVELOPMENT BUILDS ONLY (a library compiled with -DKZ_EXPERIMENTS: kz_build_flags() & KZ_BUILD_EXPERIMENTS; nano-kazen_amd/csrc/variants/experiments).
- * These five are process-global state - the product library does not contain them (`nm -D libkazen_mi355x.so | grep kz_debug` is empty), so that nothing behind the
+ * These six are process-global state - the product library does not contain them (`nm -D libkazen_mi355x.so | grep kz_debug` is empty), so that nothing behind the
  * product ABI depends on state outside the objects the caller holds. The tests that need them load the development variant.
  *   kz_debug_fail_alloc    the nth device allocation made from now on by the calling thread fails with KZ_ERR_OOM (0 = off): a failure in the middle of a call
  *                          releases what the call had allocated.
@@ -130,6 +130,12 @@ void kz_debug_fail_device(int device, int nth);
 void kz_debug_grow_delay(int ms);
 void kz_debug_trace(int on);
 void kz_debug_alias_devices(int n);
+/*   kz_debug_rr_ahead      0 = the shade kernels of renders launched from now on queue every bounce ray, as they did before the roulette-ahead test (a path whose
+ *                          next roulette draw ends it keeps its bounce ray only if the ray hits an emitter triangle); 1 = the test as the scene has it (the
+ *                          default: on, except while the counters of kz_set_stats run - they state the work of the reference's loop); 2 = counted renders
+ *                          take it too, so that the ray counter shows what it skips. The films are the same bits in every mode: one process renders them
+ *                          all (tests/test_rr_ahead_gpu.py). */
+void kz_debug_rr_ahead(int on);
 
 /* ---- the pass planner (nano-kazen_amd/csrc/kz_plan.cpp: pure host arithmetic, no GPU, no state) through the ABI: what kz_render would decide for a call.
  * tests/test_plan_cpu.py tabulates it for the BASELINE configs - the table is the documentation of the pass policy. */
@@ -169,7 +175,9 @@ int kz_kat_pow4(int32_t spp, int32_t *out4);
  * replica's table. *bytes = the table's size; at most `cap` bytes are copied to `out` (out may be NULL to ask for the size). A replica's BVH2 table
  * (KZ_TABLE_NODES) is there once a BVH2 path or an edit has used it (else KZ_ERR_STATE); KZ_TABLE_PARAMS is host-only (the render constants). */
 enum { KZ_TABLE_NODES = 0, KZ_TABLE_NODES4 = 1, KZ_TABLE_TRIS = 2, KZ_TABLE_SHADE = 3, KZ_TABLE_CDF = 4, KZ_TABLE_LIGHTS = 5, KZ_TABLE_IL_TRIS = 6, KZ_TABLE_PARAMS = 7,
-       KZ_TABLE_BSDFS = 8 /* the resolved BSDF rows (the default diffuse row behind the description's, when a mesh has no BSDF) */ };
+       KZ_TABLE_BSDFS = 8 /* the resolved BSDF rows (the default diffuse row behind the description's, when a mesh has no BSDF) */,
+       KZ_TABLE_EM_TRIS = 9 /* the emitter triangles of the roulette-ahead test (48-B leaf-triangle rows of every light mesh) and, behind them, one header row:
+                               floats 0..2 = the box's low corner, 3..5 = its high corner, word 9 = the row count or 0xFFFFFFFF (test off for this scene) */ };
 int kz_scene_table(KzScene *scene, int device, int table, void *out, size_t cap, size_t *bytes);
 
 /* How the library was built: bit 0 (KZ_BUILD_EXPERIMENTS) = it is the development variant (-DKZ_EXPERIMENTS), which exports the kz_debug_* hooks. */

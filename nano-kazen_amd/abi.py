@@ -195,9 +195,9 @@ EXPORTS = ["kz_scene_create", "kz_scene_destroy", "kz_scene_bvh_info", "kz_scene
            "kz_plan_passes", "kz_plan_schedule", "kz_pass_mode_info", "kz_scene_table"]
 # what include/kazen_mi355x_edit.h declares (checked by tests/test_scene_edit_cpu.py): editing a scene that already exists
 EDIT_EXPORTS = ["kz_scene_set_camera", "kz_scene_set_vertices", "kz_scene_set_bsdfs", "kz_scene_set_lights", "kz_scene_set_transforms"]
-KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS = range(9)
+KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
-DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices"]
+DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KZ_LIB_PATH: a development build of the library (scripts/build_variant.sh) instead of the in-tree one; probes only
@@ -214,7 +214,7 @@ class KzError(RuntimeError):
 
 def load_dev_library():
     """The development variant of the library (-DKZ_EXPERIMENTS: the same sources plus the hooks that are process-global state - kz_debug_fail_alloc /
-    fail_device / grow_delay / trace / alias_devices). Only tests load it; a second copy of the library in one process is a separate world
+    fail_device / grow_delay / trace / alias_devices / rr_ahead). Only tests load it; a second copy of the library in one process is a separate world
     (its own device pools, its own replicas)."""
     return load_library(DEV_LIB_PATH)
 

@@ -326,3 +326,10 @@ int kz_light_query(KzScene *scene, uint32_t n, const int32_t *light, const float
 
 
 } // extern "C"
+
+// ---- development builds only (-DKZ_EXPERIMENTS, kazen_mi355x_dev.h): process-global state, absent from the product library
+#ifdef KZ_EXPERIMENTS
+// kz_debug_rr_ahead: whether the shade kernels of the path_mis wavefront pipeline take the roulette-ahead test (kz_render.hip wfPass reads it per pass)
+std::atomic<int> g_kzRrAhead{1};
+extern "C" void kz_debug_rr_ahead(int on) { g_kzRrAhead.store(on == 2 ? 2 : on ? 1 : 0); }
+#endif

@@ -211,6 +211,40 @@ void kzInvisibleLights(KzScene *sc) {
         float m = std::max(std::fabs(p.ilLo[a]), std::fabs(p.ilHi[a]));
         if (std::isfinite(m)) { float e = m * 4e-7f + 1e-30f; p.ilLo[a] -= e; p.ilHi[a] += e; }
     }
+    kzEmitterTris(sc);
+}
+
+// Emitter triangles for the roulette-ahead test of kz_wf_shade (kz_wavefront.h wfShadeSurvivor): the triangles of EVERY light mesh - a bounce ray that hits a
+// light adds its radiance whatever the light's primary visibility, which concerns the first hit only (H6) - in the leaf-triangle form, and their box with the
+// padding of the BVH boxes. The test is off (KZ_EM_OFF, no rows) for more than KZ_EM_MAX triangles, for a scene with a background (a miss then adds
+// radiance) and for the integrators other than path_mis. No lights and no background: an empty table, no bounce ray of an ended path can add anything.
+void kzEmitterTris(KzScene *sc) {
+    const KzParams &p = sc->prm;
+    sc->emTris.clear();
+    for (int a = 0; a < 3; ++a) { sc->emLo[a] = INFINITY; sc->emHi[a] = -INFINITY; }
+    size_t total = 0;
+    for (const KzLightRow &lr : sc->lightRows) total += lr.nF;
+    const bool on = total <= KZ_EM_MAX && !p.bgPresent && p.integrator == KZ_INTEGRATOR_PATH_MIS;
+    if (on) for (const KzLightRow &lr : sc->lightRows)
+        for (uint32_t f = 0; f < lr.nF; ++f) {
+            const KzTriShade &s = sc->shade[lr.triOffset + f];
+            KzTri t; std::memset(&t, 0, sizeof t);
+            for (int a = 0; a < 3; ++a) {
+                t.p0[a] = s.p[a]; t.e1[a] = s.p[3 + a] - s.p[a]; t.e2[a] = s.p[6 + a] - s.p[a];
+                for (int v = 0; v < 3; ++v) { sc->emLo[a] = std::min(sc->emLo[a], s.p[3 * v + a]); sc->emHi[a] = std::max(sc->emHi[a], s.p[3 * v + a]); }
+            }
+            t.mesh = lr.mesh; t.prim = f; t.gid = lr.triOffset + f;
+            sc->emTris.push_back(t);
+        }
+    sc->nEmTris = on ? (uint32_t)sc->emTris.size() : KZ_EM_OFF;
+    for (int a = 0; a < 3; ++a) {        // same padding as BVH boxes
+        float m = std::max(std::fabs(sc->emLo[a]), std::fabs(sc->emHi[a]));
+        if (std::isfinite(m)) { float e = m * 4e-7f + 1e-30f; sc->emLo[a] -= e; sc->emHi[a] += e; }
+    }
+    KzTri h; std::memset(&h, 0, sizeof h);          // the header row (kz_internal.h)
+    for (int a = 0; a < 3; ++a) { h.p0[a] = sc->emLo[a]; h.e1[a] = sc->emHi[a]; }
+    h.mesh = sc->nEmTris;
+    sc->emTris.push_back(h);
 }
 
 // The checks of a whole BSDF row table (kz_scene_create: the description's rows; kz_scene_set_bsdfs: the scene's rows with a batch applied). `who` is put in
@@ -490,6 +524,7 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
         }
         for (int a = 0; a < 3; ++a) p.bgRadiance[a] = d->background.present ? d->background.intensity * col[a] : 0.f;
     }
+    kzEmitterTris(sc);                   // (again, now that the integrator and the background are known)
     // ---- sampler
     p.samplerType = d->sampler.type;
     p.seed = d->sampler.seed;

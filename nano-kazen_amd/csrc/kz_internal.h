@@ -13,6 +13,8 @@
 #define KZ_MAX_LEAF 4            // triangles per leaf
 #define KZ_MAX_FILTER_TAPS 9     // candidates per axis the film kernel supports (filter radius <= 4)
 #define KZ_PATH_MATS_MAX_DEPTH 512   // bounces of a path_mats path at most (the reference has no cap: LAB_NOTES H15)
+#define KZ_EM_MAX 64             // emitter triangles the roulette-ahead test of kz_wf_shade takes (one per lane of a wave)
+#define KZ_EM_OFF 0xFFFFFFFFu    // KzDevTables::nEmTris of a scene without that test (more triangles, a background, another integrator)
 
 // ---- device formats (DESIGN.md "data layout in HBM") ---------------------------------------------
 // BVH2 node, 64 B, four 16-B quads -> four global_load_dwordx4 per lane:
@@ -143,6 +145,12 @@ struct KzDevTables {
     const KzImageRow *images;
     const uint8_t *texels;
     uint32_t texPow2;           // every image has power-of-two sides: the periodic wrap of a texel coordinate is a mask (kz_scene_create)
+    // Roulette ahead (kz_wavefront.h wfShadeSurvivor): the triangles of every light mesh, visible or not, and their padded box. A path whose next roulette draw
+    // ends it keeps its bounce ray only if the ray hits one of them. (The render constants would be the place for the count and the box, but sizeof(KzParams)
+    // and its offsets are pinned by the edit tests: they travel here, in the kernel argument next to the pointer.)
+    uint32_t nEmTris = KZ_EM_OFF;   // rows of emTris (<= KZ_EM_MAX), or KZ_EM_OFF
+    const KzTri *emTris;
+    float emLo[3], emHi[3];
 };
 
 // A mesh's object-to-world matrix as kz_scene_set_transforms applies it (kz_xform.h): the matrix (row-major) and, formed once on the host in double, the nine
@@ -168,6 +176,8 @@ struct KzScene {
     std::vector<float> pixelSamples;
     std::vector<KzPcgJump> jump;
     std::vector<KzTri> ilTris;
+    // emitter triangles (kzEmitterTris): nEmTris rows, then ONE header row - p0 = emLo, e1 = emHi, mesh = nEmTris - so that kz_scene_table shows the count and the box too
+    std::vector<KzTri> emTris; uint32_t nEmTris = KZ_EM_OFF; float emLo[3] = {0, 0, 0}, emHi[3] = {0, 0, 0};
     std::vector<KzTexProg> texProgs;
     std::vector<KzTexOp> texOps;
     std::vector<KzImageRow> images;
@@ -206,7 +216,8 @@ int kz_collapse_bvh4(const std::vector<KzNode> &nodes, uint32_t rootRef, std::ve
 int kz_fail(int code, const char *fmt, ...);
 int kzCameraParams(const KzCamera &c, KzParams &p);                     // the camera part of KzParams (pixel beams included)
 void kzLightCdf(const KzTriShade *shade, uint32_t nF, std::vector<float> &t, float &normalization);   // a light mesh's area CDF (t[0] = 0, nF + 1 entries)
-void kzInvisibleLights(KzScene *sc);                                    // ilTris, ilLo / ilHi, ilGid* and shadowFast from the shading records
+void kzInvisibleLights(KzScene *sc);                                    // ilTris, ilLo / ilHi, ilGid* and shadowFast from the shading records (and kzEmitterTris)
+void kzEmitterTris(KzScene *sc);                                        // emTris, nEmTris, emLo / emHi from the shading records, the background and the integrator
 int kzCheckBsdfs(const char *who, const KzBSDF *rows, uint32_t n, uint32_t nTextures, int32_t integrator);   // the checks of a whole BSDF row table (kz_scene_create, kz_scene_set_bsdfs)
 void kzResolveBsdf(KzBSDF &b);                                          // a row as the kernels read it (the rough models' alpha)
 int32_t kzBsdfExt(const std::vector<KzBSDF> &rows);                     // KzParams::bsdfExt of a row table

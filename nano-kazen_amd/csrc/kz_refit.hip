@@ -190,6 +190,7 @@ static int refitChain(KzScene *scene, KzDeviceState *ds, const std::vector<uint3
     if (!lightRows.empty()) {
         HIP_TRY(hipMemcpy(const_cast<KzLightRow *>(ds->T.lights), scene->lightRows.data(), scene->lightRows.size() * sizeof(KzLightRow), hipMemcpyHostToDevice));
         if (!scene->ilTris.empty()) HIP_TRY(hipMemcpy(const_cast<KzTri *>(ds->T.ilTris), scene->ilTris.data(), scene->ilTris.size() * sizeof(KzTri), hipMemcpyHostToDevice));
+        const int erc = kzEmitterUpload(scene, ds); if (erc) return erc;
     }
     const int rc = beamsUnbuilt(ds); if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
@@ -249,6 +250,7 @@ int kzEditLightRows(KzScene *scene) {
         }
         if (!scene->lightRows.empty()) HIP_TRY(hipMemcpy(const_cast<KzLightRow *>(ds->T.lights), scene->lightRows.data(), scene->lightRows.size() * sizeof(KzLightRow), hipMemcpyHostToDevice));
         if (!scene->ilTris.empty()) HIP_TRY(hipMemcpy(const_cast<KzTri *>(ds->T.ilTris), scene->ilTris.data(), scene->ilTris.size() * sizeof(KzTri), hipMemcpyHostToDevice));
+        { const int erc = kzEmitterUpload(scene, ds); if (erc) return erc; }
         HIP_TRY(hipDeviceSynchronize());
         return KZ_OK;
     });
@@ -319,7 +321,7 @@ int kzEditXformCommit(KzScene *scene, const KzXformJob *jobs, uint32_t n, const 
 
 extern "C" int kz_scene_table(KzScene *scene, int device, int table, void *out, size_t cap, size_t *bytes) {
     if (!scene || !bytes) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_table: null argument");
-    if (table < KZ_TABLE_NODES || table > KZ_TABLE_BSDFS) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_table: table %d (KZ_TABLE_NODES .. KZ_TABLE_BSDFS)", table);
+    if (table < KZ_TABLE_NODES || table > KZ_TABLE_EM_TRIS) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_table: table %d (KZ_TABLE_NODES .. KZ_TABLE_EM_TRIS)", table);
     if (device >= 0 && table == KZ_TABLE_PARAMS) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_table: the render constants (KZ_TABLE_PARAMS) are a host table: device must be -1");
     kzHostSync(scene);
     const void *host = nullptr; size_t n = 0;
@@ -332,6 +334,7 @@ extern "C" int kz_scene_table(KzScene *scene, int device, int table, void *out, 
     case KZ_TABLE_LIGHTS: host = scene->lightRows.data(); n = scene->lightRows.size() * sizeof(KzLightRow); break;
     case KZ_TABLE_IL_TRIS: host = scene->ilTris.data(); n = scene->ilTris.size() * sizeof(KzTri); break;
     case KZ_TABLE_BSDFS: host = scene->bsdfs.data(); n = scene->bsdfs.size() * sizeof(KzBSDF); break;
+    case KZ_TABLE_EM_TRIS: host = scene->emTris.data(); n = scene->emTris.size() * sizeof(KzTri); break;
     default: host = &scene->prm; n = sizeof(KzParams); break;
     }
     *bytes = n;
@@ -351,6 +354,7 @@ extern "C" int kz_scene_table(KzScene *scene, int device, int table, void *out, 
     case KZ_TABLE_CDF: src = ds->T.cdf; break;
     case KZ_TABLE_LIGHTS: src = ds->T.lights; break;
     case KZ_TABLE_BSDFS: src = ds->T.bsdfs; break;
+    case KZ_TABLE_EM_TRIS: src = ds->T.emTris; break;
     default: src = ds->T.ilTris; break;
     }
     HIP_TRY(hipDeviceSynchronize());

@@ -103,6 +103,23 @@ template <class Tp> static int uploadVec(KzDeviceState *ds, const std::vector<Tp
     return KZ_OK;
 }
 
+// The emitter triangles of the roulette-ahead test (kz_host.cpp kzEmitterTris) on one replica: room for KZ_EM_MAX rows + the header row from the start, so
+// that an edit only copies; the count and the box travel in the kernel argument. The caller has made the replica's device current.
+int kzEmitterUpload(KzScene *scene, KzDeviceState *ds) {
+    if (!ds->T.emTris) {
+        void *p = nullptr;
+        KZ_ALLOC(&p, (KZ_EM_MAX + 1) * sizeof(KzTri));
+        ds->allocs.push_back(p);
+        HIP_TRY(hipMemset(p, 0, (KZ_EM_MAX + 1) * sizeof(KzTri)));
+        ds->T.emTris = (const KzTri *)p;
+    }
+    if (!scene->emTris.empty() && scene->emTris.size() <= KZ_EM_MAX + 1)
+        HIP_TRY(hipMemcpy(const_cast<KzTri *>(ds->T.emTris), scene->emTris.data(), scene->emTris.size() * sizeof(KzTri), hipMemcpyHostToDevice));
+    ds->T.nEmTris = scene->nEmTris;
+    for (int a = 0; a < 3; ++a) { ds->T.emLo[a] = scene->emLo[a]; ds->T.emHi[a] = scene->emHi[a]; }
+    return KZ_OK;
+}
+
 static void releaseReplica(KzDeviceState *ds) {
     (void)hipSetDevice(ds->hipDevice);
     (void)hipDeviceSynchronize();
@@ -218,6 +235,7 @@ static int uploadReplica(KzScene *scene, KzDeviceState *ds) {
     std::vector<float> ft(scene->filter, scene->filter + KZ_FILTER_RESOLUTION + 1);
     if ((rc = uploadVec(ds, ft, &ds->T.filter))) return rc;
     if ((rc = uploadVec(ds, scene->ilTris, &ds->T.ilTris))) return rc;
+    if ((rc = kzEmitterUpload(scene, ds))) return rc;
     if ((rc = uploadVec(ds, scene->texProgs, &ds->T.texProgs))) return rc;
     if ((rc = uploadVec(ds, scene->texOps, &ds->T.texOps))) return rc;
     if ((rc = uploadVec(ds, scene->images, &ds->T.images))) return rc;
@@ -550,6 +568,15 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
     const bool mis = scene->prm.integrator == KZ_INTEGRATOR_PATH_MIS;
     KzParams P = scene->prm;
     if (!mis) { P.anyInvisibleLight = 0; P.nIlTris = 0; P.shadowFast = 1; }
+    // The shade kernels' tables: the roulette-ahead test as the scene has it - but not while the counters run: they state the work of the reference's loop
+    // (tests/test_gpu_parity.py bounds rays and shaded hits from below against the oracle's), so a counted render traces the rays the test would skip.
+    // (A development build can switch the test off, or on for counted renders too: kz_debug_rr_ahead.)
+    KzDevTables Tsh = ds->T;
+    if (ds->statsOn) Tsh.nEmTris = KZ_EM_OFF;
+#ifdef KZ_EXPERIMENTS
+    { const int mode = g_kzRrAhead.load(std::memory_order_relaxed);
+      if (mode == 0) Tsh.nEmTris = KZ_EM_OFF; else if (mode == 2) Tsh.nEmTris = ds->T.nEmTris; }
+#endif
     KzWf W = c.wf;
     W.outJx = c.plane[0]; W.outJy = c.plane[1]; W.outR = c.plane[2]; W.outG = c.plane[3]; W.outB = c.plane[4]; W.stats = ds->stats;
     const bool st = ds->statsOn;
@@ -660,7 +687,7 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
         for (int iter = 0; iter < maxDepth; ++iter) {
             // one kernel per bounce: the path queues ping-pong (W.queue[iter & 1] is written, the other one read)
             uint32_t *nextQ = W.queue[iter & 1], *nextCount = W.counts + 4 * (iter + 1), *shQ = W.queue[2], *shCount = W.counts + 4 * (iter + 1) + 1;
-#define KZ_SHADE(ST, EX) hipLaunchKernelGGL((kz_wf_shade<ST, EX>), gShade, blk, 0, stream, P, ds->T, W, pixList, Sp, sBegin, iter, cur, curCount, items, nextQ, nextCount, shQ, shCount)
+#define KZ_SHADE(ST, EX) hipLaunchKernelGGL((kz_wf_shade<ST, EX>), gShade, blk, 0, stream, P, Tsh, W, pixList, Sp, sBegin, iter, cur, curCount, items, nextQ, nextCount, shQ, shCount)
             // the kernel compiled for what the scene's BSDF rows need (KzParams::bsdfExt): nothing beyond diffuse / kiss; other models only (four workgroups per CU,
             // no texture machinery); everything (textures, normal maps)
             const int xsel = P.bsdfExt == 0 ? 0 : (P.bsdfExt == KZ_X_MODELS ? KZ_X_MODELS : KZ_X_ALL);

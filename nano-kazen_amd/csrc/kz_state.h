@@ -67,6 +67,7 @@ extern std::atomic<int> g_kzTrace;
 void kzTraceLine(const char *fmt, ...);
 #define KZ_TRACE(...) do { if (g_kzTrace.load(std::memory_order_relaxed)) kzTraceLine(__VA_ARGS__); } while (0)
 int kzPhysicalDevice(int logical);            // kz_debug_alias_devices: the HIP device behind the index a replica is addressed by
+extern std::atomic<int> g_kzRrAhead;          // kz_debug_rr_ahead (kz_debug.hip): 0 = the shade kernels trace every bounce ray, as before the roulette-ahead test
 #else
 #define KZ_TRACE(...) do { } while (0)
 static inline int kzPhysicalDevice(int logical) { return logical; }
@@ -218,6 +219,7 @@ struct KzReplicaSet { std::mutex m; std::vector<KzDeviceState *> v; };
 static inline KzReplicaSet *replicaSet(const KzScene *scene) { return (KzReplicaSet *)scene->dev; }
 int findReplica(const KzScene *scene, int device, KzDeviceState **out);                                   // kz_render.hip
 int kzEnsureBvh2(KzScene *scene, KzDeviceState *ds);                                                      // kz_render.hip: the BVH2 table, on first use
+int kzEmitterUpload(KzScene *scene, KzDeviceState *ds);                                                   // kz_render.hip: the emitter triangles, their count and box (upload and every edit of a light)
 static inline int requireDevice(KzScene *scene, KzDeviceState **out) { return findReplica(scene, -1, out); }
 // kz_film.hip
 size_t packedFloats(const KzParams &P, const KzTile *tiles, uint32_t nTiles);

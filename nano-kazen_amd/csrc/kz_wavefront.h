@@ -177,6 +177,60 @@ struct KzSst {
 #endif
 };
 
+// The Russian roulette of integrator.cpp:237-244 on a path's throughput and eta against its next 1-D draw: true = the path ends here. ONE function for the
+// bounce that plays it (wfClassify) and for the bounce before it, which looks ahead (wfShadeSurvivor): the two cannot drift apart.
+__device__ __forceinline__ bool wfRouletteEnds(V3 throughput, float eta, float draw, float &probability) {
+    probability = fminf(maxCoeff(throughput) * eta * eta, 0.95f);
+    return probability <= draw;
+}
+
+// ---- roulette ahead -------------------------------------------------------------------------------------------------------
+// Both inputs of the roulette of bounce iter + 1 are known when shade(iter) has sampled the BSDF: the throughput and eta it has just formed, and the next
+// number of the path's sampler (the draws of a bounce do not depend on what its ray hits). A path that this roulette will end can still change the film
+// through its bounce ray in two ways only: the ray's closest hit is an emitter (integrator.cpp:226-231 comes BEFORE the roulette), or it misses and the scene
+// has a background. Without a background, such a ray is therefore queued only if it hits an emitter triangle at all - triTest with the ray's own tmin and
+// tmax = inf: the traversal kernels report hits through that same function with a tmax that only shrinks, and a triangle rejected at tmax = inf is rejected
+// at every smaller tmax, so a ray that fails on every emitter triangle cannot have an emitter as its closest hit, whatever the tie rule. A ray that does
+// hit one takes the closest-hit traversal and shade(iter + 1) decides it as before, its own roulette included. The film is the same bits.
+// The emitter triangles (T.emTris, at most 64: kz_host.cpp kzEmitterTris) sit behind their common box, a conservative prefilter in the form of
+// invisibleLightOnSegment (kz_devfn.h).
+__device__ __forceinline__ bool wfEmitterBox(const KzDevTables &T, V3 o, V3 d, float tmin) {
+    const float rx = rcpExact(d.x), ry = rcpExact(d.y), rz = rcpExact(d.z);
+    float t0 = (T.emLo[0] - o.x) * rx, t1 = (T.emHi[0] - o.x) * rx;
+    float n = fminf(t0, t1), f = fmaxf(t0, t1);
+    t0 = (T.emLo[1] - o.y) * ry; t1 = (T.emHi[1] - o.y) * ry; n = fmaxf(n, fminf(t0, t1)); f = fminf(f, fmaxf(t0, t1));
+    t0 = (T.emLo[2] - o.z) * rz; t1 = (T.emHi[2] - o.z) * rz; n = fmaxf(n, fminf(t0, t1)); f = fminf(f, fmaxf(t0, t1));
+    f *= 1.0000004f;
+    return fmaxf(n, tmin) <= f;
+}
+// Does the ray of a lane with `cand` hit an emitter triangle? Called by every lane that is in pass B together. In a full wave with fewer candidates than
+// triangles each candidate's ray is broadcast in turn (v_readlane: the ray is then scalar) and lane i tests triangle i - one triTest per candidate; otherwise
+// every candidate walks the table itself (the rows then come through the scalar cache).
+__device__ __forceinline__ bool wfEmitterHit(const KzDevTables &T, bool cand, V3 o, V3 d, float tmin) {
+    const unsigned long long m = __ballot(cand);
+    if (m == 0) return false;
+    const uint32_t n = T.nEmTris;
+    const uint32_t lane = threadIdx.x & 63u;
+    bool hit = false;
+    float t, u, v; uint32_t g;
+    if (__ballot(true) == ~0ull && (uint32_t)__popcll(m) < n) {
+        const float4 *tp = reinterpret_cast<const float4 *>(T.emTris + min(lane, n - 1u));
+        const float4 a = tp[0], b = tp[1], c = tp[2];
+        for (unsigned long long r = m; r; r &= r - 1ull) {
+            const int src = __ffsll(r) - 1;
+            const V3 so = mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(o.x), src)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o.y), src)),
+                             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(o.z), src)));
+            const V3 sd = mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(d.x), src)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d.y), src)),
+                             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d.z), src)));
+            const bool h = lane < n && triTestV(a, b, c, so, sd, tmin, KZ_INF, t, u, v, g);
+            if (__ballot(h) != 0ull && lane == (uint32_t)src) hit = true;          // (any triangle: the order does not matter)
+        }
+    } else if (cand) {
+        for (uint32_t i = 0; i < n && !hit; ++i) hit = triTest(T.emTris + i, o, d, tmin, KZ_INF, t, u, v, g);
+    }
+    return hit;
+}
+
 // Pass A of shade(iter) for one queue entry: hit record -> intersection; a miss, an emitter hit and a one-sided BSDF seen from behind end the
 // path here (integrator.cpp:210-231, 315-327), the Russian roulette of integrator.cpp:237-244 is played. True = the path goes on to the light
 // sample and the BSDF sample (wfShadeSurvivor); `its` is then complete. `compact`: see kz_wf_shade.
@@ -241,8 +295,8 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
         const float4 th = kzLoadStream(&W.thr[slot]);
         V3 throughput = mk(th.x, th.y, th.z);
         const float etaA = compact ? 1.f : th.w;
-        const float probability = fminf(maxCoeff(throughput) * etaA * etaA, 0.95f);
-        if (probability <= smp.next1D(P, T)) survivor = false;
+        float probability;
+        if (wfRouletteEnds(throughput, etaA, smp.next1D(P, T), probability)) survivor = false;
         else {
             throughput = throughput / probability;
             kzStoreStream(&W.thr[slot], make_float4(throughput.x, throughput.y, throughput.z, th.w));
@@ -256,7 +310,8 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
             Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, wfPmjDim(P, iter));
             const float4 th = kzLoadStream(&W.thr[slot]);
             const float etaA = compact ? 1.f : th.w;
-            if (fminf(maxCoeff(mk(th.x, th.y, th.z)) * etaA * etaA, 0.95f) <= smp.next1D(P, T)) alive = false;
+            float probability;
+            if (wfRouletteEnds(mk(th.x, th.y, th.z), etaA, smp.next1D(P, T), probability)) alive = false;
         }
         if (alive) cn.lsamples++;
     }
@@ -305,6 +360,8 @@ __device__ __forceinline__ void wfShadeSurvivor(const KzParams &P, const KzDevTa
         }
     }
     sst.mark(4);                                    // eval + pdf towards the light, shadow ray stores
+    // the ray after the LAST bounce only matters for the background term: without one, nothing the BSDF sample yields can be observed (uniform over the launch)
+    if (!(iter + 1 < P.maxDepth || P.bgPresent)) return;
     if (P.regularization && bsdf.type == KZ_BSDF_KAZENSTANDARD) accRough += bsdf.roughness * P.accumulatedRoughness;
     float s2x, s2y; smp.next2D(P, T, s2x, s2y);                           // H1: 2-D before 1-D
     const float s1 = smp.next1D(P, T);
@@ -314,18 +371,33 @@ __device__ __forceinline__ void wfShadeSurvivor(const KzParams &P, const KzDevTa
     sst.mark(6);                                    // BSDF sample
     throughput = throughput * weight;
     const float etaNext = eta * etaScale;
-    if (ok && !(weight.x == 0.f && weight.y == 0.f && weight.z == 0.f)) {
-        const float bpdf = pdfS >= 0.f ? pdfS : surfPdf<EXT>(bsdf, nm, its, wiLocal, woLocal, accRough, solid);
-        const V3 nd = toWorld(its.sh, woLocal);                           // H9
-        // the ray after the LAST bounce only matters for the background term
-        if (iter + 1 < P.maxDepth || P.bgPresent) {
-            kzStoreStream(&W.rayA[slot], make_float4(its.p.x, its.p.y, its.p.z, eps));
-            kzStoreStream(&W.rayB[slot], make_float4(nd.x, nd.y, nd.z, KZ_INF));
-            kzStoreStream(&W.thr[slot], make_float4(throughput.x, throughput.y, throughput.z, compact ? bpdf : etaNext));
-            if (!compact) kzStoreStream(&W.misc[slot], make_float4(bpdf, accRough, discrete ? 1.f : 0.f, 0.f));
-            wfStoreSampler(P, W, slot, smp);
-            pushNext = true;
+    bool keep = ok && !(weight.x == 0.f && weight.y == 0.f && weight.z == 0.f);
+    float bpdf = 0.f; V3 nd = mk(0.f);
+    if (keep) {
+        bpdf = pdfS >= 0.f ? pdfS : surfPdf<EXT>(bsdf, nm, its, wiLocal, woLocal, accRough, solid);
+        nd = toWorld(its.sh, woLocal);                                    // H9
+    }
+    // Roulette ahead (see wfEmitterHit): bounce iter + 1 plays the roulette from depth 3 on, against the next number of this sampler - drawn from a COPY, the
+    // state that is stored stays the one bounce iter + 1 expects. A non-finite ray misses in the traversal kernels (rayIsFinite): dropped without the test.
+    if (iter + 1 >= 3 && T.nEmTris != KZ_EM_OFF) {                        // (uniform over the launch)
+        bool cand = false;
+        if (keep) {
+            Sampler peek = smp;
+            float probability;
+            if (wfRouletteEnds(throughput, compact ? 1.f : etaNext, peek.next1D(P, T), probability)) {
+                keep = false;
+                cand = T.nEmTris != 0u && rayIsFinite(its.p, nd) && wfEmitterBox(T, its.p, nd, eps);
+            }
         }
+        if (wfEmitterHit(T, cand, its.p, nd, eps)) keep = true;
+    }
+    if (keep) {
+        kzStoreStream(&W.rayA[slot], make_float4(its.p.x, its.p.y, its.p.z, eps));
+        kzStoreStream(&W.rayB[slot], make_float4(nd.x, nd.y, nd.z, KZ_INF));
+        kzStoreStream(&W.thr[slot], make_float4(throughput.x, throughput.y, throughput.z, compact ? bpdf : etaNext));
+        if (!compact) kzStoreStream(&W.misc[slot], make_float4(bpdf, accRough, discrete ? 1.f : 0.f, 0.f));
+        wfStoreSampler(P, W, slot, smp);
+        pushNext = true;
     }
 }
 

@@ -164,6 +164,31 @@ int kz_plan_passes(const KzPlanQuery *q, KzPlanAnswer *a);
  * passes = 4 words per pass (first pixel, pixels, first sample, samples), *nPasses = how many there are (cap may be smaller). Fails with KZ_ERR_STATE if any pass
  * would exceed what its context holds - the planner's invariant. */
 int kz_plan_schedule(const KzPlanQuery *q, const uint64_t *avail, uint32_t nAvail, uint32_t pixBegin, uint32_t pixEnd, uint32_t *passes, uint32_t cap, uint32_t *nPasses);
+/* HOW a pass runs - one stream, its shadow rays beside its closest-hit rays, or as two halves (KzRenderOpts::shadowBeside / passHalves) -, the other half of the
+ * plan: what kz_render asks before every pass, with the state a replica keeps about its large passes (kz_pass_mode_info shows the replica's own). One call does
+ * what kz_render does around one pass, in its order: reset (an edit that changes the shade kernel) -> settle from `ms` when the four timed passes are out and this
+ * pass would consult them -> answer -> record a timed pass as launched. A fresh state is { kept = -1 } and zeros. The entry replays that order itself, for the
+ * table of tests/test_plan_cpu.py: the policy functions it calls are the ones kz_render calls, but the real sequencing - the event waits between them, the launch
+ * between answer and record - lives in onePass / passMode of kz_render.hip and is covered by the GPU tests of the large-pass probe. */
+typedef struct KzPassModeQuery {
+    uint64_t items; uint32_t nPixPass;      /* the pass: nPixPass pixels x items / nPixPass samples */
+    int32_t shadowBeside, passHalves;       /* KzRenderOpts */
+    int32_t pipeline;                       /* 0 / 2 = wavefront, 1 = megakernel */
+    int32_t multi, dealer, statsOn;         /* passes in flight on internal streams; the call carries a KzTileDealer; kz_set_stats is on */
+    int32_t pathMis;                        /* the integrator is path_mis */
+    int32_t nLights, maxDepth;
+    int32_t reset, launch;                  /* 1 = the state starts over first; 1 = a timed pass is recorded as launched */
+    float ms[4];                            /* device times of the four timed passes (one stream, beside, halves, one stream), read when the state settles */
+} KzPassModeQuery;
+typedef struct KzPassModeState { int32_t kept; int32_t launched; uint64_t items[4]; float ms[4]; } KzPassModeState;      /* kept as in KzPassModeInfo; launched: timed passes out */
+typedef struct KzPassModeAnswer {
+    int32_t shadowBeside, halves;           /* the option as the pass sees it (0: the size rule decides); 1 = the pass runs as two halves */
+    int32_t probe;                          /* which of the four timed passes this one is, or -1 */
+    int32_t beside, besideSecondHalf;       /* the launch code's order for the pass (or its first half), and for its second half */
+    uint32_t firstHalfPixels;               /* halves: pixels of the first half */
+    int32_t settled;                        /* 1 = this call settled the state from `ms` */
+} KzPassModeAnswer;
+int kz_plan_pass_mode(const KzPassModeQuery *q, KzPassModeState *st, KzPassModeAnswer *a);
 
 /* Known answers for the host code of kz_scene_create (no GPU): the area CDF of a light mesh - DiscretePDF::append + normalize, dpdf.h:35-37,77-89 - for n
  * pdf values (cdf: n + 1 floats; sumAndNormalization: 2 floats), and, for a sample count, { isPowerOf4, roundUpPow4, log4i of that, PMJ02BN's pixel tile }

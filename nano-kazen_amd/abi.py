@@ -145,6 +145,21 @@ class KzPlanAnswer(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KzPassModeQuery(C.Structure):
+    _fields_ = [("items", C.c_uint64), ("nPixPass", C.c_uint32), ("shadowBeside", C.c_int32), ("passHalves", C.c_int32), ("pipeline", C.c_int32),
+                ("multi", C.c_int32), ("dealer", C.c_int32), ("statsOn", C.c_int32), ("pathMis", C.c_int32), ("nLights", C.c_int32), ("maxDepth", C.c_int32),
+                ("reset", C.c_int32), ("launch", C.c_int32), ("ms", C.c_float * 4)]
+
+
+class KzPassModeState(C.Structure):
+    _fields_ = [("kept", C.c_int32), ("launched", C.c_int32), ("items", C.c_uint64 * 4), ("ms", C.c_float * 4)]
+
+
+class KzPassModeAnswer(C.Structure):
+    _fields_ = [("shadowBeside", C.c_int32), ("halves", C.c_int32), ("probe", C.c_int32), ("beside", C.c_int32), ("besideSecondHalf", C.c_int32),
+                ("firstHalfPixels", C.c_uint32), ("settled", C.c_int32)]
+
+
 class KzStats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("rays", C.c_uint64), ("nodeVisits", C.c_uint64), ("triTests", C.c_uint64),
                 ("shadedHits", C.c_uint64), ("lightSamples", C.c_uint64), ("droppedSamples", C.c_uint64),
@@ -192,7 +207,7 @@ EXPORTS = ["kz_scene_create", "kz_scene_destroy", "kz_scene_bvh_info", "kz_scene
            "kz_scene_evict", "kz_scene_devices", "kz_render_tiles", "kz_render_multi", "kz_deal_tiles", "kz_film_merge", "kz_film_download_on",
            "kz_film_clear_on", "kz_sync_on", "kz_last_pass_info", "kz_device_mem_info", "kz_camera_rays", "kz_light_query", "kz_kat_exact_math", "kz_kat_permute", "kz_kat_fresnel", "kz_kat_math", "kz_build_flags",
            "kz_tiles_packed_floats", "kz_film_download_tiles", "kz_film_merge_tiles", "kz_film_merge_rects", "kz_device_trim", "kz_kat_dpdf", "kz_kat_pow4", "kz_last_grow_note",
-           "kz_plan_passes", "kz_plan_schedule", "kz_pass_mode_info", "kz_scene_table"]
+           "kz_plan_passes", "kz_plan_schedule", "kz_plan_pass_mode", "kz_pass_mode_info", "kz_scene_table"]
 # what include/kazen_mi355x_edit.h declares (checked by tests/test_scene_edit_cpu.py): editing a scene that already exists
 EDIT_EXPORTS = ["kz_scene_set_camera", "kz_scene_set_vertices", "kz_scene_set_bsdfs", "kz_scene_set_lights", "kz_scene_set_transforms"]
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
@@ -278,6 +293,8 @@ def load_library(path=None):
     if hasattr(lib, "kz_plan_passes"):
         lib.kz_plan_passes.argtypes = [C.POINTER(KzPlanQuery), C.POINTER(KzPlanAnswer)]
         lib.kz_plan_schedule.argtypes = [C.POINTER(KzPlanQuery), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32, u32p]
+    if hasattr(lib, "kz_plan_pass_mode"):         # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_plan_pass_mode.argtypes = [C.POINTER(KzPassModeQuery), C.POINTER(KzPassModeState), C.POINTER(KzPassModeAnswer)]
     lib.kz_kat_dpdf.argtypes = [C.c_uint32, f32p, f32p, f32p]
     if hasattr(lib, "kz_scene_set_vertices"):     # (absent only in a KZ_LIB_PATH development build of older sources)
         lib.kz_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(KzCamera)]

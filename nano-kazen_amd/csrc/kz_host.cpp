@@ -493,7 +493,7 @@ int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
     // normals and ao (the camera ray is traced) and the 512-bounce cap of path_mats (LAB_NOTES H15); traceBias is unused by them
     p.integrator = integ;
     if (integ == KZ_INTEGRATOR_PATH_MIS) {
-        p.maxDepth = std::min(512, d->integrator.maxDepth);
+        p.maxDepth = std::min(KZ_PATH_MIS_MAX_DEPTH, d->integrator.maxDepth);
         p.traceBias = d->integrator.traceBias;
         p.regularization = d->integrator.regularization ? 1 : 0;
         p.accumulatedRoughness = d->integrator.accumulatedRoughness;

@@ -12,6 +12,7 @@
 #define KZ_STACK_DEPTH 32        // per-lane traversal stack entries (LDS); the builder caps the tree depth to this
 #define KZ_MAX_LEAF 4            // triangles per leaf
 #define KZ_MAX_FILTER_TAPS 9     // candidates per axis the film kernel supports (filter radius <= 4)
+#define KZ_PATH_MIS_MAX_DEPTH 512    // the deepest path_mis loop a scene may ask for (kz_scene_create clamps to it)
 #define KZ_PATH_MATS_MAX_DEPTH 512   // bounces of a path_mats path at most (the reference has no cap: LAB_NOTES H15)
 #define KZ_EM_MAX 64             // emitter triangles the roulette-ahead test of kz_wf_shade takes (one per lane of a wave)
 #define KZ_EM_OFF 0xFFFFFFFFu    // KzDevTables::nEmTris of a scene without that test (more triangles, a background, another integrator)

@@ -130,6 +130,51 @@ uint32_t kzPlanSamples(const KzPlan &pl, size_t avail, uint32_t w, uint32_t rema
     return Sp;
 }
 
+// ---- how a pass runs (kz_plan.h) ----
+// the mode of such a pass is measured: a large path_mis pass of the wavefront pipeline with both options left at 0 ...
+static bool measured(const KzPassQuery &q) { return q.pipeline == 2 && q.shadowBeside == 0 && q.passHalves == 0 && q.items > KZ_BESIDE_ITEMS && q.mis; }
+// ... one pass at a time and nobody counting (a counted render runs on one stream, whatever was kept)
+static bool alone(const KzPassQuery &q) { return !q.multi && !q.dealer && !q.statsOn; }
+
+bool kzPassModeDue(const KzPassMode &st, const KzPassQuery &q) { return measured(q) && alone(q) && st.kept < 0 && st.launched == 4; }
+
+void kzPassModeSettle(KzPassMode &st, const float ms[4]) {
+    double per[4];
+    for (int k = 0; k < 4; ++k) { st.ms[k] = ms[k]; per[k] = (double)ms[k] / (double)st.items[k]; }
+    // probe 0 ran on one stream, 1 beside, 2 as halves, 3 on one stream again: the yardstick is the better of its two timings - the first pass at a
+    // size is often slow (its context has just grown, behind the driver's wipe), and one slow pass must neither hide a gain nor invent one
+    const double one = std::min(per[0], per[3]);
+    st.kept = 0;
+    if (per[1] < KZ_PASS_MODE_GAIN * one) st.kept = 1;
+    if (per[2] < KZ_PASS_MODE_GAIN * one && per[2] < per[1]) st.kept = 2;
+}
+
+KzPassAnswer kzPassModeAsk(KzPassMode &st, const KzPassQuery &q) {
+    KzPassAnswer a;
+    int sb = q.shadowBeside;
+    a.halves = q.passHalves == 2;
+    if (measured(q)) {
+        int mode = 0;
+        if (!alone(q)) mode = 0;
+        else if (st.kept >= 0) mode = st.kept;
+        else if (st.launched == 0 || q.items > st.items[0]) { a.probe = 0; st.launched = 0; }      // (a larger pass than the one timed: the context has grown - start over at this size)
+        else if (q.items == st.items[0]) { a.probe = st.launched; mode = a.probe == 3 ? 0 : a.probe; }
+        sb = mode == 1 ? 2 : 1; a.halves = mode == 2;                   // (a remainder pass of another size: one stream, not comparable)
+    }
+    if (a.halves && (q.pipeline != 2 || q.multi || q.dealer || q.nPixPass < 256)) a.halves = false;      // (passes in flight and dealt batches overlap already)
+    if (sb == 0 && (q.multi || q.dealer) && q.items > KZ_BESIDE_ITEMS_IN_FLIGHT) sb = 1;
+    a.shadowBeside = sb;
+    // the size rule looks at what one launch chain covers: the pass, or each half of it
+    const bool can = q.nLights > 0 && q.maxDepth > 1;
+    auto beside = [&](size_t items) { return can && (sb == 2 || (sb == 0 && items <= KZ_BESIDE_ITEMS)); };
+    if (a.halves) {
+        const uint32_t n = q.nPixPass, Sp = (uint32_t)(q.items / n);
+        a.firstHalfPixels = std::min(n - 64u, ((n + 1u) / 2u + 63u) & ~63u);
+        a.beside[0] = beside((size_t)a.firstHalfPixels * Sp); a.beside[1] = beside((size_t)(n - a.firstHalfPixels) * Sp);
+    } else a.beside[0] = a.beside[1] = beside(q.items);
+    return a;
+}
+
 // ---- the planner through the C ABI (kazen_mi355x_dev.h): what tests/test_plan_cpu.py tabulates ----
 static void toIn(const KzPlanQuery *q, KzPlanIn &in) {
     in.pipeline = q->pipeline ? q->pipeline : 2; in.nPix = q->nPix; in.s0 = q->sampleBegin; in.s1 = q->sampleEnd;
@@ -173,6 +218,28 @@ int kz_plan_schedule(const KzPlanQuery *q, const uint64_t *avail, uint32_t nAvai
     *nPasses = n;
     if (rc == KZ_ERR_STATE) return kz_fail(rc, "kz_plan_schedule: a pass of more items than its context holds");
     if (rc) return kz_fail(rc, "kz_plan_schedule: a context holds nothing");
+    return KZ_OK;
+}
+
+int kz_plan_pass_mode(const KzPassModeQuery *q, KzPassModeState *st, KzPassModeAnswer *a) {
+    if (!q || !st || !a) return kz_fail(KZ_ERR_INVALID_ARG, "kz_plan_pass_mode: null argument");
+    if (!q->items || !q->nPixPass || q->items < q->nPixPass) return kz_fail(KZ_ERR_INVALID_ARG, "kz_plan_pass_mode: an empty pass");
+    if (st->kept < -1 || st->kept > 2 || st->launched < 0 || st->launched > 4) return kz_fail(KZ_ERR_INVALID_ARG, "kz_plan_pass_mode: no such state");
+    KzPassMode m;
+    m.kept = st->kept; m.launched = st->launched;
+    for (int k = 0; k < 4; ++k) { m.items[k] = (size_t)st->items[k]; m.ms[k] = st->ms[k]; }
+    KzPassQuery pq;
+    pq.items = (size_t)q->items; pq.nPixPass = q->nPixPass; pq.shadowBeside = q->shadowBeside; pq.passHalves = q->passHalves; pq.pipeline = q->pipeline ? q->pipeline : 2;
+    pq.multi = q->multi != 0; pq.dealer = q->dealer != 0; pq.statsOn = q->statsOn != 0; pq.mis = q->pathMis != 0; pq.nLights = q->nLights; pq.maxDepth = q->maxDepth;
+    // the steps of renderOn's onePass, in its order
+    if (q->reset) m.reset();
+    *a = KzPassModeAnswer{};
+    if (kzPassModeDue(m, pq)) { kzPassModeSettle(m, q->ms); a->settled = 1; }
+    const KzPassAnswer r = kzPassModeAsk(m, pq);
+    if (r.probe >= 0 && q->launch) m.record(r.probe, pq.items);
+    a->shadowBeside = r.shadowBeside; a->halves = r.halves; a->probe = r.probe; a->beside = r.beside[0]; a->besideSecondHalf = r.beside[1]; a->firstHalfPixels = r.firstHalfPixels;
+    st->kept = m.kept; st->launched = m.launched;
+    for (int k = 0; k < 4; ++k) { st->items[k] = m.items[k]; st->ms[k] = m.ms[k]; }
     return KZ_OK;
 }
 

@@ -2,9 +2,10 @@
 // nPix pixels x the sample indices [s0, s1) in PASSES of pixPerPass pixels x S samples = up to `need` (pixel, sample) items each, in nCtx pass
 // contexts; this unit decides those numbers from what the caller asked for, the memory it may use and what the first context held before
 // (the default pass size is EARNED call by call, DESIGN.md "pass policy"), and walks the schedule "pixel columns x sample ranges" against
-// what a context that may still be growing holds at the moment a pass is planned. renderOn (kz_render.hip) is plan -> ensure -> launch.
-// tests/test_plan_cpu.py drives the same code through kz_plan_passes / kz_plan_schedule (kazen_mi355x_dev.h) on the CPU box: its table is
-// the documentation of the policy.
+// what a context that may still be growing holds at the moment a pass is planned. The second half of the plan is HOW a pass runs (KzPassMode below): on
+// one stream, with its shadow rays beside its closest-hit rays, or as two halves. renderOn (kz_render.hip) is plan -> make room -> launch.
+// tests/test_plan_cpu.py drives the same code through kz_plan_passes / kz_plan_schedule / kz_plan_pass_mode (kazen_mi355x_dev.h) on the CPU box: its
+// tables are the documentation of the policy.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -76,6 +77,63 @@ int kzPlanRun(const KzPlan &pl, uint32_t b0, uint32_t b1, uint32_t sFrom, uint32
     }
     return 0;
 }
+
+// ---- how a pass runs. Three ways give the same film bit for bit: (0) one stream; (1) the shadow rays of a bounce BESIDE its closest-hit rays, on the context's
+// side stream; (2) the pass as two HALVES of its pixels side by side - two views of the context's arrays, the second on a stream of its own, disjoint pixels and
+// therefore disjoint tap sums -, which lets one half's shade kernel run beside the other half's traversal (materials_scene + 7 %, C4 - 1.4 %).
+//
+// SMALL passes run "beside". A pass of a small job (C1: 1 M items on a chip of 524 288 lanes) is a chain of ~25 dependent launches, each of which lasts as long as
+// its slowest ray whatever the number of rays: there the shadow rays of a bounce run beside its closest-hit rays instead of in front of them (C1 2.47 -> 2.03 ms;
+// the gain fades with the pass size: -4 .. -6 % at 2^22 - 2^23 items of C3 / C4-like scenes, -1 % at 2^25, nothing either way at 2^27 - where the q1 asset still
+// gains 7 %, so the rule ends there: profiles/r06v_shadow_beside).
+#ifndef KZ_BESIDE_ITEMS
+#define KZ_BESIDE_ITEMS (1u << 27)
+#endif
+// ... and earlier with passes in flight or a dealer, which overlap already: two passes of 2^22 items in flight still gain from "beside" (+1.5 .. +11 %), at
+// 2^24 - 2^25 C3 / C4 are neutral, from 2^26 they lose 2 - 3 % (the q1 asset gains at every size: whoever renders such scenes that way says shadowBeside = 2)
+#ifndef KZ_BESIDE_ITEMS_IN_FLIGHT
+#define KZ_BESIDE_ITEMS_IN_FLIGHT (1u << 24)
+#endif
+// A LARGE pass is another matter: on C4 each kernel saturates the VALUs by itself and sharing the chip costs 1 % (bench 1 798 / 1 812 one stream, 1 788 / 1 782
+// beside) - but a scene whose shadow rays are short-lived (the reference's own q1 asset: an object on a backdrop under three lights, shadow kernel at 0.67 VALU
+// busy) gains 6 - 10 % at EVERY pass size, all 22 scene files of the reference do. Nothing known at upload tells the two kinds apart, so how a large pass runs is
+// MEASURED, not guessed. With both options left at 0, one pass at a time and nobody counting, the replica times one large path_mis pass each way and one stream
+// twice (equal sizes), waits for the fourth when a fifth comes, and keeps for its scene what was fastest per item - "one stream" unless something beat it by 3 %.
+// (Such a wait is nothing new: a call already stays one pass ahead of a context that still grows. normals / ao / path_mats have no shadow rays of a bounce to
+// put beside anything: no mode is timed for them)
+constexpr double KZ_PASS_MODE_GAIN = 0.97;      // a way of running large passes is kept only when its time per item is below this x one stream's
+
+// What a replica has measured about its large passes (KzDeviceState owns one, and the events that time the passes).
+struct KzPassMode {
+    int kept = -1;                    // -1 = not known yet, 0 = one stream, 1 = shadow rays beside, 2 = halves
+    int launched = 0;                 // timed passes launched so far: [0] one stream, [1] beside, [2] halves, [3] one stream again
+    size_t items[4] = {};             // their sizes (all equal to items[0] once four are out)
+    float ms[4] = {};                 // their times, film stage included (there once settled)
+    void reset() { *this = KzPassMode{}; }                                              // (an edit changed the shade kernel the passes were timed with)
+    void record(int probe, size_t n) { items[probe] = n; launched = probe + 1; }        // timed pass `probe` of n items has been launched
+};
+// What renderOn knows before a pass.
+struct KzPassQuery {
+    size_t items = 0; uint32_t nPixPass = 0;      // the pass: items = nPixPass x its samples
+    int shadowBeside = 0, passHalves = 0;         // KzRenderOpts: 0 = default, 1 = never, 2 = always
+    int pipeline = 2;
+    bool multi = false, dealer = false, statsOn = false;      // passes in flight on internal streams; a KzTileDealer; the counters of kz_set_stats run
+    bool mis = true;                              // the integrator is path_mis
+    int nLights = 0, maxDepth = 0;
+};
+struct KzPassAnswer {
+    int shadowBeside = 0;             // the option as the pass sees it (1 or 2 where the mode is measured or kept; 0: the size rule decides)
+    bool halves = false;
+    uint32_t firstHalfPixels = 0;     // halves: pixels [0, firstHalfPixels) of the pass are its first half (a multiple of 64: aligned sub-arrays), the rest its second
+    int probe = -1;                   // which of the four timed passes this one is, or -1
+    bool beside[2] = {false, false};  // the launch code's order: shadow rays beside the closest-hit rays - [0] of the pass or its first half, [1] of its second half
+};
+// True when the pass would consult the four timed passes and all are out: the caller reads their times and settles before it asks.
+bool kzPassModeDue(const KzPassMode &st, const KzPassQuery &q);
+// Settles the mode from the times of the four timed passes (kept in st.ms).
+void kzPassModeSettle(KzPassMode &st, const float ms[4]);
+// How this pass runs. Starts the probe over (st.launched = 0) when the pass is larger than the one timed; the caller records a timed pass once it is launched.
+KzPassAnswer kzPassModeAsk(KzPassMode &st, const KzPassQuery &q);
 
 // ---- dynamic dealing: the two operations on the words the takers of one KzTileDealer share (they may live in memory shared between processes). Host code
 // only, so that the multi-device driver's threads can be run against them under ThreadSanitizer without a GPU (tests/host_cpp/multi_tsan_test.cpp).

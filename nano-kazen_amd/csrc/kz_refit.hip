@@ -233,7 +233,7 @@ int kzEditBsdfRows(KzScene *scene, const uint32_t *rows, uint32_t n, bool extCha
         for (uint32_t i = 0; i < n; ++i)                       // (rows < the table's size: kz_scene_set_bsdfs checked them against the rows of creation)
             HIP_TRY(hipMemcpy(const_cast<KzBSDF *>(ds->T.bsdfs) + rows[i], &scene->bsdfs[rows[i]], sizeof(KzBSDF), hipMemcpyHostToDevice));
         // the large-pass probe timed another shade kernel: it starts over (films are the same bits in every mode)
-        if (extChanged) { ds->largeMode = -1; ds->probeLaunched = 0; }
+        if (extChanged) ds->passMode.reset();
         HIP_TRY(hipDeviceSynchronize());
         return KZ_OK;
     });

@@ -1,12 +1,15 @@
 // kz_state.h - what the translation units of the device library share (not part of the ABI): the path-state arrays of the wavefront pipeline,
 // the per-pass contexts, the per-device replica state, error / allocation helpers, and the few host functions that cross a unit boundary.
-//   kz_render.hip   replicas + upload, pass schedule (renderOn / wfPass), every path kernel (kz_wavefront.h, the megakernel), kz_render*, stats
+//   kz_render.hip   a pass: every path kernel (kz_wavefront.h, the megakernel) and the tables that pick them, pass contexts' buffers, wfPass, renderOn, kz_render*
+//   kz_replica.hip  replicas: lifetime + upload, tile sets (prepareTiles), the queries that only read replica state (kz_last_*, kz_pass_mode_info, kz_sync*, stats)
+//   kz_refit.hip    device side of the edits of a resident scene (kz_refit.h)
 //   kz_film.hip     film reconstruction kernels + their launcher, tile packing / download, kz_film_* entry points
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kz_internal.h"
+#include "kz_plan.h"
 
 #include <atomic>
 #include <chrono>
@@ -30,10 +33,28 @@ struct KzWf {
     uint4 *smp;                    // pcg32 state (.x,.y) + dimension index (.z); the pcg32 stream id is recomputed from the pixel
     KzField<float4> shA, shB, shL; // shadow (or walk-through) ray o.xyz tmax | d.xyz tmin | pending radiance
     uint32_t *queue[3];            // two ping-pong path queues + the shadow queue
-    uint32_t *counts;              // [stage][4] zeroed per pass
+    uint32_t *counts;              // queue counters, zeroed per pass (KzCounts below)
     float *outJx, *outJy, *outR, *outG, *outB;
     unsigned long long *stats;
 };
+
+// The queue counters of a pass (PassCtx::counts; the kernels receive pointers into the block, the launch code alone knows its layout).
+//   lower half  one quad per stage: [kPaths] entries of the path queue the stage wrote, [kShadows] entries of its shadow queue, [kBounceHead] / [kShadowHead] the work
+//               heads of the persistent traversal kernels that drain the two. Quad 0 is the camera stage's - word 0 the first hits on an invisible light (queued for
+//               the walk-through), word 2 the head of the per-lane / packet camera rays, word 3 the head of the walk-through -, bounce b of a loop has quad b + 1
+//               (ao, which has one bounce, therefore counts its occlusion rays in word 5 and drains them through word 7).
+//   upper half  one pair per bounce: the shadow rays that cross an invisible-light triangle (count, head of their walk-through), pair b + 1 for bounce b;
+//               the last 8 words: the camera rays of pixels whose beam list overflowed (count, head of the packet kernel that takes them).
+struct KzCounts {
+    enum : uint32_t { kQuads = 520, kWords = 8 * kQuads, kLitBase = 4 * kQuads, kFallback = kWords - 8 };
+    enum : uint32_t { kPaths = 0, kShadows = 1, kBounceHead = 2, kShadowHead = 3 };
+    static constexpr uint32_t kCamera = 0;                                             // the camera stage's quad
+    static constexpr uint32_t quad(int bounce) { return 4u * (uint32_t)(bounce + 1); }
+    static constexpr uint32_t lit(int bounce) { return kLitBase + 2u * (uint32_t)(bounce + 1); }
+    static constexpr size_t bytes() { return kWords * sizeof(uint32_t); }
+};
+static_assert(KzCounts::quad(KZ_PATH_MATS_MAX_DEPTH - 1) + 4 <= KzCounts::kLitBase && KzCounts::quad(KZ_PATH_MIS_MAX_DEPTH - 1) + 4 <= KzCounts::kLitBase, "the deepest bounce's quad stays in the lower half");
+static_assert(KzCounts::lit(KZ_PATH_MIS_MAX_DEPTH - 1) + 2 <= KzCounts::kFallback, "the deepest bounce's lit pair stays below the fallback pair");
 
 struct KzTune { int refill, postpone, batch, travBlocksPerCU, shadeBlocksPerCU, ldsStack, packet, filmGather;
                 uint32_t *ovf; uint32_t ovfStride; };
@@ -49,9 +70,17 @@ struct KzTileDesc { int32_t x0, y0, w, h; uint32_t pixOffset; };      // a tile 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return kz_fail(KZ_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 // Every device allocation of the library goes through here (kz_debug_fail_alloc can make the nth one fail).
-hipError_t kzMalloc(void **p, size_t bytes);          // kz_render.hip
+hipError_t kzMalloc(void **p, size_t bytes);          // kz_replica.hip
 #define KZ_ALLOC(pp, bytes) do { hipError_t e_ = kzMalloc((void **)(pp), (bytes)); if (e_ != hipSuccess) \
     return kz_fail(e_ == hipErrorOutOfMemory ? KZ_ERR_OOM : KZ_ERR_HIP, "device allocation of %zu bytes failed: %s", (size_t)(bytes), hipGetErrorString(e_)); } while (0)
+// A device buffer made again for `cap` elements (nothing is kept: the caller has synchronised whatever still reads it).
+template <class Tp> static inline int kzRegrow(Tp *&p, size_t &have, size_t cap) {
+    if (p) (void)hipFree(p);
+    p = nullptr; have = 0;
+    KZ_ALLOC(&p, cap * sizeof(Tp));
+    have = cap;
+    return KZ_OK;
+}
 // A device buffer that is released on every way out of the call that made it.
 struct DevMem {
     void *p = nullptr;
@@ -67,6 +96,7 @@ extern std::atomic<int> g_kzTrace;
 void kzTraceLine(const char *fmt, ...);
 #define KZ_TRACE(...) do { if (g_kzTrace.load(std::memory_order_relaxed)) kzTraceLine(__VA_ARGS__); } while (0)
 int kzPhysicalDevice(int logical);            // kz_debug_alias_devices: the HIP device behind the index a replica is addressed by
+extern thread_local int g_failAlloc;          // kz_debug_fail_alloc (kz_replica.hip): kzMalloc counts it down, ctxEnsure (kz_render.hip) hands it to a growing arena
 extern std::atomic<int> g_kzRrAhead;          // kz_debug_rr_ahead (kz_debug.hip): 0 = the shade kernels trace every bounce ray, as before the roulette-ahead test
 #else
 #define KZ_TRACE(...) do { } while (0)
@@ -124,7 +154,7 @@ struct PassCtx {
     KzArena *arena = nullptr;                                    // the path-state arrays and the five sample planes (jx | jy | r | g | b)
     KzWf wf{};                                                   // (pointers into the arena, set by ctxEnsure)
     float *plane[5] = {};                                        // the five sample planes jx | jy | r | g | b (each its own range of the arena)
-    uint32_t *counts = nullptr;                                  // queue counters of a pass (8 x 520 words)
+    uint32_t *counts = nullptr;                                  // queue counters of a pass (KzCounts)
     uint32_t *ovf = nullptr; size_t ovfCap = 0;
     hipStream_t side = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr;      // small passes: the shadow rays of a bounce beside its closest-hit rays (wfPass)
     // A pass run as two HALVES of its pixels side by side (renderOn: KzRenderOpts::passHalves): two views of this context's arrays - the first and the second part
@@ -193,10 +223,9 @@ struct KzDeviceState {
     PassCtx &ctxAt(int i) { if (!ctx[i]) ctx[i] = kzCtxAcquire(device); return *ctx[i]; }
     std::vector<EventPair> events; size_t eventsUsed = 0;
     hipStream_t passStream[KZ_MAX_PASSES_IN_FLIGHT] = {}; hipEvent_t evFork = nullptr, evFilm[KZ_MAX_PASSES_IN_FLIGHT] = {}, evCallA = nullptr, evCallB = nullptr;
-    // LARGE passes with KzRenderOpts::shadowBeside = passHalves = 0: the replica times four passes of one size - one stream [0], the shadow rays beside the closest-hit
-    // rays [1], two halves of its pixels side by side [2], one stream again [3] - then keeps the fastest way for its scene (renderOn).
-    // largeMode: -1 = not known yet, 0 = one stream, 1 = shadow rays beside, 2 = halves.
-    hipEvent_t evProbe[4][2] = {}; size_t probeItems[4] = {}; int probeLaunched = 0; int largeMode = -1; float probeMs[4] = {};
+    // LARGE passes with KzRenderOpts::shadowBeside = passHalves = 0: the replica times four passes of one size (evProbe: their first and last event), then keeps
+    // the fastest way for its scene (kz_plan.h KzPassMode: the policy and what it has measured).
+    hipEvent_t evProbe[4][2] = {}; KzPassMode passMode;
     int lastCtx = 0; bool lastDual = false; int streamMode = 0;
     PassCtx *lastStageCtx = nullptr;                             // whose stage clock kz_last_stage_ms reads (a view, when the last pass ran as halves)
     // Beam lists (kz_wf_beam), one per pixel of the FRAME, built at most once per pixel and replica - the camera belongs to the scene - whatever tile
@@ -217,9 +246,11 @@ struct KzDeviceState {
 struct KzReplicaSet { std::mutex m; std::vector<KzDeviceState *> v; };
 
 static inline KzReplicaSet *replicaSet(const KzScene *scene) { return (KzReplicaSet *)scene->dev; }
-int findReplica(const KzScene *scene, int device, KzDeviceState **out);                                   // kz_render.hip
-int kzEnsureBvh2(KzScene *scene, KzDeviceState *ds);                                                      // kz_render.hip: the BVH2 table, on first use
-int kzEmitterUpload(KzScene *scene, KzDeviceState *ds);                                                   // kz_render.hip: the emitter triangles, their count and box (upload and every edit of a light)
+// kz_replica.hip
+int findReplica(const KzScene *scene, int device, KzDeviceState **out);
+int kzEnsureBvh2(KzScene *scene, KzDeviceState *ds);                                                      // the BVH2 table, on first use
+int kzEmitterUpload(KzScene *scene, KzDeviceState *ds);                                                   // the emitter triangles, their count and box (upload and every edit of a light)
+int prepareTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32_t nTiles, hipStream_t stream);      // makes `tiles` the replica's tile set
 static inline int requireDevice(KzScene *scene, KzDeviceState **out) { return findReplica(scene, -1, out); }
 // kz_film.hip
 size_t packedFloats(const KzParams &P, const KzTile *tiles, uint32_t nTiles);

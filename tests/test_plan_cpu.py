@@ -1,4 +1,4 @@
-"""No GPU: the pass planner of kz_render (nano-kazen_amd/csrc/kz_plan.cpp - pure host arithmetic) through kz_plan_passes / kz_plan_schedule.
+"""No GPU: the pass planner of kz_render (nano-kazen_amd/csrc/kz_plan.cpp - pure host arithmetic) through kz_plan_passes / kz_plan_schedule / kz_plan_pass_mode.
 VERDICT r05 item 5: this table IS the documentation of the pass policy: what a call of each BASELINE config is cut into, call after call,
 with and without a dealer, under a tight limit - and the one invariant of the schedule: no pass ever exceeds what its context holds."""
 import ctypes as C
@@ -160,3 +160,169 @@ def test_a_call_left_to_the_library_runs_on_what_there_is(kz):
     assert rc == 0 and a["minStart"] == a["need"] == 64 * 64 * 4
     rc, a, q, _ = plan(kz, nPix=npx, sampleBegin=0, sampleEnd=spp, passItems=1 << 24)
     assert rc == 0 and a["autoShape"] == 0 and a["minStart"] == a["need"]
+
+
+# ---- HOW a pass runs: one stream, its shadow rays beside its closest-hit rays, or as two halves (kz_plan.h KzPassMode, through kz_plan_pass_mode) ----
+L = 1920 * 1080 * 128                                      # a large pass (> 2^27 items) of 1920 x 1080 pixels
+NPIX = 1920 * 1080
+
+
+def fresh(kz):
+    st = kz.abi.KzPassModeState()
+    st.kept = -1
+    return st
+
+
+def snap(st):
+    return (st.kept, st.launched, tuple(st.items), tuple(st.ms))
+
+
+def ask(kz, st, items=L, npix=NPIX, launch=1, ms=(0, 0, 0, 0), **k):
+    """What kz_render asks before a pass (a path_mis scene with lights, maxDepth 5, unless said otherwise); launch = 1: a timed pass is recorded as launched."""
+    q = kz.abi.KzPassModeQuery()
+    q.items, q.nPixPass, q.launch, q.pipeline, q.pathMis, q.nLights, q.maxDepth = items, npix, launch, 2, 1, 3, 5
+    q.ms = (C.c_float * 4)(*ms)
+    for a, b in k.items():
+        setattr(q, a, b)
+    a = kz.abi.KzPassModeAnswer()
+    assert kz.abi.load_library().kz_plan_pass_mode(C.byref(q), C.byref(st), C.byref(a)) == 0
+    return a
+
+
+def probed(kz, n=4, items=L, npix=NPIX):
+    """A state with the first n timed passes of `items` items out, and the (sb, halves, probe) they ran with."""
+    st, ran = fresh(kz), []
+    for _ in range(n):
+        a = ask(kz, st, items, npix)
+        ran.append((a.shadowBeside, a.halves, a.probe))
+    return st, ran
+
+
+def test_pass_mode_large_passes_are_timed_four_ways(kz):
+    st, ran = probed(kz)
+    assert ran == [(1, 0, 0), (2, 0, 1), (1, 1, 2), (1, 0, 3)]                    # one stream, beside, halves, one stream again
+    assert (st.kept, st.launched, tuple(st.items)) == (-1, 4, (L,) * 4)            # nothing is kept until settled
+    # the launch code's order follows: beside only for probe 1; the halves are cut at a multiple of 64 pixels
+    st = fresh(kz)
+    assert [ask(kz, st).beside for _ in range(4)] == [0, 1, 0, 0]
+    st, _ = probed(kz, 2)
+    a = ask(kz, st)
+    assert a.halves == 1 and a.firstHalfPixels == NPIX // 2 and (a.beside, a.besideSecondHalf) == (0, 0)
+    # an unrecorded answer (launch = 0) leaves the state where it was
+    st, _ = probed(kz, 2)
+    before = snap(st)
+    assert ask(kz, st, launch=0).probe == 2 and snap(st) == before
+
+
+# per-item times of the four timed passes (one stream, beside, halves, one stream) -> what the replica keeps
+SETTLE = [((1.00, 0.98, 0.99, 1.00), 0), ((1.00, 0.96, 0.99, 1.00), 1), ((1.00, 0.96, 0.95, 1.00), 2), ((1.00, 0.99, 0.96, 1.00), 2),
+          ((1.20, 1.00, 1.10, 1.00), 0)]                                           # (the yardstick is the better of the two one-stream passes)
+
+
+@pytest.mark.parametrize("times,kept", SETTLE)
+def test_pass_mode_settles_on_what_won_by_three_percent(kz, times, kept):
+    st, _ = probed(kz)
+    ms = tuple(t * 500.0 for t in times)                                           # equal sizes: ms per pass order like times per item
+    a = ask(kz, st, ms=ms)                                                         # the fifth pass waits for the fourth and settles
+    assert a.settled == 1 and st.kept == kept and a.probe == -1 and tuple(st.ms) == tuple(np.float32(ms))
+    want = [(1, 0, 0), (2, 0, 1), (1, 1, 0)][kept]                                 # (shadowBeside, halves, beside)
+    for items, npix in ((L, NPIX), (L + 64, NPIX + 1), (L - 64 * 1080, NPIX - 540), (1 << 30, 1 << 21)):       # every large pass from now on
+        a = ask(kz, st, items, npix)
+        assert (a.shadowBeside, a.halves, a.beside, a.probe, a.settled) == want + (-1, 0) and st.kept == kept
+    # reset (an edit that changes the shade kernel): the fresh state, and the next large pass is probe 0 again
+    a = ask(kz, st, reset=1, launch=0)
+    assert a.probe == 0 and snap(st) == snap(fresh(kz))
+
+
+def test_pass_mode_probe_restarts_at_a_larger_size_and_skips_a_remainder(kz):
+    st, _ = probed(kz, 2)
+    a = ask(kz, st, L + 64, NPIX + 1)                                              # the context has grown: start over at this size
+    assert (a.shadowBeside, a.halves, a.probe) == (1, 0, 0) and (st.launched, st.items[0]) == (1, L + 64)
+    st, _ = probed(kz, 2)
+    before = snap(st)
+    a = ask(kz, st, L - 64 * 1080, NPIX - 540)                                     # a remainder pass: one stream, not timed, nothing changes
+    assert (a.shadowBeside, a.halves, a.beside, a.probe) == (1, 0, 0, -1) and snap(st) == before
+    assert ask(kz, st).probe == 2                                                  # ... and the probe goes on where it was
+
+
+@pytest.mark.parametrize("launched", [0, 2, 4])
+@pytest.mark.parametrize("who", ["multi", "dealer", "statsOn"])
+def test_pass_mode_in_company_is_one_stream_and_leaves_the_state_alone(kz, who, launched):
+    """Passes in flight, a dealer, a counted render: a large pass runs on one stream - whatever was kept, four timed passes waiting or not."""
+    st, _ = probed(kz, launched)
+    before = snap(st)
+    a = ask(kz, st, **{who: 1})
+    assert (a.shadowBeside, a.halves, a.beside, a.probe, a.settled) == (1, 0, 0, -1, 0) and snap(st) == before
+    st, _ = probed(kz)
+    ask(kz, st, ms=(500, 400, 300, 500))                                           # halves kept
+    assert st.kept == 2
+    a = ask(kz, st, **{who: 1})
+    assert (a.shadowBeside, a.halves, a.beside, a.probe) == (1, 0, 0, -1) and st.kept == 2
+
+
+@pytest.mark.parametrize("sb", [0, 1, 2])
+def test_pass_mode_other_integrators_are_never_timed(kz, sb):
+    """normals / ao / path_mats: no probe, shadowBeside as given (their maxDepth is 1 / 1 / 512; none of their launch chains has a beside)."""
+    for depth in (1, 1, 512):
+        st = fresh(kz)
+        a = ask(kz, st, pathMis=0, maxDepth=depth, shadowBeside=sb)
+        assert (a.shadowBeside, a.halves, a.probe) == (sb, 0, -1) and snap(st) == snap(fresh(kz))
+
+
+def test_pass_mode_explicit_options_bypass_the_probe(kz):
+    st = fresh(kz)
+    for items, npix in ((64 * 4, 64), (1 << 27, 1 << 20), (L, NPIX), (1 << 31, 1 << 22)):
+        a = ask(kz, st, items, npix, shadowBeside=2)                               # beside at any size
+        assert (a.shadowBeside, a.halves, a.beside, a.probe) == (2, 0, 1, -1)
+        a = ask(kz, st, items, npix, shadowBeside=1)
+        assert (a.shadowBeside, a.halves, a.beside, a.probe) == (1, 0, 0, -1)
+    a = ask(kz, st, passHalves=2)
+    assert (a.halves, a.probe, a.firstHalfPixels) == (1, -1, NPIX // 2)
+    a = ask(kz, st, 257 * 8, 257, passHalves=2)                                    # the first half: a multiple of 64 pixels, at least half
+    assert (a.halves, a.firstHalfPixels) == (1, 192)
+    assert ask(kz, st, 256 * 8, 256, passHalves=2).halves == 1
+    # dropped: too few pixels, passes in flight, a dealer, the megakernel
+    for k in ({"items": 255 * 8, "npix": 255}, {"multi": 1}, {"dealer": 1}, {"pipeline": 1}):
+        assert ask(kz, st, passHalves=2, **k).halves == 0, k
+    # passHalves = 1 and shadowBeside = 0: the size rule alone
+    assert ask(kz, st, 1 << 27, 1 << 20, passHalves=1).beside == 1
+    a = ask(kz, st, (1 << 27) + 64, (1 << 20) + 1, passHalves=1)
+    assert (a.shadowBeside, a.halves, a.beside, a.probe) == (0, 0, 0, -1)
+    # ... which a pass in halves applies to each half (a launch chain of its own)
+    a = ask(kz, st, (1 << 27) + 128 * 64, (1 << 21) + 128, passHalves=2)
+    assert (a.shadowBeside, a.halves, a.beside, a.besideSecondHalf) == (0, 1, 1, 1)
+    a = ask(kz, st, (1 << 28) + 128 * 128, (1 << 21) + 128, passHalves=2)          # halves of 2^27 + 64 x 128 | 2^27 + 64 x 128 items
+    assert (a.halves, a.firstHalfPixels, a.beside, a.besideSecondHalf) == (1, (1 << 20) + 64, 0, 0)
+    assert snap(st) == snap(fresh(kz))
+
+
+def test_pass_mode_size_thresholds(kz):
+    st = fresh(kz)
+    assert ask(kz, st, 1 << 27, 1 << 20).beside == 1
+    assert ask(kz, st, (1 << 27) + 64, (1 << 20) + 1, launch=0).beside == 0        # (a large pass: probe 0, one stream)
+    for who in ("multi", "dealer"):                                                # passes in flight, dealt batches overlap already: the rule ends earlier
+        a = ask(kz, st, 1 << 24, 1 << 18, **{who: 1})
+        assert (a.shadowBeside, a.beside) == (0, 1)
+        a = ask(kz, st, (1 << 24) + 64, (1 << 18) + 1, **{who: 1})
+        assert (a.shadowBeside, a.beside) == (1, 0)
+        assert ask(kz, st, (1 << 24) + 64, (1 << 18) + 1, shadowBeside=2, **{who: 1}).beside == 1
+    # no light, or no second bounce: nothing to put beside anything, whatever else holds
+    for k in ({"nLights": 0}, {"maxDepth": 1}, {"maxDepth": 0}):
+        for sb in (0, 2):
+            assert ask(kz, st, 1 << 20, 1 << 16, shadowBeside=sb, **k).beside == 0, (k, sb)
+        st2, _ = probed(kz, 1)
+        a = ask(kz, st2, **k)                                                      # (the probe still runs its course: it times what the launch code does)
+        assert (a.shadowBeside, a.probe, a.beside) == (2, 1, 0)
+    assert snap(st) == snap(fresh(kz))
+
+
+def test_pass_mode_rejects_what_is_no_pass_or_no_state(kz):
+    lib = kz.abi.load_library()
+    q, st, a = kz.abi.KzPassModeQuery(), fresh(kz), kz.abi.KzPassModeAnswer()
+    assert lib.kz_plan_pass_mode(None, C.byref(st), C.byref(a)) == kz.abi.KZ_ERR_INVALID_ARG
+    assert lib.kz_plan_pass_mode(C.byref(q), C.byref(st), C.byref(a)) == kz.abi.KZ_ERR_INVALID_ARG      # an empty pass
+    q.items, q.nPixPass = 63, 64
+    assert lib.kz_plan_pass_mode(C.byref(q), C.byref(st), C.byref(a)) == kz.abi.KZ_ERR_INVALID_ARG      # less than a sample per pixel
+    q.items = 64 * 16
+    st.launched = 5
+    assert lib.kz_plan_pass_mode(C.byref(q), C.byref(st), C.byref(a)) == kz.abi.KZ_ERR_INVALID_ARG

@@ -210,6 +210,10 @@ EXPORTS = ["kz_scene_create", "kz_scene_destroy", "kz_scene_bvh_info", "kz_scene
            "kz_plan_passes", "kz_plan_schedule", "kz_plan_pass_mode", "kz_pass_mode_info", "kz_scene_table"]
 # what include/kazen_mi355x_edit.h declares (checked by tests/test_scene_edit_cpu.py): editing a scene that already exists
 EDIT_EXPORTS = ["kz_scene_set_camera", "kz_scene_set_vertices", "kz_scene_set_bsdfs", "kz_scene_set_lights", "kz_scene_set_transforms"]
+# what include/kazen_mi355x_aov.h declares (checked by tests/test_aov_cpu.py): albedo / normal / depth feature films beside the picture
+AOV_EXPORTS = ["kz_scene_set_aovs", "kz_scene_aovs", "kz_aov_download", "kz_aov_download_on", "kz_aov_info", "kz_aov_samples"]
+KZ_AOV_ALBEDO, KZ_AOV_NORMAL, KZ_AOV_DEPTH, KZ_AOV_ALL = 1, 2, 4, 7
+AOV_BITS = {"albedo": KZ_AOV_ALBEDO, "normal": KZ_AOV_NORMAL, "depth": KZ_AOV_DEPTH}
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead"]
@@ -304,6 +308,13 @@ def load_library(path=None):
         lib.kz_scene_set_bsdfs.argtypes = [C.c_void_p, C.POINTER(KzBsdfUpdate), C.c_uint32]
         lib.kz_scene_set_lights.argtypes = [C.c_void_p, C.POINTER(KzLightUpdate), C.c_uint32]
         lib.kz_scene_set_transforms.argtypes = [C.c_void_p, C.POINTER(KzTransformUpdate), C.c_uint32]
+    if hasattr(lib, "kz_scene_set_aovs"):         # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_scene_set_aovs.argtypes = [C.c_void_p, C.c_uint32]
+        lib.kz_scene_aovs.argtypes = [C.c_void_p, u32p]
+        lib.kz_aov_download.argtypes = [C.c_void_p, C.c_uint32, f32p, C.c_size_t]
+        lib.kz_aov_download_on.argtypes = [C.c_void_p, C.c_int, C.c_uint32, f32p, C.c_size_t]
+        lib.kz_aov_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+        lib.kz_aov_samples.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), u32p, f32p]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

@@ -37,7 +37,9 @@
 // receives the same products in the same (sample) order whatever GROUPS is; what is paid for more groups is the per-sample set-up (validity, footprint, the
 // x weights) once per group. TAPS <= 5 (every default of the reference): two groups - 15 and 10 accumulators instead of 25, 10.5 KB of staging per wave
 // (round 5: film stage of a 2^30-item pass of C4 12.6 -> 10.5 ms); 6 .. 9 taps (radius up to 4): four groups, at most 27 accumulators per lane.
-template <int TAPS, int GROUPS>
+// SIGNED (compile time): the values are a feature film's (kazen_mi355x_aov.h) - a normal has negative components - so the sign half of Color3f::isValid is
+// skipped and the isfinite half kept. The picture's instantiations (SIGNED = false) keep the code they had.
+template <int TAPS, int GROUPS, bool SIGNED = false>
 __global__ __launch_bounds__(64) void kz_film_taps(KzParams P, const float *__restrict__ filter, const uint32_t *__restrict__ pixList, uint32_t nPix, uint32_t S,
                                                    const float *__restrict__ inJx, const float *__restrict__ inJy, const float *__restrict__ inR,
                                                    const float *__restrict__ inG, const float *__restrict__ inB, float4 *__restrict__ tapSums, size_t framePix) {
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(64) void kz_film_taps(KzParams P, const float *__re
             for (uint32_t k = 0; k < n; ++k) {
                 const float jx = s_in[0][k][pixLane], jy = s_in[1][k][pixLane];
                 const float cr = s_in[2][k][pixLane], cg = s_in[3][k][pixLane], cb = s_in[4][k][pixLane];
-                const bool valid = cr >= 0.f && cg >= 0.f && cb >= 0.f && isfinite(cr) && isfinite(cg) && isfinite(cb);   // Color3f::isValid
+                const bool valid = (SIGNED || (cr >= 0.f && cg >= 0.f && cb >= 0.f)) && isfinite(cr) && isfinite(cg) && isfinite(cb);   // Color3f::isValid
                 if (!valid) continue;                                  // an invalid sample carries weight 0 everywhere: adds exact zeros
                 const float posx = ((float)px + jx) - 0.5f - (float)(bx0 - P.border), posy = ((float)py + jy) - 0.5f - (float)(by0 - P.border);   // block.cpp:64-67
                 const float lox = ceilf(posx - r), hix = floorf(posx + r), loy = ceilf(posy - r), hiy = floorf(posy + r);                     // block.cpp:70-73
@@ -200,19 +202,22 @@ int kzFilmEnsureTapSums(KzScene *scene, KzDeviceState *ds, hipStream_t stream) {
 int kzFilmClear(KzDeviceState *ds, hipStream_t stream) {
     if (ds->tapSums) HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSumsBytes, stream));
     HIP_TRY(hipMemsetAsync(ds->film, 0, ds->filmPixels * sizeof(float4), stream));
+    for (int f = 0; f < 3; ++f) {                                      // the feature films follow the picture's
+        if (ds->aovTapSums[f]) HIP_TRY(hipMemsetAsync(ds->aovTapSums[f], 0, ds->tapSumsBytes, stream));
+        if (ds->aovFilm[f]) HIP_TRY(hipMemsetAsync(ds->aovFilm[f], 0, ds->filmPixels * sizeof(float4), stream));
+    }
     return KZ_OK;
 }
 
 // The film stage of one pass (called by renderOn, kz_render.hip): ImageBlock::put for every sample record of the pass, into the running tap sums of the pass's
 // pixels. The kernel reads and writes those sums, so it waits for the film stage of the pass before it (`waitFilm`, passes on other streams; null: same stream).
 // lanesPerPixel: 0 = default (2 lane groups per pixel up to 5 taps, 4 beyond), 1 = one lane per pixel (round 2's kernel; up to 5 taps) - the same sums bit for bit.
-int kzFilmStage(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, hipEvent_t waitFilm, int lanesPerPixel) {
-    const KzParams &P = scene->prm;
+template <bool SIGNED>
+static int launchTaps(const KzParams &P, KzDeviceState *ds, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *sJx, const float *sJy,
+                      const float *sR, const float *sG, const float *sB, float4 *tapSums, int lanesPerPixel) {
     const int ftaps = P.tapHi - P.tapLo + 1;
     const size_t framePix = (size_t)P.width * (size_t)P.height;
-    float *sJx = c.plane[0], *sJy = c.plane[1], *sR = c.plane[2], *sG = c.plane[3], *sB = c.plane[4];
-    if (waitFilm) HIP_TRY(hipStreamWaitEvent(pst, waitFilm, 0));
-#define KZ_FILM_TAPS(N, GR) hipLaunchKernelGGL((kz_film_taps<N, GR>), dim3((nPixPass + 64 / GR - 1) / (64 / GR)), dim3(64), 0, pst, P, ds->T.filter, pixList, nPixPass, Sp, sJx, sJy, sR, sG, sB, ds->tapSums, framePix)
+#define KZ_FILM_TAPS(N, GR) hipLaunchKernelGGL((kz_film_taps<N, GR, SIGNED>), dim3((nPixPass + 64 / GR - 1) / (64 / GR)), dim3(64), 0, pst, P, ds->T.filter, pixList, nPixPass, Sp, sJx, sJy, sR, sG, sB, tapSums, framePix)
     if (lanesPerPixel == 1 && ftaps <= 5) switch (ftaps) { case 1: KZ_FILM_TAPS(1, 1); break; case 2: KZ_FILM_TAPS(2, 1); break; case 3: KZ_FILM_TAPS(3, 1); break; case 4: KZ_FILM_TAPS(4, 1); break; default: KZ_FILM_TAPS(5, 1); break; }
     else switch (ftaps) {
         case 1: KZ_FILM_TAPS(1, 2); break; case 2: KZ_FILM_TAPS(2, 2); break; case 3: KZ_FILM_TAPS(3, 2); break; case 4: KZ_FILM_TAPS(4, 2); break; case 5: KZ_FILM_TAPS(5, 2); break;
@@ -222,6 +227,41 @@ int kzFilmStage(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t pst, 
 #undef KZ_FILM_TAPS
     HIP_TRY(hipGetLastError());
     return KZ_OK;
+}
+int kzFilmStage(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, hipEvent_t waitFilm, int lanesPerPixel) {
+    if (waitFilm) HIP_TRY(hipStreamWaitEvent(pst, waitFilm, 0));
+    return launchTaps<false>(scene->prm, ds, pst, pixList, nPixPass, Sp, c.plane[0], c.plane[1], c.plane[2], c.plane[3], c.plane[4], ds->tapSums, lanesPerPixel);
+}
+
+// ---- feature films (include/kazen_mi355x_aov.h): the same machine, one set of tap sums and one film per enabled AOV ----
+// Before the passes of a call: the sums and films of the enabled AOVs are there (allocated and zeroed on first use, like ds->tapSums, outside the pass contexts'
+// budget) and cleared unless the call accumulates.
+int kzAovEnsure(KzScene *scene, KzDeviceState *ds, hipStream_t stream, bool accumulate) {
+    for (int f = 0; f < 3; ++f) {
+        if (!(scene->aovMask & (1u << f))) continue;
+        const bool fresh = !ds->aovTapSums[f];
+        if (fresh) KZ_ALLOC(&ds->aovTapSums[f], ds->tapSumsBytes);
+        if (!ds->aovFilm[f]) { KZ_ALLOC(&ds->aovFilm[f], ds->filmPixels * sizeof(float4)); HIP_TRY(hipMemsetAsync(ds->aovFilm[f], 0, ds->filmPixels * sizeof(float4), stream)); }
+        if (fresh || !accumulate) HIP_TRY(hipMemsetAsync(ds->aovTapSums[f], 0, ds->tapSumsBytes, stream));
+    }
+    return KZ_OK;
+}
+// Inside a pass (wfPass), behind kz_wf_aov: ImageBlock::put of the pass's feature values, one kz_film_taps<.., true> launch per enabled AOV
+int kzAovFilmStage(KzScene *scene, KzDeviceState *ds, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *jx, const float *jy, const KzAovPlanes &A, int lanesPerPixel) {
+    for (int f = 0; f < 3; ++f) {
+        if (!(scene->aovMask & (1u << f))) continue;
+        if (!ds->aovTapSums[f]) return kz_fail(KZ_ERR_STATE, "the tap sums of AOV %u are not there", 1u << f);
+        const int rc = launchTaps<true>(scene->prm, ds, pst, pixList, nPixPass, Sp, jx, jy, A.p[f], A.p[f] + A.stride, A.p[f] + 2 * A.stride, ds->aovTapSums[f], lanesPerPixel);
+        if (rc) return rc;
+    }
+    return KZ_OK;
+}
+void kzAovFree(KzDeviceState *ds, uint32_t mask) {
+    for (int f = 0; f < 3; ++f) {
+        if (!(mask & (1u << f))) continue;
+        if (ds->aovTapSums[f]) { (void)hipFree(ds->aovTapSums[f]); ds->aovTapSums[f] = nullptr; }
+        if (ds->aovFilm[f]) { (void)hipFree(ds->aovFilm[f]); ds->aovFilm[f] = nullptr; }
+    }
 }
 
 // The film of the replica from its tap sums (once per call, on the call's stream behind every pass): ImageBlock::put(ImageBlock&) of the canonical grid's tiles in tile order.
@@ -316,6 +356,7 @@ int kz_tiles_packed_floats(const KzScene *scene, const KzTile *tiles, uint32_t n
 
 int kz_film_download_tiles(KzScene *scene, int device, const KzTile *tiles, uint32_t nTiles, float *packed, size_t nFloats) {
     KzDeviceState *ds; int rc;
+    if (scene && scene->aovMask) return kz_fail(KZ_ERR_UNSUPPORTED, "kz_film_download_tiles: refused while AOVs are enabled (mask %u): the tile-rect gather of AOV films is not built - kz_scene_set_aovs(scene, 0) first", scene->aovMask);
     if ((rc = findReplica(scene, device, &ds))) return rc;
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     return downloadTiles(scene, ds, tiles, nTiles, packed, nFloats, ds->lastStream);
@@ -337,6 +378,54 @@ int kz_film_download_on(KzScene *scene, int device, float *film, size_t nFloats)
     return KZ_OK;
 }
 int kz_film_download(KzScene *scene, float *film, size_t nFloats) { return kz_film_download_on(scene, -1, film, nFloats); }
+
+// ---- the entry points of include/kazen_mi355x_aov.h that only touch replica state (kz_aov_samples is kz_render.hip's) ----
+int kz_scene_set_aovs(KzScene *scene, uint32_t mask) {
+    if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "null scene");
+    if (mask & ~KZ_AOV_ALL) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_aovs: mask %u has bits outside KZ_AOV_ALL (%u)", mask, KZ_AOV_ALL);
+    KzReplicaSet *rs = replicaSet(scene);
+    std::vector<KzDeviceState *> v;
+    if (rs) { std::lock_guard<std::mutex> g(rs->m); v = rs->v; }
+    for (KzDeviceState *ds : v) {                                      // queued work finishes with the sums it was launched with
+        HIP_TRY(hipSetDevice(ds->hipDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        kzAovFree(ds, scene->aovMask & ~mask);
+    }
+    scene->aovMask = mask;
+    return KZ_OK;
+}
+int kz_scene_aovs(const KzScene *scene, uint32_t *mask) {
+    if (!scene || !mask) return kz_fail(KZ_ERR_INVALID_ARG, "null argument");
+    *mask = scene->aovMask;
+    return KZ_OK;
+}
+int kz_aov_download_on(KzScene *scene, int device, uint32_t aov, float *film, size_t nFloats) {
+    if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "null scene");
+    if ((aov != KZ_AOV_ALBEDO && aov != KZ_AOV_NORMAL && aov != KZ_AOV_DEPTH) || !(scene->aovMask & aov))
+        return kz_fail(KZ_ERR_INVALID_ARG, "kz_aov_download: aov %u must be exactly one enabled AOV bit (the scene's mask is %u)", aov, scene->aovMask);
+    KzDeviceState *ds; int rc;
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    if (!film || nFloats != ds->filmPixels * 4) return kz_fail(KZ_ERR_INVALID_ARG, "film buffer must hold %zu floats", ds->filmPixels * 4);
+    const int f = aov == KZ_AOV_ALBEDO ? 0 : (aov == KZ_AOV_NORMAL ? 1 : 2);
+    HIP_TRY(hipStreamSynchronize(ds->lastStream));
+    if (!ds->aovTapSums[f] || !ds->aovFilm[f]) { std::memset(film, 0, nFloats * sizeof(float)); return KZ_OK; }      // (enabled, nothing rendered yet)
+    const KzParams &P = scene->prm;
+    const int cols = P.width + 2 * P.border, rows = P.height + 2 * P.border;
+    hipLaunchKernelGGL(kz_film_resolve, dim3((cols + 15) / 16, (rows + 15) / 16), dim3(256), 0, ds->lastStream, P, (const float4 *)ds->aovTapSums[f], (size_t)P.width * (size_t)P.height, KZ_FILM_GRID, ds->aovFilm[f]);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ds->lastStream));
+    HIP_TRY(hipMemcpy(film, ds->aovFilm[f], nFloats * sizeof(float), hipMemcpyDeviceToHost));
+    return KZ_OK;
+}
+int kz_aov_download(KzScene *scene, uint32_t aov, float *film, size_t nFloats) { return kz_aov_download_on(scene, -1, aov, film, nFloats); }
+
+int kz_aov_info(KzScene *scene, int device, uint64_t *bytes) {
+    KzDeviceState *ds; int rc;
+    if (!bytes) return kz_fail(KZ_ERR_INVALID_ARG, "null bytes");
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    *bytes = ds->aovBytes();
+    return KZ_OK;
+}
 
 // ImageBlock::toBitmap (block.cpp:39-45) + Bitmap::savePNG's tone map (bitmap.cpp:45-52): the film is resolved to the 8-bit
 // sRGB raster on the device, so the host link carries 3 bytes per pixel instead of the 16-byte film texel.

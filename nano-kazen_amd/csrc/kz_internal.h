@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/kazen_mi355x_dev.h"
 #include "../../include/kazen_mi355x_edit.h"
+#include "../../include/kazen_mi355x_aov.h"
 
 #include <cstdint>
 #include <mutex>
@@ -201,6 +202,7 @@ struct KzScene {
     std::vector<KzXform> pendX;         // per mesh: the transform the host's shading records do not follow yet (pendXOn[m]); applied to baseV / baseN by kzHostSync
     std::vector<uint8_t> pendXOn;
     bool hostStale = false;             // tris, nodes, nodes4 and bvh.sahCost do not follow the last edit yet (kzHostSync brings them up to date)
+    uint32_t aovMask = 0;               // KZ_AOV_* feature films every render of the scene produces beside the picture (kazen_mi355x_aov.h; kz_scene_set_aovs)
     std::mutex editMutex;               // guards the lazy host refit (kzHostSync may be reached from several device threads of kz_render_multi)
     // device replicas, one per GPU the scene is resident on (KzReplicaSet, owned by kz_render.hip; created with the scene)
     void *dev = nullptr;

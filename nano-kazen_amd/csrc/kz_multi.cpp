@@ -112,6 +112,7 @@ int kz_film_merge_rects(float *film, int32_t width, int32_t height, int32_t bord
 int kz_render_multi(KzScene *scene, const KzRenderOpts *opts, const int32_t *devices, uint32_t nDevices, int32_t tileSize, float *film, size_t nFloats,
                     float *deviceMs) {
     if (!scene || !devices || nDevices == 0 || !film) return kz_fail(KZ_ERR_INVALID_ARG, "kz_render_multi: null argument");
+    if (scene->aovMask) return kz_fail(KZ_ERR_UNSUPPORTED, "kz_render_multi: refused while AOVs are enabled (mask %u): the tile-rect gather of AOV films is not built - kz_scene_set_aovs(scene, 0) first", scene->aovMask);
     const KzParams &P = scene->prm;
     const size_t filmFloats = (size_t)(P.width + 2 * P.border) * (size_t)(P.height + 2 * P.border) * 4;
     if (nFloats != filmFloats) return kz_fail(KZ_ERR_INVALID_ARG, "film buffer must hold %zu floats", filmFloats);

@@ -12,6 +12,7 @@
 #include "kz_devfn.h"
 #include "kz_wavefront.h"
 #include "kz_integrators.h"
+#include "kz_aov.h"
 #include "kz_state.h"
 #include <algorithm>
 #include <mutex>
@@ -250,6 +251,34 @@ static int wfCamera(WfLaunch &L, bool beams) {
     return L.mark(5);
 }
 
+// The feature films' stage of a pass (kazen_mi355x_aov.h), between the camera stage and the first shade / ao / mats launch: every item's first-hit record sits at
+// its own slot of W.hit, and the shadow arrays shA / shB / shL are DEAD there - the camera stage's walk-through has consumed the rays it kept in shA / shB, and
+// the next writers are the shade kernel (every slot it queues: kz_wavefront.h wfShade) and kz_wf_ao, each before its shadow kernel reads. Each array holds 16 B per
+// item = room for the three float planes of one feature, so the planes alias them: albedo in shA, normal in shB, depth in shL (a view of a pass in halves points
+// into its own part of every array, so the alias stays inside the view). No per-item array is added and the sample planes r / g / b are not touched.
+// kz_wf_aov's variant follows P.bsdfExt as the shade kernel's does. Then one kz_film_taps<.., true> launch per enabled AOV into that AOV's own tap sums.
+// ORDER: tap sums are read-modify-write per pixel and a pixel's samples must arrive in ascending sample order; with passes in flight the pass before this one,
+// on another stream, touches the same pixels. The AOV stages have an event chain of their own (evAov: recorded behind a pass's AOV tap launches, waited for by
+// the next pass's) - waiting for evFilm[prev], which is recorded at the END of the pass before, would serialise the passes.
+typedef decltype(&kz_wf_aov<0>) KzAovFn;
+static KzAovFn aovFn(int ext) {                      // ext: 0 / KZ_X_MODELS / KZ_X_ALL
+    static const KzAovFn tab[3] = {kz_wf_aov<0>, kz_wf_aov<KZ_X_MODELS>, kz_wf_aov<KZ_X_ALL>};
+    return tab[extCol(ext)];
+}
+static int wfAov(KzScene *scene, WfLaunch &L, hipEvent_t waitAov, hipEvent_t recordAov) {
+    const KzWf &W = L.W; hipStream_t stream = L.stream;
+    static_assert(sizeof(float4) >= 3 * sizeof(float), "a shadow array holds three float planes per item");
+    const KzAovPlanes A = {{(float *)W.shA.p, (float *)W.shB.p, (float *)W.shL.p}, (size_t)L.items};
+    const dim3 grid(std::min(L.gItems.x, (unsigned)(L.ds->numCU * 8)));
+    hipLaunchKernelGGL(aovFn(extSel(L.P.bsdfExt, KZ_X_ALL)), grid, L.blk, 0, stream, L.ds->T, W, L.items, scene->aovMask, A);
+    HIP_TRY(hipGetLastError());
+    if (waitAov) HIP_TRY(hipStreamWaitEvent(stream, waitAov, 0));
+    const int rc = kzAovFilmStage(scene, L.ds, stream, L.pixList, L.items / L.Sp, L.Sp, W.outJx, W.outJy, A, L.tune.filmGather == 3 ? 1 : 0);
+    if (rc) return rc;
+    if (recordAov) HIP_TRY(hipEventRecord(recordAov, stream));
+    return L.mark(4);                                   // (the stage clock books the AOV launches under "film")
+}
+
 //   path_mats  { kz_wf_mats(iter) -> kz_wf_trace<0> } until the path queue is empty or 512 bounces are done; the host reads the survivor count back
 //              after every 4th bounce (one stream synchronisation per 4 bounces), so a pass launches 2 + 2 x (bounces rounded up to 4) kernels after the camera's.
 static int wfMats(WfLaunch &L) {
@@ -320,7 +349,8 @@ static int wfMis(WfLaunch &L, bool beside) {
 // kernel, packet or per-lane traversal, first-hit walk-through); then path_mis runs its bounce loop and normals / ao / path_mats their tail (kz_integrators.h).
 // The three others see a copy of the parameters that names no invisible light: none of them walks through a light (H6 is path_mis's alone), so a first hit
 // on such a light is kept and an occlusion ray is blocked by it.
-static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t stream, const uint32_t *pixList, uint32_t sBegin, uint32_t Sp, uint32_t items, KzTune tune, bool beams, bool beside) {
+static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t stream, const uint32_t *pixList, uint32_t sBegin, uint32_t Sp, uint32_t items, KzTune tune, bool beams, bool beside,
+                  hipEvent_t waitAov = nullptr, hipEvent_t recordAov = nullptr) {
     int rc;
     WfLaunch L{ds, c, stream};
     const bool mis = scene->prm.integrator == KZ_INTEGRATOR_PATH_MIS;
@@ -359,8 +389,10 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
     if ((rc = L.mark(-1))) return rc;
     hipLaunchKernelGGL(kz_wf_generate, L.gItems, L.blk, 0, stream, P, ds->T, W, pixList, items, Sp, sBegin);
     if ((rc = L.mark(0))) return rc;
-    if (mis && P.maxDepth <= 0) return KZ_OK;           // Li returns 0 before the loop contributes anything
+    if (mis && P.maxDepth <= 0 && !scene->aovMask) return KZ_OK;           // Li returns 0 before the loop contributes anything
     if ((rc = wfCamera(L, beams))) return rc;
+    if (scene->aovMask && (rc = wfAov(scene, L, waitAov, recordAov))) return rc;
+    if (mis && P.maxDepth <= 0) return KZ_OK;           // (the camera stage ran for the feature films alone)
     if (P.integrator == KZ_INTEGRATOR_NORMALS) {
         //   normals    kz_wf_normals                                                    (no bounce state)
         hipLaunchKernelGGL(kz_wf_normals, L.gShade, L.blk, 0, stream, P, ds->T, W, items);
@@ -524,7 +556,16 @@ static int launchWhole(PassRun &r, PassCtx &c, int ci, hipStream_t pst, EventPai
     int rc;
     KzScene *scene = r.scene; KzDeviceState *ds = r.ds; const KzParams &P = scene->prm;
     const uint32_t items = (uint32_t)((size_t)nPixPass * Sp);
-    if (r.pipeline == 2) { if ((rc = wfPass(scene, ds, c, pst, pixList, s, Sp, items, r.tune, r.beams, beside))) return rc; }
+    if (r.pipeline == 2) {
+        // (feature films, passes in flight: this pass's AOV tap launches go behind those of the pass before it, on another stream - wfAov)
+        hipEvent_t waitAov = nullptr, recordAov = nullptr;
+        if (scene->aovMask && r.pl.multi) {
+            if (!ds->evAov[ci]) HIP_TRY(hipEventCreateWithFlags(&ds->evAov[ci], hipEventDisableTiming));
+            recordAov = ds->evAov[ci];
+            if (r.pass > 0) waitAov = ds->evAov[(ci + r.pl.nCtx - 1) % r.pl.nCtx];
+        }
+        if ((rc = wfPass(scene, ds, c, pst, pixList, s, Sp, items, r.tune, r.beams, beside, waitAov, recordAov))) return rc;
+    }
     else {
         const dim3 grid((items + KZ_BLOCK - 1) / KZ_BLOCK), blk(KZ_BLOCK);
         float *sJx = c.plane[0], *sJy = c.plane[1], *sR = c.plane[2], *sG = c.plane[3], *sB = c.plane[4];
@@ -585,9 +626,19 @@ static int onePass(PassRun &r, uint32_t p0, uint32_t nPixPass, uint32_t s, uint3
     return KZ_OK;
 }
 
+// What a scene with feature films enabled refuses (kazen_mi355x_aov.h): the megakernel pipeline, a dealer and packed tile rects. Checked before any replica is looked up.
+static int aovRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call) {
+    if (!scene || !scene->aovMask || !opts) return KZ_OK;
+    const char *what = opts->pipeline == 1 ? "KzRenderOpts.pipeline = 1 (the megakernel pipeline renders no AOVs)" : opts->dealer ? "a KzTileDealer (the tile-rect gather of AOV films is not built)"
+                     : opts->packedOutput ? "KzRenderOpts.packedOutput = 1 (the tile-rect gather of AOV films is not built)" : nullptr;
+    if (!what) return KZ_OK;
+    return kz_fail(KZ_ERR_UNSUPPORTED, "%s: %s is refused while AOVs are enabled (mask %u) - kz_scene_set_aovs(scene, 0) first", call, what, scene->aovMask);
+}
+
 static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts) {
     int rc;
     const KzParams &P = scene->prm;
+    if ((rc = aovRefuse(scene, opts, "kz_render"))) return rc;
     if (opts->pipeline < 0 || opts->pipeline > 2) return kz_fail(KZ_ERR_INVALID_ARG, "pipeline %d (0 = default, 1 = megakernel, 2 = wavefront)", opts->pipeline);
     if (opts->passesInFlight < 0 || opts->passesInFlight > KZ_MAX_PASSES_IN_FLIGHT)
         return kz_fail(KZ_ERR_INVALID_ARG, "passesInFlight %d (0 = default, 1 .. %d)", opts->passesInFlight, KZ_MAX_PASSES_IN_FLIGHT);
@@ -610,6 +661,7 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     if ((rc = prepareTiles(scene, ds, opts->tiles, opts->nTiles, stream))) return rc;
     // the film: running tap sums of the frame's pixels (kz_film.hip), part of the replica like the film itself - cleared unless the call accumulates
     { const bool fresh = !ds->tapSums; if ((rc = kzFilmEnsureTapSums(scene, ds, stream))) return rc; if (!opts->accumulate && !fresh) HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSumsBytes, stream)); }
+    if (scene->aovMask && (rc = kzAovEnsure(scene, ds, stream, opts->accumulate != 0))) return rc;      // ... and the feature films' (kazen_mi355x_aov.h)
     const KzTileDealer *dealer = opts->dealer;
     if (dealer) {
         if (!dealer->counter || (dealer->takenCap && (!dealer->taken || !dealer->nTaken))) return kz_fail(KZ_ERR_INVALID_ARG, "KzTileDealer: null counter / taken buffer");
@@ -680,6 +732,7 @@ extern "C" {
 int kz_render(KzScene *scene, const KzRenderOpts *opts) {
     if (!opts) return kz_fail(KZ_ERR_INVALID_ARG, "null opts");
     KzDeviceState *ds; int rc;
+    if ((rc = aovRefuse(scene, opts, "kz_render"))) return rc;
     // opts->device addresses a replica by HIP device index; a scene resident on ONE device is addressed by any zero-initialised opts
     if ((rc = findReplica(scene, opts->device, &ds))) {
         KzReplicaSet *rs = scene ? replicaSet(scene) : nullptr;
@@ -692,6 +745,7 @@ int kz_render(KzScene *scene, const KzRenderOpts *opts) {
 
 int kz_render_tiles(KzScene *scene, const KzRenderOpts *opts, const KzTile *tiles, uint32_t nTiles, int device, float *film, size_t nFloats) {
     KzDeviceState *ds; int rc;
+    if ((rc = aovRefuse(scene, opts, "kz_render_tiles"))) return rc;
     if ((rc = findReplica(scene, device, &ds))) return rc;
     const size_t full = ds->filmPixels * 4;
     const bool packedOut = opts && opts->packedOutput;
@@ -746,6 +800,32 @@ int kz_render_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint
         out[5 * i] = (float)pxy[2 * i] + h[i]; out[5 * i + 1] = (float)pxy[2 * i + 1] + h[n + i];
         out[5 * i + 2] = h[2 * (size_t)n + i]; out[5 * i + 3] = h[3 * (size_t)n + i]; out[5 * i + 4] = h[4 * (size_t)n + i];
     }
+    return KZ_OK;
+}
+
+// The features of single samples (kazen_mi355x_aov.h): the test surface of the feature films, shaped like kz_render_samples
+int kz_aov_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint32_t *idx, float *out) {
+    KzDeviceState *ds; int rc;
+    if ((rc = requireDevice(scene, &ds))) return rc;
+    if (n == 0) return KZ_OK;
+    if (!pxy || !idx || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null buffer");
+    if ((rc = kzEnsureBvh2(scene, ds))) return rc;
+    const KzParams &P = scene->prm;
+    std::vector<uint32_t> pl(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (pxy[2 * i] < 0 || pxy[2 * i] >= P.width || pxy[2 * i + 1] < 0 || pxy[2 * i + 1] >= P.height || idx[i] >= P.sampleCount)
+            return kz_fail(KZ_ERR_INVALID_ARG, "sample %u: pixel (%d,%d) index %u out of range", i, pxy[2 * i], pxy[2 * i + 1], idx[i]);
+        pl[i] = (uint32_t)pxy[2 * i] | ((uint32_t)pxy[2 * i + 1] << 16);
+    }
+    DevMem dP, dI, dOut;
+    KZ_ALLOC(&dP.p, (size_t)n * 4); KZ_ALLOC(&dI.p, (size_t)n * 4); KZ_ALLOC(&dOut.p, (size_t)n * 40);
+    HIP_TRY(hipMemcpy(dP.p, pl.data(), (size_t)n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dI.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(kz_aov_samples_kernel, dim3((n + KZ_BLOCK - 1) / KZ_BLOCK), dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.as<uint32_t>(), dI.as<uint32_t>(), n,
+                       P.integrator == KZ_INTEGRATOR_PATH_MIS ? 1 : 0, dOut.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dOut.p, (size_t)n * 40, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; ++i) { out[10 * (size_t)i] += (float)pxy[2 * i]; out[10 * (size_t)i + 1] += (float)pxy[2 * i + 1]; }      // sample position = pixel + jitter
     return KZ_OK;
 }
 

@@ -71,6 +71,8 @@ static void releaseReplica(KzDeviceState *ds) {
     (void)hipSetDevice(ds->hipDevice);
     (void)hipDeviceSynchronize();
     for (void *p : ds->allocs) (void)hipFree(p);
+    kzAovFree(ds, KZ_AOV_ALL);
+    for (hipEvent_t e : ds->evAov) if (e) (void)hipEventDestroy(e);
     for (void *p : {(void *)ds->film, (void *)ds->tapSums, (void *)ds->srgb, (void *)ds->pixList, (void *)ds->stats, (void *)ds->packDev, (void *)ds->rectsDev, (void *)ds->beamEntries, (void *)ds->beamCount, (void *)ds->tileDev, (void *)ds->editStage}) if (p) (void)hipFree(p);
     if (ds->tileHost) (void)hipHostFree(ds->tileHost);
     if (ds->evTiles) (void)hipEventDestroy(ds->evTiles);

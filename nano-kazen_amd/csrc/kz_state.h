@@ -207,6 +207,10 @@ struct KzDeviceState {
     bool bvh2Resident = false;                                   // T.nodes holds the BVH2 (uploaded on first use: kzEnsureBvh2)
     float4 *film = nullptr; size_t filmPixels = 0;
     float4 *tapSums = nullptr; size_t tapSumsBytes = 0;          // the running tap sums of every pixel of the frame, [tap][y * width + x] (kz_film.hip): what the film is resolved from
+    // Feature films (kazen_mi355x_aov.h; kz_film.hip): per AOV - albedo, normal, depth - running tap sums and a film like the picture's, there from the first render
+    // with the AOV enabled; evAov[i]: the AOV tap launches of the pass last run in context i (the chain passes in flight order their AOV stages by, wfPass)
+    float4 *aovTapSums[3] = {}, *aovFilm[3] = {}; hipEvent_t evAov[KZ_MAX_PASSES_IN_FLIGHT] = {};
+    size_t aovBytes() const { size_t b = 0; for (int f = 0; f < 3; ++f) b += (aovTapSums[f] ? tapSumsBytes : 0) + (aovFilm[f] ? filmPixels * sizeof(float4) : 0); return b; }
     uint8_t *srgb = nullptr;                                     // staging raster of kz_film_to_srgb8 (allocated on first use)
     float4 *packDev = nullptr; size_t packCap = 0; KzTileRect *rectsDev = nullptr; size_t rectsCap = 0;      // kz_film_download_tiles: packed tile rects + their table
     float4 *packHost = nullptr; size_t packHostCap = 0;           // pinned staging of the same (D2H at link rate)
@@ -263,3 +267,12 @@ int kzFilmEnsureTapSums(KzScene *scene, KzDeviceState *ds, hipStream_t stream);
 int kzFilmClear(KzDeviceState *ds, hipStream_t stream);
 int kzFilmStage(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, hipEvent_t waitFilm, int lanesPerPixel);
 int kzFilmResolve(KzScene *scene, KzDeviceState *ds, hipStream_t stream);
+// The feature films (kazen_mi355x_aov.h): kzAovEnsure before the passes of a call (sums and films of the enabled AOVs there, cleared unless the call accumulates),
+// kzAovFilmStage inside a pass (one kz_film_taps launch per enabled AOV from the pass's jitter planes and the feature planes kz_wf_aov wrote), kzAovFree when an
+// AOV leaves the mask or the replica goes.
+// The float planes a pass's features go to: three per feature (p[0] albedo, p[1] normal, p[2] depth replicated), `stride` floats apart. They alias the shadow
+// arrays of the pass context (wfAov, kz_render.hip), which are dead between the camera stage and the first shade / ao / mats launch.
+struct KzAovPlanes { float *p[3]; size_t stride; };
+int kzAovEnsure(KzScene *scene, KzDeviceState *ds, hipStream_t stream, bool accumulate);
+int kzAovFilmStage(KzScene *scene, KzDeviceState *ds, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *jx, const float *jy, const KzAovPlanes &planes, int lanesPerPixel);
+void kzAovFree(KzDeviceState *ds, uint32_t mask);

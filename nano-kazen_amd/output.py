@@ -90,3 +90,83 @@ def load_exr(path):
         for k, nm in enumerate(names):
             out[y - y0, :, "RGB".index(nm)] = row[k]
     return out
+
+
+def _layer_channels(layers):
+    """[(channel name, (h, w) float32 plane)] of a layer dict, sorted by name as the OpenEXR channel list requires: layer "" gives R, G, B, a named
+    layer <name>.R / .G / .B, and the layer called "depth" the single channel depth.Z (its first plane: the depth film replicates the value)."""
+    chans, shape = [], None
+    for name, a in layers.items():
+        a = np.ascontiguousarray(a, np.float32)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3 or a.shape[2] not in (1, 3) or (shape is not None and a.shape[:2] != shape):
+            raise ValueError("save_exr_layers: layer %r must be (h, w, 3) or (h, w) of one common size" % name)
+        shape = a.shape[:2]
+        if name == "depth":
+            chans.append(("depth.Z", a[:, :, 0]))
+        elif a.shape[2] != 3:
+            raise ValueError("save_exr_layers: layer %r must have three channels (only \"depth\" is a single one)" % name)
+        else:
+            chans += [((name + "." if name else "") + c, a[:, :, k]) for k, c in enumerate("RGB")]
+    if not chans:
+        raise ValueError("save_exr_layers: no layer")
+    return sorted(chans, key=lambda c: c[0].encode()), shape
+
+
+def save_exr_layers(path, layers):
+    """One uncompressed scan-line OpenEXR holding several layers as FLOAT channels: {"": rgb, "albedo": ..., "normal": ..., "depth": ...} ->
+    channels B, G, R, albedo.B, ..., depth.Z (sorted). Values are stored as given: signed normals stay signed. Appends ".exr" when missing."""
+    chans, (h, w) = _layer_channels(layers)
+    chl = b"".join(n.encode() + b"\0" + struct.pack("<iBBBBii", 2, 0, 0, 0, 0, 1, 1) for n, _ in chans) + b"\0"
+    box = struct.pack("<iiii", 0, 0, w - 1, h - 1)
+    hdr = (struct.pack("<II", 20000630, 2) + _attr("channels", "chlist", chl) + _attr("compression", "compression", b"\0") + _attr("dataWindow", "box2i", box) +
+           _attr("displayWindow", "box2i", box) + _attr("lineOrder", "lineOrder", b"\0") + _attr("pixelAspectRatio", "float", struct.pack("<f", 1.0)) +
+           _attr("screenWindowCenter", "v2f", struct.pack("<ff", 0.0, 0.0)) + _attr("screenWindowWidth", "float", struct.pack("<f", 1.0)) + b"\0")
+    line = 8 + 4 * len(chans) * w
+    first = len(hdr) + 8 * h
+    table = struct.pack("<%dQ" % h, *[first + y * line for y in range(h)])
+    planar = np.stack([p for _, p in chans], axis=1).astype("<f4")             # (h, channel, w): per scan line one row per channel
+    body = b"".join(struct.pack("<ii", y, 4 * len(chans) * w) + planar[y].tobytes() for y in range(h))
+    if not path.endswith(".exr"):
+        path += ".exr"
+    with open(path, "wb") as f:
+        f.write(hdr + table + body)
+    return path
+
+
+def load_exr_layers(path):
+    """Reader for the files save_exr_layers (and save_exr) writes: {layer: (h, w, 3) float32}, "depth" as (h, w)."""
+    b = open(path, "rb").read()
+    if struct.unpack_from("<I", b, 0)[0] != 20000630:
+        raise ValueError("not an OpenEXR file")
+    pos, attrs = 8, {}
+    while b[pos] != 0:
+        e = b.index(b"\0", pos); name = b[pos:e].decode(); pos = e + 1
+        e = b.index(b"\0", pos); typ = b[pos:e].decode(); pos = e + 1
+        n = struct.unpack_from("<i", b, pos)[0]; pos += 4
+        attrs[name] = (typ, b[pos:pos + n]); pos += n
+    pos += 1
+    if attrs["compression"][1] != b"\0":
+        raise ValueError("only uncompressed files are supported")
+    x0, y0, x1, y1 = struct.unpack("<iiii", attrs["dataWindow"][1])
+    w, h = x1 - x0 + 1, y1 - y0 + 1
+    names, cp, cl = [], 0, attrs["channels"][1]
+    while cl[cp] != 0:
+        e = cl.index(b"\0", cp); names.append(cl[cp:e].decode()); cp = e + 1
+        if struct.unpack_from("<i", cl, cp)[0] != 2:
+            raise ValueError("only FLOAT channels are supported")
+        cp += 16
+    offs = struct.unpack_from("<%dQ" % h, b, pos)
+    planes = np.zeros((len(names), h, w), np.float32)
+    for o in offs:
+        y = struct.unpack_from("<i", b, o)[0]
+        planes[:, y - y0, :] = np.frombuffer(b, "<f4", len(names) * w, o + 8).reshape(len(names), w)
+    out = {}
+    for k, nm in enumerate(names):
+        layer, _, c = nm.rpartition(".")
+        if c == "Z":
+            out[layer] = planes[k]
+        else:
+            out.setdefault(layer, np.zeros((h, w, 3), np.float32))[:, :, "RGB".index(c)] = planes[k]
+    return out

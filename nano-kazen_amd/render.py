@@ -342,6 +342,59 @@ class Scene:
                                                        idx.ctypes.data_as(abi.u32p), out.ctypes.data_as(abi.f32p)))
         return out
 
+    # ---- feature films beside the picture (include/kazen_mi355x_aov.h)
+    @staticmethod
+    def _aov_mask(names):
+        if isinstance(names, int):
+            return int(names)
+        if isinstance(names, str):
+            names = [names]
+        mask = 0
+        for n in names or ():
+            if n not in abi.AOV_BITS:
+                raise ValueError("unknown AOV %r (known: %s)" % (n, ", ".join(sorted(abi.AOV_BITS))))
+            mask |= abi.AOV_BITS[n]
+        return mask
+
+    def set_aovs(self, names):
+        """kz_scene_set_aovs: `names` = any of "albedo", "normal", "depth" (or the bit mask itself; () / 0 switches the feature films off). An AOV that is
+        switched on covers the samples rendered from then on: clear the film when accumulating."""
+        abi.check(self.lib, self.lib.kz_scene_set_aovs(self.h, self._aov_mask(names)))
+
+    def aovs(self):
+        m = C.c_uint32()
+        abi.check(self.lib, self.lib.kz_scene_aovs(self.h, C.byref(m)))
+        return [n for n, b in abi.AOV_BITS.items() if m.value & b]
+
+    def aov_film(self, name, device=None):
+        """kz_aov_download[_on]: the AOV's film, (h + 2b, w + 2b, 4) = (value * w, w) like film()."""
+        n = (self.height + 2 * self.border) * (self.width + 2 * self.border) * 4
+        out = np.empty(n, np.float32)
+        if device is None:
+            abi.check(self.lib, self.lib.kz_aov_download(self.h, self._aov_mask(name), out.ctypes.data_as(abi.f32p), n))
+        else:
+            abi.check(self.lib, self.lib.kz_aov_download_on(self.h, int(device), self._aov_mask(name), out.ctypes.data_as(abi.f32p), n))
+        return out.reshape(self.height + 2 * self.border, self.width + 2 * self.border, 4)
+
+    def aov(self, name, device=None):
+        """The AOV's values, (h, w, 3): its film divided by the filter weight (kz_film_to_rgb); depth is replicated into the three channels."""
+        return self.rgb(self.aov_film(name, device))
+
+    def aov_info(self, device=-1):
+        """kz_aov_info: bytes the AOV tap sums and films hold on that replica."""
+        b = C.c_uint64()
+        abi.check(self.lib, self.lib.kz_aov_info(self.h, int(device), C.byref(b)))
+        return int(b.value)
+
+    def aov_samples(self, pxy, idx):
+        """kz_aov_samples: (n, 10) = sample x, y | albedo rgb | normal xyz | depth | hit, shaped like render_samples."""
+        pxy = np.ascontiguousarray(pxy, np.int32)
+        idx = np.ascontiguousarray(idx, np.uint32)
+        n = idx.shape[0]
+        out = np.zeros((n, 10), np.float32)
+        abi.check(self.lib, self.lib.kz_aov_samples(self.h, n, pxy.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(abi.u32p), out.ctypes.data_as(abi.f32p)))
+        return out
+
     def bsdf_query(self, bsdf, wi, wo, acc, s3, uv=None):
         """eval (n,3), pdf (n,), sample (n,8) = weight rgb, wo xyz, alive, pdf(bRec) after sample()."""
         bsdf = np.ascontiguousarray(bsdf, np.int32)

@@ -62,6 +62,37 @@ int kz_sync_on(KzScene *scene, int device);
 int kz_trace_rays(KzScene *scene, uint32_t n, const float *o, const float *d,
                   const float *tmin, const float *tmax, KzHit *hits);
 
+/* The traversal launches of a RENDER on a caller's rays. kz_trace_rays above walks the BVH2 with the reference-shaped loop; the passes of kz_render use other
+ * code - the persistent per-lane BVH4 kernel, the wave-level packet kernel, their shadow forms - which this entry launches exactly as a pass does (the same
+ * compiled kernels, grids, LDS size, stack split and overflow stride: one statement of each in kz_render.hip) on a private path state of nSlots slots.
+ *   kernel   0 per-lane closest hit; 1 packet closest hit (KZ_ERR_INVALID_ARG when the scene's tree may need more than the packet's 128 stack entries);
+ *            2 the walk-through ray: closest hit, the slot's previous hit record kept on a miss (integrator.cpp:214-219);
+ *            3 the shadow test as a bounce launches it: any-hit with the rays that cross a light of lightPrimaryVisibility == false diverted to a second queue
+ *              and walked through by the general kernel, or the general kernel on everything when the scene has more than 64 such triangles (integrator.cpp:257-278)
+ *   stats    1 = the counting instantiations
+ *   refill, postpone, batch, ldsStack   as in KzTuning (0 = the render's default)
+ *   gridBlocks   workgroups of the launch (0 = the render's: per-lane kernels KzTuning.traceBlocksPerCU per CU, packet kernel 8 per CU)
+ *   packetBatch  packets a wave of the packet kernel claims at a time (0 = the render's 8)
+ * o, d: nSlots x 3; tmin, tmax: nSlots (a tmin that is negative - -0.0 included - or NaN is refused: the kernels order child boxes by the bits of their entry distance). queue: nQueue slot
+ * indices, each below nSlots and none twice, or NULL = every slot in order. pending: nSlots x 3, the radiance a free shadow ray adds (kernel 3).
+ * hits go up as given and come back per slot: the kernels write (t, u, v, gid) of the slots they decide - a miss of kernels 0 / 1 is (+inf, 0, 0, 0) - and the host
+ * fills in (mesh, prim) of the gid (-1 for a miss or a gid the scene does not have). sums (nSlots x 3) go up as given; kernel 3 adds the pending radiance of every
+ * free ray to its slot's. Slots outside the queue keep both. An empty queue launches nothing. The call returns after the device has finished. */
+typedef struct KzTraceWfOpts { int32_t kernel, stats, refill, postpone, batch, ldsStack, gridBlocks, packetBatch; } KzTraceWfOpts;
+typedef struct KzTraceWfHit { float t, u, v; uint32_t gid; int32_t mesh, prim; } KzTraceWfHit;
+typedef struct KzTraceWfInfo {
+    uint64_t rays, nodeVisits, triTests;     /* the launches' counters (stats = 1) */
+    uint32_t nQueueB;                        /* kernel 3: rays diverted to the second queue */
+    uint32_t nFirstHitsOnInvisibleLight;     /* kernel 1: hits the packet kernel queued for the walk-through */
+    uint32_t gridBlocks, ldsStack;           /* the launch: workgroups, stack entries per lane in LDS */
+    uint32_t stackBound;                     /* the builder's bound of the stack depth */
+    uint32_t ovfRows, ovfRowsTouched;        /* per-lane kernels: rows of the global overflow area of the launch, and how many of them a stack reached (a stack
+                                                that reaches the guard row behind them fails the call with KZ_ERR_STATE) */
+    uint32_t shadowFast;                     /* the scene takes the any-hit shadow kernel */
+} KzTraceWfInfo;
+int kz_trace_rays_wf(KzScene *scene, const KzTraceWfOpts *opts, uint32_t nSlots, const float *o, const float *d, const float *tmin, const float *tmax,
+                     const uint32_t *queue, uint32_t nQueue, const float *pending, KzTraceWfHit *hits, float *sums, KzTraceWfInfo *info);
+
 /* Debug / known-answer entry points (used by the parity tests, not by a renderer):
  * kz_render_samples: radiance of explicit (pixel, sample index) pairs = renderSample (renderer.cpp:20-40) without
  * the block.put; pxy = n x (x,y), out = n x (pixelSample.x, pixelSample.y, r, g, b).

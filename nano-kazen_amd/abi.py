@@ -175,6 +175,24 @@ class KzHit(C.Structure):
                 ("sh_n", C.c_float * 3), ("geo_n", C.c_float * 3)]
 
 
+class KzTraceWfOpts(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("stats", C.c_int32), ("refill", C.c_int32), ("postpone", C.c_int32), ("batch", C.c_int32), ("ldsStack", C.c_int32),
+                ("gridBlocks", C.c_int32), ("packetBatch", C.c_int32)]
+
+
+class KzTraceWfHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("gid", C.c_uint32), ("mesh", C.c_int32), ("prim", C.c_int32)]
+
+
+class KzTraceWfInfo(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("nodeVisits", C.c_uint64), ("triTests", C.c_uint64), ("nQueueB", C.c_uint32), ("nFirstHitsOnInvisibleLight", C.c_uint32),
+                ("gridBlocks", C.c_uint32), ("ldsStack", C.c_uint32), ("stackBound", C.c_uint32), ("ovfRows", C.c_uint32), ("ovfRowsTouched", C.c_uint32),
+                ("shadowFast", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class KzVertexUpdate(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("nV", C.c_uint32), ("V", f32p), ("N", f32p)]
 
@@ -207,7 +225,7 @@ EXPORTS = ["kz_scene_create", "kz_scene_destroy", "kz_scene_bvh_info", "kz_scene
            "kz_scene_evict", "kz_scene_devices", "kz_render_tiles", "kz_render_multi", "kz_deal_tiles", "kz_film_merge", "kz_film_download_on",
            "kz_film_clear_on", "kz_sync_on", "kz_last_pass_info", "kz_device_mem_info", "kz_camera_rays", "kz_light_query", "kz_kat_exact_math", "kz_kat_permute", "kz_kat_fresnel", "kz_kat_math", "kz_build_flags",
            "kz_tiles_packed_floats", "kz_film_download_tiles", "kz_film_merge_tiles", "kz_film_merge_rects", "kz_device_trim", "kz_kat_dpdf", "kz_kat_pow4", "kz_last_grow_note",
-           "kz_plan_passes", "kz_plan_schedule", "kz_plan_pass_mode", "kz_pass_mode_info", "kz_scene_table"]
+           "kz_plan_passes", "kz_plan_schedule", "kz_plan_pass_mode", "kz_pass_mode_info", "kz_scene_table", "kz_trace_rays_wf"]
 # what include/kazen_mi355x_edit.h declares (checked by tests/test_scene_edit_cpu.py): editing a scene that already exists
 EDIT_EXPORTS = ["kz_scene_set_camera", "kz_scene_set_vertices", "kz_scene_set_bsdfs", "kz_scene_set_lights", "kz_scene_set_transforms"]
 # what include/kazen_mi355x_aov.h declares (checked by tests/test_aov_cpu.py): albedo / normal / depth feature films beside the picture
@@ -260,6 +278,9 @@ def load_library(path=None):
     lib.kz_film_dims.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.kz_film_to_rgb.argtypes = [f32p, C.c_int32, C.c_int32, C.c_int32, f32p]
     lib.kz_trace_rays.argtypes = [C.c_void_p, C.c_uint32, f32p, f32p, f32p, f32p, C.POINTER(KzHit)]
+    if hasattr(lib, "kz_trace_rays_wf"):      # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_trace_rays_wf.argtypes = [C.c_void_p, C.POINTER(KzTraceWfOpts), C.c_uint32, f32p, f32p, f32p, f32p, u32p, C.c_uint32, f32p,
+                                         C.POINTER(KzTraceWfHit), f32p, C.POINTER(KzTraceWfInfo)]
     lib.kz_set_stats.argtypes = [C.c_void_p, C.c_int]
     lib.kz_get_stats.argtypes = [C.c_void_p, C.POINTER(KzStats), C.c_int]
     lib.kz_sync.argtypes = [C.c_void_p]

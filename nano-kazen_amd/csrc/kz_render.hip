@@ -15,6 +15,8 @@
 #include "kz_aov.h"
 #include "kz_state.h"
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <mutex>
 #include <string>
 
@@ -195,12 +197,53 @@ static int ensureBeams(KzScene *scene, KzDeviceState *ds, hipStream_t stream, ui
     return KZ_OK;
 }
 
+// The launch shape of the persistent traversal kernels on a scene: the grids, the per-lane stack's split between LDS and the global overflow area, the
+// batch of the packet kernel. ONE statement of it for every caller - the passes (wfPass, ensureOverflow) and the ray-level entry of the development surface
+// (kz_trace_rays_wf), which exists to run the very launches a render makes on a caller's rays.
+#define KZ_PACKET_BATCH 8                  // packets a wave of the packet kernel claims per reservation
+static unsigned travGridBlocks(const KzDeviceState *ds, const KzTune &tune) { return (unsigned)(ds->numCU * tune.travBlocksPerCU); }
+static unsigned packetGridBlocks(const KzDeviceState *ds) { return (unsigned)(ds->numCU * 8); }      // the packet kernel is compiled for 8 waves per SIMD whatever KZ_TRACE_WAVES is
+static bool packetFits(const KzParams &P) { return P.stackBound4 <= 128; }                            // its stack is two VGPRs: 128 entries
+struct TraceShape {
+    int ldsStack;            // entries per lane in LDS: tune.ldsStack clamped to [2, the builder's worst case]
+    size_t traceLds;         // bytes of dynamic LDS per workgroup: + one scratch slot per lane (branch-free pushes)
+    uint32_t ovfStride;      // words per overflow row: one per thread of the grid
+    size_t ovfRows, ovfPart; // rows, and words, one launch's stacks may spill into: the rest of the worst case (known from the builder)
+};
+static TraceShape traceShape(const KzParams &P, unsigned gridBlocks, int ldsStackAsked) {
+    TraceShape s;
+    const int stackBound = std::max(P.stackBound4, 2);
+    s.ldsStack = std::max(2, std::min(ldsStackAsked, stackBound));
+    s.traceLds = (size_t)(s.ldsStack + 1) * KZ_BLOCK * sizeof(uint32_t);
+    s.ovfStride = (uint32_t)((size_t)gridBlocks * KZ_BLOCK);
+    s.ovfRows = (size_t)std::max(1, stackBound - s.ldsStack);
+    s.ovfPart = (size_t)s.ovfStride * s.ovfRows;
+    return s;
+}
+// One kz_wf_trace launch: mode 0 / 1 / 2 / 4 on queue q (nullptr: identity) of *cptr (nullptr: cimm) entries, with the defaults a tuning leaves open.
+static void launchTrace(int mode, bool stats, dim3 grid, size_t traceLds, hipStream_t on, const KzParams &P, const KzDevTables &T, const KzWf &W, const uint32_t *q, const uint32_t *cptr,
+                        uint32_t cimm, uint32_t *head, KzTune t, uint32_t *qb, uint32_t *cb) {
+    if (t.batch <= 0) t.batch = 128;                 // (the least a wave reserves per global atomic: kz_wf_trace asks for more while much is left)
+    // idle lanes are refilled once fewer than this many are busy. A refill of the shadow kernel is the dearer one (the invisible-light test of every new
+    // ray), so it waits for more idle lanes: same-call sweep, shadow stage 21.7 / 20.9 / 20.9 ms at 40 / 32 / 28 on C3, 20.3 / 20.0 / 20.3 on C4; the
+    // closest-hit kernel 32.85 / 33.3 / 34.2 on C4
+    if (t.refill <= 0) t.refill = (mode == 2 || mode == 4) ? 32 : 40;
+    hipLaunchKernelGGL(traceFn(mode, stats), grid, dim3(KZ_BLOCK), traceLds, on, P, T, W, q, cptr, cimm, head, t, qb, cb);
+}
+// The shadow rays of queue q: with P.shadowFast the any-hit kernel without the walk-through machinery; the (rare) rays whose segment crosses an
+// invisible-light triangle go to litQ and are walked through by the general kernel. Without it the general kernel takes everything.
+// trace(mode, q, cptr, cimm, head, qb, cb) launches.
+template <class Trace>
+static void shadowLaunches(const KzParams &P, Trace &&trace, const uint32_t *q, const uint32_t *cptr, uint32_t cimm, uint32_t *head, uint32_t *litQ, uint32_t *litCount, uint32_t *litHead) {
+    if (P.shadowFast) {
+        trace(4, q, cptr, cimm, head, litQ, litCount);
+        if (P.anyInvisibleLight) trace(2, (const uint32_t *)litQ, (const uint32_t *)litCount, 0u, litHead, (uint32_t *)nullptr, (uint32_t *)nullptr);
+    } else trace(2, q, cptr, cimm, head, (uint32_t *)nullptr, (uint32_t *)nullptr);
+}
+
 // The global overflow area of the traversal stacks (entries beyond tune.ldsStack per lane, sized from the builder's worst-case bound) of one pass context.
 static int ensureOverflow(KzScene *scene, KzDeviceState *ds, PassCtx &c, const KzTune &tune, hipStream_t stream) {
-    const KzParams &P = scene->prm;
-    const int stackBound = std::max(P.stackBound4, 2);
-    const int ldsStack = std::max(2, std::min(tune.ldsStack, stackBound));
-    const size_t stride = (size_t)(ds->numCU * tune.travBlocksPerCU) * KZ_BLOCK, needOvf = stride * (size_t)std::max(1, stackBound - ldsStack) * 3;      // (x 3: part 0 the pass's own stream, part 1 spare, part 2 the shadow kernels of a small pass on the side stream, wfPass)
+    const size_t needOvf = traceShape(scene->prm, travGridBlocks(ds, tune), tune.ldsStack).ovfPart * 3;      // (x 3: part 0 the pass's own stream, part 1 spare, part 2 the shadow kernels of a small pass on the side stream, wfPass)
     if (needOvf <= c.ovfCap) return KZ_OK;
     HIP_TRY(hipStreamSynchronize(stream));
     return kzRegrow(c.ovf, c.ovfCap, needOvf);
@@ -219,12 +262,7 @@ struct WfLaunch {
         KzTune t = tune;
         const bool side = on != nullptr;                 // (a launch beside the pass's own stream walks its own part of the overflow area)
         if (side) t.ovf = tune.ovf + 2 * ovfPart; else on = stream;
-        if (t.batch <= 0) t.batch = 128;                 // (the least a wave reserves per global atomic: kz_wf_trace asks for more while much is left)
-        // idle lanes are refilled once fewer than this many are busy. A refill of the shadow kernel is the dearer one (the invisible-light test of every new
-        // ray), so it waits for more idle lanes: same-call sweep, shadow stage 21.7 / 20.9 / 20.9 ms at 40 / 32 / 28 on C3, 20.3 / 20.0 / 20.3 on C4; the
-        // closest-hit kernel 32.85 / 33.3 / 34.2 on C4
-        if (t.refill <= 0) t.refill = (mode == 2 || mode == 4) ? 32 : 40;
-        hipLaunchKernelGGL(traceFn(mode, st), gTrav, blk, traceLds, on, P, ds->T, W, q, cptr, cimm, head, t, qb, cb);
+        launchTrace(mode, st, gTrav, traceLds, on, P, ds->T, W, q, cptr, cimm, head, t, qb, cb);
     }
 };
 
@@ -233,16 +271,16 @@ struct WfLaunch {
 static int wfCamera(WfLaunch &L, bool beams) {
     const KzParams &P = L.P; const KzWf &W = L.W; KzDeviceState *ds = L.ds; hipStream_t stream = L.stream;
     uint32_t *cam = W.counts + KzCounts::kCamera, *fixCount = cam + KzCounts::kPaths;      // (fixCount: first hits on an invisible light, in W.queue[2])
-    const bool packet = L.tune.packet != 1 && P.stackBound4 <= 128, fix = P.anyInvisibleLight != 0;
+    const bool packet = L.tune.packet != 1 && packetFits(P), fix = P.anyInvisibleLight != 0;
     if (packet && beams) {
         // (the lists of this pass's pixels were handed to kz_wf_beam on the call's stream - ensureBeams - and this stream has waited for it)
         uint32_t *fbQ = W.queue[0], *fbCount = W.counts + KzCounts::kFallback, *fbHead = fbCount + 1;      // rays of pixels whose list overflowed: the packet kernel's
         hipLaunchKernelGGL(listFn(L.st, fix), L.gItems, L.blk, 0, stream, P, ds->T, W, L.pixList, L.items, L.Sp, (const uint2 *)ds->beamEntries, (const uint2 *)ds->beamCount,
                            fbQ, fbCount, W.queue[2], fixCount);
-        hipLaunchKernelGGL(packetFn(L.st, fix), L.gPacket, L.blk, 0, stream, P, ds->T, W, (const uint32_t *)fbQ, (const uint32_t *)fbCount, 0u, fbHead, 8, W.queue[2], fixCount);
+        hipLaunchKernelGGL(packetFn(L.st, fix), L.gPacket, L.blk, 0, stream, P, ds->T, W, (const uint32_t *)fbQ, (const uint32_t *)fbCount, 0u, fbHead, KZ_PACKET_BATCH, W.queue[2], fixCount);
     } else if (packet) {
         // (scenes with an invisible light: the epilogue queues the first hits on such a light for the walk-through launch below)
-        hipLaunchKernelGGL(packetFn(L.st, fix), L.gPacket, L.blk, 0, stream, P, ds->T, W, (const uint32_t *)nullptr, (const uint32_t *)nullptr, L.items, cam + KzCounts::kBounceHead, 8, W.queue[2], fixCount);
+        hipLaunchKernelGGL(packetFn(L.st, fix), L.gPacket, L.blk, 0, stream, P, ds->T, W, (const uint32_t *)nullptr, (const uint32_t *)nullptr, L.items, cam + KzCounts::kBounceHead, KZ_PACKET_BATCH, W.queue[2], fixCount);
     } else {
         L.trace(0, nullptr, nullptr, L.items, cam + KzCounts::kBounceHead, nullptr, nullptr);
         if (fix) hipLaunchKernelGGL(kz_wf_primary_fix, L.gShade, L.blk, 0, stream, P, ds->T, W, L.items, W.queue[2], fixCount);
@@ -323,13 +361,10 @@ static int wfMis(WfLaunch &L, bool beside) {
         hipStream_t shOn = nullptr;
         if (beside && needExtend) { HIP_TRY(hipEventRecord(c.evFork, stream)); HIP_TRY(hipStreamWaitEvent(c.side, c.evFork, 0)); shOn = c.side; }
         if (P.nLights > 0) {
-            if (P.shadowFast) {
-                // any-hit kernel without the walk-through machinery; the (rare) rays whose segment crosses an invisible-light triangle go to a
-                // queue - the ping-pong path queue this bounce's shade has just consumed - and are walked through by the general kernel
-                uint32_t *litQ = W.queue[(iter & 1) ^ 1], *litCount = W.counts + KzCounts::lit(iter), *litHead = litCount + 1;
-                L.trace(4, shQ, shCount, 0u, nextCount + KzCounts::kShadowHead, litQ, litCount, shOn);
-                if (P.anyInvisibleLight) L.trace(2, litQ, litCount, 0u, litHead, nullptr, nullptr, shOn);
-            } else L.trace(2, shQ, shCount, 0u, nextCount + KzCounts::kShadowHead, nullptr, nullptr, shOn);
+            // (the queue of the rays that cross an invisible-light triangle is the ping-pong path queue this bounce's shade has just consumed)
+            uint32_t *litQ = W.queue[(iter & 1) ^ 1], *litCount = W.counts + KzCounts::lit(iter), *litHead = litCount + 1;
+            shadowLaunches(P, [&](int mode, const uint32_t *q, const uint32_t *cptr, uint32_t cimm, uint32_t *head, uint32_t *qb, uint32_t *cb) { L.trace(mode, q, cptr, cimm, head, qb, cb, shOn); },
+                           shQ, shCount, 0u, nextCount + KzCounts::kShadowHead, litQ, litCount, litHead);
         }
         if (shOn) HIP_TRY(hipEventRecord(c.evJoin, c.side));
         if ((rc = L.mark(3))) return rc;
@@ -375,15 +410,15 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
     // other integrators run 8 per CU.
     const int shadeBlocks = tune.shadeBlocksPerCU > 0 ? tune.shadeBlocksPerCU : !mis ? 8 : (P.bsdfExt ? 6 : KZ_SHADE_WAVES);
     L.blk = dim3(KZ_BLOCK); L.gItems = dim3((items + KZ_BLOCK - 1) / KZ_BLOCK);
-    L.gTrav = dim3((unsigned)(ds->numCU * tune.travBlocksPerCU)); L.gShade = dim3((unsigned)(ds->numCU * shadeBlocks));
-    L.gPacket = dim3((unsigned)(ds->numCU * 8));                   // the packet kernel is compiled for 8 waves per SIMD whatever KZ_TRACE_WAVES is
+    L.gTrav = dim3(travGridBlocks(ds, tune)); L.gShade = dim3((unsigned)(ds->numCU * shadeBlocks));
+    L.gPacket = dim3(packetGridBlocks(ds));
     // stack: tune.ldsStack entries per lane in LDS, the rest of the worst case (known from the builder) in a global overflow area
-    const int stackBound = std::max(P.stackBound4, 2);
-    tune.ldsStack = std::max(2, std::min(tune.ldsStack, stackBound));
-    L.traceLds = (size_t)(tune.ldsStack + 1) * KZ_BLOCK * sizeof(uint32_t);      // + one scratch slot per lane (branch-free pushes)
+    const TraceShape shape = traceShape(P, L.gTrav.x, tune.ldsStack);
+    tune.ldsStack = shape.ldsStack;
+    L.traceLds = shape.traceLds;
     if ((rc = ensureOverflow(scene, ds, c, tune, stream))) return rc;
-    tune.ovf = c.ovf; tune.ovfStride = (uint32_t)((size_t)L.gTrav.x * KZ_BLOCK);
-    L.tune = tune; L.ovfPart = (size_t)tune.ovfStride * (size_t)std::max(1, stackBound - tune.ldsStack);
+    tune.ovf = c.ovf; tune.ovfStride = shape.ovfStride;
+    L.tune = tune; L.ovfPart = shape.ovfPart;
     c.stageUsed = 0;
     HIP_TRY(hipMemsetAsync(W.counts, 0, KzCounts::bytes(), stream));
     if ((rc = L.mark(-1))) return rc;
@@ -826,6 +861,115 @@ int kz_aov_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint32_
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dOut.p, (size_t)n * 40, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; ++i) { out[10 * (size_t)i] += (float)pxy[2 * i]; out[10 * (size_t)i + 1] += (float)pxy[2 * i + 1]; }      // sample position = pixel + jitter
+    return KZ_OK;
+}
+
+// The product traversal launches on a caller's rays (kazen_mi355x_dev.h): the kernels come from the tables the passes pick from (traceFn, packetFn), their
+// grids, LDS size, stack split and overflow stride from the functions the passes call (traceShape, launchTrace, shadowLaunches) - what runs here is what a
+// render runs, on rays a render rarely or never makes. The path state is the call's own: only the arrays these kernels touch.
+int kz_trace_rays_wf(KzScene *scene, const KzTraceWfOpts *opts, uint32_t nSlots, const float *o, const float *d, const float *tmin, const float *tmax,
+                     const uint32_t *queue, uint32_t nQueue, const float *pending, KzTraceWfHit *hits, float *sums, KzTraceWfInfo *info) {
+    KzDeviceState *ds; int rc;
+    if (info) memset(info, 0, sizeof *info);
+    if ((rc = requireDevice(scene, &ds))) return rc;
+    if (!opts) return kz_fail(KZ_ERR_INVALID_ARG, "null options");
+    if (opts->kernel < 0 || opts->kernel > 3) return kz_fail(KZ_ERR_INVALID_ARG, "kernel %d (0 per-lane closest hit, 1 packet, 2 walk-through ray, 3 shadow test)", opts->kernel);
+    const KzParams &P = scene->prm;
+    if (opts->kernel == 1 && !packetFits(P)) return kz_fail(KZ_ERR_INVALID_ARG, "the packet kernel's stack holds 128 entries and this scene's tree may need %d: a render takes the per-lane kernel", P.stackBound4);
+    if (opts->gridBlocks < 0 || opts->gridBlocks > (int)packetGridBlocks(ds) || opts->packetBatch < 0 || opts->ldsStack > 63)
+        return kz_fail(KZ_ERR_INVALID_ARG, "gridBlocks %d (0 .. %u), packetBatch %d (>= 0) or ldsStack %d (<= 63) out of range", opts->gridBlocks, packetGridBlocks(ds), opts->packetBatch, opts->ldsStack);
+    const uint32_t count = queue ? nQueue : nSlots;
+    if (nSlots == 0 || count == 0) return KZ_OK;
+    if (!o || !d || !tmin || !tmax || !hits || !sums || (opts->kernel == 3 && !pending)) return kz_fail(KZ_ERR_INVALID_ARG, "null ray, hit, sum or pending-radiance buffer");
+    // (the child keys of a node order as unsigned integers only for entry distances with a clear sign bit, and a render never passes anything else: -0.0 is refused too)
+    for (uint32_t i = 0; i < nSlots; ++i) if (!(tmin[i] >= 0.f) || std::signbit(tmin[i])) return kz_fail(KZ_ERR_INVALID_ARG, "slot %u: tmin %g (negative or NaN)", i, (double)tmin[i]);
+    if (queue) {
+        if (nQueue > nSlots) return kz_fail(KZ_ERR_INVALID_ARG, "%u queue entries for %u slots: one would repeat", nQueue, nSlots);
+        std::vector<uint8_t> seen(nSlots, 0);
+        for (uint32_t i = 0; i < nQueue; ++i) {
+            if (queue[i] >= nSlots) return kz_fail(KZ_ERR_INVALID_ARG, "queue entry %u names slot %u of %u", i, queue[i], nSlots);
+            if (seen[queue[i]]) return kz_fail(KZ_ERR_INVALID_ARG, "queue entry %u repeats slot %u", i, queue[i]);
+            seen[queue[i]] = 1;
+        }
+    }
+    KzTuning asked{};
+    asked.refill = opts->refill; asked.postpone = opts->postpone; asked.batch = opts->batch; asked.ldsStack = opts->ldsStack;
+    KzTune tune;
+    if ((rc = resolveTune(asked, tune))) return rc;
+    const bool packet = opts->kernel == 1, st = opts->stats != 0;
+    const unsigned gridBlocks = opts->gridBlocks > 0 ? (unsigned)opts->gridBlocks : (packet ? packetGridBlocks(ds) : travGridBlocks(ds, tune));
+    const TraceShape shape = traceShape(P, gridBlocks, tune.ldsStack);
+    tune.ldsStack = shape.ldsStack;
+
+    // ---- the call's own path state: rays both as a path's ray (rayA / rayB) and as a shadow / walk-through ray (shA / shB), hit records, pending radiance, sums
+    const size_t n = nSlots;
+    std::vector<float4> a(n), b(n), sa(n), sb(n), sl(n), h(n);
+    std::vector<float> planes(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+        a[i] = make_float4(o[3 * i], o[3 * i + 1], o[3 * i + 2], tmin[i]); b[i] = make_float4(d[3 * i], d[3 * i + 1], d[3 * i + 2], tmax[i]);
+        sa[i] = make_float4(o[3 * i], o[3 * i + 1], o[3 * i + 2], tmax[i]); sb[i] = make_float4(d[3 * i], d[3 * i + 1], d[3 * i + 2], tmin[i]);
+        sl[i] = pending ? make_float4(pending[3 * i], pending[3 * i + 1], pending[3 * i + 2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float gidBits; memcpy(&gidBits, &hits[i].gid, 4);
+        h[i] = make_float4(hits[i].t, hits[i].u, hits[i].v, gidBits);
+        for (int k = 0; k < 3; ++k) planes[k * n + i] = sums[3 * i + k];
+    }
+    DevMem dA, dB, dSA, dSB, dSL, dH, dPl, dQ, dQB, dCounts, dStats, dOvf;
+    KZ_ALLOC(&dA.p, n * 16); KZ_ALLOC(&dB.p, n * 16); KZ_ALLOC(&dSA.p, n * 16); KZ_ALLOC(&dSB.p, n * 16); KZ_ALLOC(&dSL.p, n * 16); KZ_ALLOC(&dH.p, n * 16);
+    KZ_ALLOC(&dPl.p, 3 * n * 4); KZ_ALLOC(&dQ.p, (size_t)count * 4); KZ_ALLOC(&dQB.p, (size_t)count * 4);
+    KZ_ALLOC(&dCounts.p, 16 * 4); KZ_ALLOC(&dStats.p, 32 * 8);
+    // the overflow area of ONE launch at a time (the launches below run one after another on one stream) and, behind it, one guard row: words no stack may reach
+    const size_t ovfWords = shape.ovfPart + shape.ovfStride;
+    KZ_ALLOC(&dOvf.p, ovfWords * 4);
+    HIP_TRY(hipMemcpy(dA.p, a.data(), n * 16, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dB.p, b.data(), n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dSA.p, sa.data(), n * 16, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dSB.p, sb.data(), n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dSL.p, sl.data(), n * 16, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dH.p, h.data(), n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dPl.p, planes.data(), 3 * n * 4, hipMemcpyHostToDevice));
+    if (queue) HIP_TRY(hipMemcpy(dQ.p, queue, (size_t)count * 4, hipMemcpyHostToDevice));
+    // counter words: 0 the queue's count, 1 .. 3 the work heads of up to three launches, 4 / 5 queueB's count and head, 6 the packet kernel's first hits on an invisible light
+    uint32_t cw[16] = {count};
+    HIP_TRY(hipMemcpy(dCounts.p, cw, sizeof cw, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dStats.p, 0, 32 * 8));
+    HIP_TRY(hipMemset(dOvf.p, 0xFF, ovfWords * 4));
+    KzWf W{};
+    W.rayA.p = dA.as<float4>(); W.rayB.p = dB.as<float4>(); W.hit.p = dH.as<float4>(); W.shA.p = dSA.as<float4>(); W.shB.p = dSB.as<float4>(); W.shL.p = dSL.as<float4>();
+    W.outR = dPl.as<float>(); W.outG = W.outR + n; W.outB = W.outG + n; W.counts = dCounts.as<uint32_t>(); W.stats = dStats.as<unsigned long long>();
+    tune.ovf = dOvf.as<uint32_t>(); tune.ovfStride = shape.ovfStride;
+    uint32_t *c = W.counts;
+    const uint32_t *q = queue ? dQ.as<uint32_t>() : nullptr, *cptr = queue ? c : nullptr;      // (a queue's count is read on the device, as a pass's are; the identity queue's travels as an argument, as the camera rays' does)
+    const uint32_t cimm = queue ? 0u : count;
+    hipStream_t stream = nullptr;
+    auto trace = [&](int mode, const uint32_t *q_, const uint32_t *cptr_, uint32_t cimm_, uint32_t *head, uint32_t *qb, uint32_t *cb) {
+        launchTrace(mode, st, dim3(gridBlocks), shape.traceLds, stream, P, ds->T, W, q_, cptr_, cimm_, head, tune, qb, cb);
+    };
+    if (opts->kernel == 0) trace(0, q, cptr, cimm, c + 1, nullptr, nullptr);
+    else if (packet) hipLaunchKernelGGL(packetFn(st, P.anyInvisibleLight != 0), dim3(gridBlocks), dim3(KZ_BLOCK), 0, stream, P, ds->T, W, q, cptr, cimm, c + 1,
+                                        opts->packetBatch > 0 ? opts->packetBatch : KZ_PACKET_BATCH, dQB.as<uint32_t>(), c + 6);
+    else if (opts->kernel == 2) trace(1, q, cptr, cimm, c + 1, nullptr, nullptr);
+    else shadowLaunches(P, trace, q, cptr, cimm, c + 1, dQB.as<uint32_t>(), c + 4, c + 5);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(h.data(), dH.p, n * 16, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(planes.data(), dPl.p, 3 * n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cw, dCounts.p, sizeof cw, hipMemcpyDeviceToHost));
+    unsigned long long stats[32];
+    HIP_TRY(hipMemcpy(stats, dStats.p, sizeof stats, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> ovf(packet ? 0 : ovfWords);
+    if (!packet) HIP_TRY(hipMemcpy(ovf.data(), dOvf.p, ovfWords * 4, hipMemcpyDeviceToHost));
+    size_t touched = 0;                                         // overflow rows a stack reached (the guard row included)
+    for (size_t w = ovf.size(); w > 0; --w) if (ovf[w - 1] != 0xFFFFFFFFu) { touched = (w - 1) / shape.ovfStride + 1; break; }
+    if (touched > shape.ovfRows) return kz_fail(KZ_ERR_STATE, "a traversal stack spilled past the %zu overflow rows of the launch (LDS entries %d, the builder's bound %d)", shape.ovfRows, shape.ldsStack, P.stackBound4);
+    for (size_t i = 0; i < n; ++i) {
+        KzTraceWfHit &r = hits[i];
+        r.t = h[i].x; r.u = h[i].y; r.v = h[i].z; memcpy(&r.gid, &h[i].w, 4);
+        const bool known = r.t < KZ_INF && (size_t)r.gid < scene->shade.size();      // (mesh and primitive of a triangle never change: the host's shading records name them)
+        r.mesh = known ? (int32_t)scene->shade[r.gid].mesh : -1; r.prim = known ? (int32_t)scene->shade[r.gid].prim : -1;
+        for (int k = 0; k < 3; ++k) sums[3 * i + k] = planes[k * n + i];
+    }
+    if (info) {
+        info->rays = stats[1]; info->nodeVisits = stats[2]; info->triTests = stats[3];
+        info->nQueueB = opts->kernel == 3 ? cw[4] : 0; info->nFirstHitsOnInvisibleLight = packet ? cw[6] : 0;
+        info->gridBlocks = gridBlocks; info->ldsStack = (uint32_t)shape.ldsStack; info->stackBound = (uint32_t)std::max(P.stackBound4, 0);
+        info->ovfRows = packet ? 0 : (uint32_t)shape.ovfRows; info->ovfRowsTouched = (uint32_t)touched; info->shadowFast = (uint32_t)P.shadowFast;
+    }
     return KZ_OK;
 }
 

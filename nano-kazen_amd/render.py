@@ -333,6 +333,37 @@ class Scene:
                                                    tmin.ctypes.data_as(abi.f32p), tmax.ctypes.data_as(abi.f32p), hits))
         return hits_to_arrays(hits, n)
 
+    def trace_rays_wf(self, o, d, tmin, tmax, kernel=0, queue=None, pending=None, hits=None, sums=None, stats=False, refill=0, postpone=0, batch=0,
+                      lds_stack=0, grid_blocks=0, packet_batch=0):
+        """kz_trace_rays_wf (include/kazen_mi355x_dev.h): the traversal launches of a render - kernel 0 per-lane closest hit, 1 packet, 2 walk-through ray, 3 shadow
+        test - on these rays, one per slot. hits: (n, 4) float32 = t, u, v and the bits of gid, the slots' records before the launch (default: NaN, NaN, NaN,
+        0xFFFFFFFF); sums, pending: (n, 3). Returns {"t", "u", "v", "gid", "mesh", "prim", "sums", "info"}."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        tmin = np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, np.float32), (n,)))
+        tmax = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        rec = np.zeros(n, np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("gid", "<u4"), ("mesh", "<i4"), ("prim", "<i4")]))
+        assert rec.itemsize == C.sizeof(abi.KzTraceWfHit)
+        if hits is None:
+            rec["t"] = rec["u"] = rec["v"] = np.nan
+            rec["gid"] = 0xFFFFFFFF
+        else:
+            hits = np.ascontiguousarray(hits, np.float32).reshape(n, 4)
+            rec["t"], rec["u"], rec["v"], rec["gid"] = hits[:, 0], hits[:, 1], hits[:, 2], hits[:, 3].view(np.uint32)
+        sums = np.zeros((n, 3), np.float32) if sums is None else np.array(sums, np.float32).reshape(n, 3)
+        pend = None if pending is None else np.ascontiguousarray(pending, np.float32).reshape(n, 3)
+        q = None if queue is None else np.ascontiguousarray(queue, np.uint32).reshape(-1)
+        opts = abi.KzTraceWfOpts(int(kernel), 1 if stats else 0, int(refill), int(postpone), int(batch), int(lds_stack), int(grid_blocks), int(packet_batch))
+        info = abi.KzTraceWfInfo()
+        abi.check(self.lib, self.lib.kz_trace_rays_wf(self.h, C.byref(opts), n, o.ctypes.data_as(abi.f32p), d.ctypes.data_as(abi.f32p), tmin.ctypes.data_as(abi.f32p),
+                                                      tmax.ctypes.data_as(abi.f32p), None if q is None else q.ctypes.data_as(abi.u32p), 0 if q is None else q.size,
+                                                      None if pend is None else pend.ctypes.data_as(abi.f32p), rec.ctypes.data_as(C.POINTER(abi.KzTraceWfHit)),
+                                                      sums.ctypes.data_as(abi.f32p), C.byref(info)))
+        out = {k: rec[k].copy() for k in rec.dtype.names}
+        out["sums"], out["info"] = sums, info.as_dict()
+        return out
+
     def render_samples(self, pxy, idx):
         pxy = np.ascontiguousarray(pxy, np.int32)
         idx = np.ascontiguousarray(idx, np.uint32)

@@ -2,7 +2,8 @@
 // first hit the scene's integrator shades - the record W.hit[slot] holds when the camera stage (wfCamera, kz_render.hip) returns: for path_mis after the H6
 // walk-through of an invisible light, for the three others the first hit itself. Two forms, as for the integrators: the wavefront kernel kz_wf_aov that
 // wfPass launches between the camera stage and the first shade / ao / mats launch, and a reference-shaped kernel (one lane = one sample, BVH2) behind
-// kz_aov_samples. Nothing here is shared with the path kernels: their compiled code stays what it was.
+// kz_aov_samples. Sample to camera ray, hit record to RawHit and the walk-through test are the path kernels' own functions (kz_devfn.h); that those kernels'
+// compiled code stays what it was is checked by scripts/device_code_diff.sh.
 #pragma once
 #include "kz_devfn.h"
 #include "kz_wavefront.h"
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_aov(KzDevTables T, KzWf W, uin
         const float4 h = kzLoadStream(&W.hit[slot]);
         V3 albedo = mk(0.f), normal = mk(0.f); float depth = 0.f;
         if (h.x < KZ_INF) {
-            RawHit rh; rh.t = h.x; rh.u = h.y; rh.v = h.z; rh.tri = 0; rh.gid = __float_as_uint(h.w);
+            const RawHit rh = rawHitOf(h);
             Its its; postIntersect<false>(T, rh, its);
             aovFeatures<EXT>(T, its, albedo, normal);
             depth = h.x;
@@ -54,21 +55,15 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_aov_samples_kernel(KzParams P, Kz
     if (item >= nItems) return;
     uint32_t *stk = s_stack + threadIdx.x;
     Counters cn = {0, 0, 0, 0, 0, 0};
-    const uint32_t pxy = pixList[item];
-    const int px = (int)(pxy & 0xffffu), py = (int)(pxy >> 16);
-    Sampler smp; smp.type = P.samplerType;
-    smp.generateSample(P, T, px, py, itemSample[item]);
-    float jx, jy; smp.nextPixel2D(P, T, jx, jy);
-    const float sx = (float)px + jx, sy = (float)py + jy;
-    float ax, ay; smp.next2D(P, T, ax, ay);
-    V3 ro, rd; float mint, maxt;
-    cameraRay(P, sx, sy, ax, ay, ro, rd, mint, maxt);
+    int px, py; pixelOf(pixList[item], px, py);
+    Sampler smp; float jx, jy; V3 ro, rd; float mint, maxt;
+    cameraSample(P, T, px, py, itemSample[item], smp, jx, jy, ro, rd, mint, maxt);
     V3 albedo = mk(0.f), normal = mk(0.f); float depth = 0.f, hit = 0.f;
     RawHit rh; Its its;
     if (closestHit<false>(T, P.rootRef, ro, rd, mint, maxt, rh, stk, cn)) {
         postIntersect<false>(T, rh, its);
-        if (mis && its.light >= 0 && !T.lights[its.light].primaryVisibility) {                // integrator.cpp:214-219 (H6): the result is ignored on a miss
-            const V3 no = its.p + P.traceBias * rd;
+        if (mis && isInvisibleLight(T, its.light)) {                                          // integrator.cpp:214-219 (H6): the result is ignored on a miss
+            const V3 no = walkThroughOrigin(P, its, rd);
             if (closestHit<false>(T, P.rootRef, no, rd, KZ_EPSILON, KZ_INF, rh, stk, cn)) postIntersect<false>(T, rh, its);
         }
         aovFeatures<KZ_X_ALL>(T, its, albedo, normal);

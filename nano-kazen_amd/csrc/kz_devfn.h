@@ -63,6 +63,20 @@ __device__ __forceinline__ float sqrtExact(float x) {
 #define KZ_PI_F 3.14159265358979323846f
 
 struct Counters { uint32_t rays, nodes, tris, hits, lsamples, dropped; };
+// A kernel's counters to the statistics: each summed over the wave, then one atomic per counter per wave (none for a zero sum). For every kernel that counts:
+// the wavefront kernels and the megakernel. (The sum is not a function of its own: inlined one level deeper, the same lines come out of the compiler with
+// other registers in every counting kernel - scripts/device_code_diff.sh. kz_wf_beam_count, which sums three values of its own, therefore repeats the loop.)
+__device__ __forceinline__ void statsFlush(unsigned long long *stats, const Counters &cn, uint32_t samples) {
+    unsigned long long v[7] = {samples, cn.rays, cn.nodes, cn.tris, cn.hits, cn.lsamples, cn.dropped};
+    for (int k = 0; k < 7; ++k) {
+        unsigned long long x = v[k];
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+        if ((threadIdx.x & 63) == 0 && x) atomicAdd(&stats[k], x);
+    }
+}
+// A packed pixel of a pixel list (x | y << 16), and its index in the frame
+__device__ __forceinline__ void pixelOf(uint32_t pxy, int &px, int &py) { px = (int)(pxy & 0xffffu); py = (int)(pxy >> 16); }
+__device__ __forceinline__ uint32_t framePixelOf(uint32_t pxy, uint32_t width) { return (pxy >> 16) * width + (pxy & 0xffffu); }
 
 // ============================================================================================
 // a6/a7/a8 integer sampler plumbing (hash.h:15-65,71-78,100-108; pcg32.h:54-73,108-117; common.cpp:316-344)
@@ -237,6 +251,9 @@ struct Sampler {
 // (mesh.cpp:55-92), a16 slab node test (bbox.h:316-343; conservative form on padded boxes).
 // ============================================================================================
 struct RawHit { float t, u, v; uint32_t tri; uint32_t gid; };
+// ... of a traversal's closest hit (t, u, v, triangle id), and of the hit record the wavefront kernels keep it in
+__device__ __forceinline__ RawHit rawHitOf(float t, float u, float v, uint32_t gid) { RawHit rh; rh.t = t; rh.u = u; rh.v = v; rh.tri = 0; rh.gid = gid; return rh; }
+__device__ __forceinline__ RawHit rawHitOf(float4 h) { return rawHitOf(h.x, h.y, h.z, __float_as_uint(h.w)); }
 
 // One 64-B node packet: slab tests of both children (a16). Conservative on the builder's padded boxes: fminf/fmaxf drop
 // the NaN of 0*inf on a degenerate axis (that slab then does not constrain) and the far side is widened by 2 ulp.
@@ -437,12 +454,16 @@ __device__ __forceinline__ bool anyHit(const KzDevTables &T, uint32_t rootRef, V
     return false;
 }
 
-// The reference's shadow test, literally (integrator.cpp:257-278): closest hits, walking through lights whose
-// lightPrimaryVisibility is false; note that the far end moves out by traceBias per walk-through (maxt - t).
 // light row of the mesh a triangle belongs to (-1: not an emitter), from the last quad of its shading record
 __device__ __forceinline__ int lightOfGid(const KzDevTables &T, uint32_t gid) {
     return (int)(__float_as_uint(reinterpret_cast<const float4 *>(T.shade + gid)[6].w) >> 2) - 1;
 }
+// The invisible-light walk-through of a first hit (integrator.cpp:214-219, H6): a hit on a light with lightPrimaryVisibility == false is looked through -
+// the test on the hit's light row (-1: no emitter) here, the origin of the continuation ray Ray3f(o, d) - mint = Epsilon, maxt = inf - in walkThroughOrigin. ONE statement for the
+// megakernel (pathLi), the per-sample feature kernel and the three wavefront sites (kz_wavefront.h wfStoreWalkThrough).
+__device__ __forceinline__ bool isInvisibleLight(const KzDevTables &T, int li) { return li >= 0 && !T.lights[li].primaryVisibility; }
+// The reference's shadow test, literally (integrator.cpp:257-278): closest hits, walking through lights whose
+// lightPrimaryVisibility is false; note that the far end moves out by traceBias per walk-through (maxt - t).
 template <bool STATS>
 __device__ __forceinline__ bool shadowOccludedLiteral(const KzParams &P, const KzDevTables &T, V3 so, V3 dir, float smin, float smax,
                                                       uint32_t *stk, Counters &cn) {
@@ -1363,6 +1384,31 @@ __device__ __forceinline__ void cameraRay(const KzParams &P, float sx, float sy,
     mint = P.nearClip * invZ; maxt = P.farClip * invZ;
 }
 
+// renderSample up to the camera ray (renderer.cpp:20-33): the sample's sampler, the pixel jitter, the aperture draw (always consumed, renderer.cpp:28)
+// and the ray - the head of the megakernels, of kz_wf_generate and of the per-sample feature kernel.
+__device__ __forceinline__ void cameraSample(const KzParams &P, const KzDevTables &T, int px, int py, uint32_t sampleIndex, Sampler &smp, float &jx, float &jy,
+                                             V3 &ro, V3 &rd, float &mint, float &maxt) {
+    smp.type = P.samplerType;
+    smp.generateSample(P, T, px, py, sampleIndex);
+    smp.nextPixel2D(P, T, jx, jy);
+    const float sx = (float)px + jx, sy = (float)py + jy;
+    float ax, ay; smp.next2D(P, T, ax, ay);
+    cameraRay(P, sx, sy, ax, ay, ro, rd, mint, maxt);
+}
+__device__ __forceinline__ V3 walkThroughOrigin(const KzParams &P, const Its &its, V3 d) { return its.p + P.traceBias * d; }      // (see isInvisibleLight)
+
+// AreaLight::eval of a hit emitter reached along wi (integrator.cpp:226-231, 151-154): nothing from behind (emitterFaces), else (weight x throughput) x the
+// light's radiance. The weight is the caller's MIS weight (path_mats has none: 1).
+__device__ __forceinline__ bool emitterFaces(const Its &its, V3 wi) { return dot(its.sh.n, -wi) > 0.f; }
+__device__ __forceinline__ V3 emitterTerm(const KzLightRow &lr, float weight, V3 throughput) { return (weight * throughput) * mk(lr.radiance[0], lr.radiance[1], lr.radiance[2]); }
+
+// The Russian roulette of integrator.cpp:237-244 on a path's throughput and eta against its next 1-D draw: true = the path ends here. ONE function for the
+// megakernel, for the wavefront bounce that plays it (wfClassify) and for the bounce before it, which looks ahead (wfShadeSurvivor): they cannot drift apart.
+__device__ __forceinline__ bool rouletteEnds(V3 throughput, float eta, float draw, float &probability) {
+    probability = fminf(maxCoeff(throughput) * eta * eta, 0.95f);
+    return probability <= draw;
+}
+
 // ============================================================================================
 // a10 PathMisIntegrator::Li (integrator.cpp:195-338) — megakernel form, one lane per path
 // ============================================================================================
@@ -1375,24 +1421,19 @@ __device__ V3 pathLi(const KzParams &P, const KzDevTables &T, Sampler &smp, V3 r
     RawHit rh; Its its;
     if (!closestHit<STATS>(T, P.rootRef, ro, rd, rmint, rmaxt, rh, stk, cn)) return L;       // H5: primary miss is black
     postIntersect<false>(T, rh, its); if (STATS) cn.hits++;
-    {
-        const int li = its.light;
-        if (li >= 0 && !T.lights[li].primaryVisibility) {                                     // integrator.cpp:214-219 (H6)
-            V3 no = its.p + eps * rd;
-            if (closestHit<STATS>(T, P.rootRef, no, rd, KZ_EPSILON, KZ_INF, rh, stk, cn)) { postIntersect<false>(T, rh, its); if (STATS) cn.hits++; }
-        }
+    if (isInvisibleLight(T, its.light)) {                                                     // integrator.cpp:214-219 (H6)
+        const V3 no = walkThroughOrigin(P, its, rd);
+        if (closestHit<STATS>(T, P.rootRef, no, rd, KZ_EPSILON, KZ_INF, rh, stk, cn)) { postIntersect<false>(T, rh, its); if (STATS) cn.hits++; }
     }
     int depth = 0;
     while (depth < P.maxDepth) {
         if (its.light >= 0) {                                                                 // integrator.cpp:226-231
-            const KzLightRow &lr = T.lights[its.light];
-            V3 wi = normalized(its.p - ro);
-            if (dot(its.sh.n, -wi) > 0.f) L = L + (bsdfWeight * throughput) * mk(lr.radiance[0], lr.radiance[1], lr.radiance[2]);
+            if (emitterFaces(its, normalized(its.p - ro))) L = L + emitterTerm(T.lights[its.light], bsdfWeight, throughput);
             break;
         }
         if (depth >= 3) {                                                                     // integrator.cpp:237-244
-            float probability = fminf(maxCoeff(throughput) * eta * eta, 0.95f);
-            if (probability <= smp.next1D(P, T)) break;
+            float probability;
+            if (rouletteEnds(throughput, eta, smp.next1D(P, T), probability)) break;
             throughput = throughput / probability;
         }
         KzBSDF bsdf = T.bsdfs[its.bsdf];

@@ -1,7 +1,9 @@
 // kz_integrators.h - the integrators other than path_mis: "normals" (integrator.cpp:11-34), "ao" (:37-71) and "path_mats" (:137-181), in the two forms
 // the library has for path_mis: a reference-shaped megakernel (one lane = one sample, BVH2; pipeline 1 and kz_render_samples) and the wavefront kernels of
 // the default pipeline (wfPassIntegrator in kz_render.hip launches them around the unchanged camera-ray and traversal kernels of kz_wavefront.h).
-// Nothing here is shared with the path_mis kernels: their compiled code stays what it was.
+// The per-path steps these kernels have in common with the path_mis kernels and with each other - sample to camera ray, hit record to RawHit, the emitter
+// term, a slot's pixel and sample index, the radiance add - are stated once, as __forceinline__ functions of kz_devfn.h and
+// kz_wavefront.h. That the path_mis kernels' compiled code stays what it was is checked, not assumed: scripts/device_code_diff.sh.
 #pragma once
 #include "kz_devfn.h"
 #include "kz_wavefront.h"
@@ -55,14 +57,11 @@ __device__ V3 matsLi(const KzParams &P, const KzDevTables &T, Sampler &smp, V3 r
     for (int depth = 0; depth < KZ_PATH_MATS_MAX_DEPTH; ++depth) {                                     // (H15: the reference has no cap)
         if (!closestHit<false>(T, P.rootRef, ro, rd, mint, maxt, rh, stk, cn)) break;               // a miss: no background term
         postIntersect<false>(T, rh, its);
-        if (its.light >= 0) {                                                                       // AreaLight::eval, no MIS weight (integrator.cpp:151-154)
-            const KzLightRow &lr = T.lights[its.light];
-            const V3 wi = normalized(its.p - ro);
-            if (dot(its.sh.n, -wi) > 0.f) color = color + t * mk(lr.radiance[0], lr.radiance[1], lr.radiance[2]);
-        }
+        if (its.light >= 0 && emitterFaces(its, normalized(its.p - ro))) color = color + emitterTerm(T.lights[its.light], 1.f, t);      // AreaLight::eval, no MIS weight (integrator.cpp:151-154)
         const float probability = matsRoulette(t.x);                                                // integrator.cpp:157-162
         if (smp.next1D(P, T) >= probability) break;
         t = t / probability;
+        // (the bounce from here on is kz_wf_mats's, line for line: as one function of both forms it changed that kernel's compiled code - profiles/r13a_shared_steps)
         KzBSDF bsdf = T.bsdfs[its.bsdf];
         NMap nm; surfaceSetup<EXT>(T, its, bsdf, nm);                                               // (the record's uv: textures; no normal maps, H16)
         const V3 wiLocal = toLocal(its.sh, -rd);
@@ -87,15 +86,9 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_integrator_megakernel(KzParams P,
     const uint32_t item = blockIdx.x * KZ_BLOCK + threadIdx.x;
     if (item >= nItems) return;
     const uint32_t pl = item / S, so = item - pl * S;
-    const uint32_t pxy = pixList[pl];
-    const int px = (int)(pxy & 0xffffu), py = (int)(pxy >> 16);
-    Sampler smp; smp.type = P.samplerType;
-    smp.generateSample(P, T, px, py, itemSample ? itemSample[item] : sampleBegin + so);
-    float jx, jy; smp.nextPixel2D(P, T, jx, jy);
-    const float sx = (float)px + jx, sy = (float)py + jy;
-    float ax, ay; smp.next2D(P, T, ax, ay);
-    V3 ro, rd; float mint, maxt;
-    cameraRay(P, sx, sy, ax, ay, ro, rd, mint, maxt);
+    int px, py; pixelOf(pixList[pl], px, py);
+    Sampler smp; float jx, jy; V3 ro, rd; float mint, maxt;
+    cameraSample(P, T, px, py, itemSample ? itemSample[item] : sampleBegin + so, smp, jx, jy, ro, rd, mint, maxt);
     V3 L;
     if (INTEG == KZ_INTEGRATOR_NORMALS) L = normalsLi<EXT>(P, T, ro, rd, mint, maxt, s_stack + threadIdx.x);
     else if (INTEG == KZ_INTEGRATOR_AO) L = aoLi(P, T, smp, ro, rd, mint, maxt, s_stack + threadIdx.x);
@@ -112,7 +105,7 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_normals(KzParams P, KzDevTable
     for (uint32_t slot = blockIdx.x * KZ_BLOCK + threadIdx.x; slot < nItems; slot += gridDim.x * KZ_BLOCK) {
         const float4 h = kzLoadStream(&W.hit[slot]);
         if (!(h.x < KZ_INF)) continue;
-        RawHit rh; rh.t = h.x; rh.u = h.y; rh.v = h.z; rh.tri = 0; rh.gid = __float_as_uint(h.w);
+        const RawHit rh = rawHitOf(h);
         Its its; postIntersect<true>(T, rh, its);
         W.outR[slot] = fabsf(its.geoN.x); W.outG[slot] = fabsf(its.geoN.y); W.outB[slot] = fabsf(its.geoN.z);
     }
@@ -132,10 +125,10 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_ao(KzParams P, KzDevTables T, 
         if (slot < nItems) {
             const float4 h = kzLoadStream(&W.hit[slot]);
             if (h.x < KZ_INF) {
-                RawHit rh; rh.t = h.x; rh.u = h.y; rh.v = h.z; rh.tri = 0; rh.gid = __float_as_uint(h.w);
+                const RawHit rh = rawHitOf(h);
                 Its its; postIntersect<false>(T, rh, its);
-                const uint32_t pl = slot / S; const uint32_t pxy = pixList[pl];
-                Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, 4u);
+                int px, py; uint32_t sampleIndex; wfSampleOf(pixList, S, sampleBegin, slot, px, py, sampleIndex);
+                Sampler smp; wfLoadSampler(P, W, slot, px, py, sampleIndex, smp, 4u);
                 float sx, sy; smp.next2D(P, T, sx, sy);
                 const V3 dir = aoDirection(its, sx, sy);
                 const float v = 0.f + aoValue(its, dir);
@@ -172,22 +165,15 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & KZ_X_TEX) ? 3 : 4)) void kz_wf_ma
             slot = queue ? queue[qi] : qi;
             const float4 h = kzLoadStream(&W.hit[slot]);
             if (h.x < KZ_INF) {
-                RawHit rh; rh.t = h.x; rh.u = h.y; rh.v = h.z; rh.tri = 0; rh.gid = __float_as_uint(h.w);
+                const RawHit rh = rawHitOf(h);
                 Its its; postIntersect<false>(T, rh, its);
                 const float4 ra = kzLoadStream(&W.rayA[slot]), rb = kzLoadStream(&W.rayB[slot]);
                 const V3 ro = mk(ra.x, ra.y, ra.z), rd = mk(rb.x, rb.y, rb.z);
                 V3 t = mk(1.f);
                 if (iter > 0) { const float4 th = kzLoadStream(&W.thr[slot]); t = mk(th.x, th.y, th.z); }
-                if (its.light >= 0) {
-                    const KzLightRow &lr = T.lights[its.light];
-                    const V3 wi = normalized(its.p - ro);
-                    if (dot(its.sh.n, -wi) > 0.f) {
-                        const V3 c = t * mk(lr.radiance[0], lr.radiance[1], lr.radiance[2]);
-                        unsafeAtomicAdd(W.outR + slot, c.x); unsafeAtomicAdd(W.outG + slot, c.y); unsafeAtomicAdd(W.outB + slot, c.z);   // (one writer per slot)
-                    }
-                }
-                const uint32_t pl = slot / S; const uint32_t pxy = pixList[pl];
-                Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, 4u + 4u * (uint32_t)iter);
+                if (its.light >= 0) { if (emitterFaces(its, normalized(its.p - ro))) wfAddRadiance(W, slot, emitterTerm(T.lights[its.light], 1.f, t)); }      // (no MIS weight; one writer per slot)
+                int px, py; uint32_t sampleIndex; wfSampleOf(pixList, S, sampleBegin, slot, px, py, sampleIndex);
+                Sampler smp; wfLoadSampler(P, W, slot, px, py, sampleIndex, smp, 4u + 4u * (uint32_t)iter);
                 const float probability = matsRoulette(t.x);
                 if (!(smp.next1D(P, T) >= probability)) {
                     t = t / probability;

@@ -32,15 +32,9 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_path_megakernel(KzParams P, KzDev
     Counters cn = {0, 0, 0, 0, 0, 0};
     if (item < nItems) {
         const uint32_t pl = item / S, so = item - pl * S;
-        const uint32_t pxy = pixList[pl];
-        const int px = (int)(pxy & 0xffffu), py = (int)(pxy >> 16);
-        Sampler smp; smp.type = P.samplerType;
-        smp.generateSample(P, T, px, py, itemSample ? itemSample[item] : sampleBegin + so);
-        float jx, jy; smp.nextPixel2D(P, T, jx, jy);
-        const float sx = (float)px + jx, sy = (float)py + jy;
-        float ax, ay; smp.next2D(P, T, ax, ay);                  // aperture sample, always consumed (renderer.cpp:28)
-        V3 ro, rd; float mint, maxt;
-        cameraRay(P, sx, sy, ax, ay, ro, rd, mint, maxt);
+        int px, py; pixelOf(pixList[pl], px, py);
+        Sampler smp; float jx, jy; V3 ro, rd; float mint, maxt;
+        cameraSample(P, T, px, py, itemSample ? itemSample[item] : sampleBegin + so, smp, jx, jy, ro, rd, mint, maxt);
         V3 L = pathLi<STATS, EXT>(P, T, smp, ro, rd, mint, maxt, s_stack + threadIdx.x, cn);
         outJx[item] = jx; outJy[item] = jy; outR[item] = L.x; outG[item] = L.y; outB[item] = L.z;
         if (STATS) {
@@ -48,15 +42,7 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_path_megakernel(KzParams P, KzDev
             if (!valid) cn.dropped++;
         }
     }
-    if (STATS) {
-        // wave reduction then one atomic per counter per wave
-        unsigned long long v[7] = {item < nItems ? 1ull : 0ull, cn.rays, cn.nodes, cn.tris, cn.hits, cn.lsamples, cn.dropped};
-        for (int k = 0; k < 7; ++k) {
-            unsigned long long x = v[k];
-            for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-            if ((threadIdx.x & 63) == 0 && x) atomicAdd(&stats[k], x);
-        }
-    }
+    if (STATS) statsFlush(stats, cn, item < nItems ? 1u : 0u);
 }
 
 // KzTuning -> the kernels' KzTune. Zero = the library default. (The KZ_* environment overrides of ABI v2 / v3 are gone: nothing in the
@@ -803,10 +789,10 @@ int kz_render_tiles(KzScene *scene, const KzRenderOpts *opts, const KzTile *tile
     return KZ_OK;
 }
 
-int kz_render_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint32_t *idx, float *out) {
-    KzDeviceState *ds; int rc;
-    if ((rc = requireDevice(scene, &ds))) return rc;
-    if (n == 0) return KZ_OK;
+// What the per-sample entry points share: n > 0 samples (pixel x, y and sample index) checked against the scene, the megakernels' BVH2 made sure of, and the
+// pixels (packed as a pixel list) and indices uploaded into dP / dI.
+static int uploadSamples(KzScene *scene, KzDeviceState *ds, uint32_t n, const int32_t *pxy, const uint32_t *idx, const float *out, DevMem &dP, DevMem &dI) {
+    int rc;
     if (!pxy || !idx || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null buffer");
     if ((rc = kzEnsureBvh2(scene, ds))) return rc;
     const KzParams &P = scene->prm;
@@ -816,10 +802,20 @@ int kz_render_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint
             return kz_fail(KZ_ERR_INVALID_ARG, "sample %u: pixel (%d,%d) index %u out of range", i, pxy[2 * i], pxy[2 * i + 1], idx[i]);
         pl[i] = (uint32_t)pxy[2 * i] | ((uint32_t)pxy[2 * i + 1] << 16);
     }
-    DevMem dP, dI, dOut;
-    KZ_ALLOC(&dP.p, (size_t)n * 4); KZ_ALLOC(&dI.p, (size_t)n * 4); KZ_ALLOC(&dOut.p, (size_t)n * 20);
-    float *dO = dOut.as<float>();
+    KZ_ALLOC(&dP.p, (size_t)n * 4); KZ_ALLOC(&dI.p, (size_t)n * 4);
     HIP_TRY(hipMemcpy(dP.p, pl.data(), (size_t)n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dI.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
+    return KZ_OK;
+}
+
+int kz_render_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint32_t *idx, float *out) {
+    KzDeviceState *ds; int rc;
+    if ((rc = requireDevice(scene, &ds))) return rc;
+    if (n == 0) return KZ_OK;
+    DevMem dP, dI, dOut;
+    if ((rc = uploadSamples(scene, ds, n, pxy, idx, out, dP, dI))) return rc;
+    const KzParams &P = scene->prm;
+    KZ_ALLOC(&dOut.p, (size_t)n * 20);
+    float *dO = dOut.as<float>();
     const dim3 gS((n + KZ_BLOCK - 1) / KZ_BLOCK);
     // one kernel per integrator serves every scene here: the variant for everything its BSDF rows may need (normals / ao read no BSDF row; path_mats has no normal maps)
     if (P.integrator == KZ_INTEGRATOR_NORMALS || P.integrator == KZ_INTEGRATOR_AO || P.integrator == KZ_INTEGRATOR_PATH_MATS)
@@ -843,18 +839,10 @@ int kz_aov_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint32_
     KzDeviceState *ds; int rc;
     if ((rc = requireDevice(scene, &ds))) return rc;
     if (n == 0) return KZ_OK;
-    if (!pxy || !idx || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null buffer");
-    if ((rc = kzEnsureBvh2(scene, ds))) return rc;
-    const KzParams &P = scene->prm;
-    std::vector<uint32_t> pl(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (pxy[2 * i] < 0 || pxy[2 * i] >= P.width || pxy[2 * i + 1] < 0 || pxy[2 * i + 1] >= P.height || idx[i] >= P.sampleCount)
-            return kz_fail(KZ_ERR_INVALID_ARG, "sample %u: pixel (%d,%d) index %u out of range", i, pxy[2 * i], pxy[2 * i + 1], idx[i]);
-        pl[i] = (uint32_t)pxy[2 * i] | ((uint32_t)pxy[2 * i + 1] << 16);
-    }
     DevMem dP, dI, dOut;
-    KZ_ALLOC(&dP.p, (size_t)n * 4); KZ_ALLOC(&dI.p, (size_t)n * 4); KZ_ALLOC(&dOut.p, (size_t)n * 40);
-    HIP_TRY(hipMemcpy(dP.p, pl.data(), (size_t)n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dI.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
+    if ((rc = uploadSamples(scene, ds, n, pxy, idx, out, dP, dI))) return rc;
+    const KzParams &P = scene->prm;
+    KZ_ALLOC(&dOut.p, (size_t)n * 40);
     hipLaunchKernelGGL(kz_aov_samples_kernel, dim3((n + KZ_BLOCK - 1) / KZ_BLOCK), dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.as<uint32_t>(), dI.as<uint32_t>(), n,
                        P.integrator == KZ_INTEGRATOR_PATH_MIS ? 1 : 0, dOut.as<float>());
     HIP_TRY(hipGetLastError());

@@ -55,21 +55,18 @@ struct WfAppender {
     }
 };
 
-__device__ __forceinline__ void wfStatsFlush(unsigned long long *stats, const Counters &cn, uint32_t samples) {
-    unsigned long long v[7] = {samples, cn.rays, cn.nodes, cn.tris, cn.hits, cn.lsamples, cn.dropped};
-    for (int k = 0; k < 7; ++k) {
-        unsigned long long x = v[k];
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-        if ((threadIdx.x & 63) == 0 && x) atomicAdd(&stats[k], x);
-    }
-}
-
 // dimPmj: the dimension counter of a pmj02bn path at this point of this bounce (wfPmjDim). That sampler has no other state, so its paths
 // neither load nor store a sampler record (16 B each way per shaded hit).
 __device__ __forceinline__ uint32_t wfPmjDim(const KzParams &P, int iter) {
     // generate leaves the counter at 4 (max(2, 0), then the aperture's 2-D draw); bounce j draws the roulette sample (j >= 3), the light pick,
     // three light-sample dimensions when there are lights, and 2 + 1 for the BSDF sample
     return 4u + (uint32_t)iter * (4u + (P.nLights > 0 ? 3u : 0u)) + (iter > 3 ? (uint32_t)(iter - 3) : 0u);
+}
+// Path `slot` of a pass is item pixel * S + sample of its pixel list: the pixel and the sample's index. (slot % S, not slot - pl * S: the compiler forms the
+// remainder from the quotient either way, but reassociates the written-out difference with sampleBegin inside this function - other code in kz_wf_ao.)
+__device__ __forceinline__ void wfSampleOf(const uint32_t *__restrict__ pixList, uint32_t S, uint32_t sampleBegin, uint32_t slot, int &px, int &py, uint32_t &sampleIndex) {
+    sampleIndex = sampleBegin + slot % S;
+    pixelOf(pixList[slot / S], px, py);
 }
 __device__ __forceinline__ void wfLoadSampler(const KzParams &P, const KzWf &W, uint32_t slot, int px, int py, uint32_t sampleIndex, Sampler &s, uint32_t dimPmj) {
     s.type = P.samplerType; s.px = px; s.py = py; s.idx = sampleIndex;
@@ -93,6 +90,17 @@ __device__ __forceinline__ void wfStoreSampler(const KzParams &P, const KzWf &W,
     v.x = (uint32_t)s.state; v.y = (uint32_t)(s.state >> 32); v.z = s.dim; v.w = 0;
     W.smp[slot] = v;
 }
+// Radiance into the sums of a path's sample: returnless float atomics (no wait; one writer per slot, so the same single rounding as a plain add)
+__device__ __forceinline__ void wfAddRadiance(const KzWf &W, uint32_t slot, V3 c) {
+    unsafeAtomicAdd(W.outR + slot, c.x); unsafeAtomicAdd(W.outG + slot, c.y); unsafeAtomicAdd(W.outB + slot, c.z);
+}
+// The continuation ray of a first hit on an invisible light (isInvisibleLight, walkThroughOrigin: kz_devfn.h) into shA / shB, where kz_wf_trace<1> reads it.
+// The queue push is the caller's: an appender in kz_wf_primary_fix, an atomic in the epilogues of the camera-ray kernels.
+__device__ __forceinline__ void wfStoreWalkThrough(const KzParams &P, const KzWf &W, uint32_t slot, const Its &its, V3 d) {
+    const V3 no = walkThroughOrigin(P, its, d);
+    kzStoreStream(&W.shA[slot], make_float4(no.x, no.y, no.z, KZ_INF));            // Ray3f(o, d): mint = Epsilon, maxt = inf
+    kzStoreStream(&W.shB[slot], make_float4(d.x, d.y, d.z, KZ_EPSILON));
+}
 
 // ---- generate: renderSample up to the camera ray (renderer.cpp:20-33) ------------------------------------------------
 __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_generate(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__ pixList,
@@ -105,7 +113,8 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_generate(KzParams P, KzDevTabl
     if ((S & 63u) == 0) { pl = (uint32_t)__builtin_amdgcn_readfirstlane((int)item) / S; pxy = (uint32_t)__builtin_amdgcn_readfirstlane((int)pixList[pl]); }
     else { pl = item / S; pxy = pixList[pl]; }
     const uint32_t so = item - pl * S;
-    const int px = (int)(pxy & 0xffffu), py = (int)(pxy >> 16);
+    int px, py; pixelOf(pxy, px, py);
+    // (cameraSample of kz_devfn.h, kept as its own lines: inlined through that function the blue-noise index of the aperture draw is associated differently in this kernel)
     Sampler smp; smp.type = P.samplerType;
     smp.generateSample(P, T, px, py, sampleBegin + so);
     float jx, jy; smp.nextPixel2D(P, T, jx, jy);
@@ -134,15 +143,11 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_primary_fix(KzParams P, KzDevT
         if (slot < nItems) {
             const float4 h = kzLoadStream(&W.hit[slot]);
             if (h.x < KZ_INF) {
-                RawHit rh; rh.t = h.x; rh.u = h.y; rh.v = h.z; rh.tri = 0; rh.gid = __float_as_uint(h.w);
-                const int li = lightOfGid(T, rh.gid);
-                if (li >= 0 && !T.lights[li].primaryVisibility) {
+                const RawHit rh = rawHitOf(h);
+                if (isInvisibleLight(T, lightOfGid(T, rh.gid))) {
                     Its its; postIntersect<false>(T, rh, its);
                     const float4 b = kzLoadStream(&W.rayB[slot]);
-                    const V3 rd = mk(b.x, b.y, b.z);
-                    const V3 no = its.p + P.traceBias * rd;
-                    kzStoreStream(&W.shA[slot], make_float4(no.x, no.y, no.z, KZ_INF));            // Ray3f(o, d): mint = Epsilon, maxt = inf
-                    kzStoreStream(&W.shB[slot], make_float4(rd.x, rd.y, rd.z, KZ_EPSILON));
+                    wfStoreWalkThrough(P, W, slot, its, mk(b.x, b.y, b.z));
                     need = true;
                 }
             }
@@ -176,13 +181,6 @@ struct KzSst {
     __device__ __forceinline__ void flush(unsigned long long *) {}
 #endif
 };
-
-// The Russian roulette of integrator.cpp:237-244 on a path's throughput and eta against its next 1-D draw: true = the path ends here. ONE function for the
-// bounce that plays it (wfClassify) and for the bounce before it, which looks ahead (wfShadeSurvivor): the two cannot drift apart.
-__device__ __forceinline__ bool wfRouletteEnds(V3 throughput, float eta, float draw, float &probability) {
-    probability = fminf(maxCoeff(throughput) * eta * eta, 0.95f);
-    return probability <= draw;
-}
 
 // ---- roulette ahead -------------------------------------------------------------------------------------------------------
 // Both inputs of the roulette of bounce iter + 1 are known when shade(iter) has sampled the BSDF: the throughput and eta it has just formed, and the next
@@ -250,12 +248,11 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
         // miss: black for the primary ray (H5), background after a bounce (integrator.cpp:315-318)
         if (iter > 0 && P.bgPresent) {
             const float4 th = kzLoadStream(&W.thr[slot]);
-            const V3 c = mk(th.x, th.y, th.z) * backgroundRadiance(P, T, rd);
-            unsafeAtomicAdd(W.outR + slot, c.x); unsafeAtomicAdd(W.outG + slot, c.y); unsafeAtomicAdd(W.outB + slot, c.z);      // (returnless: no wait, one writer per slot)
+            wfAddRadiance(W, slot, mk(th.x, th.y, th.z) * backgroundRadiance(P, T, rd));
         }
         return false;
     }
-    RawHit rh; rh.t = h.x; rh.u = h.y; rh.v = h.z; rh.tri = 0; rh.gid = __float_as_uint(h.w);
+    const RawHit rh = rawHitOf(h);
     postIntersect<false>(T, rh, its); if (STATS) cn.hits++;
     sst.markw(12);                                  // pass A: postIntersect
     if (its.light >= 0) {                                                         // integrator.cpp:226-231, 322-327
@@ -267,10 +264,7 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
         const V3 wi = normalized(its.p - ro);
         float bsdfWeight = 1.f;
         if (iter > 0 && mi.z == 0.f) bsdfWeight = powerHeuristic(mi.x, lightPdfSolidAngle(lr.normalization, its.sh.n, wi, its.p, ro));   // mi.z: EDiscrete (integrator.cpp:329-331)
-        if (dot(its.sh.n, -wi) > 0.f) {
-            const V3 c = (bsdfWeight * mk(th.x, th.y, th.z)) * mk(lr.radiance[0], lr.radiance[1], lr.radiance[2]);
-            unsafeAtomicAdd(W.outR + slot, c.x); unsafeAtomicAdd(W.outG + slot, c.y); unsafeAtomicAdd(W.outB + slot, c.z);      // (returnless: no wait, one writer per slot)
-        }
+        if (emitterFaces(its, wi)) wfAddRadiance(W, slot, emitterTerm(lr, bsdfWeight, mk(th.x, th.y, th.z)));
         return false;
     }
     // A one-sided BSDF seen from below evaluates to 0 for every light sample (no shadow ray, nothing added) and its
@@ -290,13 +284,14 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
         // Russian roulette (integrator.cpp:237-244) here, in front of the compaction: a path it ends does not take a lane of
         // pass B (at depth 3 and 4 that was 2 of 3 lanes). The survivor's scaled throughput and advanced sampler go back to
         // the path state, where pass B reads them.
+        // (wfSampleOf, kept as its own lines at the three sites of kz_wf_shade: see wfShadeSurvivor)
         const uint32_t pl = slot / S; const uint32_t pxy = pixList[pl];
         Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, wfPmjDim(P, iter));
         const float4 th = kzLoadStream(&W.thr[slot]);
         V3 throughput = mk(th.x, th.y, th.z);
         const float etaA = compact ? 1.f : th.w;
         float probability;
-        if (wfRouletteEnds(throughput, etaA, smp.next1D(P, T), probability)) survivor = false;
+        if (rouletteEnds(throughput, etaA, smp.next1D(P, T), probability)) survivor = false;
         else {
             throughput = throughput / probability;
             kzStoreStream(&W.thr[slot], make_float4(throughput.x, throughput.y, throughput.z, th.w));
@@ -311,7 +306,7 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
             const float4 th = kzLoadStream(&W.thr[slot]);
             const float etaA = compact ? 1.f : th.w;
             float probability;
-            if (wfRouletteEnds(mk(th.x, th.y, th.z), etaA, smp.next1D(P, T), probability)) alive = false;
+            if (rouletteEnds(mk(th.x, th.y, th.z), etaA, smp.next1D(P, T), probability)) alive = false;
         }
         if (alive) cn.lsamples++;
     }
@@ -330,6 +325,8 @@ __device__ __forceinline__ void wfShadeSurvivor(const KzParams &P, const KzDevTa
     V3 throughput = mk(th.x, th.y, th.z);
     const float eta = compact ? 1.f : th.w;
     float accRough = (iter == 0 || compact) ? 0.f : W.misc[slot].y;
+    // (wfSampleOf, kept as its own lines: through the shared function kz_wf_shade's division here takes another copy of the slot - one register of one
+    // instruction - and the two sites of wfClassify come out in another order in the counting variants)
     const uint32_t pl = slot / S;
     const uint32_t pxy = pixList[pl];
     Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, wfPmjDim(P, iter) + (iter >= 3 ? 1u : 0u));
@@ -384,7 +381,7 @@ __device__ __forceinline__ void wfShadeSurvivor(const KzParams &P, const KzDevTa
         if (keep) {
             Sampler peek = smp;
             float probability;
-            if (wfRouletteEnds(throughput, compact ? 1.f : etaNext, peek.next1D(P, T), probability)) {
+            if (rouletteEnds(throughput, compact ? 1.f : etaNext, peek.next1D(P, T), probability)) {
                 keep = false;
                 cand = T.nEmTris != 0u && rayIsFinite(its.p, nd) && wfEmitterBox(T, its.p, nd, eps);
             }
@@ -545,7 +542,7 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
     }
     __syncthreads();
     qp.flush(true);
-    if (STATS) wfStatsFlush(W.stats, cn, 0);
+    if (STATS) statsFlush(W.stats, cn, 0);
     sst.flush(W.stats);
 }
 
@@ -806,7 +803,7 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
         }
         KZ_TST(2);
     }
-    if (STATS) wfStatsFlush(W.stats, cn, 0);
+    if (STATS) statsFlush(W.stats, cn, 0);
 #ifdef KZ_TRACESTAT
     if (lane == 0) { for (int k = 0; k < 4; ++k) atomicAdd(W.stats + 8 + (SHADOW ? 4 : 0) + k, tsAcc[k]); atomicAdd(W.stats + 16 + (SHADOW ? 1 : 0), tsTri); }
 #endif
@@ -955,18 +952,15 @@ __global__ __launch_bounds__(KZ_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))
         }
         if (have) kzStoreStream(&W.hit[slot], make_float4(bt, bu, bv, __uint_as_float(bgid)))        /* no hit: still +inf, 0, 0, 0 */;
         if (FIX && found && bgid - P.ilGidLo <= P.ilGidSpan) {              // (rare) may be a triangle of an invisible light: look
-            const int li = lightOfGid(T, bgid);
-            if (li >= 0 && !T.lights[li].primaryVisibility) {
-                RawHit rh; rh.t = bt; rh.u = bu; rh.v = bv; rh.tri = 0; rh.gid = bgid;
+            if (isInvisibleLight(T, lightOfGid(T, bgid))) {
+                const RawHit rh = rawHitOf(bt, bu, bv, bgid);
                 Its its; postIntersect<false>(T, rh, its);
-                const V3 no = its.p + P.traceBias * d;
-                kzStoreStream(&W.shA[slot], make_float4(no.x, no.y, no.z, KZ_INF));            // Ray3f(o, d): mint = Epsilon, maxt = inf
-                kzStoreStream(&W.shB[slot], make_float4(d.x, d.y, d.z, KZ_EPSILON));
+                wfStoreWalkThrough(P, W, slot, its, d);
                 fixQueue[atomicAdd(fixCount, 1u)] = slot;
             }
         }
     }
-    if (STATS) wfStatsFlush(W.stats, cn, 0);
+    if (STATS) statsFlush(W.stats, cn, 0);
 }
 
 // ---- pixel beams for the camera rays: one traversal per PIXEL, triangle tests per SAMPLE ----------------------------------------
@@ -1006,10 +1000,11 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_beam(KzParams P, KzDevTables T
     const uint32_t pxy = pl < nPix ? pixList[pl] : 0u;
     // The lists live per pixel of the FRAME (index y * width + x), whatever tile set or pixel chunk the pixel is rendered in: a pixel's list is built
     // once per replica (the camera belongs to the scene) - a head count of KZ_BEAM_UNBUILT marks a pixel nobody has built yet.
-    const uint32_t fpix = (pxy >> 16) * (uint32_t)P.width + (pxy & 0xffffu);
+    const uint32_t fpix = framePixelOf(pxy, (uint32_t)P.width);
     const bool todo = pl < nPix && heads[fpix].x == KZ_BEAM_UNBUILT;
     bool active = todo && root != 0xFFFFFFFFu;
-    const float fx = (float)(pxy & 0xffffu), fy = (float)(pxy >> 16);
+    int px, py; pixelOf(pxy, px, py);
+    const float fx = (float)px, fy = (float)py;
     const V3 O = mk(P.beamO[0], P.beamO[1], P.beamO[2]), U = mk(P.beamU[0], P.beamU[1], P.beamU[2]), V = mk(P.beamV[0], P.beamV[1], P.beamV[2]);
     // unit directions through the pixel's centre and corners (world axes; nearP = A + sx U + sy V)
     const V3 c00 = mk(P.beamA[0], P.beamA[1], P.beamA[2]) + fx * U + fy * V;
@@ -1083,9 +1078,9 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_beam(KzParams P, KzDevTables T
 __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_beam_count(const uint2 *__restrict__ heads, const uint32_t *__restrict__ pixList, int width, uint32_t nPix, unsigned long long *__restrict__ out) {
     const uint32_t pl = blockIdx.x * KZ_BLOCK + threadIdx.x;
     uint2 h = make_uint2(0u, 0u);
-    if (pl < nPix) { const uint32_t pxy = pixList[pl]; h = heads[(pxy >> 16) * (uint32_t)width + (pxy & 0xffffu)]; }
+    if (pl < nPix) h = heads[framePixelOf(pixList[pl], (uint32_t)width)];
     unsigned long long v[3] = {pl < nPix ? 1ull : 0ull, (unsigned long long)h.x, (pl < nPix && !(__uint_as_float(h.y) < KZ_INF)) ? 1ull : 0ull};
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 3; ++k) {                                     // (statsFlush's wave sum, kept as its own lines: through a shared function this kernel compiles to other registers)
         unsigned long long x = v[k];
         for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
         if ((threadIdx.x & 63) == 0 && x) atomicAdd(&out[k], x);
@@ -1160,8 +1155,8 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_trace_list(KzParams P, KzDevTa
         // first lane's pixel (an SGPR), so the head and the entries arrive through the scalar cache and an entry's load no longer queues behind the
         // lanes' vector loads of the triangle before it. Waves that span pixels walk per-lane lists.
         const uint32_t plU = (uint32_t)__builtin_amdgcn_readfirstlane((int)pl);
-        if (__all(pl == plU)) { const uint32_t pxy = pixList[plU], fp = (pxy >> 16) * (uint32_t)P.width + (pxy & 0xffffu); walkShared(entries + (size_t)fp * KZ_BEAM_CAP, heads[fp]); }
-        else { const uint32_t pxy = pixList[pl], fp = (pxy >> 16) * (uint32_t)P.width + (pxy & 0xffffu); walk(entries + (size_t)fp * KZ_BEAM_CAP, heads[fp]); }
+        if (__all(pl == plU)) { const uint32_t fp = framePixelOf(pixList[plU], (uint32_t)P.width); walkShared(entries + (size_t)fp * KZ_BEAM_CAP, heads[fp]); }
+        else { const uint32_t fp = framePixelOf(pixList[pl], (uint32_t)P.width); walk(entries + (size_t)fp * KZ_BEAM_CAP, heads[fp]); }
         // decided: a hit in front of everything unexplored, or nothing unexplored at all (a non-finite ray hits nothing)
         undecided = finite && !(found ? bt * lenUp < tvalidDist : !(tvalidDist < KZ_INF));
         if (STATS && !undecided) cn.rays++;                                    // (an undecided ray is counted by the kernel that decides it)
@@ -1172,13 +1167,10 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_trace_list(KzParams P, KzDevTa
         } else {
             kzStoreStream(&W.hit[slot], make_float4(bt, bu, bv, __uint_as_float(bgid)))        /* no hit: still +inf, 0, 0, 0 */;
             if (FIX && found && bgid - P.ilGidLo <= P.ilGidSpan) {              // (rare) may be a triangle of an invisible light: see kz_wf_trace_packet
-                const int li = lightOfGid(T, bgid);
-                if (li >= 0 && !T.lights[li].primaryVisibility) {
-                    RawHit rh; rh.t = bt; rh.u = bu; rh.v = bv; rh.tri = 0; rh.gid = bgid;
+                if (isInvisibleLight(T, lightOfGid(T, bgid))) {
+                    const RawHit rh = rawHitOf(bt, bu, bv, bgid);
                     Its its; postIntersect<false>(T, rh, its);
-                    const V3 no = its.p + P.traceBias * d;
-                    kzStoreStream(&W.shA[slot], make_float4(no.x, no.y, no.z, KZ_INF));
-                    kzStoreStream(&W.shB[slot], make_float4(d.x, d.y, d.z, KZ_EPSILON));
+                    wfStoreWalkThrough(P, W, slot, its, d);
                     fixQueue[atomicAdd(fixCount, 1u)] = slot;
                 }
             }
@@ -1193,7 +1185,7 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_trace_list(KzParams P, KzDevTa
             if (undecided) fbQueue[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = slot;
         }
     }
-    if (STATS) wfStatsFlush(W.stats, cn, 0);
+    if (STATS) statsFlush(W.stats, cn, 0);
 }
 
 // ---- final: the ray after the last bounce contributes only the background on a miss (integrator.cpp:315-318) ------------
@@ -1205,6 +1197,7 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_final(KzParams P, KzDevTables 
         if (h.x < KZ_INF) continue;
         const float4 rb = kzLoadStream(&W.rayB[slot]), th = kzLoadStream(&W.thr[slot]);
         const V3 bg = backgroundRadiance(P, T, mk(rb.x, rb.y, rb.z));
+        // (wfAddRadiance, kept as its own lines: with the three products formed in front of the three adds this kernel's instructions change order)
         unsafeAtomicAdd(W.outR + slot, th.x * bg.x); unsafeAtomicAdd(W.outG + slot, th.y * bg.y); unsafeAtomicAdd(W.outB + slot, th.z * bg.z);
     }
 }
@@ -1217,5 +1210,5 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_count(KzWf W, uint32_t nItems)
         const float r = W.outR[i], g = W.outG[i], b = W.outB[i];
         if (!(r >= 0 && g >= 0 && b >= 0 && isfinite(r) && isfinite(g) && isfinite(b))) cn.dropped++;
     }
-    wfStatsFlush(W.stats, cn, i < nItems ? 1u : 0u);
+    statsFlush(W.stats, cn, i < nItems ? 1u : 0u);
 }

@@ -343,7 +343,7 @@ PassCtx *kzCtxAcquire(int device) {
         }
     }
     PassCtx *c = new PassCtx();
-    c->arena = new KzArena(kzPhysicalDevice(device));
+    c->arena.reset(new KzArena(kzPhysicalDevice(device)));
     return c;
 }
 
@@ -382,7 +382,7 @@ size_t kzCtxPoolTrim(int device, size_t keepBytes) {
     }
     size_t freed = 0;
     if (!gone.empty()) { (void)hipSetDevice(kzPhysicalDevice(device)); (void)hipDeviceSynchronize(); }
-    for (PassCtx *c : gone) { freed += c->bytes(); c->destroy(); delete c; }
+    for (PassCtx *c : gone) { freed += c->bytes(); delete c; }
     return freed;
 }
 

@@ -98,8 +98,6 @@ __global__ void kz_light_kernel(KzDevTables T, uint32_t n, const int32_t *__rest
     r[9] = ls.pdf; r[10] = ls.Ls.x; r[11] = ls.Ls.y; r[12] = ls.Ls.z; r[13] = (float)ls.tri;
 }
 
-// Exhaustive self-check of rcpExact / sqrtExact (kz_devfn.h) as compiled into THIS library: every one of the 2^32 float bit patterns,
-// against the compiler's IEEE division / square root. counts[0] rcp mismatches, [1] sqrt mismatches, [2] patterns checked.
 __global__ void kz_permute_kernel(uint32_t n, const uint32_t *__restrict__ i, const uint32_t *__restrict__ l, const uint32_t *__restrict__ p, uint32_t *__restrict__ out) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) out[k] = permuteIdx(i[k], l[k], p[k]);
@@ -112,6 +110,8 @@ __global__ void kz_fresnel_kernel(uint32_t n, int form, const float *__restrict_
     out[2 * k] = form == 0 ? fresnelIOR(c[k], a[k], b[k]) : fresnelDielectricT(c[k], a[k], ct);
     out[2 * k + 1] = ct;
 }
+// Exhaustive self-check of rcpExact / sqrtExact (kz_devfn.h) as compiled into THIS library: every one of the 2^32 float bit patterns,
+// against the compiler's IEEE division / square root. counts[0] rcp mismatches, [1] sqrt mismatches, [2] patterns checked.
 __global__ void kz_exact_math_kernel(unsigned long long base, unsigned long long *__restrict__ counts) {
     const uint32_t bits = (uint32_t)(base + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x);
     const float x = __uint_as_float(bits);
@@ -154,68 +154,54 @@ extern "C" {
 
 // random::permute on the device (the function the sampler kernels call), for the known-answer vectors minted from the reference's own text
 int kz_kat_permute(int device, uint32_t n, const uint32_t *i, const uint32_t *l, const uint32_t *p, uint32_t *out) {
-    int nd = kz_device_count();
-    if (device < 0 || device >= nd) return kz_fail(nd ? KZ_ERR_INVALID_ARG : KZ_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, nd);
+    int rc;
+    if ((rc = kzUseDevice(device))) return rc;
     if (!n) return KZ_OK;
     if (!i || !l || !p || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null argument");
-    HIP_TRY(hipSetDevice(kzPhysicalDevice(device)));
-    DevMem dI, dL, dP, dO;
-    const size_t bytes = (size_t)n * sizeof(uint32_t);
-    KZ_ALLOC(&dI.p, bytes); KZ_ALLOC(&dL.p, bytes); KZ_ALLOC(&dP.p, bytes); KZ_ALLOC(&dO.p, bytes);
-    HIP_TRY(hipMemcpy(dI.p, i, bytes, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dL.p, l, bytes, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dP.p, p, bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kz_permute_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, dI.as<uint32_t>(), dL.as<uint32_t>(), dP.as<uint32_t>(), dO.as<uint32_t>());
+    DevBuf<uint32_t> dI, dL, dP, dO;
+    if ((rc = dI.alloc(n)) || (rc = dL.alloc(n)) || (rc = dP.alloc(n)) || (rc = dO.alloc(n)) || (rc = dI.upload(i, n)) || (rc = dL.upload(l, n)) || (rc = dP.upload(p, n))) return rc;
+    hipLaunchKernelGGL(kz_permute_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, dI.get(), dL.get(), dP.get(), dO.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dO.p, bytes, hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return dO.download(out, n);
 }
 
 int kz_kat_fresnel(int device, uint32_t n, int form, const float *cosThetaI, const float *a, const float *b, float *out) {
-    int nd = kz_device_count();
-    if (device < 0 || device >= nd) return kz_fail(nd ? KZ_ERR_INVALID_ARG : KZ_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, nd);
+    int rc;
+    if ((rc = kzUseDevice(device))) return rc;
     if (!n) return KZ_OK;
     if (!cosThetaI || !a || !out || (form == 0 && !b) || (form != 0 && form != 1)) return kz_fail(KZ_ERR_INVALID_ARG, "null argument or form %d (0 = fresnel(cos, extIOR, intIOR), 1 = fresnelDielectric(cos, eta))", form);
-    HIP_TRY(hipSetDevice(kzPhysicalDevice(device)));
-    DevMem dC, dA, dB, dO;
-    const size_t bytes = (size_t)n * sizeof(float);
-    KZ_ALLOC(&dC.p, bytes); KZ_ALLOC(&dA.p, bytes); KZ_ALLOC(&dB.p, bytes); KZ_ALLOC(&dO.p, 2 * bytes);
-    HIP_TRY(hipMemcpy(dC.p, cosThetaI, bytes, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dA.p, a, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dB.p, b ? b : a, bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kz_fresnel_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, form, dC.as<float>(), dA.as<float>(), dB.as<float>(), dO.as<float>());
+    DevBuf<float> dC, dA, dB, dO;
+    if ((rc = dC.alloc(n)) || (rc = dA.alloc(n)) || (rc = dB.alloc(n)) || (rc = dO.alloc(2 * (size_t)n)) || (rc = dC.upload(cosThetaI, n)) || (rc = dA.upload(a, n)) || (rc = dB.upload(b ? b : a, n))) return rc;
+    hipLaunchKernelGGL(kz_fresnel_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, form, dC.get(), dA.get(), dB.get(), dO.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dO.p, 2 * bytes, hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return dO.download(out, 2 * (size_t)n);
 }
 
 int kz_kat_math(int device, int fn, uint32_t n, const float *x, const float *y, float *out) {
-    int nd = kz_device_count();
-    if (device < 0 || device >= nd) return kz_fail(nd ? KZ_ERR_INVALID_ARG : KZ_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, nd);
+    int rc;
+    if ((rc = kzUseDevice(device))) return rc;
     if (!n) return KZ_OK;
     if (!x || !out || fn < 0 || fn > 11) return kz_fail(KZ_ERR_INVALID_ARG, "null argument or function %d (0..11)", fn);
-    HIP_TRY(hipSetDevice(kzPhysicalDevice(device)));
-    DevMem dX, dY, dO;
-    const size_t bytes = (size_t)n * sizeof(float);
-    KZ_ALLOC(&dX.p, bytes); KZ_ALLOC(&dY.p, bytes); KZ_ALLOC(&dO.p, bytes);
-    HIP_TRY(hipMemcpy(dX.p, x, bytes, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dY.p, y ? y : x, bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kz_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, fn, dX.as<float>(), dY.as<float>(), dO.as<float>());
+    DevBuf<float> dX, dY, dO;
+    if ((rc = dX.alloc(n)) || (rc = dY.alloc(n)) || (rc = dO.alloc(n)) || (rc = dX.upload(x, n)) || (rc = dY.upload(y ? y : x, n))) return rc;
+    hipLaunchKernelGGL(kz_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, fn, dX.get(), dY.get(), dO.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dO.p, bytes, hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return dO.download(out, n);
 }
 
 int kz_kat_exact_math(int device, uint64_t *rcpMismatches, uint64_t *sqrtMismatches, uint64_t *checked) {
-    int n = kz_device_count();
-    if (device < 0 || device >= n) return kz_fail(n ? KZ_ERR_INVALID_ARG : KZ_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, n);
-    HIP_TRY(hipSetDevice(kzPhysicalDevice(device)));
-    DevMem dC;
-    KZ_ALLOC(&dC.p, 3 * sizeof(unsigned long long));
-    HIP_TRY(hipMemset(dC.p, 0, 3 * sizeof(unsigned long long)));
+    int rc;
+    if ((rc = kzUseDevice(device))) return rc;
+    DevBuf<unsigned long long> dC;
+    if ((rc = dC.alloc(3))) return rc;
+    HIP_TRY(hipMemset(dC, 0, dC.bytes()));
     for (unsigned long long base = 0; base < (1ull << 32); base += (1ull << 28)) {
-        hipLaunchKernelGGL(kz_exact_math_kernel, dim3(1u << 20), dim3(256), 0, 0, base, dC.as<unsigned long long>());
+        hipLaunchKernelGGL(kz_exact_math_kernel, dim3(1u << 20), dim3(256), 0, 0, base, dC.get());
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipDeviceSynchronize());
     unsigned long long h[3];
-    HIP_TRY(hipMemcpy(h, dC.p, sizeof h, hipMemcpyDeviceToHost));
+    if ((rc = dC.download(h, 3))) return rc;
     if (rcpMismatches) *rcpMismatches = h[0];
     if (sqrtMismatches) *sqrtMismatches = h[1];
     if (checked) *checked = h[2];
@@ -228,20 +214,15 @@ int kz_trace_rays(KzScene *scene, uint32_t n, const float *o, const float *d, co
     if (n == 0) return KZ_OK;
     if (!o || !d || !tmin || !tmax || !hits) return kz_fail(KZ_ERR_INVALID_ARG, "null ray buffer");
     if ((rc = kzEnsureBvh2(scene, ds))) return rc;
-    DevMem dO, dD, dA, dB, dH;
-    KZ_ALLOC(&dO.p, (size_t)n * 12); KZ_ALLOC(&dD.p, (size_t)n * 12); KZ_ALLOC(&dA.p, (size_t)n * 4); KZ_ALLOC(&dB.p, (size_t)n * 4);
-    KZ_ALLOC(&dH.p, (size_t)n * sizeof(KzHit));
-    HIP_TRY(hipMemcpy(dO.p, o, (size_t)n * 12, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dD.p, d, (size_t)n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dA.p, tmin, (size_t)n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dB.p, tmax, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kz_trace_kernel, dim3((n + KZ_BLOCK - 1) / KZ_BLOCK), dim3(KZ_BLOCK), 0, 0, scene->prm, ds->T, n, dO.as<float>(), dD.as<float>(), dA.as<float>(),
-                       dB.as<float>(), dH.as<KzHit>());
+    DevBuf<float> dO, dD, dA, dB; DevBuf<KzHit> dH;
+    if ((rc = dO.alloc(3 * (size_t)n)) || (rc = dD.alloc(3 * (size_t)n)) || (rc = dA.alloc(n)) || (rc = dB.alloc(n)) || (rc = dH.alloc(n)) ||
+        (rc = dO.upload(o, 3 * (size_t)n)) || (rc = dD.upload(d, 3 * (size_t)n)) || (rc = dA.upload(tmin, n)) || (rc = dB.upload(tmax, n))) return rc;
+    hipLaunchKernelGGL(kz_trace_kernel, dim3((n + KZ_BLOCK - 1) / KZ_BLOCK), dim3(KZ_BLOCK), 0, 0, scene->prm, ds->T, n, dO.get(), dD.get(), dA.get(), dB.get(), dH.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(hits, dH.p, (size_t)n * sizeof(KzHit), hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return dH.download(hits, n);
 }
 
-// Radiance of explicit (pixel, sample index) pairs without touching the film: out = n x (sx, sy, r, g, b).
 // BSDF::eval / pdf / sample of bsdf rows on the device: evalOut 3n, pdfOut n, sampleOut 8n (weight, wo, alive, pdf after sample).
 int kz_bsdf_query(KzScene *scene, uint32_t n, const int32_t *bsdf, const float *wi, const float *wo, const float *accRough, const float *s3,
                   const float *uv, float *evalOut, float *pdfOut, float *sampleOut) {
@@ -250,22 +231,17 @@ int kz_bsdf_query(KzScene *scene, uint32_t n, const int32_t *bsdf, const float *
     if (n == 0) return KZ_OK;
     if (!bsdf || !wi || !wo || !accRough || !s3 || !evalOut || !pdfOut || !sampleOut) return kz_fail(KZ_ERR_INVALID_ARG, "null buffer");
     for (uint32_t i = 0; i < n; ++i) if (bsdf[i] < 0 || (size_t)bsdf[i] >= scene->bsdfs.size()) return kz_fail(KZ_ERR_INVALID_ARG, "bsdf index %d", bsdf[i]);
-    DevMem dF, dBs;
-    const size_t fl = (size_t)n * (3 + 3 + 1 + 3 + 3 + 1 + 8 + 2);
-    KZ_ALLOC(&dF.p, fl * 4); KZ_ALLOC(&dBs.p, (size_t)n * 4);
-    float *d = dF.as<float>(); int32_t *dB = dBs.as<int32_t>();
-    float *dWi = d, *dWo = d + 3 * (size_t)n, *dAcc = d + 6 * (size_t)n, *dS = d + 7 * (size_t)n, *dE = d + 10 * (size_t)n, *dP = d + 13 * (size_t)n,
-          *dSm = d + 14 * (size_t)n, *dUv = d + 22 * (size_t)n;
-    HIP_TRY(hipMemcpy(dB, bsdf, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dWi, wi, (size_t)n * 12, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dWo, wo, (size_t)n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dAcc, accRough, (size_t)n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dS, s3, (size_t)n * 12, hipMemcpyHostToDevice));
-    if (uv) HIP_TRY(hipMemcpy(dUv, uv, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kz_bsdf_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, ds->T, n, dB, dWi, dWo, dAcc, dS, uv ? dUv : (const float *)nullptr, dE, dP, dSm);
+    // one float buffer, in units of N floats: wi 0..3 | wo 3..6 | accRough 6 | s3 7..10 | eval 10..13 | pdf 13 | sample 14..22 | uv 22..24
+    DevBuf<float> dF; DevBuf<int32_t> dB;
+    const size_t N = n;
+    if ((rc = dF.alloc(24 * N)) || (rc = dB.alloc(N)) || (rc = dB.upload(bsdf, N)) || (rc = dF.upload(wi, 3 * N)) || (rc = dF.upload(wo, 3 * N, 3 * N)) ||
+        (rc = dF.upload(accRough, N, 6 * N)) || (rc = dF.upload(s3, 3 * N, 7 * N)) || (uv && (rc = dF.upload(uv, 2 * N, 22 * N)))) return rc;
+    float *d = dF;
+    hipLaunchKernelGGL(kz_bsdf_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, ds->T, n, dB.get(), d, d + 3 * N, d + 6 * N, d + 7 * N, uv ? d + 22 * N : (const float *)nullptr, d + 10 * N, d + 13 * N, d + 14 * N);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(evalOut, dE, (size_t)n * 12, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(pdfOut, dP, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sampleOut, dSm, (size_t)n * 32, hipMemcpyDeviceToHost));
-    return KZ_OK;
+    if ((rc = dF.download(evalOut, 3 * N, 10 * N)) || (rc = dF.download(pdfOut, N, 13 * N))) return rc;
+    return dF.download(sampleOut, 8 * N, 14 * N);
 }
 
 // Texture<Color3f>::eval(uv) of texture rows on the device: out 3n.
@@ -275,16 +251,13 @@ int kz_texture_query(KzScene *scene, uint32_t n, const int32_t *tex, const float
     if (n == 0) return KZ_OK;
     if (!tex || !uv || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null buffer");
     for (uint32_t i = 0; i < n; ++i) if (tex[i] < 0 || (size_t)tex[i] >= scene->texProgs.size()) return kz_fail(KZ_ERR_INVALID_ARG, "texture index %d", tex[i]);
-    DevMem dF, dTx;
-    KZ_ALLOC(&dF.p, (size_t)n * 5 * 4); KZ_ALLOC(&dTx.p, (size_t)n * 4);
-    float *d = dF.as<float>(); int32_t *dT = dTx.as<int32_t>();
-    float *dUv = d, *dO = d + 2 * (size_t)n;
-    HIP_TRY(hipMemcpy(dT, tex, (size_t)n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dUv, uv, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kz_texture_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, ds->T, n, dT, dUv, dO);
+    DevBuf<float> dF; DevBuf<int32_t> dT;      // dF, in units of N floats: uv 0..2 | out 2..5
+    const size_t N = n;
+    if ((rc = dF.alloc(5 * N)) || (rc = dT.alloc(N)) || (rc = dT.upload(tex, N)) || (rc = dF.upload(uv, 2 * N))) return rc;
+    hipLaunchKernelGGL(kz_texture_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, ds->T, n, dT.get(), dF.get(), dF + 2 * N);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dO, (size_t)n * 12, hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return dF.download(out, 3 * N, 2 * N);
 }
 
 // PerspectiveCamera / ThinLensCamera::sampleRay (camera.cpp:70-91, 191-223) of the scene's camera: out n x 8.
@@ -293,16 +266,13 @@ int kz_camera_rays(KzScene *scene, uint32_t n, const float *sxy, const float *ax
     if ((rc = requireDevice(scene, &ds))) return rc;
     if (n == 0) return KZ_OK;
     if (!sxy || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null buffer");
-    DevMem dF;
-    KZ_ALLOC(&dF.p, (size_t)n * 12 * 4);
-    float *d = dF.as<float>(), *dS = d, *dA = d + 2 * (size_t)n, *dO = d + 4 * (size_t)n;
-    HIP_TRY(hipMemcpy(dS, sxy, (size_t)n * 8, hipMemcpyHostToDevice));
-    if (axy) HIP_TRY(hipMemcpy(dA, axy, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kz_camera_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, scene->prm, n, dS, axy ? dA : (const float *)nullptr, dO);
+    DevBuf<float> dF;                          // in units of N floats: sxy 0..2 | axy 2..4 | out 4..12
+    const size_t N = n;
+    if ((rc = dF.alloc(12 * N)) || (rc = dF.upload(sxy, 2 * N)) || (axy && (rc = dF.upload(axy, 2 * N, 2 * N)))) return rc;
+    hipLaunchKernelGGL(kz_camera_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, scene->prm, n, dF.get(), axy ? dF + 2 * N : (const float *)nullptr, dF + 4 * N);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dO, (size_t)n * 32, hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return dF.download(out, 8 * N, 4 * N);
 }
 
 // AreaLight::sample (light.cpp:16-34) of light rows (the order of Scene::m_lights) from reference points: out n x 14.
@@ -312,16 +282,13 @@ int kz_light_query(KzScene *scene, uint32_t n, const int32_t *light, const float
     if (n == 0) return KZ_OK;
     if (!light || !ref || !u3 || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null buffer");
     for (uint32_t i = 0; i < n; ++i) if (light[i] < 0 || (uint32_t)light[i] >= scene->prm.nLights) return kz_fail(KZ_ERR_INVALID_ARG, "light index %d", light[i]);
-    DevMem dF, dL;
-    KZ_ALLOC(&dF.p, (size_t)n * 20 * 4); KZ_ALLOC(&dL.p, (size_t)n * 4);
-    float *d = dF.as<float>(), *dR = d, *dU = d + 3 * (size_t)n, *dO = d + 6 * (size_t)n;
-    HIP_TRY(hipMemcpy(dL.p, light, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dR, ref, (size_t)n * 12, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dU, u3, (size_t)n * 12, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kz_light_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, ds->T, n, dL.as<int32_t>(), dR, dU, dO);
+    DevBuf<float> dF; DevBuf<int32_t> dL;      // dF, in units of N floats: ref 0..3 | u3 3..6 | out 6..20
+    const size_t N = n;
+    if ((rc = dF.alloc(20 * N)) || (rc = dL.alloc(N)) || (rc = dL.upload(light, N)) || (rc = dF.upload(ref, 3 * N)) || (rc = dF.upload(u3, 3 * N, 3 * N))) return rc;
+    hipLaunchKernelGGL(kz_light_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, ds->T, n, dL.get(), dF.get(), dF + 3 * N, dF + 6 * N);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dO, (size_t)n * 56, hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return dF.download(out, 14 * N, 6 * N);
 }
 
 

@@ -192,18 +192,17 @@ int kzFilmEnsureTapSums(KzScene *scene, KzDeviceState *ds, hipStream_t stream) {
     const size_t taps = (size_t)(P.tapHi - P.tapLo + 1), framePix = (size_t)P.width * (size_t)P.height;
     if (ds->tapSums) return KZ_OK;
     KZ_TRACE("film: tap sums, %.0f MB ...", taps * taps * framePix * sizeof(float4) / 1e6);
-    KZ_ALLOC(&ds->tapSums, taps * taps * framePix * sizeof(float4));
-    ds->tapSumsBytes = taps * taps * framePix * sizeof(float4);
-    HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSumsBytes, stream));
+    if (const int rc = ds->tapSums.alloc(taps * taps * framePix)) return rc;
+    HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSums.bytes(), stream));
     KZ_TRACE("film: ... there");
     return KZ_OK;
 }
 
 int kzFilmClear(KzDeviceState *ds, hipStream_t stream) {
-    if (ds->tapSums) HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSumsBytes, stream));
+    if (ds->tapSums) HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSums.bytes(), stream));
     HIP_TRY(hipMemsetAsync(ds->film, 0, ds->filmPixels * sizeof(float4), stream));
     for (int f = 0; f < 3; ++f) {                                      // the feature films follow the picture's
-        if (ds->aovTapSums[f]) HIP_TRY(hipMemsetAsync(ds->aovTapSums[f], 0, ds->tapSumsBytes, stream));
+        if (ds->aovTapSums[f]) HIP_TRY(hipMemsetAsync(ds->aovTapSums[f], 0, ds->tapSums.bytes(), stream));
         if (ds->aovFilm[f]) HIP_TRY(hipMemsetAsync(ds->aovFilm[f], 0, ds->filmPixels * sizeof(float4), stream));
     }
     return KZ_OK;
@@ -240,9 +239,10 @@ int kzAovEnsure(KzScene *scene, KzDeviceState *ds, hipStream_t stream, bool accu
     for (int f = 0; f < 3; ++f) {
         if (!(scene->aovMask & (1u << f))) continue;
         const bool fresh = !ds->aovTapSums[f];
-        if (fresh) KZ_ALLOC(&ds->aovTapSums[f], ds->tapSumsBytes);
-        if (!ds->aovFilm[f]) { KZ_ALLOC(&ds->aovFilm[f], ds->filmPixels * sizeof(float4)); HIP_TRY(hipMemsetAsync(ds->aovFilm[f], 0, ds->filmPixels * sizeof(float4), stream)); }
-        if (fresh || !accumulate) HIP_TRY(hipMemsetAsync(ds->aovTapSums[f], 0, ds->tapSumsBytes, stream));
+        int rc;
+        if (fresh && (rc = ds->aovTapSums[f].alloc(ds->tapSums.cap()))) return rc;
+        if (!ds->aovFilm[f]) { if ((rc = ds->aovFilm[f].alloc(ds->filmPixels))) return rc; HIP_TRY(hipMemsetAsync(ds->aovFilm[f], 0, ds->filmPixels * sizeof(float4), stream)); }
+        if (fresh || !accumulate) HIP_TRY(hipMemsetAsync(ds->aovTapSums[f], 0, ds->tapSums.bytes(), stream));
     }
     return KZ_OK;
 }
@@ -259,8 +259,7 @@ int kzAovFilmStage(KzScene *scene, KzDeviceState *ds, hipStream_t pst, const uin
 void kzAovFree(KzDeviceState *ds, uint32_t mask) {
     for (int f = 0; f < 3; ++f) {
         if (!(mask & (1u << f))) continue;
-        if (ds->aovTapSums[f]) { (void)hipFree(ds->aovTapSums[f]); ds->aovTapSums[f] = nullptr; }
-        if (ds->aovFilm[f]) { (void)hipFree(ds->aovFilm[f]); ds->aovFilm[f] = nullptr; }
+        ds->aovTapSums[f].free(); ds->aovFilm[f].free();
     }
 }
 
@@ -305,33 +304,16 @@ int downloadTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32
         maxRows = std::max(maxRows, tiles[t].h + 2 * P.border);
     }
     if (off >= (1ull << 32)) return kz_fail(KZ_ERR_UNSUPPORTED, "tile set of %zu film pixels (limit 2^32)", off);
-    if (nTiles > ds->rectsCap) {
-        if (ds->rectsDev) (void)hipFree(ds->rectsDev);
-        ds->rectsDev = nullptr; ds->rectsCap = 0;
-        KZ_ALLOC(&ds->rectsDev, (size_t)nTiles * sizeof(KzTileRect));
-        ds->rectsCap = nTiles;
-    }
-    if (off > ds->packCap) {
-        if (ds->packDev) (void)hipFree(ds->packDev);
-        ds->packDev = nullptr; ds->packCap = 0;
-        const size_t cap = off + off / 8;                              // (headroom: the next tile set of about this size reuses the buffers)
-        KZ_ALLOC(&ds->packDev, cap * sizeof(float4));
-        ds->packCap = cap;
-    }
-    if (off > ds->packHostCap) {
-        if (ds->packHost) (void)hipHostFree(ds->packHost);
-        ds->packHost = nullptr; ds->packHostCap = 0;
-        const size_t cap = off + off / 8;
-        if (hipHostMalloc((void **)&ds->packHost, cap * sizeof(float4), hipHostMallocDefault) == hipSuccess) ds->packHostCap = cap;
-        else ds->packHost = nullptr;                                   // (no pinned memory to be had: the copy below goes to the caller's pageable buffer)
-    }
+    if (nTiles > ds->rectsDev.cap() && (rc = ds->rectsDev.regrow(nTiles))) return rc;
+    if (off > ds->packDev.cap() && (rc = ds->packDev.regrow(off + off / 8))) return rc;      // (headroom: the next tile set of about this size reuses the buffers)
+    if (off > ds->packHost.cap()) (void)ds->packHost.regrow(off + off / 8);                  // (no pinned memory to be had: the copy below goes to the caller's pageable buffer)
     HIP_TRY(hipMemcpyAsync(ds->rectsDev, rects.data(), (size_t)nTiles * sizeof(KzTileRect), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));                              // (the tables are host vectors of this call)
     if (nTiles > 65535u * 65535u) return kz_fail(KZ_ERR_UNSUPPORTED, "kz_film_download_tiles: %u tiles in one call", nTiles);
     const unsigned gz = (nTiles + 65534u) / 65535u, gy = gz > 1 ? 65535u : nTiles;
     if ((rc = kzFilmEnsureTapSums(scene, ds, stream))) return rc;      // (a replica nothing has been rendered on: zeros)
-    hipLaunchKernelGGL(kz_film_tile_rects, dim3((unsigned)maxRows, gy, gz), dim3(128), 0, stream, P, (const float4 *)ds->tapSums, (size_t)P.width * (size_t)P.height, (const KzTileRect *)ds->rectsDev,
-                       ds->packDev, nTiles);
+    hipLaunchKernelGGL(kz_film_tile_rects, dim3((unsigned)maxRows, gy, gz), dim3(128), 0, stream, P, (const float4 *)ds->tapSums, (size_t)P.width * (size_t)P.height, (const KzTileRect *)ds->rectsDev.get(),
+                       ds->packDev.get(), nTiles);
     HIP_TRY(hipGetLastError());
     if (ds->packHost) {
         HIP_TRY(hipMemcpyAsync(ds->packHost, ds->packDev, off * sizeof(float4), hipMemcpyDeviceToHost, stream));
@@ -435,7 +417,7 @@ int kz_film_to_srgb8(KzScene *scene, uint8_t *rgb8, size_t nBytes) {
     const KzParams &P = scene->prm;
     const size_t need = (size_t)P.width * (size_t)P.height * 3;
     if (!rgb8 || nBytes != need) return kz_fail(KZ_ERR_INVALID_ARG, "rgb8 buffer must hold %zu bytes", need);
-    if (!ds->srgb) KZ_ALLOC(&ds->srgb, need);                          // staging raster kept with the replica
+    if (!ds->srgb && (rc = ds->srgb.alloc(need))) return rc;                        // staging raster kept with the replica
     const uint32_t n = (uint32_t)(P.width * P.height);
     hipLaunchKernelGGL(kz_film_srgb8, dim3((n + 255) / 256), dim3(256), 0, ds->lastStream, ds->film, P.width, P.height, P.border, ds->srgb);
     HIP_TRY(hipGetLastError());

@@ -120,7 +120,7 @@ int kzEditWait(KzScene *scene) {
 }
 
 static int beamsUnbuilt(KzDeviceState *ds) {
-    if (ds->beamCount) HIP_TRY(hipMemset(ds->beamCount, 0xFF, ds->beamCap * sizeof(uint2)));         // every pixel: KZ_BEAM_UNBUILT
+    if (ds->beamCount) HIP_TRY(hipMemset(ds->beamCount, 0xFF, ds->beamCount.bytes()));         // every pixel: KZ_BEAM_UNBUILT
     ds->beamDone.clear();
     return KZ_OK;
 }
@@ -137,33 +137,19 @@ int kzEditPrepare(KzScene *scene) {
     return forEachReplica(scene, [scene](KzDeviceState *ds) -> int {
         int rc;
         if ((rc = kzEnsureBvh2(scene, ds))) return rc;
-        auto up = [&](const std::vector<uint32_t> &v, uint32_t **out) -> int {
-            if (*out) return KZ_OK;
-            void *p = nullptr;
-            const size_t bytes = std::max<size_t>(256, v.size() * sizeof(uint32_t));
-            KZ_ALLOC(&p, bytes);
-            ds->allocs.push_back(p);
-            if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            *out = (uint32_t *)p; ds->editBytes += bytes;
-            return KZ_OK;
+        auto up = [](const std::vector<uint32_t> &v, DevBuf<uint32_t> &buf) -> int {      // (at least 256 bytes, so the kernels never see null)
+            if (buf) return KZ_OK;
+            if (const int rc_ = buf.alloc(std::max<size_t>(64, v.size()))) return rc_;
+            return v.empty() ? KZ_OK : buf.upload(v.data(), v.size());
         };
-        if ((rc = up(scene->triVtx, &ds->editTriVtx))) return rc;
-        if ((rc = up(scene->slotSrc, &ds->editSlotSrc))) return rc;
-        if (!ds->editPad) {
-            void *p = nullptr;
-            KZ_ALLOC(&p, 256);
-            ds->allocs.push_back(p); ds->editPad = (float *)p; ds->editBytes += 256;
-        }
-        return KZ_OK;
+        if ((rc = up(scene->triVtx, ds->editTriVtx))) return rc;
+        if ((rc = up(scene->slotSrc, ds->editSlotSrc))) return rc;
+        return ds->editPad ? KZ_OK : ds->editPad.alloc(64);
     });
 }
 
 static int stageRoom(KzDeviceState *ds, size_t floats) {
-    if (ds->editStageCap >= floats) return KZ_OK;
-    if (ds->editStage) { (void)hipFree(ds->editStage); ds->editBytes -= ds->editStageCap * sizeof(float); ds->editStage = nullptr; ds->editStageCap = 0; }
-    KZ_ALLOC(&ds->editStage, floats * sizeof(float));
-    ds->editStageCap = floats; ds->editBytes += floats * sizeof(float);
-    return KZ_OK;
+    return ds->editStage.cap() >= floats ? KZ_OK : ds->editStage.regrow(floats);
 }
 
 // The refit of one replica behind kz_edit_shade (launched by the caller for every mesh of the batch): triangles, BVH2 levels, padding, BVH4 packets; then the rows the
@@ -242,11 +228,11 @@ int kzEditBsdfRows(KzScene *scene, const uint32_t *rows, uint32_t n, bool extCha
 int kzEditLightRows(KzScene *scene) {
     return forEachReplica(scene, [&](KzDeviceState *ds) -> int {
         if (!ds->ilTrisRoomy) {                                 // a visibility toggle changes the length of the invisible-light list: room for the 64 rows it may have
-            void *p = nullptr;
-            KZ_ALLOC(&p, 64 * sizeof(KzTri));
-            ds->allocs.push_back(p);
-            HIP_TRY(hipMemset(p, 0, 64 * sizeof(KzTri)));
-            ds->T.ilTris = (const KzTri *)p; ds->ilTrisRoomy = true; ds->editBytes += 64 * sizeof(KzTri);
+            DevBuf<KzTri> roomy;
+            if (const int rc = roomy.alloc(64)) return rc;
+            HIP_TRY(hipMemset(roomy, 0, roomy.bytes()));
+            ds->ilTris = std::move(roomy);                      // (the table of the upload is freed here: the edit has waited for the device, kzEditWait)
+            ds->T.ilTris = ds->ilTris; ds->ilTrisRoomy = true;
         }
         if (!scene->lightRows.empty()) HIP_TRY(hipMemcpy(const_cast<KzLightRow *>(ds->T.lights), scene->lightRows.data(), scene->lightRows.size() * sizeof(KzLightRow), hipMemcpyHostToDevice));
         if (!scene->ilTris.empty()) HIP_TRY(hipMemcpy(const_cast<KzTri *>(ds->T.ilTris), scene->ilTris.data(), scene->ilTris.size() * sizeof(KzTri), hipMemcpyHostToDevice));
@@ -267,12 +253,8 @@ int kzEditXformStage(KzScene *scene, const KzXformJob *jobs, uint32_t n, int32_t
     return forEachReplica(scene, [&](KzDeviceState *ds) -> int {
         int rc;
         if ((rc = stageRoom(ds, floats))) return rc;
-        if (ds->editBase.size() != scene->meshRows.size()) ds->editBase.assign(scene->meshRows.size(), nullptr);
-        if (!ds->editFlag) {
-            void *p = nullptr;
-            KZ_ALLOC(&p, 4096 * sizeof(uint32_t));
-            ds->allocs.push_back(p); ds->editFlag = (uint32_t *)p; ds->editBytes += 4096 * sizeof(uint32_t);
-        }
+        if (ds->editBase.size() != scene->meshRows.size()) ds->editBase.resize(scene->meshRows.size());
+        if (!ds->editFlag && (rc = ds->editFlag.alloc(4096))) return rc;
         size_t off = 0;
         for (uint32_t first = 0; first < n; first += 4096) {       // (4096 flags: a longer batch is staged in pieces; nothing but the staging area is written)
             const uint32_t cnt = std::min<uint32_t>(4096, n - first);
@@ -282,12 +264,8 @@ int kzEditXformStage(KzScene *scene, const KzXformJob *jobs, uint32_t n, int32_t
                 const size_t k = 3 * (size_t)nV, all = xformFloats(scene, m);
                 if (!k) continue;
                 if (!ds->editBase[m]) {                            // this replica's first transform of the mesh: its base V / N go up once (the host holds them: kz_edit.cpp captureBase)
-                    void *p = nullptr;
-                    KZ_ALLOC(&p, all * sizeof(float));
-                    ds->allocs.push_back(p); ds->editBytes += all * sizeof(float);
-                    HIP_TRY(hipMemcpy(p, scene->baseV[m].data(), k * sizeof(float), hipMemcpyHostToDevice));
-                    if (all > k) HIP_TRY(hipMemcpy((float *)p + k, scene->baseN[m].data(), k * sizeof(float), hipMemcpyHostToDevice));
-                    ds->editBase[m] = (float *)p;
+                    DevBuf<float> &base = ds->editBase[m];
+                    if ((rc = base.alloc(all)) || (rc = base.upload(scene->baseV[m].data(), k)) || (all > k && (rc = base.upload(scene->baseN[m].data(), k, k)))) return rc;
                 }
                 const float *bV = ds->editBase[m], *bN = all > k ? bV + k : nullptr;
                 float *V = ds->editStage + off, *N = bN ? V + k : nullptr;
@@ -295,7 +273,7 @@ int kzEditXformStage(KzScene *scene, const KzXformJob *jobs, uint32_t n, int32_t
                 hipLaunchKernelGGL(kz_edit_xform, editGrid(nV), dim3(KZ_EDIT_BLOCK), 0, 0, bV, bN, V, N, nV, *jobs[first + j].x, ds->editFlag + j);
             }
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpy(flags.data() + first, ds->editFlag, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));      // (blocking: behind the kernels above)
+            if ((rc = ds->editFlag.download(flags.data() + first, cnt))) return rc;      // (blocking: behind the kernels above)
         }
         for (uint32_t i = 0; i < n; ++i) if (flags[i] && *bad < 0) *bad = (int32_t)i;
         return KZ_OK;

@@ -62,7 +62,7 @@ static int resolveTune(const KzTuning &t, KzTune &r) {
 }
 
 static int stageMark(PassCtx &c, hipStream_t stream, int kind) {
-    if (c.stageUsed == c.stageEv.size()) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c.stageEv.push_back(e); c.stageKind.push_back(0); }
+    if (c.stageUsed == c.stageEv.size()) { Event e; if (const int rc = e.ensure()) return rc; c.stageEv.push_back(std::move(e)); c.stageKind.push_back(0); }
     c.stageKind[c.stageUsed] = kind;
     HIP_TRY(hipEventRecord(c.stageEv[c.stageUsed++], stream));
     return KZ_OK;
@@ -88,7 +88,7 @@ static void ctxPoint(PassCtx &c, const KzArena &A, size_t off) {
 // thread: `want` items are asked for, the call returns as soon as `minItems` are there and the arena has stopped making quick progress (graceMs; < 0: wait
 // for everything), and tells how many items a pass may use now (*usable, never more than `want`). Nothing is left half-allocated on failure. ----
 static int ctxEnsure(PassCtx &c, size_t want, size_t minItems, double graceMs, hipStream_t stream, size_t *usable) {
-    if (!c.counts) { KZ_ALLOC(&c.counts, KzCounts::bytes()); }
+    if (!c.counts) { if (const int rc = c.counts.alloc(KzCounts::kWords)) return rc; }
     KzArena &A = *c.arena;
     if (A.wouldReallocate(want)) HIP_TRY(hipDeviceSynchronize());      // (a small context outgrown, or a pass beyond the reserved ranges: what is there is given up first)
 #ifdef KZ_EXPERIMENTS
@@ -156,11 +156,11 @@ static KzIntegratorMegaFn integratorMegaFn(int integrator, int ext) {      // no
 static int ensureBeamBuffers(KzScene *scene, KzDeviceState *ds, hipStream_t stream) {
     const KzParams &P = scene->prm;
     const size_t framePix = (size_t)P.width * P.height;
-    if (!ds->evBeam) HIP_TRY(hipEventCreateWithFlags(&ds->evBeam, hipEventDisableTiming));
+    int rc;
+    if ((rc = ds->evBeam.ensure(hipEventDisableTiming))) return rc;
     if (!ds->beamEntries || !ds->beamCount) {
-        if (!ds->beamEntries) KZ_ALLOC(&ds->beamEntries, framePix * KZ_BEAM_CAP * sizeof(uint2));
-        if (!ds->beamCount) KZ_ALLOC(&ds->beamCount, framePix * sizeof(uint2));
-        ds->beamCap = framePix;
+        if (!ds->beamEntries && (rc = ds->beamEntries.alloc(framePix * KZ_BEAM_CAP))) return rc;
+        if (!ds->beamCount && (rc = ds->beamCount.alloc(framePix))) return rc;
         HIP_TRY(hipMemsetAsync(ds->beamCount, 0xFF, framePix * sizeof(uint2), stream));       // every pixel: KZ_BEAM_UNBUILT
         ds->beamDone.clear(); ds->beamDoneGen = ds->tileGen;
     }
@@ -230,9 +230,9 @@ static void shadowLaunches(const KzParams &P, Trace &&trace, const uint32_t *q, 
 // The global overflow area of the traversal stacks (entries beyond tune.ldsStack per lane, sized from the builder's worst-case bound) of one pass context.
 static int ensureOverflow(KzScene *scene, KzDeviceState *ds, PassCtx &c, const KzTune &tune, hipStream_t stream) {
     const size_t needOvf = traceShape(scene->prm, travGridBlocks(ds, tune), tune.ldsStack).ovfPart * 3;      // (x 3: part 0 the pass's own stream, part 1 spare, part 2 the shadow kernels of a small pass on the side stream, wfPass)
-    if (needOvf <= c.ovfCap) return KZ_OK;
+    if (needOvf <= c.ovf.cap()) return KZ_OK;
     HIP_TRY(hipStreamSynchronize(stream));
-    return kzRegrow(c.ovf, c.ovfCap, needOvf);
+    return c.ovf.regrow(needOvf);
 }
 
 // What the launches of one wfPass share: the stream, the kernels' arguments, the grids.
@@ -332,7 +332,7 @@ static int wfMis(WfLaunch &L, bool beside) {
     int rc;
     const KzParams &P = L.P; const KzWf &W = L.W; PassCtx &c = L.c; hipStream_t stream = L.stream;
     L.ds->lastInfo.shadowBeside = beside ? 1u : 0u;      // (what the last pass did: kz_last_pass_info)
-    if (beside && !c.side) { HIP_TRY(hipStreamCreateWithFlags(&c.side, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&c.evFork, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&c.evJoin, hipEventDisableTiming)); }
+    if (beside && ((rc = c.side.ensure(hipStreamNonBlocking)) || (rc = c.evFork.ensure(hipEventDisableTiming)) || (rc = c.evJoin.ensure(hipEventDisableTiming)))) return rc;
     const KzShadeFn shade = shadeFn(L.st, extSel(P.bsdfExt, KZ_X_ALL));
     const uint32_t *cur = nullptr, *curCount = nullptr;
     for (int iter = 0; iter < P.maxDepth; ++iter) {
@@ -488,18 +488,16 @@ static int passStreams(KzDeviceState *ds, int streamPriority, int nCtx) {
     const int mode = streamPriority > 0 ? streamPriority : 3;
     if (mode != ds->streamMode) {                                  // another policy than the streams were made with: make them again
         HIP_TRY(hipDeviceSynchronize());
-        for (hipStream_t &st : ds->passStream) if (st) { (void)hipStreamDestroy(st); st = nullptr; }
+        for (Stream &st : ds->passStream) st.reset();
         ds->streamMode = mode;
     }
     const int nPr = std::max(1, prLeast - prGreatest + 1);
     for (int i = 0; i < nCtx; ++i) {
-        if (!ds->evFilm[i]) HIP_TRY(hipEventCreateWithFlags(&ds->evFilm[i], hipEventDisableTiming));
-        if (ds->passStream[i]) continue;
         const int pr = mode == 1 ? (prLeast + prGreatest) / 2 : mode == 2 ? ((i & 1) ? prGreatest : prLeast) : prLeast - (i % nPr);
-        HIP_TRY(hipStreamCreateWithPriority(&ds->passStream[i], hipStreamNonBlocking, pr));
+        if (const int rc = ds->evFilm[i].ensure(hipEventDisableTiming)) return rc;
+        if (const int rc = ds->passStream[i].ensure(hipStreamNonBlocking, pr)) return rc;
     }
-    if (!ds->evFork) HIP_TRY(hipEventCreateWithFlags(&ds->evFork, hipEventDisableTiming));
-    return KZ_OK;
+    return ds->evFork.ensure(hipEventDisableTiming);
 }
 
 // The passes of one call: what they share (the call's arguments and its plan) and what one leaves for the next and for the call's summary.
@@ -581,7 +579,7 @@ static int launchWhole(PassRun &r, PassCtx &c, int ci, hipStream_t pst, EventPai
         // (feature films, passes in flight: this pass's AOV tap launches go behind those of the pass before it, on another stream - wfAov)
         hipEvent_t waitAov = nullptr, recordAov = nullptr;
         if (scene->aovMask && r.pl.multi) {
-            if (!ds->evAov[ci]) HIP_TRY(hipEventCreateWithFlags(&ds->evAov[ci], hipEventDisableTiming));
+            if ((rc = ds->evAov[ci].ensure(hipEventDisableTiming))) return rc;
             recordAov = ds->evAov[ci];
             if (r.pass > 0) waitAov = ds->evAov[(ci + r.pl.nCtx - 1) % r.pl.nCtx];
         }
@@ -619,22 +617,22 @@ static int onePass(PassRun &r, uint32_t p0, uint32_t nPixPass, uint32_t s, uint3
         if ((rc = ensureBeams(r.scene, ds, r.stream, p0, nPixPass))) return rc;
         if (pst != r.stream && c.beamSeen != ds->beamSeq) { HIP_TRY(hipStreamWaitEvent(pst, ds->evBeam, 0)); c.beamSeen = ds->beamSeq; }
     }
-    if (ds->eventsUsed == ds->events.size()) { EventPair ep; HIP_TRY(hipEventCreate(&ep.a)); HIP_TRY(hipEventCreate(&ep.b)); ds->events.push_back(ep); }
+    if (ds->eventsUsed == ds->events.size()) { EventPair ep; if ((rc = ep.a.ensure()) || (rc = ep.b.ensure())) return rc; ds->events.push_back(std::move(ep)); }
     EventPair &ep = ds->events[ds->eventsUsed++];
     HIP_TRY(hipEventRecord(ep.a, pst));
     KzPassAnswer how;
     if ((rc = passMode(r, items, nPixPass, how))) return rc;
     if (how.halves) {                                                       // (what the halves need - a second stream, per view counters and overflow stacks - is made before the clock of a timed pass starts)
-        if (!c.halfStream) { HIP_TRY(hipStreamCreateWithFlags(&c.halfStream, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&c.evHalfFork, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&c.evHalfJoin, hipEventDisableTiming)); }
+        if ((rc = c.halfStream.ensure(hipStreamNonBlocking)) || (rc = c.evHalfFork.ensure(hipEventDisableTiming)) || (rc = c.evHalfJoin.ensure(hipEventDisableTiming))) return rc;
         for (int h = 0; h < 2; ++h) {
-            if (!c.view[h]) c.view[h] = new PassCtx();
-            if (!c.view[h]->counts) KZ_ALLOC(&c.view[h]->counts, KzCounts::bytes());
+            if (!c.view[h]) c.view[h].reset(new PassCtx());
+            if (!c.view[h]->counts && (rc = c.view[h]->counts.alloc(KzCounts::kWords))) return rc;
             if ((rc = ensureOverflow(r.scene, ds, *c.view[h], r.tune, h ? c.halfStream : pst))) return rc;
         }
     }
     const int probe = how.probe;
     if (probe >= 0) {
-        for (int k = 0; k < 2; ++k) if (!ds->evProbe[probe][k]) HIP_TRY(hipEventCreate(&ds->evProbe[probe][k]));
+        for (int k = 0; k < 2; ++k) if ((rc = ds->evProbe[probe][k].ensure())) return rc;
         HIP_TRY(hipEventRecord(ds->evProbe[probe][0], pst));
     }
     ds->lastStageCtx = nullptr;
@@ -681,7 +679,7 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     if (tune.filmGather != 0 && tune.filmGather != 3) return kz_fail(KZ_ERR_UNSUPPORTED, "KzTuning.filmGather %d: the staged gather kernel of round 1 is gone (round 6: the film is resolved from running tap sums for every filter); 0 = default, 3 = one lane per pixel", tune.filmGather);
     if ((rc = prepareTiles(scene, ds, opts->tiles, opts->nTiles, stream))) return rc;
     // the film: running tap sums of the frame's pixels (kz_film.hip), part of the replica like the film itself - cleared unless the call accumulates
-    { const bool fresh = !ds->tapSums; if ((rc = kzFilmEnsureTapSums(scene, ds, stream))) return rc; if (!opts->accumulate && !fresh) HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSumsBytes, stream)); }
+    { const bool fresh = !ds->tapSums; if ((rc = kzFilmEnsureTapSums(scene, ds, stream))) return rc; if (!opts->accumulate && !fresh) HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSums.bytes(), stream)); }
     if (scene->aovMask && (rc = kzAovEnsure(scene, ds, stream, opts->accumulate != 0))) return rc;      // ... and the feature films' (kazen_mi355x_aov.h)
     const KzTileDealer *dealer = opts->dealer;
     if (dealer) {
@@ -704,9 +702,9 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     r.lastAvail = pl.need;
     // ---- make room
     if ((rc = makeRoom(ds, nCtx, pl.need, in.perItem, in.limit))) return rc;
-    if (!ds->evCallA) { HIP_TRY(hipEventCreate(&ds->evCallA)); HIP_TRY(hipEventCreate(&ds->evCallB)); }
+    if ((rc = ds->evCallA.ensure()) || (rc = ds->evCallB.ensure())) return rc;
     if (multi && (rc = passStreams(ds, opts->tune.streamPriority, nCtx))) return rc;
-    if (dealer && !ds->evFilm[0]) HIP_TRY(hipEventCreateWithFlags(&ds->evFilm[0], hipEventDisableTiming));
+    if (dealer && (rc = ds->evFilm[0].ensure(hipEventDisableTiming))) return rc;
     ds->eventsUsed = 0;
     HIP_TRY(hipEventRecord(ds->evCallA, stream));
     if (multi) {
@@ -791,7 +789,7 @@ int kz_render_tiles(KzScene *scene, const KzRenderOpts *opts, const KzTile *tile
 
 // What the per-sample entry points share: n > 0 samples (pixel x, y and sample index) checked against the scene, the megakernels' BVH2 made sure of, and the
 // pixels (packed as a pixel list) and indices uploaded into dP / dI.
-static int uploadSamples(KzScene *scene, KzDeviceState *ds, uint32_t n, const int32_t *pxy, const uint32_t *idx, const float *out, DevMem &dP, DevMem &dI) {
+static int uploadSamples(KzScene *scene, KzDeviceState *ds, uint32_t n, const int32_t *pxy, const uint32_t *idx, const float *out, DevBuf<uint32_t> &dP, DevBuf<uint32_t> &dI) {
     int rc;
     if (!pxy || !idx || !out) return kz_fail(KZ_ERR_INVALID_ARG, "null buffer");
     if ((rc = kzEnsureBvh2(scene, ds))) return rc;
@@ -802,31 +800,31 @@ static int uploadSamples(KzScene *scene, KzDeviceState *ds, uint32_t n, const in
             return kz_fail(KZ_ERR_INVALID_ARG, "sample %u: pixel (%d,%d) index %u out of range", i, pxy[2 * i], pxy[2 * i + 1], idx[i]);
         pl[i] = (uint32_t)pxy[2 * i] | ((uint32_t)pxy[2 * i + 1] << 16);
     }
-    KZ_ALLOC(&dP.p, (size_t)n * 4); KZ_ALLOC(&dI.p, (size_t)n * 4);
-    HIP_TRY(hipMemcpy(dP.p, pl.data(), (size_t)n * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dI.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
+    if ((rc = dP.alloc(n)) || (rc = dI.alloc(n)) || (rc = dP.upload(pl.data(), n)) || (rc = dI.upload(idx, n))) return rc;
     return KZ_OK;
 }
 
+// Radiance of explicit (pixel, sample index) pairs without touching the film: out = n x (sx, sy, r, g, b).
 int kz_render_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint32_t *idx, float *out) {
     KzDeviceState *ds; int rc;
     if ((rc = requireDevice(scene, &ds))) return rc;
     if (n == 0) return KZ_OK;
-    DevMem dP, dI, dOut;
+    DevBuf<uint32_t> dP, dI; DevBuf<float> dOut;
     if ((rc = uploadSamples(scene, ds, n, pxy, idx, out, dP, dI))) return rc;
     const KzParams &P = scene->prm;
-    KZ_ALLOC(&dOut.p, (size_t)n * 20);
-    float *dO = dOut.as<float>();
+    if ((rc = dOut.alloc((size_t)n * 5))) return rc;
+    float *dO = dOut;
     const dim3 gS((n + KZ_BLOCK - 1) / KZ_BLOCK);
     // one kernel per integrator serves every scene here: the variant for everything its BSDF rows may need (normals / ao read no BSDF row; path_mats has no normal maps)
     if (P.integrator == KZ_INTEGRATOR_NORMALS || P.integrator == KZ_INTEGRATOR_AO || P.integrator == KZ_INTEGRATOR_PATH_MATS)
-        hipLaunchKernelGGL(integratorMegaFn(P.integrator, KZ_X_MATS), gS, dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.as<uint32_t>(), n, 1u, 0u, dI.as<uint32_t>(),
+        hipLaunchKernelGGL(integratorMegaFn(P.integrator, KZ_X_MATS), gS, dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.get(), n, 1u, 0u, dI.get(),
                            dO, dO + n, dO + 2 * (size_t)n, dO + 3 * (size_t)n, dO + 4 * (size_t)n);
-    else hipLaunchKernelGGL(megaFn(false, KZ_X_ALL), gS, dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.as<uint32_t>(), n, 1u, 0u, dI.as<uint32_t>(),
-                            dO, dO + n, dO + 2 * (size_t)n, dO + 3 * (size_t)n, dO + 4 * (size_t)n, ds->stats);
+    else hipLaunchKernelGGL(megaFn(false, KZ_X_ALL), gS, dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.get(), n, 1u, 0u, dI.get(),
+                            dO, dO + n, dO + 2 * (size_t)n, dO + 3 * (size_t)n, dO + 4 * (size_t)n, ds->stats.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     std::vector<float> h((size_t)n * 5);
-    HIP_TRY(hipMemcpy(h.data(), dO, (size_t)n * 20, hipMemcpyDeviceToHost));
+    if ((rc = dOut.download(h.data(), h.size()))) return rc;
     for (uint32_t i = 0; i < n; ++i) {
         out[5 * i] = (float)pxy[2 * i] + h[i]; out[5 * i + 1] = (float)pxy[2 * i + 1] + h[n + i];
         out[5 * i + 2] = h[2 * (size_t)n + i]; out[5 * i + 3] = h[3 * (size_t)n + i]; out[5 * i + 4] = h[4 * (size_t)n + i];
@@ -839,15 +837,15 @@ int kz_aov_samples(KzScene *scene, uint32_t n, const int32_t *pxy, const uint32_
     KzDeviceState *ds; int rc;
     if ((rc = requireDevice(scene, &ds))) return rc;
     if (n == 0) return KZ_OK;
-    DevMem dP, dI, dOut;
+    DevBuf<uint32_t> dP, dI; DevBuf<float> dOut;
     if ((rc = uploadSamples(scene, ds, n, pxy, idx, out, dP, dI))) return rc;
     const KzParams &P = scene->prm;
-    KZ_ALLOC(&dOut.p, (size_t)n * 40);
-    hipLaunchKernelGGL(kz_aov_samples_kernel, dim3((n + KZ_BLOCK - 1) / KZ_BLOCK), dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.as<uint32_t>(), dI.as<uint32_t>(), n,
-                       P.integrator == KZ_INTEGRATOR_PATH_MIS ? 1 : 0, dOut.as<float>());
+    if ((rc = dOut.alloc((size_t)n * 10))) return rc;
+    hipLaunchKernelGGL(kz_aov_samples_kernel, dim3((n + KZ_BLOCK - 1) / KZ_BLOCK), dim3(KZ_BLOCK), 0, 0, P, ds->T, dP.get(), dI.get(), n,
+                       P.integrator == KZ_INTEGRATOR_PATH_MIS ? 1 : 0, dOut.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dOut.p, (size_t)n * 40, hipMemcpyDeviceToHost));
+    if ((rc = dOut.download(out, (size_t)n * 10))) return rc;
     for (uint32_t i = 0; i < n; ++i) { out[10 * (size_t)i] += (float)pxy[2 * i]; out[10 * (size_t)i + 1] += (float)pxy[2 * i + 1]; }      // sample position = pixel + jitter
     return KZ_OK;
 }
@@ -901,29 +899,24 @@ int kz_trace_rays_wf(KzScene *scene, const KzTraceWfOpts *opts, uint32_t nSlots,
         h[i] = make_float4(hits[i].t, hits[i].u, hits[i].v, gidBits);
         for (int k = 0; k < 3; ++k) planes[k * n + i] = sums[3 * i + k];
     }
-    DevMem dA, dB, dSA, dSB, dSL, dH, dPl, dQ, dQB, dCounts, dStats, dOvf;
-    KZ_ALLOC(&dA.p, n * 16); KZ_ALLOC(&dB.p, n * 16); KZ_ALLOC(&dSA.p, n * 16); KZ_ALLOC(&dSB.p, n * 16); KZ_ALLOC(&dSL.p, n * 16); KZ_ALLOC(&dH.p, n * 16);
-    KZ_ALLOC(&dPl.p, 3 * n * 4); KZ_ALLOC(&dQ.p, (size_t)count * 4); KZ_ALLOC(&dQB.p, (size_t)count * 4);
-    KZ_ALLOC(&dCounts.p, 16 * 4); KZ_ALLOC(&dStats.p, 32 * 8);
+    DevBuf<float4> dA, dB, dSA, dSB, dSL, dH; DevBuf<float> dPl; DevBuf<uint32_t> dQ, dQB, dCounts, dOvf; DevBuf<unsigned long long> dStats;
     // the overflow area of ONE launch at a time (the launches below run one after another on one stream) and, behind it, one guard row: words no stack may reach
     const size_t ovfWords = shape.ovfPart + shape.ovfStride;
-    KZ_ALLOC(&dOvf.p, ovfWords * 4);
-    HIP_TRY(hipMemcpy(dA.p, a.data(), n * 16, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dB.p, b.data(), n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dSA.p, sa.data(), n * 16, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dSB.p, sb.data(), n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dSL.p, sl.data(), n * 16, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(dH.p, h.data(), n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dPl.p, planes.data(), 3 * n * 4, hipMemcpyHostToDevice));
-    if (queue) HIP_TRY(hipMemcpy(dQ.p, queue, (size_t)count * 4, hipMemcpyHostToDevice));
+    if ((rc = dA.alloc(n)) || (rc = dB.alloc(n)) || (rc = dSA.alloc(n)) || (rc = dSB.alloc(n)) || (rc = dSL.alloc(n)) || (rc = dH.alloc(n)) || (rc = dPl.alloc(3 * n)) ||
+        (rc = dQ.alloc(count)) || (rc = dQB.alloc(count)) || (rc = dCounts.alloc(16)) || (rc = dStats.alloc(32)) || (rc = dOvf.alloc(ovfWords))) return rc;
+    if ((rc = dA.upload(a.data(), n)) || (rc = dB.upload(b.data(), n)) || (rc = dSA.upload(sa.data(), n)) || (rc = dSB.upload(sb.data(), n)) || (rc = dSL.upload(sl.data(), n)) ||
+        (rc = dH.upload(h.data(), n)) || (rc = dPl.upload(planes.data(), 3 * n)) || (queue && (rc = dQ.upload(queue, count)))) return rc;
     // counter words: 0 the queue's count, 1 .. 3 the work heads of up to three launches, 4 / 5 queueB's count and head, 6 the packet kernel's first hits on an invisible light
     uint32_t cw[16] = {count};
-    HIP_TRY(hipMemcpy(dCounts.p, cw, sizeof cw, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(dStats.p, 0, 32 * 8));
-    HIP_TRY(hipMemset(dOvf.p, 0xFF, ovfWords * 4));
+    if ((rc = dCounts.upload(cw, 16))) return rc;
+    HIP_TRY(hipMemset(dStats, 0, dStats.bytes()));
+    HIP_TRY(hipMemset(dOvf, 0xFF, dOvf.bytes()));
     KzWf W{};
-    W.rayA.p = dA.as<float4>(); W.rayB.p = dB.as<float4>(); W.hit.p = dH.as<float4>(); W.shA.p = dSA.as<float4>(); W.shB.p = dSB.as<float4>(); W.shL.p = dSL.as<float4>();
-    W.outR = dPl.as<float>(); W.outG = W.outR + n; W.outB = W.outG + n; W.counts = dCounts.as<uint32_t>(); W.stats = dStats.as<unsigned long long>();
-    tune.ovf = dOvf.as<uint32_t>(); tune.ovfStride = shape.ovfStride;
+    W.rayA.p = dA; W.rayB.p = dB; W.hit.p = dH; W.shA.p = dSA; W.shB.p = dSB; W.shL.p = dSL;
+    W.outR = dPl; W.outG = W.outR + n; W.outB = W.outG + n; W.counts = dCounts; W.stats = dStats;
+    tune.ovf = dOvf; tune.ovfStride = shape.ovfStride;
     uint32_t *c = W.counts;
-    const uint32_t *q = queue ? dQ.as<uint32_t>() : nullptr, *cptr = queue ? c : nullptr;      // (a queue's count is read on the device, as a pass's are; the identity queue's travels as an argument, as the camera rays' does)
+    const uint32_t *q = queue ? dQ.get() : nullptr, *cptr = queue ? c : nullptr;      // (a queue's count is read on the device, as a pass's are; the identity queue's travels as an argument, as the camera rays' does)
     const uint32_t cimm = queue ? 0u : count;
     hipStream_t stream = nullptr;
     auto trace = [&](int mode, const uint32_t *q_, const uint32_t *cptr_, uint32_t cimm_, uint32_t *head, uint32_t *qb, uint32_t *cb) {
@@ -931,17 +924,15 @@ int kz_trace_rays_wf(KzScene *scene, const KzTraceWfOpts *opts, uint32_t nSlots,
     };
     if (opts->kernel == 0) trace(0, q, cptr, cimm, c + 1, nullptr, nullptr);
     else if (packet) hipLaunchKernelGGL(packetFn(st, P.anyInvisibleLight != 0), dim3(gridBlocks), dim3(KZ_BLOCK), 0, stream, P, ds->T, W, q, cptr, cimm, c + 1,
-                                        opts->packetBatch > 0 ? opts->packetBatch : KZ_PACKET_BATCH, dQB.as<uint32_t>(), c + 6);
+                                        opts->packetBatch > 0 ? opts->packetBatch : KZ_PACKET_BATCH, dQB.get(), c + 6);
     else if (opts->kernel == 2) trace(1, q, cptr, cimm, c + 1, nullptr, nullptr);
-    else shadowLaunches(P, trace, q, cptr, cimm, c + 1, dQB.as<uint32_t>(), c + 4, c + 5);
+    else shadowLaunches(P, trace, q, cptr, cimm, c + 1, dQB.get(), c + 4, c + 5);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h.data(), dH.p, n * 16, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(planes.data(), dPl.p, 3 * n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cw, dCounts.p, sizeof cw, hipMemcpyDeviceToHost));
     unsigned long long stats[32];
-    HIP_TRY(hipMemcpy(stats, dStats.p, sizeof stats, hipMemcpyDeviceToHost));
+    if ((rc = dH.download(h.data(), n)) || (rc = dPl.download(planes.data(), 3 * n)) || (rc = dCounts.download(cw, 16)) || (rc = dStats.download(stats, 32))) return rc;
     std::vector<uint32_t> ovf(packet ? 0 : ovfWords);
-    if (!packet) HIP_TRY(hipMemcpy(ovf.data(), dOvf.p, ovfWords * 4, hipMemcpyDeviceToHost));
+    if (!packet && (rc = dOvf.download(ovf.data(), ovfWords))) return rc;
     size_t touched = 0;                                         // overflow rows a stack reached (the guard row included)
     for (size_t w = ovf.size(); w > 0; --w) if (ovf[w - 1] != 0xFFFFFFFFu) { touched = (w - 1) / shape.ovfStride + 1; break; }
     if (touched > shape.ovfRows) return kz_fail(KZ_ERR_STATE, "a traversal stack spilled past the %zu overflow rows of the launch (LDS entries %d, the builder's bound %d)", shape.ovfRows, shape.ldsStack, P.stackBound4);

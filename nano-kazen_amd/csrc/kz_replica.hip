@@ -18,6 +18,13 @@ thread_local int g_failAlloc = 0;
 // allocation inside ONE device thread of kz_render_multi, which no caller's thread-local countdown reaches
 static std::atomic<int> g_failDevice[64];
 #endif
+// Makes the device a caller addresses by `device` current, for the entry points that take a device index and no scene.
+int kzUseDevice(int device) {
+    const int n = kzLogicalDeviceCount();
+    if (device < 0 || device >= n) return kz_fail(n ? KZ_ERR_INVALID_ARG : KZ_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, n);
+    HIP_TRY(hipSetDevice(kzPhysicalDevice(device)));
+    return KZ_OK;
+}
 hipError_t kzMalloc(void **p, size_t bytes) {
     *p = nullptr;
 #ifdef KZ_EXPERIMENTS
@@ -32,57 +39,39 @@ hipError_t kzMalloc(void **p, size_t bytes) {
     return e;
 }
 
-// A device table for `v` (a valid dummy when it is empty, so kernels never see null), owned by the replica; not yet filled unless empty.
-template <class Tp> static int allocVec(KzDeviceState *ds, const std::vector<Tp> &v, const Tp **out, size_t *bytes) {
+// A device table for `v` in its owner (a valid dummy of at least 256 bytes when it is empty, so kernels never see null); not yet filled unless empty.
+template <class Tp> static int allocVec(DevBuf<Tp> &buf, const std::vector<Tp> &v, const Tp **out) {
     *out = nullptr;
-    void *p = nullptr;
-    *bytes = v.empty() ? 256 : v.size() * sizeof(Tp);
-    KZ_ALLOC(&p, *bytes);
-    ds->allocs.push_back(p);
-    if (v.empty()) HIP_TRY(hipMemset(p, 0, *bytes));
-    *out = (const Tp *)p;
+    if (const int rc = buf.alloc(v.empty() ? (256 + sizeof(Tp) - 1) / sizeof(Tp) : v.size())) return rc;
+    if (v.empty()) HIP_TRY(hipMemset(buf, 0, buf.bytes()));
+    *out = buf;
     return KZ_OK;
 }
-template <class Tp> static int uploadVec(KzDeviceState *ds, const std::vector<Tp> &v, const Tp **out) {
-    size_t bytes;
-    if (const int rc = allocVec(ds, v, out, &bytes)) return rc;
-    if (!v.empty()) HIP_TRY(hipMemcpy(const_cast<Tp *>(*out), v.data(), bytes, hipMemcpyHostToDevice));
-    return KZ_OK;
+template <class Tp> static int uploadVec(DevBuf<Tp> &buf, const std::vector<Tp> &v, const Tp **out) {
+    if (const int rc = allocVec(buf, v, out)) return rc;
+    return v.empty() ? KZ_OK : buf.upload(v.data(), v.size());
 }
 
 // The emitter triangles of the roulette-ahead test (kz_host.cpp kzEmitterTris) on one replica: room for KZ_EM_MAX rows + the header row from the start, so
 // that an edit only copies; the count and the box travel in the kernel argument. The caller has made the replica's device current.
 int kzEmitterUpload(KzScene *scene, KzDeviceState *ds) {
-    if (!ds->T.emTris) {
-        void *p = nullptr;
-        KZ_ALLOC(&p, (KZ_EM_MAX + 1) * sizeof(KzTri));
-        ds->allocs.push_back(p);
-        HIP_TRY(hipMemset(p, 0, (KZ_EM_MAX + 1) * sizeof(KzTri)));
-        ds->T.emTris = (const KzTri *)p;
+    if (!ds->emTris) {
+        if (const int rc = ds->emTris.alloc(KZ_EM_MAX + 1)) return rc;
+        HIP_TRY(hipMemset(ds->emTris, 0, ds->emTris.bytes()));
+        ds->T.emTris = ds->emTris;
     }
     if (!scene->emTris.empty() && scene->emTris.size() <= KZ_EM_MAX + 1)
-        HIP_TRY(hipMemcpy(const_cast<KzTri *>(ds->T.emTris), scene->emTris.data(), scene->emTris.size() * sizeof(KzTri), hipMemcpyHostToDevice));
+        if (const int rc = ds->emTris.upload(scene->emTris.data(), scene->emTris.size())) return rc;
     ds->T.nEmTris = scene->nEmTris;
     for (int a = 0; a < 3; ++a) { ds->T.emLo[a] = scene->emLo[a]; ds->T.emHi[a] = scene->emHi[a]; }
     return KZ_OK;
 }
 
+// The replica goes, and with it everything its members own (kz_own.h); its pass contexts go back to the device's pool, memory and all.
 static void releaseReplica(KzDeviceState *ds) {
     (void)hipSetDevice(ds->hipDevice);
     (void)hipDeviceSynchronize();
-    for (void *p : ds->allocs) (void)hipFree(p);
-    kzAovFree(ds, KZ_AOV_ALL);
-    for (hipEvent_t e : ds->evAov) if (e) (void)hipEventDestroy(e);
-    for (void *p : {(void *)ds->film, (void *)ds->tapSums, (void *)ds->srgb, (void *)ds->pixList, (void *)ds->stats, (void *)ds->packDev, (void *)ds->rectsDev, (void *)ds->beamEntries, (void *)ds->beamCount, (void *)ds->tileDev, (void *)ds->editStage}) if (p) (void)hipFree(p);
-    if (ds->tileHost) (void)hipHostFree(ds->tileHost);
-    if (ds->evTiles) (void)hipEventDestroy(ds->evTiles);
-    if (ds->evBeam) (void)hipEventDestroy(ds->evBeam);
-    if (ds->packHost) (void)hipHostFree(ds->packHost);
-    for (PassCtx *&c : ds->ctx) if (c) { kzCtxRelease(ds->device, c); c = nullptr; }      // (the device is idle: the contexts go back to its pool, memory and all)
-    for (auto &e : ds->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (hipStream_t st : ds->passStream) if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t e : ds->evFilm) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ds->evFork, ds->evCallA, ds->evCallB, ds->evProbe[0][0], ds->evProbe[0][1], ds->evProbe[1][0], ds->evProbe[1][1], ds->evProbe[2][0], ds->evProbe[2][1], ds->evProbe[3][0], ds->evProbe[3][1]}) if (e) (void)hipEventDestroy(e);
+    for (PassCtx *&c : ds->ctx) if (c) { kzCtxRelease(ds->device, c); c = nullptr; }
     delete ds;
 }
 
@@ -129,18 +118,18 @@ static int uploadReplica(KzScene *scene, KzDeviceState *ds) {
     {
         struct Job { const void *src; void *dst; size_t bytes; hipError_t err; };
         Job jobs[4] = {};
-        auto prep = [&](auto &vec, auto **out, Job &j) -> int {
-            const int rc_ = allocVec(ds, vec, out, &j.bytes);
-            j.src = vec.empty() ? nullptr : (const void *)vec.data(); j.dst = (void *)*out;
+        auto prep = [&](auto &buf, auto &vec, auto **out, Job &j) -> int {
+            const int rc_ = allocVec(buf, vec, out);
+            j.src = vec.empty() ? nullptr : (const void *)vec.data(); j.dst = (void *)*out; j.bytes = buf.bytes();
             return rc_;
         };
         // (the BVH2 - C4: 62 MB of the 248 - serves the reference-shaped megakernel, kz_trace_rays and kz_render_samples only: it goes up on the first of those
         //  calls, kzEnsureBvh2; a one-frame job through the wavefront pipeline never pays for it)
         static const std::vector<KzNode> noNodes;
-        if ((rc = prep(noNodes, &ds->T.nodes, jobs[0]))) return rc;
-        if ((rc = prep(scene->nodes4, &ds->T.nodes4, jobs[1]))) return rc;
-        if ((rc = prep(scene->tris, &ds->T.tris, jobs[2]))) return rc;
-        if ((rc = prep(scene->shade, &ds->T.shade, jobs[3]))) return rc;
+        if ((rc = prep(ds->noNodes, noNodes, &ds->T.nodes, jobs[0]))) return rc;
+        if ((rc = prep(ds->nodes4, scene->nodes4, &ds->T.nodes4, jobs[1]))) return rc;
+        if ((rc = prep(ds->tris, scene->tris, &ds->T.tris, jobs[2]))) return rc;
+        if ((rc = prep(ds->shade, scene->shade, &ds->T.shade, jobs[3]))) return rc;
         std::vector<std::thread> th;
         const int dev = ds->hipDevice;
         for (Job &j : jobs) if (j.src && j.bytes >= ((size_t)4 << 20)) th.emplace_back([&j, dev] { j.err = hipSetDevice(dev); if (j.err == hipSuccess) j.err = hipMemcpy(j.dst, j.src, j.bytes, hipMemcpyHostToDevice); });
@@ -149,22 +138,22 @@ static int uploadReplica(KzScene *scene, KzDeviceState *ds) {
         for (Job &j : jobs) if (j.err != hipSuccess) return kz_fail(KZ_ERR_HIP, "upload of a scene table (%zu bytes) failed: %s", j.bytes, hipGetErrorString(j.err));
     }
     KZ_TRACE("upload: nodes, nodes4, tris, shade there");
-    if ((rc = uploadVec(ds, scene->meshRows, &ds->T.meshes)) || (rc = uploadVec(ds, scene->bsdfs, &ds->T.bsdfs)) || (rc = uploadVec(ds, scene->lightRows, &ds->T.lights)) ||
-        (rc = uploadVec(ds, scene->cdf, &ds->T.cdf)) || (rc = uploadVec(ds, scene->pmj, &ds->T.pmj)) || (rc = uploadVec(ds, scene->bn, &ds->T.bn)) ||
-        (rc = uploadVec(ds, scene->pixelSamples, &ds->T.pixelSamples)) || (rc = uploadVec(ds, scene->jump, &ds->T.jump))) return rc;
+    if ((rc = uploadVec(ds->meshes, scene->meshRows, &ds->T.meshes)) || (rc = uploadVec(ds->bsdfs, scene->bsdfs, &ds->T.bsdfs)) || (rc = uploadVec(ds->lights, scene->lightRows, &ds->T.lights)) ||
+        (rc = uploadVec(ds->cdf, scene->cdf, &ds->T.cdf)) || (rc = uploadVec(ds->pmj, scene->pmj, &ds->T.pmj)) || (rc = uploadVec(ds->bn, scene->bn, &ds->T.bn)) ||
+        (rc = uploadVec(ds->pixelSamples, scene->pixelSamples, &ds->T.pixelSamples)) || (rc = uploadVec(ds->jump, scene->jump, &ds->T.jump))) return rc;
     std::vector<float> ft(scene->filter, scene->filter + KZ_FILTER_RESOLUTION + 1);
-    if ((rc = uploadVec(ds, ft, &ds->T.filter))) return rc;
-    if ((rc = uploadVec(ds, scene->ilTris, &ds->T.ilTris))) return rc;
+    if ((rc = uploadVec(ds->filter, ft, &ds->T.filter))) return rc;
+    if ((rc = uploadVec(ds->ilTris, scene->ilTris, &ds->T.ilTris))) return rc;
     if ((rc = kzEmitterUpload(scene, ds))) return rc;
-    if ((rc = uploadVec(ds, scene->texProgs, &ds->T.texProgs)) || (rc = uploadVec(ds, scene->texOps, &ds->T.texOps)) ||
-        (rc = uploadVec(ds, scene->images, &ds->T.images)) || (rc = uploadVec(ds, scene->texels, &ds->T.texels))) return rc;
+    if ((rc = uploadVec(ds->texProgs, scene->texProgs, &ds->T.texProgs)) || (rc = uploadVec(ds->texOps, scene->texOps, &ds->T.texOps)) ||
+        (rc = uploadVec(ds->images, scene->images, &ds->T.images)) || (rc = uploadVec(ds->texels, scene->texels, &ds->T.texels))) return rc;
     ds->T.texPow2 = scene->texPow2;
     const KzParams &P = scene->prm;
     ds->filmPixels = (size_t)(P.width + 2 * P.border) * (size_t)(P.height + 2 * P.border);
     KZ_TRACE("upload: small tables there");
-    KZ_ALLOC(&ds->film, ds->filmPixels * sizeof(float4));
+    if ((rc = ds->film.alloc(ds->filmPixels))) return rc;
     HIP_TRY(hipMemset(ds->film, 0, ds->filmPixels * sizeof(float4)));
-    KZ_ALLOC(&ds->stats, 32 * sizeof(unsigned long long));             // 8 counters of KzStats + 16 lane statistics of the -DKZ_LANESTAT development build + 3 beam-list counters
+    if ((rc = ds->stats.alloc(32))) return rc;                         // 8 counters of KzStats + 16 lane statistics of the -DKZ_LANESTAT development build + 3 beam-list counters
     HIP_TRY(hipMemset(ds->stats, 0, 32 * sizeof(unsigned long long)));
     { hipDeviceProp_t prop; HIP_TRY(hipGetDeviceProperties(&prop, ds->hipDevice)); ds->numCU = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256; ds->totalMem = prop.totalGlobalMem; }
     KZ_TRACE("upload: film + counters there");
@@ -177,12 +166,10 @@ static int uploadReplica(KzScene *scene, KzDeviceState *ds) {
 int kzEnsureBvh2(KzScene *scene, KzDeviceState *ds) {
     if (ds->bvh2Resident || scene->nodes.empty()) return KZ_OK;
     kzHostSync(scene);                                  // (the host BVH2 follows the last edit before it goes up)
-    void *p = nullptr;
-    const size_t bytes = scene->nodes.size() * sizeof(KzNode);
-    KZ_ALLOC(&p, bytes);
-    ds->allocs.push_back(p);
-    HIP_TRY(hipMemcpy(p, scene->nodes.data(), bytes, hipMemcpyHostToDevice));      // (blocking, behind everything queued on the device: a rare call)
-    ds->T.nodes = (const KzNode *)p;
+    int rc;
+    if ((rc = ds->bvh2.alloc(scene->nodes.size()))) return rc;
+    if ((rc = ds->bvh2.upload(scene->nodes.data(), scene->nodes.size()))) return rc;      // (blocking, behind everything queued on the device: a rare call)
+    ds->T.nodes = ds->bvh2;
     ds->bvh2Resident = true;
     return KZ_OK;
 }
@@ -249,29 +236,25 @@ int prepareTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32_
         }
     }
     const size_t framePix = (size_t)P.width * P.height;
-    if (ds->pixCap < framePix || ds->tileDevCap < nTiles) {          // first use (or a longer tile list than ever before): allocate
+    if (ds->pixList.cap() < framePix || ds->tileDev.cap() < nTiles) {          // first use (or a longer tile list than ever before): allocate
         HIP_TRY(hipDeviceSynchronize());
         int rc;
-        if (ds->pixCap < framePix && (rc = kzRegrow(ds->pixList, ds->pixCap, framePix))) return rc;
-        if (ds->tileDevCap < nTiles && (rc = kzRegrow(ds->tileDev, ds->tileDevCap, std::max<size_t>(nTiles, 4096)))) return rc;
+        if (ds->pixList.cap() < framePix && (rc = ds->pixList.regrow(framePix))) return rc;
+        if (ds->tileDev.cap() < nTiles && (rc = ds->tileDev.regrow(std::max<size_t>(nTiles, 4096)))) return rc;
     }
     ds->tilesValid = false;
     if (ds->evCallB) HIP_TRY(hipStreamWaitEvent(stream, ds->evCallB, 0));        // behind everything the previous call (on whatever stream) queued
     // the descriptors travel through a pinned buffer of the replica (the copy of the previous tile set has left it: evTiles)
-    if (ds->tileHostCap < nTiles) {
+    if (ds->tileHost.cap() < nTiles) {
         if (ds->evTiles) HIP_TRY(hipEventSynchronize(ds->evTiles));
-        if (ds->tileHost) (void)hipHostFree(ds->tileHost);
-        ds->tileHost = nullptr; ds->tileHostCap = 0;
-        const size_t cap = std::max<size_t>(nTiles, 4096);
-        HIP_TRY(hipHostMalloc((void **)&ds->tileHost, cap * sizeof(KzTileDesc), hipHostMallocDefault));
-        ds->tileHostCap = cap;
+        if (const int rc = ds->tileHost.regrow(std::max<size_t>(nTiles, 4096))) return rc;
     }
-    if (!ds->evTiles) HIP_TRY(hipEventCreateWithFlags(&ds->evTiles, hipEventDisableTiming));
+    if (!ds->evTiles) { if (const int rc = ds->evTiles.ensure(hipEventDisableTiming)) return rc; }
     else HIP_TRY(hipEventSynchronize(ds->evTiles));
     std::memcpy(ds->tileHost, desc.data(), nTiles * sizeof(KzTileDesc));
     HIP_TRY(hipMemcpyAsync(ds->tileDev, ds->tileHost, nTiles * sizeof(KzTileDesc), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(ds->evTiles, stream));
-    hipLaunchKernelGGL(kz_tiles_expand, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const KzTileDesc *)ds->tileDev, nTiles, (uint32_t)total, P.width, ds->pixList);
+    hipLaunchKernelGGL(kz_tiles_expand, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const KzTileDesc *)ds->tileDev.get(), nTiles, (uint32_t)total, P.width, ds->pixList);
     HIP_TRY(hipGetLastError());
     ds->nPix = (uint32_t)total;
     ds->curTiles.assign(tiles, tiles + nTiles);
@@ -290,9 +273,7 @@ void kz_debug_fail_device(int device, int nth) { g_failDevice[device & 63].store
 int kz_device_count(void) { return kzLogicalDeviceCount(); }
 
 int kz_device_mem_info(int device, uint64_t *freeBytes, uint64_t *totalBytes) {
-    int n = kz_device_count();
-    if (device < 0 || device >= n) return kz_fail(n ? KZ_ERR_INVALID_ARG : KZ_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, n);
-    HIP_TRY(hipSetDevice(kzPhysicalDevice(device)));
+    if (const int rc = kzUseDevice(device)) return rc;
     size_t f = 0, t = 0;
     HIP_TRY(hipMemGetInfo(&f, &t));
     if (freeBytes) *freeBytes = f;

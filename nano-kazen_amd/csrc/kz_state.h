@@ -6,14 +6,17 @@
 //   kz_film.hip     film reconstruction kernels + their launcher, tile packing / download, kz_film_* entry points
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
+// Every device buffer, pinned buffer, event and stream named below is a member of one of the four move-only owners of kz_own.h (DevBuf, PinnedBuf, Event, Stream).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kz_internal.h"
+#include "kz_own.h"
 #include "kz_plan.h"
 
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -67,29 +70,6 @@ struct KzTune { int refill, postpone, batch, travBlocksPerCU, shadeBlocksPerCU, 
 struct KzTileRect { int32_t x0, y0, w, h; uint32_t offset; };
 struct KzTileDesc { int32_t x0, y0, w, h; uint32_t pixOffset; };      // a tile of the current set and the position of its first pixel in the pixel list
 
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return kz_fail(KZ_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-
-// Every device allocation of the library goes through here (kz_debug_fail_alloc can make the nth one fail).
-hipError_t kzMalloc(void **p, size_t bytes);          // kz_replica.hip
-#define KZ_ALLOC(pp, bytes) do { hipError_t e_ = kzMalloc((void **)(pp), (bytes)); if (e_ != hipSuccess) \
-    return kz_fail(e_ == hipErrorOutOfMemory ? KZ_ERR_OOM : KZ_ERR_HIP, "device allocation of %zu bytes failed: %s", (size_t)(bytes), hipGetErrorString(e_)); } while (0)
-// A device buffer made again for `cap` elements (nothing is kept: the caller has synchronised whatever still reads it).
-template <class Tp> static inline int kzRegrow(Tp *&p, size_t &have, size_t cap) {
-    if (p) (void)hipFree(p);
-    p = nullptr; have = 0;
-    KZ_ALLOC(&p, cap * sizeof(Tp));
-    have = cap;
-    return KZ_OK;
-}
-// A device buffer that is released on every way out of the call that made it.
-struct DevMem {
-    void *p = nullptr;
-    DevMem() = default;
-    DevMem(const DevMem &) = delete; DevMem &operator=(const DevMem &) = delete;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    template <class Tp> Tp *as() const { return (Tp *)p; }
-};
-
 // kz_debug_trace (kazen_mi355x_dev.h, development builds): a timeline of the allocation / growth / pass-planning events of the calling process on stderr
 #ifdef KZ_EXPERIMENTS
 extern std::atomic<int> g_kzTrace;
@@ -103,8 +83,9 @@ extern std::atomic<int> g_kzRrAhead;          // kz_debug_rr_ahead (kz_debug.hip
 static inline int kzPhysicalDevice(int logical) { return logical; }
 #endif
 int kzLogicalDeviceCount();                   // kz_arena.cpp: devices the library presents (= hipGetDeviceCount unless a development build aliases them)
+int kzUseDevice(int device);                  // kz_replica.hip: range check + hipSetDevice of the device behind a caller's index
 
-struct EventPair { hipEvent_t a, b; };
+struct EventPair { Event a, b; };
 // The path-state memory of one pass context (kz_arena.cpp). Up to 2^23 items: hipMalloc arrays of the size asked for. Beyond: one reserved virtual range
 // per array, physical memory mapped into them in levels of 2^23 items on a side thread; `mapped` items of EVERY array are usable at any moment, and only
 // ever more (until shrinkTo / releaseAll, which the owner calls on an idle device).
@@ -151,46 +132,33 @@ private:
 };
 // path state + sample records + stage events of one pass in flight
 struct PassCtx {
-    KzArena *arena = nullptr;                                    // the path-state arrays and the five sample planes (jx | jy | r | g | b)
+    std::unique_ptr<KzArena> arena;                              // the path-state arrays and the five sample planes (jx | jy | r | g | b)
     KzWf wf{};                                                   // (pointers into the arena, set by ctxEnsure)
     float *plane[5] = {};                                        // the five sample planes jx | jy | r | g | b (each its own range of the arena)
-    uint32_t *counts = nullptr;                                  // queue counters of a pass (KzCounts)
-    uint32_t *ovf = nullptr; size_t ovfCap = 0;
-    hipStream_t side = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr;      // small passes: the shadow rays of a bounce beside its closest-hit rays (wfPass)
+    DevBuf<uint32_t> counts;                                     // queue counters of a pass (KzCounts)
+    DevBuf<uint32_t> ovf;                                        // the global overflow area of the traversal stacks (ensureOverflow)
+    Stream side; Event evFork, evJoin;                           // small passes: the shadow rays of a bounce beside its closest-hit rays (wfPass)
     // A pass run as two HALVES of its pixels side by side (renderOn: KzRenderOpts::passHalves): two views of this context's arrays - the first and the second part
     // of every array - each with its own counters, overflow stacks, side stream and stage clock, the second on a stream of its own. A view owns no arena.
-    PassCtx *view[2] = {nullptr, nullptr}; hipStream_t halfStream = nullptr; hipEvent_t evHalfFork = nullptr, evHalfJoin = nullptr;
+    std::unique_ptr<PassCtx> view[2]; Stream halfStream; Event evHalfFork, evHalfJoin;
     size_t wanted = 0;                                           // items the last call with the default schedule asked this context to hold (kz_render.hip: `earned`)
     uint64_t beamSeen = 0;                                       // the last beam-list build (KzDeviceState::beamSeq) this context's stream has waited for
-    std::vector<hipEvent_t> stageEv; std::vector<int> stageKind; size_t stageUsed = 0;
+    std::vector<Event> stageEv; std::vector<int> stageKind; size_t stageUsed = 0;
     size_t items() const { return arena ? arena->mapped.load() : 0; }
-    size_t bytes() const { return (arena ? arena->bytes() : 0) + ovfCap * sizeof(uint32_t) + (view[0] ? view[0]->bytes() : 0) + (view[1] ? view[1]->bytes() : 0); }
+    size_t bytes() const { return (arena ? arena->bytes() : 0) + ovf.bytes() + (view[0] ? view[0]->bytes() : 0) + (view[1] ? view[1]->bytes() : 0); }
     // gives the memory back (the context stays usable: it grows again on demand); the caller has synchronised the device
     void release() {
         if (arena) arena->shrinkTo(0);
         wf = KzWf{}; for (float *&q : plane) q = nullptr; wanted = 0;
-        if (ovf) (void)hipFree(ovf); ovf = nullptr; ovfCap = 0;
-        for (PassCtx *v : view) if (v) v->release();
+        ovf.free();
+        for (auto &v : view) if (v) v->release();
     }
     // buffers sized for another frame (a pooled context): given back when a call is short of memory (the caller has synchronised the device)
     void trimAux() {
-        if (ovf) { (void)hipFree(ovf); ovf = nullptr; ovfCap = 0; }
-        for (PassCtx *v : view) if (v) v->trimAux();
+        ovf.free();
+        for (auto &v : view) if (v) v->trimAux();
     }
-    void destroy() {
-        release();
-        for (PassCtx *&v : view) if (v) { v->destroy(); delete v; v = nullptr; }
-        if (halfStream) { (void)hipStreamDestroy(halfStream); halfStream = nullptr; }
-        if (evHalfFork) { (void)hipEventDestroy(evHalfFork); evHalfFork = nullptr; }
-        if (evHalfJoin) { (void)hipEventDestroy(evHalfJoin); evHalfJoin = nullptr; }
-        if (counts) (void)hipFree(counts); counts = nullptr;
-        delete arena; arena = nullptr;
-        for (auto &e : stageEv) (void)hipEventDestroy(e);
-        stageEv.clear(); stageKind.clear();
-        if (side) { (void)hipStreamDestroy(side); side = nullptr; }
-        if (evFork) { (void)hipEventDestroy(evFork); evFork = nullptr; }
-        if (evJoin) { (void)hipEventDestroy(evJoin); evJoin = nullptr; }
-    }
+    // (a context that goes - kzCtxPoolTrim, on an idle device - takes its views, buffers, streams, events and arena with it: the members' destructors)
 };
 // Pass contexts live in a per-device pool between replicas (kz_arena.cpp): a replica takes them on first use and hands them back when it goes.
 PassCtx *kzCtxAcquire(int device);
@@ -202,50 +170,58 @@ size_t kzCtxPoolTrimPhysical(int hipDevice);      // every idle pooled context t
 struct KzDeviceState {
     int device = -1;                                             // the index the caller addresses this replica by
     int hipDevice = -1;                                          // the HIP device it lives on (the same number, unless a development build aliases devices: kz_debug_alias_devices)
-    KzDevTables T{};
-    std::vector<void *> allocs;
-    bool bvh2Resident = false;                                   // T.nodes holds the BVH2 (uploaded on first use: kzEnsureBvh2)
-    float4 *film = nullptr; size_t filmPixels = 0;
-    float4 *tapSums = nullptr; size_t tapSumsBytes = 0;          // the running tap sums of every pixel of the frame, [tap][y * width + x] (kz_film.hip): what the film is resolved from
+    KzDevTables T{};                                             // what the kernels take by value: filled from the tables' owners below
+    DevBuf<KzNode> noNodes, bvh2;                                // T.nodes: a placeholder until the BVH2 goes up on first use (kzEnsureBvh2; bvh2Resident)
+    DevBuf<KzNode4> nodes4; DevBuf<KzTri> tris, ilTris, emTris; DevBuf<KzTriShade> shade; DevBuf<KzMeshRow> meshes; DevBuf<KzBSDF> bsdfs; DevBuf<KzLightRow> lights;
+    DevBuf<float> cdf, pmj, bn, pixelSamples, filter; DevBuf<KzPcgJump> jump;
+    DevBuf<KzTexProg> texProgs; DevBuf<KzTexOp> texOps; DevBuf<KzImageRow> images; DevBuf<uint8_t> texels;
+    bool bvh2Resident = false;
+    DevBuf<float4> film; size_t filmPixels = 0;
+    DevBuf<float4> tapSums;                                      // the running tap sums of every pixel of the frame, [tap][y * width + x] (kz_film.hip): what the film is resolved from
     // Feature films (kazen_mi355x_aov.h; kz_film.hip): per AOV - albedo, normal, depth - running tap sums and a film like the picture's, there from the first render
     // with the AOV enabled; evAov[i]: the AOV tap launches of the pass last run in context i (the chain passes in flight order their AOV stages by, wfPass)
-    float4 *aovTapSums[3] = {}, *aovFilm[3] = {}; hipEvent_t evAov[KZ_MAX_PASSES_IN_FLIGHT] = {};
-    size_t aovBytes() const { size_t b = 0; for (int f = 0; f < 3; ++f) b += (aovTapSums[f] ? tapSumsBytes : 0) + (aovFilm[f] ? filmPixels * sizeof(float4) : 0); return b; }
-    uint8_t *srgb = nullptr;                                     // staging raster of kz_film_to_srgb8 (allocated on first use)
-    float4 *packDev = nullptr; size_t packCap = 0; KzTileRect *rectsDev = nullptr; size_t rectsCap = 0;      // kz_film_download_tiles: packed tile rects + their table
-    float4 *packHost = nullptr; size_t packHostCap = 0;           // pinned staging of the same (D2H at link rate)
+    DevBuf<float4> aovTapSums[3], aovFilm[3]; Event evAov[KZ_MAX_PASSES_IN_FLIGHT];
+    size_t aovBytes() const { size_t b = 0; for (int f = 0; f < 3; ++f) b += aovTapSums[f].bytes() + aovFilm[f].bytes(); return b; }
+    DevBuf<uint8_t> srgb;                                        // staging raster of kz_film_to_srgb8 (allocated on first use)
+    DevBuf<float4> packDev; DevBuf<KzTileRect> rectsDev;         // kz_film_download_tiles: packed tile rects + their table
+    PinnedBuf<float4> packHost;                                  // pinned staging of the same (D2H at link rate)
     // The tile set: pixList = its pixels (tile after tile, 8x8 blocks row-major inside a tile, row-major inside a block), written on the device from the
     // tile descriptors (kz_tiles_expand).
-    uint32_t *pixList = nullptr; size_t pixCap = 0; uint32_t nPix = 0;
-    KzTileDesc *tileDev = nullptr; size_t tileDevCap = 0; KzTileDesc *tileHost = nullptr; size_t tileHostCap = 0; hipEvent_t evTiles = nullptr;
+    DevBuf<uint32_t> pixList; uint32_t nPix = 0;
+    DevBuf<KzTileDesc> tileDev; PinnedBuf<KzTileDesc> tileHost; Event evTiles;
     std::vector<KzTile> curTiles; std::vector<uint32_t> tilePixOffset;      // tilePixOffset[t]: first list position of tile t (+ the total at the end)
     bool tilesValid = false; uint64_t tileGen = 0;                          // tileGen: bumped whenever the pixel list changes
-    unsigned long long *stats = nullptr; bool statsOn = false;
+    DevBuf<unsigned long long> stats; bool statsOn = false;
     hipStream_t lastStream = nullptr;
     int numCU = 256; size_t totalMem = 0;
     PassCtx *ctx[KZ_MAX_PASSES_IN_FLIGHT] = {};                  // taken from the device's pool on first use (ctxAt), handed back by releaseReplica
     PassCtx &ctxAt(int i) { if (!ctx[i]) ctx[i] = kzCtxAcquire(device); return *ctx[i]; }
     std::vector<EventPair> events; size_t eventsUsed = 0;
-    hipStream_t passStream[KZ_MAX_PASSES_IN_FLIGHT] = {}; hipEvent_t evFork = nullptr, evFilm[KZ_MAX_PASSES_IN_FLIGHT] = {}, evCallA = nullptr, evCallB = nullptr;
+    Stream passStream[KZ_MAX_PASSES_IN_FLIGHT]; Event evFork, evFilm[KZ_MAX_PASSES_IN_FLIGHT], evCallA, evCallB;
     // LARGE passes with KzRenderOpts::shadowBeside = passHalves = 0: the replica times four passes of one size (evProbe: their first and last event), then keeps
     // the fastest way for its scene (kz_plan.h KzPassMode: the policy and what it has measured).
-    hipEvent_t evProbe[4][2] = {}; KzPassMode passMode;
+    Event evProbe[4][2]; KzPassMode passMode;
     int lastCtx = 0; bool lastDual = false; int streamMode = 0;
     PassCtx *lastStageCtx = nullptr;                             // whose stage clock kz_last_stage_ms reads (a view, when the last pass ran as halves)
     // Beam lists (kz_wf_beam), one per pixel of the FRAME, built at most once per pixel and replica - the camera belongs to the scene - whatever tile
     // sets and pixel chunks the pixel is rendered in. They are built on the call's stream (evBeam / beamSeq: the passes wait for the latest build);
     // beamDone remembers the ranges of the CURRENT pixel list that have been handed to the kernel (it skips pixels that already have a list).
-    uint2 *beamEntries = nullptr, *beamCount = nullptr; size_t beamCap = 0; hipEvent_t evBeam = nullptr; uint64_t beamSeq = 0;
+    DevBuf<uint2> beamEntries, beamCount; Event evBeam; uint64_t beamSeq = 0;
     std::vector<std::pair<uint32_t, uint32_t>> beamDone; uint64_t beamDoneGen = 0;
-    size_t beamBytes() const { return beamCap * (KZ_BEAM_CAP + 1) * sizeof(uint2); }
+    size_t beamBytes() const { return beamCount.cap() * (KZ_BEAM_CAP + 1) * sizeof(uint2); }
     size_t ctxBytes() const { size_t b = 0; for (const PassCtx *c : ctx) if (c) b += c->bytes(); return b; }
     KzPassInfo lastInfo{}; std::string growNote;
     // Edits (kz_refit.hip): the triangles' vertex indices and the BVH4 slot map, uploaded on the replica's first kz_scene_set_vertices (with the BVH2, which the
-    // refit keeps resident), a staging area for the vertex data of a batch, and the refit's absolute box padding. editBytes: what they hold.
-    uint32_t *editTriVtx = nullptr, *editSlotSrc = nullptr; float *editPad = nullptr; float *editStage = nullptr; size_t editStageCap = 0; size_t editBytes = 0;
+    // refit keeps resident), a staging area for the vertex data of a batch, and the refit's absolute box padding. editBytes(): what they hold.
+    DevBuf<uint32_t> editTriVtx, editSlotSrc; DevBuf<float> editPad, editStage;
     // kz_scene_set_transforms: per mesh its base V (then N) on this replica, there from the replica's first transform of the mesh (kz_scene_set_vertices keeps it current);
     // the flag kz_edit_xform raises for a non-finite position. kz_scene_set_lights: T.ilTris re-allocated once to hold the 64 rows a visibility toggle may need.
-    std::vector<float *> editBase; uint32_t *editFlag = nullptr; bool ilTrisRoomy = false;
+    std::vector<DevBuf<float>> editBase; DevBuf<uint32_t> editFlag; bool ilTrisRoomy = false;
+    size_t editBytes() const {
+        size_t b = editTriVtx.bytes() + editSlotSrc.bytes() + editPad.bytes() + editStage.bytes() + editFlag.bytes() + (ilTrisRoomy ? ilTris.bytes() : 0);
+        for (const DevBuf<float> &e : editBase) b += e.bytes();
+        return b;
+    }
 };
 struct KzReplicaSet { std::mutex m; std::vector<KzDeviceState *> v; };
 

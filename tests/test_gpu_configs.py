@@ -588,6 +588,61 @@ def test_pass_contexts_outlive_their_replica(gpu_lib, kz):
     assert _free_gb(gpu_lib) > free0 - 0.5
 
 
+def _lifecycle(gpu_lib, kz):
+    """One life of a scene through everything that makes a replica or a pass context hold a device resource; returns the films of its three renders of the untouched scene."""
+    desc = kz.scenes.cornell_box(64, 64, 4)
+    sc = kz.Scene(desc, device=0)
+    films = []
+    for kw in ({"passes_in_flight": 2}, {"shadow_beside": 2}, {"pass_halves": 2}):      # pass streams, the side stream of a context, its two views
+        sc.render(**kw)
+        films.append(sc.film())
+    tiles = [(0, 0, 32, 64), (32, 0, 32, 64)]
+    sc.render(tiles=tiles)                                                           # tile descriptors, their pinned staging; then the packed rects and theirs
+    assert sc.film_tiles(tiles).size == sc.packed_floats(tiles)
+    assert sc.srgb8().shape == (64, 64, 3)
+    sc.set_aovs(("albedo", "normal", "depth"))
+    sc.render()
+    assert sc.aov_info() > 0 and np.isfinite(sc.aov_film("depth")).all()
+    sc.set_aovs(())
+    assert sc.aov_info() == 0
+    m = desc.meshes[5]
+    sc.set_vertices({5: m["V"] if m["N"] is None else (m["V"], m["N"])})             # the edit tables, the BVH2, the staging area
+    sc.set_transforms({5: np.eye(4, dtype=np.float32)})                              # the mesh's base data, the flag words
+    light = dict(desc.meshes[7]["light"])
+    for vis in (not light["lightPrimaryVisibility"], light["lightPrimaryVisibility"]):      # the roomy invisible-light table replaces the upload's
+        sc.set_lights({7: dict(light, lightPrimaryVisibility=vis)})
+    o = np.zeros((64, 3), np.float32)
+    d = np.tile(np.array([[0, 0, -1]], np.float32), (64, 1))
+    sc.trace_rays(o, d, 1e-3, np.inf)
+    sc.close()
+    assert gpu_lib.kz_device_trim(0) == 0
+    return films
+
+
+def test_a_scene_life_cycle_returns_every_byte_of_device_memory(gpu_lib, kz):
+    """Create, render every way a pass runs, tiles, sRGB, feature films, every edit, trace, close, trim - and again: after a first cycle (the HIP runtime's own pools
+    settle) free device memory after cycle 3 equals free device memory after cycle 2, and every cycle renders the first one's film. (The parent of the commit that
+    gave every buffer, stream and event one owner was measured the same way: 0 bytes per cycle, profiles/r14a_owners/README.md - so equality, with no allowance.)"""
+    def free_now():
+        f, t = C.c_uint64(), C.c_uint64()
+        assert gpu_lib.kz_device_mem_info(0, C.byref(f), C.byref(t)) == 0
+        return f.value
+
+    gpu_lib.kz_device_trim(0)
+    first = _lifecycle(gpu_lib, kz)
+    assert np.array_equal(first[1], first[0]) and np.array_equal(first[2], first[0])
+    free = []
+    for cycle in (2, 3):
+        films = _lifecycle(gpu_lib, kz)
+        assert all(np.array_equal(f, first[0]) for f in films), cycle
+        free.append(free_now())
+    t0 = time.perf_counter()                                                         # (released memory counts as free once the driver has wiped it)
+    while free_now() != free[0] and time.perf_counter() - t0 < 5.0:
+        time.sleep(0.05)
+    print("free device memory after cycle 2: %d, after cycle 3: %d (at once), %d (polled): %+d bytes per cycle" % (free[0], free[1], free_now(), free[0] - free_now()))
+    assert free_now() == free[0], (free, free_now())
+
+
 @pytest.mark.parametrize("radius,taps", [(0.25, 1), (1.5, 4), (2.5, 6), (3.5, 8), (4.0, 9)])
 def test_every_filter_width_runs_on_the_tap_sums(gpu_lib, kz, O, radius, taps):
     """Round 6: every reconstruction filter of 1 .. 9 taps per axis (radius up to 4) runs on the running per-pixel tap sums - `kz_film_taps<TAPS, GROUPS>` with two lane

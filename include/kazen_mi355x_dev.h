@@ -143,7 +143,7 @@ int kz_pass_mode_info(KzScene *scene, int device, KzPassModeInfo *out);
 int kz_last_grow_note(KzScene *scene, char *buf, size_t cap);
 
 /* ---- DEVELOPMENT BUILDS ONLY (a library compiled with -DKZ_EXPERIMENTS: kz_build_flags() & KZ_BUILD_EXPERIMENTS; nano-kazen_amd/csrc/variants/experiments).
- * These six are process-global state - the product library does not contain them (`nm -D libkazen_mi355x.so | grep kz_debug` is empty), so that nothing behind the
+ * These seven are process-global state - the product library does not contain them (`nm -D libkazen_mi355x.so | grep kz_debug` is empty), so that nothing behind the
  * product ABI depends on state outside the objects the caller holds. The tests that need them load the development variant.
  *   kz_debug_fail_alloc    the nth device allocation made from now on by the calling thread fails with KZ_ERR_OOM (0 = off): a failure in the middle of a call
  *                          releases what the call had allocated.
@@ -167,6 +167,10 @@ void kz_debug_alias_devices(int n);
  *                          take it too, so that the ray counter shows what it skips. The films are the same bits in every mode: one process renders them
  *                          all (tests/test_rr_ahead_gpu.py). */
 void kz_debug_rr_ahead(int on);
+/*   kz_debug_shadow_order  0 = the any-hit shadow launches (kz_wf_trace<4>) started from now on descend into the child with the nearest entry, as the closest-hit
+ *                          kernels do and as they did before; 1 = into the child whose box holds the longest part of the segment (the default). Which occluder
+ *                          an any-hit ray finds first does not change its answer: the films are the same bits either way (tests/test_shadow_order_gpu.py). */
+void kz_debug_shadow_order(int on);
 
 /* ---- the pass planner (nano-kazen_amd/csrc/kz_plan.cpp: pure host arithmetic, no GPU, no state) through the ABI: what kz_render would decide for a call.
  * tests/test_plan_cpu.py tabulates it for the BASELINE configs - the table is the documentation of the pass policy. */

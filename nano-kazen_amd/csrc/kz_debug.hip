@@ -299,4 +299,7 @@ int kz_light_query(KzScene *scene, uint32_t n, const int32_t *light, const float
 // kz_debug_rr_ahead: whether the shade kernels of the path_mis wavefront pipeline take the roulette-ahead test (kz_render.hip wfPass reads it per pass)
 std::atomic<int> g_kzRrAhead{1};
 extern "C" void kz_debug_rr_ahead(int on) { g_kzRrAhead.store(on == 2 ? 2 : on ? 1 : 0); }
+// kz_debug_shadow_order: whether the any-hit shadow launches descend first into the child that holds most of the segment (kz_render.hip launchTrace reads it per launch)
+std::atomic<int> g_kzShadowOrder{1};
+extern "C" void kz_debug_shadow_order(int on) { g_kzShadowOrder.store(on ? 1 : 0); }
 #endif

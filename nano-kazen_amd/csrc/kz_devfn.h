@@ -317,6 +317,10 @@ __device__ __forceinline__ uint32_t kzLdsGet(uint32_t a) { return *(const KzLds3
 struct Node4Test { uint32_t k0, k1, k2, k3; uint4 refs; };
 typedef float kz_f2 __attribute__((ext_vector_type(2)));
 // keys in slot order: (bits of max(tnear, tmin) with the two low bits replaced by the child slot), 0xFFFFFFFF for a miss
+// OVERLAP (any-hit rays, whose answer does not depend on the visiting order): the key of a hit child carries the length f - n of the part of the segment
+// [tmin, tmax] inside its box instead - not negative, so its bits order as an unsigned integer and the child to take is the MAXIMUM - with the three low bits
+// replaced by 4 + slot: a hit child's key is never 0, which is the key of a miss (a box the segment only touches, f == n, is still a hit).
+template <bool OVERLAP = false>
 __device__ __forceinline__ void node4KeysOf(const uint4 q0, const uint4 q1, const uint4 q2, V3 o, float rx, float ry, float rz, float tmin, float tmax,
                                             uint32_t (&key)[4]) {
     const float ax = __uint_as_float(q0.w) * rx, ay = __uint_as_float(q2.z) * ry, az = __uint_as_float(q2.w) * rz;      // the packet carries 2^e per axis as floats
@@ -337,7 +341,8 @@ __device__ __forceinline__ void node4KeysOf(const uint4 q0, const uint4 q1, cons
         const kz_f2 tx = __builtin_elementwise_fma(qx, AX, BX), ty = __builtin_elementwise_fma(qy, AY, BY), tz = __builtin_elementwise_fma(qz, AZ, BZ);
         const float n = fmaxf(fmaxf(fmaxf(tx.x, ty.x), tz.x), tmin);
         const float f = fminf(fminf(fminf(tx.y, ty.y), tz.y) * 1.0000004f, tmax);
-        key[i] = (n <= f) ? ((__float_as_uint(n) & ~3u) | (uint32_t)i) : 0xFFFFFFFFu;
+        if (OVERLAP) key[i] = (n <= f) ? ((__float_as_uint(f - n) & ~7u) | (4u + (uint32_t)i)) : 0u;
+        else key[i] = (n <= f) ? ((__float_as_uint(n) & ~3u) | (uint32_t)i) : 0xFFFFFFFFu;
     }
 }
 // The packet of node `node`: table base (scalar) + a 32-BIT byte offset, so the fetches take the base from SGPRs and the offset from one
@@ -345,12 +350,13 @@ __device__ __forceinline__ void node4KeysOf(const uint4 q0, const uint4 q1, cons
 __device__ __forceinline__ const uint4 *kzNode4Ptr(const KzDevTables &T, uint32_t node) {
     return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(T.nodes4) + (uint32_t)(node << 6));
 }
+template <bool OVERLAP = false>
 __device__ __forceinline__ void node4Keys(const KzDevTables &T, uint32_t node, V3 o, float rx, float ry, float rz, float tmin, float tmax,
                                           uint32_t (&key)[4], uint4 &refs) {
     const uint4 *np = kzNode4Ptr(T, node);
     const uint4 q0 = np[0], q1 = np[1], q2 = np[2];
     refs = np[3];
-    node4KeysOf(q0, q1, q2, o, rx, ry, rz, tmin, tmax, key);
+    node4KeysOf<OVERLAP>(q0, q1, q2, o, rx, ry, rz, tmin, tmax, key);
 }
 __device__ __forceinline__ Node4Test node4Test(const KzDevTables &T, uint32_t node, V3 o, float rx, float ry, float rz, float tmin, float tmax) {
     Node4Test r; uint32_t key[4];

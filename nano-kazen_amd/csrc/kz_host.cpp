@@ -207,10 +207,16 @@ void kzInvisibleLights(KzScene *sc) {
     if (sc->ilTris.size() > 64) { p.shadowFast = 0; sc->ilTris.clear(); }      // big emissive meshes: literal closest-hit loop
     p.nIlTris = (uint32_t)sc->ilTris.size();
     p.ilGidLo = ilGidLo <= ilGidHi ? ilGidLo : 1u; p.ilGidSpan = ilGidLo <= ilGidHi ? ilGidHi - ilGidLo : 0u;
-    for (int a = 0; a < 3; ++a) {        // same padding as BVH boxes
-        float m = std::max(std::fabs(p.ilLo[a]), std::fabs(p.ilHi[a]));
-        if (std::isfinite(m)) { float e = m * 4e-7f + 1e-30f; p.ilLo[a] -= e; p.ilHi[a] += e; }
-    }
+    // Padding. The box only gates the brute-force triangle tests (invisibleLightOnSegment, kz_devfn.h), so a wider box changes no answer, but it must not be
+    // NARROWER than the triangle test: a segment that ends (or starts) exactly on a light has its Moeller-Trumbore t a few ulps to either side of the distance
+    // to the light's plane, and with the BVH boxes' padding (4e-7 of the coordinate: an ulp or two of t) the gate closed in front of such a hit - the any-hit
+    // kernel then kept the ray and was blocked by the invisible light itself (tests/test_shadow_order_gpu.py: segments with tmin == tmax at a hit on a light
+    // that hangs flat at y = 0.2). Ten times that, of the box's largest coordinate or extent, on every axis. Not more: every shadow ray that ends inside the
+    // padded box runs the triangle loop, and the rays towards a light end 1e-3 in front of it (1e-4 cost C4 2 % of its shadow kernel's instructions).
+    float m = 0.f;
+    for (int a = 0; a < 3; ++a) m = std::max(m, std::max(std::max(std::fabs(p.ilLo[a]), std::fabs(p.ilHi[a])), p.ilHi[a] - p.ilLo[a]));
+    for (int a = 0; a < 3; ++a)
+        if (std::isfinite(m)) { float e = m * 4e-6f + 1e-30f; p.ilLo[a] -= e; p.ilHi[a] += e; }
     kzEmitterTris(sc);
 }
 

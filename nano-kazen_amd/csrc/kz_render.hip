@@ -111,6 +111,10 @@ static int ctxEnsure(PassCtx &c, size_t want, size_t minItems, double graceMs, h
 static decltype(&kz_wf_trace<0, false>) traceFn(int mode, bool stats) {
     static const decltype(&kz_wf_trace<0, false>) tab[5][2] = {{kz_wf_trace<0, false>, kz_wf_trace<0, true>}, {kz_wf_trace<1, false>, kz_wf_trace<1, true>},
                                         {kz_wf_trace<2, false>, kz_wf_trace<2, true>}, {nullptr, nullptr}, {kz_wf_trace<4, false>, kz_wf_trace<4, true>}};
+#ifdef KZ_EXPERIMENTS
+    // kz_debug_shadow_order(0): the any-hit shadow launches in the closest-hit child order (mode 5, a development build's instantiation)
+    if (mode == 4 && !g_kzShadowOrder.load(std::memory_order_relaxed)) return stats ? kz_wf_trace<5, true> : kz_wf_trace<5, false>;
+#endif
     return tab[mode][stats ? 1 : 0];
 }
 // ... and the camera-ray kernels by (stats, fix): FIX = the scene has an invisible light, whose first hits are queued for the walk-through

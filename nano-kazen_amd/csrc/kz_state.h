@@ -78,6 +78,7 @@ void kzTraceLine(const char *fmt, ...);
 int kzPhysicalDevice(int logical);            // kz_debug_alias_devices: the HIP device behind the index a replica is addressed by
 extern thread_local int g_failAlloc;          // kz_debug_fail_alloc (kz_replica.hip): kzMalloc counts it down, ctxEnsure (kz_render.hip) hands it to a growing arena
 extern std::atomic<int> g_kzRrAhead;          // kz_debug_rr_ahead (kz_debug.hip): 0 = the shade kernels trace every bounce ray, as before the roulette-ahead test
+extern std::atomic<int> g_kzShadowOrder;      // kz_debug_shadow_order (kz_debug.hip): 0 = the any-hit shadow launches descend in closest-hit order (kz_wf_trace<5>), as before the overlap order
 #else
 #define KZ_TRACE(...) do { } while (0)
 static inline int kzPhysicalDevice(int logical) { return logical; }

@@ -561,7 +561,8 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
 // 4: MODE 2 without the walk-through machinery — a shadow ray whose segment crosses a triangle of an invisible light (rare) is
 // not traced here but appended to the queue passed in queueB / countPtrB, which a MODE 2 launch takes afterwards. With `literal`
 // constant false the closest-hit bookkeeping of the shadow lanes (hit distance, barycentrics, triangle ids) disappears from that
-// instantiation: 57 VGPRs and no spills instead of 64 with 9 spilled.
+// instantiation: 57 VGPRs and no spills instead of 64 with 9 spilled. It also descends in an order of its own (largest overlap, see the node step);
+// 5 (development builds, kz_debug_shadow_order): MODE 4 in the closest-hit order, for comparing the two.
 // Shadow test (exact, see kz_devfn.h shadowOccluded): any-hit unless an invisible-light triangle lies on the segment.
 // (Round 2 measured and rejected a BVH2 form, a per-lane key stack, an LDS top-of-tree and mixed launches: LAB_NOTES 4.)
 #ifndef KZ_TRACE_WAVES
@@ -574,8 +575,10 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
                                                         uint32_t *__restrict__ queueB, uint32_t *__restrict__ countPtrB) {
     extern __shared__ uint32_t s_stack[];
     const uint32_t count = countPtr ? *countPtr : countImm;
-    [[maybe_unused]] constexpr bool SHADOW = MODE == 2 || MODE == 4;      // (read by the counters of the -DKZ_LANESTAT / -DKZ_TRACESTAT builds)
-    constexpr int kind = MODE == 4 ? 2 : MODE;                        // ray kind: 0 closest hit, 1 closest hit on the walk-through ray, 2 shadow
+    constexpr bool FAST = MODE == 4 || MODE == 5;                     // the any-hit shadow kernel; 5 (development builds): with the closest-hit child order
+    constexpr bool OVERLAP = MODE == 4;                               // child order of the node step: largest overlap with the segment (below)
+    [[maybe_unused]] constexpr bool SHADOW = MODE == 2 || FAST;       // (read by the counters of the -DKZ_LANESTAT / -DKZ_TRACESTAT builds)
+    constexpr int kind = FAST ? 2 : MODE;                        // ray kind: 0 closest hit, 1 closest hit on the walk-through ray, 2 shadow
     const int lane = threadIdx.x & 63;
     // The lane's stack is a column of the [entry][lane] LDS array (+ one scratch row). Its state is `top`, the LDS BYTE ADDRESS of the next
     // free entry: pushes and pops are ds_write / ds_read at that address, one v_add_u32 apart (an entry index costs a v_lshl_add_u32 - a
@@ -640,7 +643,7 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
     float plR = 0.f, plG = 0.f, plB = 0.f;
     auto addPending = [&]() {
         uint32_t s_ = slot; asm volatile("" : "+v"(s_));          // (the three addresses are formed here: hoisted to the refill they were six registers held through the loop)
-        if (MODE != 4) { const float4 l = W.shL[s_]; plR = l.x; plG = l.y; plB = l.z; }
+        if (!FAST) { const float4 l = W.shL[s_]; plR = l.x; plG = l.y; plB = l.z; }
         unsafeAtomicAdd(W.outR + s_, plR); unsafeAtomicAdd(W.outG + s_, plG); unsafeAtomicAdd(W.outB + s_, plB);
     };
     // the lane's stack ran empty: publish the result (or, for a literal shadow lane, decide / walk through the light)
@@ -649,7 +652,7 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
         if (kind == 0) kzStoreStream(&W.hit[slot], make_float4(bt, bu, bv, __uint_as_float(bgid)));      // (without a hit the record still holds what the refill put there: +inf, 0, 0, 0 = the miss record)
         if (kind == 1) { if (found) kzStoreStream(&W.hit[slot], make_float4(bt, bu, bv, __uint_as_float(bgid))); }
         if (kind == 2) {
-            if (MODE == 4 || !literal || !found) addPending();                       // nothing on the segment
+            if (FAST || !literal || !found) addPending();                       // nothing on the segment
             else {
                 const uint32_t om = __float_as_uint(reinterpret_cast<const float4 *>(T.tris + btri)[2].y);      // (the leaf triangle is in cache; its shading record is not)
                 const int ol = T.meshes[om].light;
@@ -705,11 +708,11 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
                     float4 a, b;
                     if (kind == 0) { a = kzLoadStream(&W.rayA[slot]); b = kzLoadStream(&W.rayB[slot]); }
                     else { const float4 sa = kzLoadStream(&W.shA[slot]), sb = kzLoadStream(&W.shB[slot]); a = make_float4(sa.x, sa.y, sa.z, sb.w); b = make_float4(sb.x, sb.y, sb.z, sa.w);
-                           if (MODE == 4) { const float4 l = kzLoadStream(&W.shL[slot]); plR = l.x; plG = l.y; plB = l.z; } }
+                           if (FAST) { const float4 l = kzLoadStream(&W.shL[slot]); plR = l.x; plG = l.y; plB = l.z; } }
                     o = mk(a.x, a.y, a.z); d = mk(b.x, b.y, b.z); tmin = a.w; tmax = b.w; segMax = b.w;
                     if (MODE == 2) asm volatile("" : "+v"(segMax));          // (a value of its own, not a deferred copy of tmax's register: see `top` above)
                     found = false; bt = KZ_INF; bu = bv = 0.f; btri = 0; bgid = 0; literal = false;
-                    if (STATS && MODE != 4) cn.rays++;
+                    if (STATS && !FAST) cn.rays++;
                     if ((root != 0xFFFFFFFFu) && rayIsFinite(o, d)) {
                         // The FMA slab form q*(s*rcp) + (p-o)*rcp turns into inf - inf = NaN for a zero direction component,
                         // which would switch that axis off (a huge slab of the tree gets walked). A tiny signed stand-in keeps
@@ -718,7 +721,7 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
                         ry = rcpExact(fabsf(d.y) < 1e-20f ? copysignf(1e-20f, d.y) : d.y);
                         rz = rcpExact(fabsf(d.z) < 1e-20f ? copysignf(1e-20f, d.z) : d.z);
                         cur = root; active = true;
-                        if (MODE == 4) {
+                        if (FAST) {
                             if (invisibleLightOnSegment(P, T, o, d, rx, ry, rz, tmin, tmax)) {       // (launched only when P.shadowFast)
                                 queueB[atomicAdd(countPtrB, 1u)] = slot;
                                 active = false;
@@ -729,7 +732,7 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
                         // (the constants are made HERE: hoisted out of the loop they took four registers for the whole kernel, then a spill slot)
                         if (kind == 0) { float inf = KZ_INF, zero = 0.f; asm volatile("" : "+v"(inf), "+v"(zero)); kzStoreStream(&W.hit[slot], make_float4(inf, zero, zero, zero)); }
                         if (kind == 2) addPending();
-                        if (STATS && MODE == 4) cn.rays++;
+                        if (STATS && FAST) cn.rays++;
                     }
                 }
                 poolNext += take;
@@ -752,14 +755,20 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
                 // sort of the siblings buys 6 % fewer node visits and costs 12 % more instructions per visit). Any-hit shadow rays took the
                 // hit children in slot order altogether until the pushes got cheap (round 3): in dense geometry the nearest child is where
                 // the occluder is, and the selection now costs less than the visits it saves. Pushes are branch-free (below).
+                // The any-hit kernel (MODE 4) is free in its order - "occluded" is the same answer whichever occluder is found first - and in a soup most
+                // children of a node contain the ray's origin: their entry distances tie at tmin and the lowest slot won, an arbitrary choice. It descends
+                // into the child that holds the LONGEST part of the segment instead (node4KeysOf<true>: one v_sub_f32 per child, the maximum for the
+                // minimum, 0 for the miss key): 12 % fewer node steps of C4's shadow launches, 17 % in the walk model
+                // (scripts/dev/bvh4_walk_model.cpp; profiles/r15a_shadow_order). The literal lanes of MODE 2 return a closest hit and keep the closest-hit order.
                 uint32_t key[4]; uint4 refs;
-                node4Keys(T, cur, o, rx, ry, rz, tmin, tmax, key, refs);
-                const uint32_t kmin = min(min(key[0], key[1]), min(key[2], key[3]));
-                const bool any = kmin != 0xFFFFFFFFu;
+                node4Keys<OVERLAP>(T, cur, o, rx, ry, rz, tmin, tmax, key, refs);
+                constexpr uint32_t kMiss = OVERLAP ? 0u : 0xFFFFFFFFu;
+                const uint32_t kmin = OVERLAP ? max(max(key[0], key[1]), max(key[2], key[3])) : min(min(key[0], key[1]), min(key[2], key[3]));      // (the key of the child to take)
+                const bool any = kmin != kMiss;
                 const uint32_t nxt = pick4b(refs, kmin);
                 // child i goes on the stack
-                const bool p0 = key[0] != 0xFFFFFFFFu && key[0] != kmin, p1 = key[1] != 0xFFFFFFFFu && key[1] != kmin;
-                const bool p2 = key[2] != 0xFFFFFFFFu && key[2] != kmin, p3 = key[3] != 0xFFFFFFFFu && key[3] != kmin;
+                const bool p0 = key[0] != kMiss && key[0] != kmin, p1 = key[1] != kMiss && key[1] != kmin;
+                const bool p2 = key[2] != kMiss && key[2] != kmin, p3 = key[3] != kMiss && key[3] != kmin;
                 if (top - stkBase + 3u * rowB <= ldsRows) {                      // common case: everything stays in LDS
                     // every child is written at the running top, which advances only past the children that stay: one that does not is
                     // overwritten by the next store or left above the top (the last row it can reach is the scratch row). No address selects.
@@ -792,7 +801,7 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
                 float t, u, v; uint32_t g;
                 if (STATS) cn.tris++;
                 if (!triTest(T.tris + start + i, o, d, tmin, tmax, t, u, v, g)) continue;
-                if (kind == 2 && (MODE == 4 || !literal)) { occluded = true; break; }   // any hit blocks: nothing to add
+                if (kind == 2 && (FAST || !literal)) { occluded = true; break; }   // any hit blocks: nothing to add
                 if (!found || t < bt || (t == bt && g < bgid)) { found = true; bt = t; bu = u; bv = v; btri = start + i; bgid = g; tmax = t; }
             }
 #ifdef KZ_TRACESTAT

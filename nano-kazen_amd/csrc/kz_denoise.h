@@ -1,0 +1,57 @@
+// kz_denoise.h - the edge-avoiding a-trous filter of include/kazen_mi355x_denoise.h, stated once for the device: what one film texel is worth, what a tap
+// weighs, and what one iteration makes of a pixel. The reference renderer has no denoiser; THIS ARITHMETIC defines the result, and tests/cpu_ref/kz_denoise_ref.cpp
+// restates it independently in plain C++ (same bits: the unit that includes this file is compiled without flush-to-zero and without contraction, build.sh).
+// Every operation below is one fp32 IEEE operation in the order written; dnMax(a, b) is a > b ? a : b (no fmaxf: its NaN rule is not part of the definition).
+//
+//   value of a film texel t:  t.w != 0 ? t.xyz / t.w : 0                               (dnValue; a null film: 0)
+//   planes, frame-sized, no apron:  colour (e.rgb, valid ? 1 : 0) | (n.xyz, z) | (a.rgb, 0)
+//   e_0 = demodulate ? c / dnMax(a, 1e-3f) : c     per channel                           (kz_dn_prepare)
+//   one iteration at a valid pixel p (kz_dn_atrous, dnPixel), taps dy = -2..2 outer, dx = -2..2 inner, q = p + step * (dx, dy) inside the frame and valid:
+//       dc = dnSq(e(q) - e(p)), dn = dnSq(n(q) - n(p)), da = dnSq(a(q) - a(p))           dnSq(v) = (v.x * v.x + v.y * v.y) + v.z * v.z
+//       m = dnMax(dnMax(z_p, z_q), 1e-20f), t = (z_q - z_p) / m, dz = t * t
+//       arg = ((dc * kc + dn * kn) + dz * kz) + da * ka                                  (colour weights only: arg = dc * kc)
+//       wgt = (h[dy + 2] * h[dx + 2]) * dnExp(-arg)                                      h = {1/16, 1/4, 3/8, 1/4, 1/16}; the products are exact
+//       num.k += wgt * e(q).k (k = r, g, b), den += wgt;     e'(p) = num / den
+//   result = demodulate ? e_last * dnMax(a, 1e-3f) : e_last, weight 1; (0, 0, 0, 0) where the pixel is not valid and in the apron   (kz_dn_finish)
+// The constants kc (per iteration: sigmaColor halves), kn, kz, ka = 1.0f / (sigma * sigma) are computed on the host (kz_denoise.hip dnPlan).
+#pragma once
+#include "kz_crmath.h"
+
+// One iteration's constants, by value to the kernel
+struct KzDnIter { int width, height, step; float kc, kn, kz, ka; };
+
+#define KZ_DN_FN __device__ __forceinline__
+KZ_DN_FN float dnMax(float a, float b) { return a > b ? a : b; }
+KZ_DN_FN float dnSq(float x, float y, float z) { return (x * x + y * y) + z * z; }
+KZ_DN_FN float4 dnValue(const float4 *__restrict__ film, size_t i) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (film) { const float4 t = film[i]; if (t.w != 0.f) { v.x = t.x / t.w; v.y = t.y / t.w; v.z = t.z / t.w; } v.w = t.w; }
+    return v;
+}
+// kzExp (kz_crmath.h), the same statement inlined: as a call inside the 25-tap loop it keeps the taps' loads from being issued ahead of the arithmetic
+KZ_DN_FN float dnExp(float x) {
+    if (!(x > -104.0f)) return x != x ? x : 0.0f;
+    if (x > 89.0f) return __builtin_inff();
+    return kzcrNarrow(kzcrExpD((double)x));
+}
+// the B3-spline weights: h[|d|] for d = -2..2
+KZ_DN_FN float dnH(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
+
+// What tap q adds to the sums of pixel p: (wgt * e(q), wgt). ep / eq: colour plane texels, gp / gq: (n.xyz, z), ap / aq: (a.rgb, -).
+template <bool GUIDED>
+KZ_DN_FN void dnTap(const KzDnIter &I, float hh, const float4 &ep, const float4 &eq, const float4 &gp, const float4 &gq, const float4 &ap, const float4 &aq,
+                    float &nr, float &ng, float &nb, float &den) {
+    const float dc = dnSq(eq.x - ep.x, eq.y - ep.y, eq.z - ep.z);
+    float arg = dc * I.kc;
+    if (GUIDED) {
+        const float dn = dnSq(gq.x - gp.x, gq.y - gp.y, gq.z - gp.z);
+        const float da = dnSq(aq.x - ap.x, aq.y - ap.y, aq.z - ap.z);
+        const float m = dnMax(dnMax(gp.w, gq.w), 1e-20f);
+        const float t = (gq.w - gp.w) / m;
+        const float dz = t * t;
+        arg = ((arg + dn * I.kn) + dz * I.kz) + da * I.ka;
+    }
+    const float wgt = hh * dnExp(-arg);
+    nr += wgt * eq.x; ng += wgt * eq.y; nb += wgt * eq.z;
+    den += wgt;
+}

@@ -256,6 +256,13 @@ int kzAovFilmStage(KzScene *scene, KzDeviceState *ds, hipStream_t pst, const uin
     }
     return KZ_OK;
 }
+int kzAovResolve(KzScene *scene, KzDeviceState *ds, int f, hipStream_t stream) {
+    const KzParams &P = scene->prm;
+    const int cols = P.width + 2 * P.border, rows = P.height + 2 * P.border;
+    hipLaunchKernelGGL(kz_film_resolve, dim3((cols + 15) / 16, (rows + 15) / 16), dim3(256), 0, stream, P, (const float4 *)ds->aovTapSums[f], (size_t)P.width * (size_t)P.height, KZ_FILM_GRID, ds->aovFilm[f]);
+    HIP_TRY(hipGetLastError());
+    return KZ_OK;
+}
 void kzAovFree(KzDeviceState *ds, uint32_t mask) {
     for (int f = 0; f < 3; ++f) {
         if (!(mask & (1u << f))) continue;
@@ -391,10 +398,7 @@ int kz_aov_download_on(KzScene *scene, int device, uint32_t aov, float *film, si
     const int f = aov == KZ_AOV_ALBEDO ? 0 : (aov == KZ_AOV_NORMAL ? 1 : 2);
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     if (!ds->aovTapSums[f] || !ds->aovFilm[f]) { std::memset(film, 0, nFloats * sizeof(float)); return KZ_OK; }      // (enabled, nothing rendered yet)
-    const KzParams &P = scene->prm;
-    const int cols = P.width + 2 * P.border, rows = P.height + 2 * P.border;
-    hipLaunchKernelGGL(kz_film_resolve, dim3((cols + 15) / 16, (rows + 15) / 16), dim3(256), 0, ds->lastStream, P, (const float4 *)ds->aovTapSums[f], (size_t)P.width * (size_t)P.height, KZ_FILM_GRID, ds->aovFilm[f]);
-    HIP_TRY(hipGetLastError());
+    if ((rc = kzAovResolve(scene, ds, f, ds->lastStream))) return rc;
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     HIP_TRY(hipMemcpy(film, ds->aovFilm[f], nFloats * sizeof(float), hipMemcpyDeviceToHost));
     return KZ_OK;
@@ -414,16 +418,22 @@ int kz_aov_info(KzScene *scene, int device, uint64_t *bytes) {
 int kz_film_to_srgb8(KzScene *scene, uint8_t *rgb8, size_t nBytes) {
     KzDeviceState *ds; int rc;
     if ((rc = requireDevice(scene, &ds))) return rc;
+    return kzFilmSrgb8(scene, ds, ds->film, rgb8, nBytes);
+}
+
+} // extern "C"
+
+// kz_film_srgb8 of a film-shaped buffer of the replica (its film, or the denoiser's result: kz_denoise.hip), behind the work queued on ds->lastStream
+int kzFilmSrgb8(KzScene *scene, KzDeviceState *ds, const float4 *film, uint8_t *rgb8, size_t nBytes) {
+    int rc;
     const KzParams &P = scene->prm;
     const size_t need = (size_t)P.width * (size_t)P.height * 3;
     if (!rgb8 || nBytes != need) return kz_fail(KZ_ERR_INVALID_ARG, "rgb8 buffer must hold %zu bytes", need);
     if (!ds->srgb && (rc = ds->srgb.alloc(need))) return rc;                        // staging raster kept with the replica
     const uint32_t n = (uint32_t)(P.width * P.height);
-    hipLaunchKernelGGL(kz_film_srgb8, dim3((n + 255) / 256), dim3(256), 0, ds->lastStream, ds->film, P.width, P.height, P.border, ds->srgb);
+    hipLaunchKernelGGL(kz_film_srgb8, dim3((n + 255) / 256), dim3(256), 0, ds->lastStream, film, P.width, P.height, P.border, ds->srgb);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     HIP_TRY(hipMemcpy(rgb8, ds->srgb, need, hipMemcpyDeviceToHost));
     return KZ_OK;
 }
-
-} // extern "C"

@@ -4,6 +4,7 @@
 //   kz_replica.hip  replicas: lifetime + upload, tile sets (prepareTiles), the queries that only read replica state (kz_last_*, kz_pass_mode_info, kz_sync*, stats)
 //   kz_refit.hip    device side of the edits of a resident scene (kz_refit.h)
 //   kz_film.hip     film reconstruction kernels + their launcher, tile packing / download, kz_film_* entry points
+//   kz_denoise.hip  the a-trous denoiser of include/kazen_mi355x_denoise.h: its kernels, the replica's denoise buffers, kz_denoise* entry points
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
 // Every device buffer, pinned buffer, event and stream named below is a member of one of the four move-only owners of kz_own.h (DevBuf, PinnedBuf, Event, Stream).
@@ -183,7 +184,12 @@ struct KzDeviceState {
     // with the AOV enabled; evAov[i]: the AOV tap launches of the pass last run in context i (the chain passes in flight order their AOV stages by, wfPass)
     DevBuf<float4> aovTapSums[3], aovFilm[3]; Event evAov[KZ_MAX_PASSES_IN_FLIGHT];
     size_t aovBytes() const { size_t b = 0; for (int f = 0; f < 3; ++f) b += aovTapSums[f].bytes() + aovFilm[f].bytes(); return b; }
-    DevBuf<uint8_t> srgb;                                        // staging raster of kz_film_to_srgb8 (allocated on first use)
+    DevBuf<uint8_t> srgb;                                        // staging raster of kz_film_to_srgb8 / kz_denoise_to_srgb8 (allocated on first use)
+    // The denoiser (kazen_mi355x_denoise.h; kz_denoise.hip), allocated by the first kz_denoise outside the pass contexts' budget: frame-sized planes without an
+    // apron - the colour plane (e.rgb, valid) twice, the iterations ping-pong between the two; (n.xyz, z); (a.rgb, -) - and the result, laid out like the film.
+    // dnValid: dnOut holds the result of a kz_denoise (a snapshot: renders, clears and edits leave it alone).
+    DevBuf<float4> dnColor[2], dnNormalZ, dnAlbedo, dnOut; bool dnValid = false;
+    size_t dnBytes() const { return dnColor[0].bytes() + dnColor[1].bytes() + dnNormalZ.bytes() + dnAlbedo.bytes() + dnOut.bytes(); }
     DevBuf<float4> packDev; DevBuf<KzTileRect> rectsDev;         // kz_film_download_tiles: packed tile rects + their table
     PinnedBuf<float4> packHost;                                  // pinned staging of the same (D2H at link rate)
     // The tile set: pixList = its pixels (tile after tile, 8x8 blocks row-major inside a tile, row-major inside a block), written on the device from the
@@ -253,3 +259,7 @@ struct KzAovPlanes { float *p[3]; size_t stride; };
 int kzAovEnsure(KzScene *scene, KzDeviceState *ds, hipStream_t stream, bool accumulate);
 int kzAovFilmStage(KzScene *scene, KzDeviceState *ds, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *jx, const float *jy, const KzAovPlanes &planes, int lanesPerPixel);
 void kzAovFree(KzDeviceState *ds, uint32_t mask);
+// The film of AOV f (0 albedo, 1 normal, 2 depth) from its tap sums, on `stream`: what kz_aov_download copies out and kz_denoise reads. The AOV has been rendered (sums and film are there).
+int kzAovResolve(KzScene *scene, KzDeviceState *ds, int f, hipStream_t stream);
+// The 8-bit sRGB raster of a film-shaped device buffer of the replica (kz_film_srgb8 on ds->lastStream, through ds->srgb): kz_film_to_srgb8 and kz_denoise_to_srgb8
+int kzFilmSrgb8(KzScene *scene, KzDeviceState *ds, const float4 *film, uint8_t *rgb8, size_t nBytes);

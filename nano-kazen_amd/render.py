@@ -426,6 +426,38 @@ class Scene:
         abi.check(self.lib, self.lib.kz_aov_samples(self.h, n, pxy.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(abi.u32p), out.ctypes.data_as(abi.f32p)))
         return out
 
+    # ---- the picture denoised on the device, guided by its feature films (include/kazen_mi355x_denoise.h)
+    def denoise(self, device=None, **opts):
+        """kz_denoise[_on]: filters the replica's picture with the enabled feature films as guides; the result stays on the device (denoised_film,
+        denoised_srgb8) until the next denoise. Options: see denoise_opts."""
+        o = denoise_opts(**opts)
+        if device is None:
+            abi.check(self.lib, self.lib.kz_denoise(self.h, C.byref(o)))
+        else:
+            abi.check(self.lib, self.lib.kz_denoise_on(self.h, int(device), C.byref(o)))
+
+    def denoised_film(self, device=None):
+        """kz_denoise_download: (h + 2b, w + 2b, 4) = (rgb, 1) in the frame pixels that had samples, zeros elsewhere - rgb() and the writers of output.py take it like film()."""
+        n = (self.height + 2 * self.border) * (self.width + 2 * self.border) * 4
+        out = np.empty(n, np.float32)
+        abi.check(self.lib, self.lib.kz_denoise_download(self.h, -1 if device is None else int(device), out.ctypes.data_as(abi.f32p), n))
+        return out.reshape(self.height + 2 * self.border, self.width + 2 * self.border, 4)
+
+    def denoised_srgb8(self, device=None):
+        """kz_denoise_to_srgb8: (h, w, 3) uint8, the raster srgb8() makes of the film, of the denoised picture."""
+        out = np.zeros((self.height, self.width, 3), np.uint8)
+        abi.check(self.lib, self.lib.kz_denoise_to_srgb8(self.h, -1 if device is None else int(device), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+        return out
+
+    def denoise_info(self, device=-1):
+        """kz_denoise_info: bytes the denoiser's buffers hold on that replica."""
+        b = C.c_uint64()
+        abi.check(self.lib, self.lib.kz_denoise_info(self.h, int(device), C.byref(b)))
+        return int(b.value)
+
+    def denoise_release(self, device=-1):
+        abi.check(self.lib, self.lib.kz_denoise_release(self.h, int(device)))
+
     def bsdf_query(self, bsdf, wi, wo, acc, s3, uv=None):
         """eval (n,3), pdf (n,), sample (n,8) = weight rgb, wo xyz, alive, pdf(bRec) after sample()."""
         bsdf = np.ascontiguousarray(bsdf, np.int32)
@@ -490,6 +522,33 @@ class Scene:
         ms = C.c_float()
         abi.check(self.lib, self.lib.kz_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
+
+
+def denoise_opts(iterations=0, guides=0, demodulate=True, use_guides=True, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, sigma_albedo=0.0, flags=None, reserved=0):
+    """A KzDenoiseOpts: 0 means the default (5 iterations; every available guide; sigmas 1.0, 0.3, 0.1, 0.1). guides: names or the KZ_AOV_* mask;
+    demodulate=False / use_guides=False set KZ_DENOISE_NO_DEMODULATE / KZ_DENOISE_NO_GUIDES (`flags` overrides the two)."""
+    if flags is None:
+        flags = (0 if demodulate else abi.KZ_DENOISE_NO_DEMODULATE) | (0 if use_guides else abi.KZ_DENOISE_NO_GUIDES)
+    return abi.KzDenoiseOpts(int(iterations), Scene._aov_mask(guides), int(flags), int(reserved), float(sigma_color), float(sigma_normal), float(sigma_depth), float(sigma_albedo))
+
+
+def denoise_films(film, albedo=None, normal=None, depth=None, border=0, device=0, lib=None, **opts):
+    """kz_denoise_films: the device's denoiser on host films of (h + 2 border, w + 2 border, 4) float32 each (albedo / normal / depth may be None: an absent
+    guide); needs a device, no scene. Returns the denoised film, same shape."""
+    lib = lib or abi.load_library()
+    film = np.ascontiguousarray(film, np.float32)
+    rows, cols = film.shape[0], film.shape[1]
+    if film.ndim != 3 or film.shape[2] != 4:
+        raise ValueError("a film is (h + 2 border, w + 2 border, 4)")
+    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (albedo, normal, depth)]
+    for a in g:
+        if a is not None and a.shape != film.shape:
+            raise ValueError("a guide film has the picture's shape")
+    out = np.empty_like(film)
+    o = denoise_opts(**opts)
+    abi.check(lib, lib.kz_denoise_films(int(device), cols - 2 * int(border), rows - 2 * int(border), int(border), film.ctypes.data_as(abi.f32p),
+                                        *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g], C.byref(o), out.ctypes.data_as(abi.f32p)))
+    return out
 
 
 def hits_to_arrays(hits, n):

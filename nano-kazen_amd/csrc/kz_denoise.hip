@@ -212,16 +212,17 @@ int kz_denoise_on(KzScene *scene, int device, const KzDenoiseOpts *opts) {
     const float4 *guide[3] = {nullptr, nullptr, nullptr};
     for (int f = 0; f < 3; ++f) {
         const bool wanted = f == 0 ? (plan.demodulate || (plan.guided && (plan.guides & KZ_AOV_ALBEDO))) : (plan.guided && (plan.guides & (1u << f)));
-        if (!wanted || !ds->aovTapSums[f] || !ds->aovFilm[f]) continue;      // (enabled, nothing rendered yet: zeros, as kz_aov_download gives)
-        if ((rc = kzAovResolve(scene, ds, f, ds->lastStream))) return rc;
-        guide[f] = ds->aovFilm[f];
+        KzFilm &film = ds->aov(f);
+        if (!wanted || !film.sums || !film.texels) continue;                // (enabled, nothing rendered yet: zeros, as kz_aov_download gives)
+        if ((rc = kzFilmResolve(scene, film, ds->lastStream))) return rc;
+        guide[f] = film.texels;
     }
     ds->dnValid = false;
     for (DevBuf<float4> *b : {&ds->dnColor[0], &ds->dnColor[1], &ds->dnNormalZ, &ds->dnAlbedo})
         if (b->cap() != nPix && (rc = b->regrow(nPix))) return rc;
     if (ds->dnOut.cap() != ds->filmPixels && (rc = ds->dnOut.regrow(ds->filmPixels))) return rc;
     float4 *const colour[2] = {ds->dnColor[0].get(), ds->dnColor[1].get()};
-    if ((rc = dnRun(plan, P.width, P.height, P.border, ds->film, guide[0], guide[1], guide[2], colour, ds->dnNormalZ, ds->dnAlbedo, ds->dnOut, ds->lastStream))) return rc;
+    if ((rc = dnRun(plan, P.width, P.height, P.border, ds->picture().texels, guide[0], guide[1], guide[2], colour, ds->dnNormalZ, ds->dnAlbedo, ds->dnOut, ds->lastStream))) return rc;
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     ds->dnValid = true;
     return KZ_OK;

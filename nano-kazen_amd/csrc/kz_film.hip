@@ -186,30 +186,26 @@ __global__ void kz_film_srgb8(const float4 *__restrict__ film, int width, int he
     }
 }
 
-// The replica's running tap sums: taps^2 float4 per pixel of the frame (C4, 5 taps: 829 MB; C5: 3.3 GB), allocated and zeroed on first use.
-int kzFilmEnsureTapSums(KzScene *scene, KzDeviceState *ds, hipStream_t stream) {
+// Before the passes of a call (renderOn), and before a film's rects are packed (downloadTiles): KzFilm::ensure with the scene's geometry - taps^2 float4 of sums per
+// pixel of the frame (C4, 5 taps: 829 MB; C5: 3.3 GB), allocated and zeroed on first use outside the pass contexts' budget.
+int kzFilmEnsure(KzScene *scene, KzFilm &film, size_t filmPixels, bool accumulate, hipStream_t stream) {
     const KzParams &P = scene->prm;
-    const size_t taps = (size_t)(P.tapHi - P.tapLo + 1), framePix = (size_t)P.width * (size_t)P.height;
-    if (ds->tapSums) return KZ_OK;
-    KZ_TRACE("film: tap sums, %.0f MB ...", taps * taps * framePix * sizeof(float4) / 1e6);
-    if (const int rc = ds->tapSums.alloc(taps * taps * framePix)) return rc;
-    HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSums.bytes(), stream));
-    KZ_TRACE("film: ... there");
-    return KZ_OK;
+    const size_t taps = (size_t)(P.tapHi - P.tapLo + 1), nSums = taps * taps * (size_t)P.width * (size_t)P.height;
+    const bool fresh = !film.sums;
+    if (fresh) KZ_TRACE("film: tap sums, %.0f MB ...", nSums * sizeof(float4) / 1e6);
+    const int rc = film.ensure(nSums, filmPixels, accumulate, stream);
+    if (fresh && !rc) KZ_TRACE("film: ... there");
+    return rc;
 }
 
 int kzFilmClear(KzDeviceState *ds, hipStream_t stream) {
-    if (ds->tapSums) HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSums.bytes(), stream));
-    HIP_TRY(hipMemsetAsync(ds->film, 0, ds->filmPixels * sizeof(float4), stream));
-    for (int f = 0; f < 3; ++f) {                                      // the feature films follow the picture's
-        if (ds->aovTapSums[f]) HIP_TRY(hipMemsetAsync(ds->aovTapSums[f], 0, ds->tapSums.bytes(), stream));
-        if (ds->aovFilm[f]) HIP_TRY(hipMemsetAsync(ds->aovFilm[f], 0, ds->filmPixels * sizeof(float4), stream));
-    }
+    for (KzFilm &film : ds->films) if (const int rc = film.clear(stream)) return rc;      // the picture, then the feature films
     return KZ_OK;
 }
 
-// The film stage of one pass (called by renderOn, kz_render.hip): ImageBlock::put for every sample record of the pass, into the running tap sums of the pass's
-// pixels. The kernel reads and writes those sums, so it waits for the film stage of the pass before it (`waitFilm`, passes on other streams; null: same stream).
+// The film stage of one pass (kz_render.hip: launchWhole / launchHalves for the picture, wfAov once per enabled feature film): ImageBlock::put for every sample record
+// of the pass - its five planes jx | jy | r | g | b - into `film`'s running tap sums of the pass's pixels. The kernel reads and writes those sums, so it waits for the
+// film stage of the pass before it (`waitFilm`, passes on other streams; null: same stream). isSigned: kz_film_taps<.., SIGNED = true>, a feature film's values.
 // lanesPerPixel: 0 = default (2 lane groups per pixel up to 5 taps, 4 beyond), 1 = one lane per pixel (round 2's kernel; up to 5 taps) - the same sums bit for bit.
 template <bool SIGNED>
 static int launchTaps(const KzParams &P, KzDeviceState *ds, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *sJx, const float *sJy,
@@ -227,54 +223,18 @@ static int launchTaps(const KzParams &P, KzDeviceState *ds, hipStream_t pst, con
     HIP_TRY(hipGetLastError());
     return KZ_OK;
 }
-int kzFilmStage(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, hipEvent_t waitFilm, int lanesPerPixel) {
+int kzFilmStage(KzScene *scene, KzDeviceState *ds, KzFilm &film, bool isSigned, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *const plane[5], hipEvent_t waitFilm, int lanesPerPixel) {
     if (waitFilm) HIP_TRY(hipStreamWaitEvent(pst, waitFilm, 0));
-    return launchTaps<false>(scene->prm, ds, pst, pixList, nPixPass, Sp, c.plane[0], c.plane[1], c.plane[2], c.plane[3], c.plane[4], ds->tapSums, lanesPerPixel);
+    // (the picture's instantiations first: the code the compiler gives the 9-tap kernels follows the order in which the two sets are instantiated)
+    return (!isSigned ? launchTaps<false> : launchTaps<true>)(scene->prm, ds, pst, pixList, nPixPass, Sp, plane[0], plane[1], plane[2], plane[3], plane[4], film.sums, lanesPerPixel);
 }
 
-// ---- feature films (include/kazen_mi355x_aov.h): the same machine, one set of tap sums and one film per enabled AOV ----
-// Before the passes of a call: the sums and films of the enabled AOVs are there (allocated and zeroed on first use, like ds->tapSums, outside the pass contexts'
-// budget) and cleared unless the call accumulates.
-int kzAovEnsure(KzScene *scene, KzDeviceState *ds, hipStream_t stream, bool accumulate) {
-    for (int f = 0; f < 3; ++f) {
-        if (!(scene->aovMask & (1u << f))) continue;
-        const bool fresh = !ds->aovTapSums[f];
-        int rc;
-        if (fresh && (rc = ds->aovTapSums[f].alloc(ds->tapSums.cap()))) return rc;
-        if (!ds->aovFilm[f]) { if ((rc = ds->aovFilm[f].alloc(ds->filmPixels))) return rc; HIP_TRY(hipMemsetAsync(ds->aovFilm[f], 0, ds->filmPixels * sizeof(float4), stream)); }
-        if (fresh || !accumulate) HIP_TRY(hipMemsetAsync(ds->aovTapSums[f], 0, ds->tapSums.bytes(), stream));
-    }
-    return KZ_OK;
-}
-// Inside a pass (wfPass), behind kz_wf_aov: ImageBlock::put of the pass's feature values, one kz_film_taps<.., true> launch per enabled AOV
-int kzAovFilmStage(KzScene *scene, KzDeviceState *ds, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *jx, const float *jy, const KzAovPlanes &A, int lanesPerPixel) {
-    for (int f = 0; f < 3; ++f) {
-        if (!(scene->aovMask & (1u << f))) continue;
-        if (!ds->aovTapSums[f]) return kz_fail(KZ_ERR_STATE, "the tap sums of AOV %u are not there", 1u << f);
-        const int rc = launchTaps<true>(scene->prm, ds, pst, pixList, nPixPass, Sp, jx, jy, A.p[f], A.p[f] + A.stride, A.p[f] + 2 * A.stride, ds->aovTapSums[f], lanesPerPixel);
-        if (rc) return rc;
-    }
-    return KZ_OK;
-}
-int kzAovResolve(KzScene *scene, KzDeviceState *ds, int f, hipStream_t stream) {
+// The texels of a film from its tap sums, on `stream` behind whatever fed the sums: ImageBlock::put(ImageBlock&) of the canonical grid's tiles in tile order. The picture's:
+// once per call, behind every pass; a feature film's: where it is read (kz_aov_download, kz_denoise). Sums and texels are there.
+int kzFilmResolve(KzScene *scene, KzFilm &film, hipStream_t stream) {
     const KzParams &P = scene->prm;
     const int cols = P.width + 2 * P.border, rows = P.height + 2 * P.border;
-    hipLaunchKernelGGL(kz_film_resolve, dim3((cols + 15) / 16, (rows + 15) / 16), dim3(256), 0, stream, P, (const float4 *)ds->aovTapSums[f], (size_t)P.width * (size_t)P.height, KZ_FILM_GRID, ds->aovFilm[f]);
-    HIP_TRY(hipGetLastError());
-    return KZ_OK;
-}
-void kzAovFree(KzDeviceState *ds, uint32_t mask) {
-    for (int f = 0; f < 3; ++f) {
-        if (!(mask & (1u << f))) continue;
-        ds->aovTapSums[f].free(); ds->aovFilm[f].free();
-    }
-}
-
-// The film of the replica from its tap sums (once per call, on the call's stream behind every pass): ImageBlock::put(ImageBlock&) of the canonical grid's tiles in tile order.
-int kzFilmResolve(KzScene *scene, KzDeviceState *ds, hipStream_t stream) {
-    const KzParams &P = scene->prm;
-    const int cols = P.width + 2 * P.border, rows = P.height + 2 * P.border;
-    hipLaunchKernelGGL(kz_film_resolve, dim3((cols + 15) / 16, (rows + 15) / 16), dim3(256), 0, stream, P, (const float4 *)ds->tapSums, (size_t)P.width * (size_t)P.height, KZ_FILM_GRID, ds->film);
+    hipLaunchKernelGGL(kz_film_resolve, dim3((cols + 15) / 16, (rows + 15) / 16), dim3(256), 0, stream, P, (const float4 *)film.sums, (size_t)P.width * (size_t)P.height, KZ_FILM_GRID, film.texels);
     HIP_TRY(hipGetLastError());
     return KZ_OK;
 }
@@ -295,8 +255,8 @@ int checkTiles(const KzParams &P, const KzTile *tiles, uint32_t nTiles) {
     return KZ_OK;
 }
 
-// the film rects of `tiles` of replica ds -> host `packed` (through a device-side pack and a pinned staging buffer: one D2H copy at link rate)
-int downloadTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32_t nTiles, float *packed, size_t nFloats, hipStream_t stream) {
+// the rects of `tiles` of film `film` of replica ds -> host `packed` (through a device-side pack and a pinned staging buffer: one D2H copy at link rate)
+int downloadTiles(KzScene *scene, KzDeviceState *ds, KzFilm &film, const KzTile *tiles, uint32_t nTiles, float *packed, size_t nFloats, hipStream_t stream) {
     const KzParams &P = scene->prm;
     int rc;
     if ((rc = checkTiles(P, tiles, nTiles))) return rc;
@@ -318,8 +278,8 @@ int downloadTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32
     HIP_TRY(hipStreamSynchronize(stream));                              // (the tables are host vectors of this call)
     if (nTiles > 65535u * 65535u) return kz_fail(KZ_ERR_UNSUPPORTED, "kz_film_download_tiles: %u tiles in one call", nTiles);
     const unsigned gz = (nTiles + 65534u) / 65535u, gy = gz > 1 ? 65535u : nTiles;
-    if ((rc = kzFilmEnsureTapSums(scene, ds, stream))) return rc;      // (a replica nothing has been rendered on: zeros)
-    hipLaunchKernelGGL(kz_film_tile_rects, dim3((unsigned)maxRows, gy, gz), dim3(128), 0, stream, P, (const float4 *)ds->tapSums, (size_t)P.width * (size_t)P.height, (const KzTileRect *)ds->rectsDev.get(),
+    if ((rc = kzFilmEnsure(scene, film, ds->filmPixels, true, stream))) return rc;      // (a replica nothing has been rendered on: zeros)
+    hipLaunchKernelGGL(kz_film_tile_rects, dim3((unsigned)maxRows, gy, gz), dim3(128), 0, stream, P, (const float4 *)film.sums, (size_t)P.width * (size_t)P.height, (const KzTileRect *)ds->rectsDev.get(),
                        ds->packDev.get(), nTiles);
     HIP_TRY(hipGetLastError());
     if (ds->packHost) {
@@ -345,10 +305,9 @@ int kz_tiles_packed_floats(const KzScene *scene, const KzTile *tiles, uint32_t n
 
 int kz_film_download_tiles(KzScene *scene, int device, const KzTile *tiles, uint32_t nTiles, float *packed, size_t nFloats) {
     KzDeviceState *ds; int rc;
-    if (scene && scene->aovMask) return kz_fail(KZ_ERR_UNSUPPORTED, "kz_film_download_tiles: refused while AOVs are enabled (mask %u): the tile-rect gather of AOV films is not built - kz_scene_set_aovs(scene, 0) first", scene->aovMask);
-    if ((rc = findReplica(scene, device, &ds))) return rc;
+    if ((rc = kzAovRefuseGather(scene, "kz_film_download_tiles")) || (rc = findReplica(scene, device, &ds))) return rc;
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
-    return downloadTiles(scene, ds, tiles, nTiles, packed, nFloats, ds->lastStream);
+    return downloadTiles(scene, ds, ds->picture(), tiles, nTiles, packed, nFloats, ds->lastStream);
 }
 
 int kz_film_clear_on(KzScene *scene, int device, void *stream) {
@@ -358,13 +317,23 @@ int kz_film_clear_on(KzScene *scene, int device, void *stream) {
 }
 int kz_film_clear(KzScene *scene, void *stream) { return kz_film_clear_on(scene, -1, stream); }
 
+// What the two film downloads share: the buffer's size, the wait for the replica's queued work, the copy of the texels. `resolved`: the texels are current (the picture's:
+// every render ends with their resolve); otherwise - a feature film - they are resolved first, and a film nothing has been rendered into yet is zeros.
+static int downloadFilm(KzScene *scene, KzDeviceState *ds, KzFilm &film, bool resolved, float *out, size_t nFloats) {
+    if (!out || nFloats != ds->filmPixels * 4) return kz_fail(KZ_ERR_INVALID_ARG, "film buffer must hold %zu floats", ds->filmPixels * 4);
+    HIP_TRY(hipStreamSynchronize(ds->lastStream));
+    if (!resolved) {
+        if (!film.sums || !film.texels) { std::memset(out, 0, nFloats * sizeof(float)); return KZ_OK; }      // (enabled, nothing rendered yet)
+        if (const int rc = kzFilmResolve(scene, film, ds->lastStream)) return rc;
+        HIP_TRY(hipStreamSynchronize(ds->lastStream));
+    }
+    HIP_TRY(hipMemcpy(out, film.texels, nFloats * sizeof(float), hipMemcpyDeviceToHost));
+    return KZ_OK;
+}
 int kz_film_download_on(KzScene *scene, int device, float *film, size_t nFloats) {
     KzDeviceState *ds; int rc;
     if ((rc = findReplica(scene, device, &ds))) return rc;
-    if (!film || nFloats != ds->filmPixels * 4) return kz_fail(KZ_ERR_INVALID_ARG, "film buffer must hold %zu floats", ds->filmPixels * 4);
-    HIP_TRY(hipStreamSynchronize(ds->lastStream));
-    HIP_TRY(hipMemcpy(film, ds->film, nFloats * sizeof(float), hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return downloadFilm(scene, ds, ds->picture(), true, film, nFloats);
 }
 int kz_film_download(KzScene *scene, float *film, size_t nFloats) { return kz_film_download_on(scene, -1, film, nFloats); }
 
@@ -378,7 +347,7 @@ int kz_scene_set_aovs(KzScene *scene, uint32_t mask) {
     for (KzDeviceState *ds : v) {                                      // queued work finishes with the sums it was launched with
         HIP_TRY(hipSetDevice(ds->hipDevice));
         HIP_TRY(hipDeviceSynchronize());
-        kzAovFree(ds, scene->aovMask & ~mask);
+        for (int f = 0; f < 3; ++f) if (scene->aovMask & ~mask & (1u << f)) ds->aov(f).free();
     }
     scene->aovMask = mask;
     return KZ_OK;
@@ -394,14 +363,7 @@ int kz_aov_download_on(KzScene *scene, int device, uint32_t aov, float *film, si
         return kz_fail(KZ_ERR_INVALID_ARG, "kz_aov_download: aov %u must be exactly one enabled AOV bit (the scene's mask is %u)", aov, scene->aovMask);
     KzDeviceState *ds; int rc;
     if ((rc = findReplica(scene, device, &ds))) return rc;
-    if (!film || nFloats != ds->filmPixels * 4) return kz_fail(KZ_ERR_INVALID_ARG, "film buffer must hold %zu floats", ds->filmPixels * 4);
-    const int f = aov == KZ_AOV_ALBEDO ? 0 : (aov == KZ_AOV_NORMAL ? 1 : 2);
-    HIP_TRY(hipStreamSynchronize(ds->lastStream));
-    if (!ds->aovTapSums[f] || !ds->aovFilm[f]) { std::memset(film, 0, nFloats * sizeof(float)); return KZ_OK; }      // (enabled, nothing rendered yet)
-    if ((rc = kzAovResolve(scene, ds, f, ds->lastStream))) return rc;
-    HIP_TRY(hipStreamSynchronize(ds->lastStream));
-    HIP_TRY(hipMemcpy(film, ds->aovFilm[f], nFloats * sizeof(float), hipMemcpyDeviceToHost));
-    return KZ_OK;
+    return downloadFilm(scene, ds, ds->aov(aov == KZ_AOV_ALBEDO ? 0 : (aov == KZ_AOV_NORMAL ? 1 : 2)), false, film, nFloats);
 }
 int kz_aov_download(KzScene *scene, uint32_t aov, float *film, size_t nFloats) { return kz_aov_download_on(scene, -1, aov, film, nFloats); }
 
@@ -418,7 +380,7 @@ int kz_aov_info(KzScene *scene, int device, uint64_t *bytes) {
 int kz_film_to_srgb8(KzScene *scene, uint8_t *rgb8, size_t nBytes) {
     KzDeviceState *ds; int rc;
     if ((rc = requireDevice(scene, &ds))) return rc;
-    return kzFilmSrgb8(scene, ds, ds->film, rgb8, nBytes);
+    return kzFilmSrgb8(scene, ds, ds->picture().texels, rgb8, nBytes);
 }
 
 } // extern "C"

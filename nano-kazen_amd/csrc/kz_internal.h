@@ -215,6 +215,10 @@ int kz_build_bvh(const std::vector<KzBuildTri> &in, std::vector<KzNode> &nodes, 
 int kz_collapse_bvh4(const std::vector<KzNode> &nodes, uint32_t rootRef, std::vector<KzNode4> &out, uint32_t &rootRef4, int &stackBound,
                      std::vector<uint32_t> *slotSrc = nullptr);
 
+// kz_multi.cpp: what a scene with feature films enabled refuses (kazen_mi355x_aov.h) - of a render's options the megakernel pipeline, a dealer and packed tile rects
+// (kzAovRefuse), and every call that is the tile-rect gather itself (kzAovRefuseGather). KZ_OK for a scene without AOVs.
+int kzAovRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call);
+int kzAovRefuseGather(const KzScene *scene, const char *call);
 // kz_host.cpp
 int kz_fail(int code, const char *fmt, ...);
 int kzCameraParams(const KzCamera &c, KzParams &p);                     // the camera part of KzParams (pixel beams included)

@@ -20,6 +20,21 @@ static size_t packedFloats(const KzParams &P, const KzTile *tiles, uint32_t nTil
     return n;
 }
 
+// What a scene with feature films enabled refuses (kazen_mi355x_aov.h): of a render's options the megakernel pipeline, a dealer and packed tile rects, and every call
+// that is the tile-rect gather itself. Checked before any replica is looked up.
+#define KZ_NO_AOV_GATHER "the tile-rect gather of AOV films is not built"
+int kzAovRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call) {
+    if (!scene || !scene->aovMask || !opts) return KZ_OK;
+    const char *what = opts->pipeline == 1 ? "KzRenderOpts.pipeline = 1 (the megakernel pipeline renders no AOVs)" : opts->dealer ? "a KzTileDealer (" KZ_NO_AOV_GATHER ")"
+                     : opts->packedOutput ? "KzRenderOpts.packedOutput = 1 (" KZ_NO_AOV_GATHER ")" : nullptr;
+    if (!what) return KZ_OK;
+    return kz_fail(KZ_ERR_UNSUPPORTED, "%s: %s is refused while AOVs are enabled (mask %u) - kz_scene_set_aovs(scene, 0) first", call, what, scene->aovMask);
+}
+int kzAovRefuseGather(const KzScene *scene, const char *call) {
+    if (!scene || !scene->aovMask) return KZ_OK;
+    return kz_fail(KZ_ERR_UNSUPPORTED, "%s: refused while AOVs are enabled (mask %u): " KZ_NO_AOV_GATHER " - kz_scene_set_aovs(scene, 0) first", call, scene->aovMask);
+}
+
 extern "C" {
 
 int kz_deal_tiles(int32_t width, int32_t height, int32_t tileSize, uint32_t nParts, uint32_t part, KzTile *out, uint32_t cap, uint32_t *count) {
@@ -112,7 +127,7 @@ int kz_film_merge_rects(float *film, int32_t width, int32_t height, int32_t bord
 int kz_render_multi(KzScene *scene, const KzRenderOpts *opts, const int32_t *devices, uint32_t nDevices, int32_t tileSize, float *film, size_t nFloats,
                     float *deviceMs) {
     if (!scene || !devices || nDevices == 0 || !film) return kz_fail(KZ_ERR_INVALID_ARG, "kz_render_multi: null argument");
-    if (scene->aovMask) return kz_fail(KZ_ERR_UNSUPPORTED, "kz_render_multi: refused while AOVs are enabled (mask %u): the tile-rect gather of AOV films is not built - kz_scene_set_aovs(scene, 0) first", scene->aovMask);
+    if (const int rc = kzAovRefuseGather(scene, "kz_render_multi")) return rc;
     const KzParams &P = scene->prm;
     const size_t filmFloats = (size_t)(P.width + 2 * P.border) * (size_t)(P.height + 2 * P.border) * 4;
     if (nFloats != filmFloats) return kz_fail(KZ_ERR_INVALID_ARG, "film buffer must hold %zu floats", filmFloats);

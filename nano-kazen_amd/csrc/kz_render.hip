@@ -288,6 +288,7 @@ static int wfCamera(WfLaunch &L, bool beams) {
 // ORDER: tap sums are read-modify-write per pixel and a pixel's samples must arrive in ascending sample order; with passes in flight the pass before this one,
 // on another stream, touches the same pixels. The AOV stages have an event chain of their own (evAov: recorded behind a pass's AOV tap launches, waited for by
 // the next pass's) - waiting for evFilm[prev], which is recorded at the END of the pass before, would serialise the passes.
+static int filmLanes(const KzTune &tune) { return tune.filmGather == 3 ? 1 : 0; }      // kzFilmStage's lanesPerPixel: KzTuning.filmGather = 3 asks for one lane per pixel
 typedef decltype(&kz_wf_aov<0>) KzAovFn;
 static KzAovFn aovFn(int ext) {                      // ext: 0 / KZ_X_MODELS / KZ_X_ALL
     static const KzAovFn tab[3] = {kz_wf_aov<0>, kz_wf_aov<KZ_X_MODELS>, kz_wf_aov<KZ_X_ALL>};
@@ -301,8 +302,13 @@ static int wfAov(KzScene *scene, WfLaunch &L, hipEvent_t waitAov, hipEvent_t rec
     hipLaunchKernelGGL(aovFn(extSel(L.P.bsdfExt, KZ_X_ALL)), grid, L.blk, 0, stream, L.ds->T, W, L.items, scene->aovMask, A);
     HIP_TRY(hipGetLastError());
     if (waitAov) HIP_TRY(hipStreamWaitEvent(stream, waitAov, 0));
-    const int rc = kzAovFilmStage(scene, L.ds, stream, L.pixList, L.items / L.Sp, L.Sp, W.outJx, W.outJy, A, L.tune.filmGather == 3 ? 1 : 0);
-    if (rc) return rc;
+    for (int f = 0; f < 3; ++f) {                       // one kz_film_taps<.., true> launch per enabled AOV, in ascending order
+        if (!(scene->aovMask & (1u << f))) continue;
+        KzFilm &film = L.ds->aov(f);
+        if (!film.sums) return kz_fail(KZ_ERR_STATE, "the tap sums of AOV %u are not there", 1u << f);
+        const float *const plane[5] = {W.outJx, W.outJy, A.p[f], A.p[f] + A.stride, A.p[f] + 2 * A.stride};
+        if (const int rc = kzFilmStage(scene, L.ds, film, true, stream, L.pixList, L.items / L.Sp, L.Sp, plane, nullptr, filmLanes(L.tune))) return rc;
+    }
     if (recordAov) HIP_TRY(hipEventRecord(recordAov, stream));
     return L.mark(4);                                   // (the stage clock books the AOV launches under "film")
 }
@@ -559,14 +565,14 @@ static int launchHalves(PassRun &r, PassCtx &c, hipStream_t pst, EventPair &ep, 
     const size_t itemsA = (size_t)nA * Sp, itemsB = (size_t)nB * Sp;
     PassCtx &va = *c.view[0], &vb = *c.view[1];
     ctxPoint(va, *c.arena, 0); ctxPoint(vb, *c.arena, itemsA);
-    const int lanes = r.tune.filmGather == 3 ? 1 : 0;
+    const int lanes = filmLanes(r.tune);
     HIP_TRY(hipEventRecord(c.evHalfFork, pst)); HIP_TRY(hipStreamWaitEvent(c.halfStream, c.evHalfFork, 0));
     if ((rc = wfPass(scene, ds, va, pst, pixList, s, Sp, (uint32_t)itemsA, r.tune, r.beams, how.beside[0]))) return rc;
     if ((rc = wfPass(scene, ds, vb, c.halfStream, pixList + nA, s, Sp, (uint32_t)itemsB, r.tune, r.beams, how.beside[1]))) return rc;
     ds->lastInfo.shadowBeside = 2u;                                   // (kz_last_pass_info: the last pass ran as halves)
     // the halves' pixels are disjoint, so are their tap sums: the two film stages need no order between them
-    if ((rc = kzFilmStage(scene, ds, va, pst, pixList, nA, Sp, nullptr, lanes))) return rc;
-    if ((rc = kzFilmStage(scene, ds, vb, c.halfStream, pixList + nA, nB, Sp, nullptr, lanes))) return rc;
+    if ((rc = kzFilmStage(scene, ds, ds->picture(), false, pst, pixList, nA, Sp, va.plane, nullptr, lanes))) return rc;
+    if ((rc = kzFilmStage(scene, ds, ds->picture(), false, c.halfStream, pixList + nA, nB, Sp, vb.plane, nullptr, lanes))) return rc;
     if ((rc = stageMark(va, pst, 4))) return rc;
     HIP_TRY(hipEventRecord(c.evHalfJoin, c.halfStream)); HIP_TRY(hipStreamWaitEvent(pst, c.evHalfJoin, 0));
     HIP_TRY(hipEventRecord(ep.b, pst)); HIP_TRY(hipGetLastError());
@@ -601,7 +607,7 @@ static int launchWhole(PassRun &r, PassCtx &c, int ci, hipStream_t pst, EventPai
     HIP_TRY(hipEventRecord(ep.b, pst)); HIP_TRY(hipGetLastError());
     // the film stage adds this pass's samples to the running tap sums of its pixels, behind the film stage of the pass before it (another stream's)
     const int prev = (ci + r.pl.nCtx - 1) % r.pl.nCtx;
-    if ((rc = kzFilmStage(scene, ds, c, pst, pixList, nPixPass, Sp, (r.pl.multi && r.pass > 0) ? ds->evFilm[prev] : nullptr, r.tune.filmGather == 3 ? 1 : 0))) return rc;
+    if ((rc = kzFilmStage(scene, ds, ds->picture(), false, pst, pixList, nPixPass, Sp, c.plane, (r.pl.multi && r.pass > 0) ? ds->evFilm[prev] : nullptr, filmLanes(r.tune)))) return rc;
     return r.pipeline == 2 ? stageMark(c, pst, 4) : KZ_OK;
 }
 
@@ -649,19 +655,9 @@ static int onePass(PassRun &r, uint32_t p0, uint32_t nPixPass, uint32_t s, uint3
     return KZ_OK;
 }
 
-// What a scene with feature films enabled refuses (kazen_mi355x_aov.h): the megakernel pipeline, a dealer and packed tile rects. Checked before any replica is looked up.
-static int aovRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call) {
-    if (!scene || !scene->aovMask || !opts) return KZ_OK;
-    const char *what = opts->pipeline == 1 ? "KzRenderOpts.pipeline = 1 (the megakernel pipeline renders no AOVs)" : opts->dealer ? "a KzTileDealer (the tile-rect gather of AOV films is not built)"
-                     : opts->packedOutput ? "KzRenderOpts.packedOutput = 1 (the tile-rect gather of AOV films is not built)" : nullptr;
-    if (!what) return KZ_OK;
-    return kz_fail(KZ_ERR_UNSUPPORTED, "%s: %s is refused while AOVs are enabled (mask %u) - kz_scene_set_aovs(scene, 0) first", call, what, scene->aovMask);
-}
-
 static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts) {
     int rc;
     const KzParams &P = scene->prm;
-    if ((rc = aovRefuse(scene, opts, "kz_render"))) return rc;
     if (opts->pipeline < 0 || opts->pipeline > 2) return kz_fail(KZ_ERR_INVALID_ARG, "pipeline %d (0 = default, 1 = megakernel, 2 = wavefront)", opts->pipeline);
     if (opts->passesInFlight < 0 || opts->passesInFlight > KZ_MAX_PASSES_IN_FLIGHT)
         return kz_fail(KZ_ERR_INVALID_ARG, "passesInFlight %d (0 = default, 1 .. %d)", opts->passesInFlight, KZ_MAX_PASSES_IN_FLIGHT);
@@ -682,9 +678,10 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     if ((rc = resolveTune(opts->tune, tune))) return rc;
     if (tune.filmGather != 0 && tune.filmGather != 3) return kz_fail(KZ_ERR_UNSUPPORTED, "KzTuning.filmGather %d: the staged gather kernel of round 1 is gone (round 6: the film is resolved from running tap sums for every filter); 0 = default, 3 = one lane per pixel", tune.filmGather);
     if ((rc = prepareTiles(scene, ds, opts->tiles, opts->nTiles, stream))) return rc;
-    // the film: running tap sums of the frame's pixels (kz_film.hip), part of the replica like the film itself - cleared unless the call accumulates
-    { const bool fresh = !ds->tapSums; if ((rc = kzFilmEnsureTapSums(scene, ds, stream))) return rc; if (!opts->accumulate && !fresh) HIP_TRY(hipMemsetAsync(ds->tapSums, 0, ds->tapSums.bytes(), stream)); }
-    if (scene->aovMask && (rc = kzAovEnsure(scene, ds, stream, opts->accumulate != 0))) return rc;      // ... and the feature films' (kazen_mi355x_aov.h)
+    // the films: the picture's running tap sums (kz_film.hip), then those of the enabled feature films (kazen_mi355x_aov.h) in ascending order - part of the replica,
+    // outside the pass contexts' budget, cleared unless the call accumulates
+    if ((rc = kzFilmEnsure(scene, ds->picture(), ds->filmPixels, opts->accumulate != 0, stream))) return rc;
+    for (int f = 0; f < 3; ++f) if ((scene->aovMask & (1u << f)) && (rc = kzFilmEnsure(scene, ds->aov(f), ds->filmPixels, opts->accumulate != 0, stream))) return rc;
     const KzTileDealer *dealer = opts->dealer;
     if (dealer) {
         if (!dealer->counter || (dealer->takenCap && (!dealer->taken || !dealer->nTaken))) return kz_fail(KZ_ERR_INVALID_ARG, "KzTileDealer: null counter / taken buffer");
@@ -738,7 +735,7 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     }
     if (multi)                                                         // join: everything after this call on `stream` sees the film
         for (int i = 0; i < nCtx; ++i) if (r.inFlight[i]) HIP_TRY(hipStreamWaitEvent(stream, ds->evFilm[i], 0));
-    if ((rc = kzFilmResolve(scene, ds, stream))) return rc;           // the film texels from the tap sums: once per call
+    if ((rc = kzFilmResolve(scene, ds->picture(), stream))) return rc;          // the film texels from the tap sums: once per call
     HIP_TRY(hipEventRecord(ds->evCallB, stream));
     // what the call leaves for kz_last_pass_info / kz_last_grow_note
     ds->lastDual = multi;
@@ -755,7 +752,7 @@ extern "C" {
 int kz_render(KzScene *scene, const KzRenderOpts *opts) {
     if (!opts) return kz_fail(KZ_ERR_INVALID_ARG, "null opts");
     KzDeviceState *ds; int rc;
-    if ((rc = aovRefuse(scene, opts, "kz_render"))) return rc;
+    if ((rc = kzAovRefuse(scene, opts, "kz_render"))) return rc;
     // opts->device addresses a replica by HIP device index; a scene resident on ONE device is addressed by any zero-initialised opts
     if ((rc = findReplica(scene, opts->device, &ds))) {
         KzReplicaSet *rs = scene ? replicaSet(scene) : nullptr;
@@ -768,7 +765,7 @@ int kz_render(KzScene *scene, const KzRenderOpts *opts) {
 
 int kz_render_tiles(KzScene *scene, const KzRenderOpts *opts, const KzTile *tiles, uint32_t nTiles, int device, float *film, size_t nFloats) {
     KzDeviceState *ds; int rc;
-    if ((rc = aovRefuse(scene, opts, "kz_render_tiles"))) return rc;
+    if ((rc = kzAovRefuse(scene, opts, "kz_render_tiles"))) return rc;
     if ((rc = findReplica(scene, device, &ds))) return rc;
     const size_t full = ds->filmPixels * 4;
     const bool packedOut = opts && opts->packedOutput;
@@ -786,8 +783,8 @@ int kz_render_tiles(KzScene *scene, const KzRenderOpts *opts, const KzTile *tile
     o.tiles = tiles; o.nTiles = nTiles; o.device = device;
     if ((rc = renderOn(scene, ds, &o))) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)o.stream));
-    if (film && !packedOut) HIP_TRY(hipMemcpy(film, ds->film, nFloats * sizeof(float), hipMemcpyDeviceToHost));
-    else if (film) return downloadTiles(scene, ds, tiles, nTiles, film, nFloats, (hipStream_t)o.stream);
+    if (film && !packedOut) HIP_TRY(hipMemcpy(film, ds->picture().texels, nFloats * sizeof(float), hipMemcpyDeviceToHost));
+    else if (film) return downloadTiles(scene, ds, ds->picture(), tiles, nTiles, film, nFloats, (hipStream_t)o.stream);
     return KZ_OK;
 }
 

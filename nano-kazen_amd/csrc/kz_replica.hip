@@ -151,8 +151,8 @@ static int uploadReplica(KzScene *scene, KzDeviceState *ds) {
     const KzParams &P = scene->prm;
     ds->filmPixels = (size_t)(P.width + 2 * P.border) * (size_t)(P.height + 2 * P.border);
     KZ_TRACE("upload: small tables there");
-    if ((rc = ds->film.alloc(ds->filmPixels))) return rc;
-    HIP_TRY(hipMemset(ds->film, 0, ds->filmPixels * sizeof(float4)));
+    if ((rc = ds->picture().texels.alloc(ds->filmPixels))) return rc;      // (the picture's sums: its first render)
+    HIP_TRY(hipMemset(ds->picture().texels, 0, ds->filmPixels * sizeof(float4)));
     if ((rc = ds->stats.alloc(32))) return rc;                         // 8 counters of KzStats + 16 lane statistics of the -DKZ_LANESTAT development build + 3 beam-list counters
     HIP_TRY(hipMemset(ds->stats, 0, 32 * sizeof(unsigned long long)));
     { hipDeviceProp_t prop; HIP_TRY(hipGetDeviceProperties(&prop, ds->hipDevice)); ds->numCU = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256; ds->totalMem = prop.totalGlobalMem; }
@@ -205,10 +205,9 @@ int prepareTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32_
     std::vector<uint32_t> offs(nTiles + 1);
     bool grid = true;
     uint64_t total = 0;
+    if (const int rc = checkTiles(P, tiles, nTiles)) return rc;
     for (uint32_t t = 0; t < nTiles; ++t) {
         const KzTile &tl = tiles[t];
-        if (tl.x0 < 0 || tl.y0 < 0 || tl.w <= 0 || tl.h <= 0 || tl.x0 + tl.w > P.width || tl.y0 + tl.h > P.height)
-            return kz_fail(KZ_ERR_INVALID_ARG, "tile %u (%d,%d %dx%d) outside the %dx%d image", t, tl.x0, tl.y0, tl.w, tl.h, P.width, P.height);
         if ((tl.x0 & 7) || (tl.y0 & 7) || ((tl.w & 7) && tl.x0 + tl.w != P.width) || ((tl.h & 7) && tl.y0 + tl.h != P.height)) grid = false;
         desc[t] = KzTileDesc{tl.x0, tl.y0, tl.w, tl.h, (uint32_t)total};
         offs[t] = (uint32_t)total;

@@ -3,7 +3,8 @@
 //   kz_render.hip   a pass: every path kernel (kz_wavefront.h, the megakernel) and the tables that pick them, pass contexts' buffers, wfPass, renderOn, kz_render*
 //   kz_replica.hip  replicas: lifetime + upload, tile sets (prepareTiles), the queries that only read replica state (kz_last_*, kz_pass_mode_info, kz_sync*, stats)
 //   kz_refit.hip    device side of the edits of a resident scene (kz_refit.h)
-//   kz_film.hip     film reconstruction kernels + their launcher, tile packing / download, kz_film_* entry points
+//   kz_film.hip     film reconstruction kernels + their launchers, each taking the film (kz_film.h: KzFilm, the picture or a feature film) it works on, tile packing /
+//                   download, the kz_film_* entry points and those of kazen_mi355x_aov.h that only touch replica state
 //   kz_denoise.hip  the a-trous denoiser of include/kazen_mi355x_denoise.h: its kernels, the replica's denoise buffers, kz_denoise* entry points
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
@@ -11,7 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kz_internal.h"
-#include "kz_own.h"
+#include "kz_film.h"
 #include "kz_plan.h"
 
 #include <atomic>
@@ -178,12 +179,13 @@ struct KzDeviceState {
     DevBuf<float> cdf, pmj, bn, pixelSamples, filter; DevBuf<KzPcgJump> jump;
     DevBuf<KzTexProg> texProgs; DevBuf<KzTexOp> texOps; DevBuf<KzImageRow> images; DevBuf<uint8_t> texels;
     bool bvh2Resident = false;
-    DevBuf<float4> film; size_t filmPixels = 0;
-    DevBuf<float4> tapSums;                                      // the running tap sums of every pixel of the frame, [tap][y * width + x] (kz_film.hip): what the film is resolved from
-    // Feature films (kazen_mi355x_aov.h; kz_film.hip): per AOV - albedo, normal, depth - running tap sums and a film like the picture's, there from the first render
-    // with the AOV enabled; evAov[i]: the AOV tap launches of the pass last run in context i (the chain passes in flight order their AOV stages by, wfPass)
-    DevBuf<float4> aovTapSums[3], aovFilm[3]; Event evAov[KZ_MAX_PASSES_IN_FLIGHT];
-    size_t aovBytes() const { size_t b = 0; for (int f = 0; f < 3; ++f) b += aovTapSums[f].bytes() + aovFilm[f].bytes(); return b; }
+    // The films (kz_film.h): [0] the picture - its texels there from the upload, its sums from the first render -, [1 + f] the feature film of AOV f (kazen_mi355x_aov.h:
+    // 0 albedo, 1 normal, 2 depth), there from the first render with the AOV enabled. filmPixels: the texels of each. evAov[i]: the AOV tap launches of the pass last
+    // run in context i (the chain passes in flight order their AOV stages by, wfPass)
+    KzFilm films[4]; size_t filmPixels = 0; Event evAov[KZ_MAX_PASSES_IN_FLIGHT];
+    KzFilm &picture() { return films[0]; }
+    KzFilm &aov(int f) { return films[1 + f]; }
+    size_t aovBytes() const { return films[1].bytes() + films[2].bytes() + films[3].bytes(); }
     DevBuf<uint8_t> srgb;                                        // staging raster of kz_film_to_srgb8 / kz_denoise_to_srgb8 (allocated on first use)
     // The denoiser (kazen_mi355x_denoise.h; kz_denoise.hip), allocated by the first kz_denoise outside the pass contexts' budget: frame-sized planes without an
     // apron - the colour plane (e.rgb, valid) twice, the iterations ping-pong between the two; (n.xyz, z); (a.rgb, -) - and the result, laid out like the film.
@@ -242,24 +244,17 @@ static inline int requireDevice(KzScene *scene, KzDeviceState **out) { return fi
 // kz_film.hip
 size_t packedFloats(const KzParams &P, const KzTile *tiles, uint32_t nTiles);
 int checkTiles(const KzParams &P, const KzTile *tiles, uint32_t nTiles);
-int downloadTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32_t nTiles, float *packed, size_t nFloats, hipStream_t stream);
-// The film (kz_film.hip): running tap sums per frame pixel, fed by every pass (kzFilmStage: ImageBlock::put for the sample records of the pass, launched on `pst` behind
-// `waitFilm`), resolved into the film texels once per call (kzFilmResolve).
+int downloadTiles(KzScene *scene, KzDeviceState *ds, KzFilm &film, const KzTile *tiles, uint32_t nTiles, float *packed, size_t nFloats, hipStream_t stream);      // the rects of `film`
+// The film machine (kz_film.hip), each function for the film it is handed: kzFilmEnsure before the passes of a call (KzFilm::ensure with the scene's geometry), kzFilmStage
+// after every pass (ImageBlock::put for the pass's sample records - five planes jx | jy | r | g | b - into the film's running tap sums, launched on `pst` behind `waitFilm`;
+// isSigned: a feature film's values, which may be negative), kzFilmResolve once per call and wherever a feature film is read (the texels from the sums).
 #define KZ_FILM_GRID 64                      // the canonical tile grid of the resolve = kz_deal_tiles' default tile: the film of one device equals the host merge of its tiles' rects bit for bit
-int kzFilmEnsureTapSums(KzScene *scene, KzDeviceState *ds, hipStream_t stream);
-int kzFilmClear(KzDeviceState *ds, hipStream_t stream);
-int kzFilmStage(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, hipEvent_t waitFilm, int lanesPerPixel);
-int kzFilmResolve(KzScene *scene, KzDeviceState *ds, hipStream_t stream);
-// The feature films (kazen_mi355x_aov.h): kzAovEnsure before the passes of a call (sums and films of the enabled AOVs there, cleared unless the call accumulates),
-// kzAovFilmStage inside a pass (one kz_film_taps launch per enabled AOV from the pass's jitter planes and the feature planes kz_wf_aov wrote), kzAovFree when an
-// AOV leaves the mask or the replica goes.
+int kzFilmEnsure(KzScene *scene, KzFilm &film, size_t filmPixels, bool accumulate, hipStream_t stream);
+int kzFilmClear(KzDeviceState *ds, hipStream_t stream);          // every film of the replica: the picture's sums and texels, then each feature film's
+int kzFilmStage(KzScene *scene, KzDeviceState *ds, KzFilm &film, bool isSigned, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *const plane[5], hipEvent_t waitFilm, int lanesPerPixel);
+int kzFilmResolve(KzScene *scene, KzFilm &film, hipStream_t stream);
 // The float planes a pass's features go to: three per feature (p[0] albedo, p[1] normal, p[2] depth replicated), `stride` floats apart. They alias the shadow
 // arrays of the pass context (wfAov, kz_render.hip), which are dead between the camera stage and the first shade / ao / mats launch.
 struct KzAovPlanes { float *p[3]; size_t stride; };
-int kzAovEnsure(KzScene *scene, KzDeviceState *ds, hipStream_t stream, bool accumulate);
-int kzAovFilmStage(KzScene *scene, KzDeviceState *ds, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *jx, const float *jy, const KzAovPlanes &planes, int lanesPerPixel);
-void kzAovFree(KzDeviceState *ds, uint32_t mask);
-// The film of AOV f (0 albedo, 1 normal, 2 depth) from its tap sums, on `stream`: what kz_aov_download copies out and kz_denoise reads. The AOV has been rendered (sums and film are there).
-int kzAovResolve(KzScene *scene, KzDeviceState *ds, int f, hipStream_t stream);
 // The 8-bit sRGB raster of a film-shaped device buffer of the replica (kz_film_srgb8 on ds->lastStream, through ds->srgb): kz_film_to_srgb8 and kz_denoise_to_srgb8
 int kzFilmSrgb8(KzScene *scene, KzDeviceState *ds, const float4 *film, uint8_t *rgb8, size_t nBytes);

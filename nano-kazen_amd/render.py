@@ -201,14 +201,11 @@ class Scene:
         o, _ = self._opts(sample_begin, sample_end, **kw)
         arr = (abi.KzTile * len(tiles))(*[abi.KzTile(*t) for t in tiles])
         dev = (self.device or 0) if device is None else int(device)
-        n = self.packed_floats(tiles) if packed else (self.height + 2 * self.border) * (self.width + 2 * self.border) * 4
         o.packedOutput = 1 if packed else 0
-        out = np.empty(n, np.float32) if (download or packed) else None
+        out = np.empty(self.packed_floats(tiles), np.float32) if packed else self._film_out()[0] if download else None
         abi.check(self.lib, self.lib.kz_render_tiles(self.h, C.byref(o), arr, len(tiles), dev,
-                                                      out.ctypes.data_as(abi.f32p) if out is not None else None, n if out is not None else 0))
-        if out is None or packed:
-            return out
-        return out.reshape(self.height + 2 * self.border, self.width + 2 * self.border, 4)
+                                                      out.ctypes.data_as(abi.f32p) if out is not None else None, out.size if out is not None else 0))
+        return out
 
     def render_dealt(self, tiles, counter, takers=1, batch_tiles=0, device=None, sample_begin=0, sample_end=0, **kw):
         """kz_render_tiles with a KzTileDealer: `tiles` is the WHOLE list every taker passes, `counter` a numpy uint32 array of one element that all
@@ -266,22 +263,29 @@ class Scene:
         abi.check(self.lib, self.lib.kz_film_merge_rects(film.ctypes.data_as(abi.f32p), self.width, self.height, self.border, arr, ptrs, n, int(threads)))
         return film
 
+    def _film_shape(self):
+        return (self.height + 2 * self.border, self.width + 2 * self.border, 4)       # the frame with its filter apron, (rgb * w, w) per texel
+
     def empty_film(self):
-        return np.zeros((self.height + 2 * self.border, self.width + 2 * self.border, 4), np.float32)
+        return np.zeros(self._film_shape(), np.float32)
+
+    def _film_out(self):
+        """An uninitialised film for a download to fill: (the array, its float pointer, its number of floats)."""
+        out = np.empty(self._film_shape(), np.float32)
+        return out, out.ctypes.data_as(abi.f32p), out.size
 
     def render_multi(self, devices, tile_size=0, sample_begin=0, sample_end=0, **kw):
         """kz_render_multi: one host thread per device, tiles dealt by area, films summed on the host in device order.
         Returns (film, per-device ms)."""
         o, _ = self._opts(sample_begin, sample_end, **kw)
         devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
-        n = (self.height + 2 * self.border) * (self.width + 2 * self.border) * 4
-        out = np.empty(n, np.float32)
+        out, ptr, n = self._film_out()
         ms = np.zeros(len(devices), np.float32)
-        abi.check(self.lib, self.lib.kz_render_multi(self.h, C.byref(o), devs, len(devices), int(tile_size), out.ctypes.data_as(abi.f32p), n,
+        abi.check(self.lib, self.lib.kz_render_multi(self.h, C.byref(o), devs, len(devices), int(tile_size), ptr, n,
                                                       ms.ctypes.data_as(abi.f32p)))
         if self.device is None:
             self.device = int(devices[0])
-        return out.reshape(self.height + 2 * self.border, self.width + 2 * self.border, 4), ms
+        return out, ms
 
     def last_pass_info(self):
         info = abi.KzPassInfo()
@@ -307,10 +311,9 @@ class Scene:
         abi.check(self.lib, self.lib.kz_sync(self.h))
 
     def film(self):
-        n = (self.height + 2 * self.border) * (self.width + 2 * self.border) * 4
-        out = np.empty(n, np.float32)
-        abi.check(self.lib, self.lib.kz_film_download(self.h, out.ctypes.data_as(abi.f32p), n))
-        return out.reshape(self.height + 2 * self.border, self.width + 2 * self.border, 4)
+        out, ptr, n = self._film_out()
+        abi.check(self.lib, self.lib.kz_film_download(self.h, ptr, n))
+        return out
 
     def film_clear(self, stream=None):
         abi.check(self.lib, self.lib.kz_film_clear(self.h, stream))
@@ -399,13 +402,12 @@ class Scene:
 
     def aov_film(self, name, device=None):
         """kz_aov_download[_on]: the AOV's film, (h + 2b, w + 2b, 4) = (value * w, w) like film()."""
-        n = (self.height + 2 * self.border) * (self.width + 2 * self.border) * 4
-        out = np.empty(n, np.float32)
+        out, ptr, n = self._film_out()
         if device is None:
-            abi.check(self.lib, self.lib.kz_aov_download(self.h, self._aov_mask(name), out.ctypes.data_as(abi.f32p), n))
+            abi.check(self.lib, self.lib.kz_aov_download(self.h, self._aov_mask(name), ptr, n))
         else:
-            abi.check(self.lib, self.lib.kz_aov_download_on(self.h, int(device), self._aov_mask(name), out.ctypes.data_as(abi.f32p), n))
-        return out.reshape(self.height + 2 * self.border, self.width + 2 * self.border, 4)
+            abi.check(self.lib, self.lib.kz_aov_download_on(self.h, int(device), self._aov_mask(name), ptr, n))
+        return out
 
     def aov(self, name, device=None):
         """The AOV's values, (h, w, 3): its film divided by the filter weight (kz_film_to_rgb); depth is replicated into the three channels."""
@@ -438,10 +440,9 @@ class Scene:
 
     def denoised_film(self, device=None):
         """kz_denoise_download: (h + 2b, w + 2b, 4) = (rgb, 1) in the frame pixels that had samples, zeros elsewhere - rgb() and the writers of output.py take it like film()."""
-        n = (self.height + 2 * self.border) * (self.width + 2 * self.border) * 4
-        out = np.empty(n, np.float32)
-        abi.check(self.lib, self.lib.kz_denoise_download(self.h, -1 if device is None else int(device), out.ctypes.data_as(abi.f32p), n))
-        return out.reshape(self.height + 2 * self.border, self.width + 2 * self.border, 4)
+        out, ptr, n = self._film_out()
+        abi.check(self.lib, self.lib.kz_denoise_download(self.h, -1 if device is None else int(device), ptr, n))
+        return out
 
     def denoised_srgb8(self, device=None):
         """kz_denoise_to_srgb8: (h, w, 3) uint8, the raster srgb8() makes of the film, of the denoised picture."""

@@ -1,5 +1,5 @@
 #!/bin/sh
-# Did the compiled device code stay? Compiles the device side of the five device units of the working tree and of another revision with build.sh's flags
+# Did the compiled device code stay? Compiles the device side of the six device units of the working tree and of another revision with build.sh's flags
 # (plain and -DKZ_EXPERIMENTS), disassembles the gfx950 code objects and compares them kernel by kernel. Needs no GPU.
 #   scripts/device_code_diff.sh <git-rev>
 # Prints the kernels whose instructions differ - their own, or those of a device function they call (pathLi, matsLi, the texture filters ...) - with the
@@ -30,7 +30,7 @@ for build in plain exp; do
     for side in this rev; do
         [ $side = this ] && TREE=$ROOT || TREE=$WT
         for u in kz_render kz_replica kz_film kz_debug; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fgpu-flush-denormals-to-zero -fno-slp-vectorize" & PIDS="$PIDS $!"; done
-        one $side "$TREE" $build kz_refit "--offload-arch=gfx950 -fno-slp-vectorize" & PIDS="$PIDS $!"
+        for u in kz_refit kz_denoise; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fno-slp-vectorize" & PIDS="$PIDS $!"; done      # (build.sh's IEEE units: no flush to zero)
     done
 done
 FAILED=0
@@ -88,7 +88,7 @@ def demangle(names):
 
 differing = 0
 for build in ("plain", "exp"):
-    for unit in ("kz_render", "kz_replica", "kz_film", "kz_debug", "kz_refit"):
+    for unit in ("kz_render", "kz_replica", "kz_film", "kz_debug", "kz_refit", "kz_denoise"):
         a, b = "%s/this.%s.%s" % (out, build, unit), "%s/rev.%s.%s" % (out, build, unit)
         (fa, ka), (fb, kb) = functions(a), functions(b)
         ra, rb = resources(a + ".rem"), resources(b + ".rem")

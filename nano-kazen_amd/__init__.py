@@ -5,4 +5,4 @@ product is csrc/ (hand-written HIP for gfx950 + host BVH builder + the C-ABI shi
 Import with importlib.import_module("nano-kazen_amd") (the directory name has a hyphen).
 """
 from . import abi, output, scenes, shard, xmlscene     # noqa: F401
-from .render import Scene, denoise_films, denoise_opts            # noqa: F401
+from .render import Scene, denoise_films, denoise_opts, denoise_variance_films, variance_opts      # noqa: F401

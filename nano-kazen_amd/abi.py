@@ -215,6 +215,11 @@ class KzDenoiseOpts(C.Structure):
                 ("sigmaColor", C.c_float), ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float), ("sigmaAlbedo", C.c_float)]
 
 
+class KzVarianceOpts(C.Structure):
+    # include/kazen_mi355x_variance.h: 16 bytes, a zero field means its default
+    _fields_ = [("sigmaVariance", C.c_float), ("samples", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class KzBvhInfo(C.Structure):
     _fields_ = [("nNodes", C.c_uint32), ("nLeaves", C.c_uint32), ("nTris", C.c_uint32), ("maxDepth", C.c_uint32),
                 ("maxLeafSize", C.c_uint32), ("sahCost", C.c_float), ("buildSeconds", C.c_double)]
@@ -241,6 +246,9 @@ AOV_BITS = {"albedo": KZ_AOV_ALBEDO, "normal": KZ_AOV_NORMAL, "depth": KZ_AOV_DE
 # what include/kazen_mi355x_denoise.h declares (checked by tests/test_denoise_cpu.py): the picture denoised on the device, guided by its feature films
 DENOISE_EXPORTS = ["kz_denoise", "kz_denoise_on", "kz_denoise_download", "kz_denoise_to_srgb8", "kz_denoise_info", "kz_denoise_release", "kz_denoise_films"]
 KZ_DENOISE_NO_DEMODULATE, KZ_DENOISE_NO_GUIDES, KZ_DENOISE_MAX_ITERATIONS = 1, 2, 8
+# what include/kazen_mi355x_variance.h declares (checked by tests/test_variance_cpu.py): a second-moment film beside the picture's and the denoiser guided by its variance
+VARIANCE_EXPORTS = ["kz_scene_set_variance", "kz_scene_variance", "kz_variance_download", "kz_variance_info", "kz_denoise_variance", "kz_denoise_variance_films"]
+KZ_VARIANCE_OFF, KZ_VARIANCE_ON, KZ_VARIANCE_TWO_LAUNCHES, KZ_VARIANCE_ONE_PASS = 0, 1, 2, 3
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead", "kz_debug_shadow_order"]
@@ -353,6 +361,13 @@ def load_library(path=None):
         lib.kz_denoise_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
         lib.kz_denoise_release.argtypes = [C.c_void_p, C.c_int]
         lib.kz_denoise_films.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, C.POINTER(KzDenoiseOpts), f32p]
+    if hasattr(lib, "kz_denoise_variance"):       # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_scene_set_variance.argtypes = [C.c_void_p, C.c_int32]
+        lib.kz_scene_variance.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        lib.kz_variance_download.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
+        lib.kz_variance_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), u32p]
+        lib.kz_denoise_variance.argtypes = [C.c_void_p, C.c_int, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts)]
+        lib.kz_denoise_variance_films.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts), f32p, f32p]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

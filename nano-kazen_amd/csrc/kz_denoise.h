@@ -15,10 +15,24 @@
 //   result = demodulate ? e_last * dnMax(a, 1e-3f) : e_last, weight 1; (0, 0, 0, 0) where the pixel is not valid and in the apron   (kz_dn_finish)
 // The constants kc (per iteration: sigmaColor halves), kn, kz, ka = 1.0f / (sigma * sigma) are computed on the host (kz_denoise.hip dnPlan).
 #pragma once
+#include "../../include/kazen_mi355x_denoise.h"
 #include "kz_crmath.h"
 
 // One iteration's constants, by value to the kernel
 struct KzDnIter { int width, height, step; float kc, kn, kz, ka; };
+
+#define KZ_DN_BLOCK 256
+#define KZ_DN_ROW 64                  // pixels of a row per block (one wave), KZ_DN_BLOCK / KZ_DN_ROW rows
+// The a-trous form per step (measured): the LDS-tile kernel for the steps up to KZ_DN_LDS_MAX_STEP, the direct-gather kernel beyond. 0 builds the
+// direct form alone (scripts/denoise_rates.py and scripts/variance_rates.py time the two side by side); the results are the same bits.
+#ifndef KZ_DN_LDS_MAX_STEP
+#define KZ_DN_LDS_MAX_STEP 2
+#endif
+static_assert(KZ_DN_LDS_MAX_STEP == 0 || KZ_DN_LDS_MAX_STEP == 1 || KZ_DN_LDS_MAX_STEP == 2, "the LDS-tile kernel is built for the steps 1 and 2");
+
+// Host side, shared by kz_denoise.hip and kz_variance.hip: what a call does, from its options (dnPlan, kz_denoise.hip)
+struct KzDnPlan { uint32_t iterations, guides; bool demodulate, guided; float kc[KZ_DENOISE_MAX_ITERATIONS], kn, kz, ka; };
+int dnPlan(const KzDenoiseOpts *opts, uint32_t avail, const char *call, KzDnPlan *plan, float defaultSigmaColor = 1.0f);
 
 #define KZ_DN_FN __device__ __forceinline__
 KZ_DN_FN float dnMax(float a, float b) { return a > b ? a : b; }
@@ -54,4 +68,43 @@ KZ_DN_FN void dnTap(const KzDnIter &I, float hh, const float4 &ep, const float4 
     const float wgt = hh * dnExp(-arg);
     nr += wgt * eq.x; ng += wgt * eq.y; nb += wgt * eq.z;
     den += wgt;
+}
+
+// ---- the variance-guided filter of include/kazen_mi355x_variance.h, stated once for the device. Everything not restated here is the definition above. ----
+// The colour plane's fourth float holds v, the variance estimate of the pixel's (demodulated) colour, and a NEGATIVE value (-1) where the pixel is not valid: a tap's
+// v(q) arrives with the 16 bytes the tap loads anyway, and the call needs no plane beyond kz_denoise's.
+//   s = dnValue(moment), c = dnValue(picture), n = (float)samples:  var_k = dnMax(s_k - c_k * c_k, 0) / n                                  (kz_dn_prepare_var)
+//   v_0 = demodulate ? (var_r / (am_r * am_r) + var_g / (am_g * am_g)) + var_b / (am_b * am_b) : (var_r + var_g) + var_b
+//   one iteration at a valid pixel p (kz_dn_atrous_var[_lds]):
+//       gn = gd = 0; dy = -1..1 outer, dx = -1..1 inner, q = p + (dx, dy) inside the frame and valid: gn += dnK(dy) * dnK(dx) * v(q), gd += dnK(dy) * dnK(dx)   (dnPrefilter)
+//       kv = 1.0f / (sv2 * (gn / gd) + 1e-12f), kcv = dnMax(kc, kv)          sv2 = sigmaVariance * sigmaVariance, formed on the host                 (dnTolerance)
+//       per tap: dnTap's arg with kcv in the place of kc; additionally nv += (wgt * wgt) * v(q)                                                      (dnTapVar)
+//       e'(p) = num / den, v'(p) = nv / (den * den)
+//   result as kz_dn_finish's; v_last of a valid pixel beside it (kz_dn_finish_var)
+KZ_DN_FN bool dnValidVar(const float4 &e) { return !(e.w < 0.f); }
+// the 3 x 3 prefilter's weights: k[|d|] for d = -1..1; the products are exact
+KZ_DN_FN float dnK(int d) { return d == 0 ? 0.5f : 0.25f; }
+KZ_DN_FN void dnPrefilter(int dy, int dx, float vq, float &gn, float &gd) { const float kk = dnK(dy) * dnK(dx); gn += kk * vq; gd += kk; }
+KZ_DN_FN float dnTolerance(float kc, float sv2, float gn, float gd) {
+    const float g = gn / gd;
+    const float kv = 1.0f / (sv2 * g + 1e-12f);
+    return dnMax(kc, kv);
+}
+template <bool GUIDED>
+KZ_DN_FN void dnTapVar(const KzDnIter &I, float kcv, float hh, const float4 &ep, const float4 &eq, const float4 &gp, const float4 &gq, const float4 &ap, const float4 &aq,
+                       float &nr, float &ng, float &nb, float &den, float &nv) {
+    const float dc = dnSq(eq.x - ep.x, eq.y - ep.y, eq.z - ep.z);
+    float arg = dc * kcv;
+    if (GUIDED) {
+        const float dn = dnSq(gq.x - gp.x, gq.y - gp.y, gq.z - gp.z);
+        const float da = dnSq(aq.x - ap.x, aq.y - ap.y, aq.z - ap.z);
+        const float m = dnMax(dnMax(gp.w, gq.w), 1e-20f);
+        const float t = (gq.w - gp.w) / m;
+        const float dz = t * t;
+        arg = ((arg + dn * I.kn) + dz * I.kz) + da * I.ka;
+    }
+    const float wgt = hh * dnExp(-arg);
+    nr += wgt * eq.x; ng += wgt * eq.y; nb += wgt * eq.z;
+    den += wgt;
+    nv += (wgt * wgt) * eq.w;
 }

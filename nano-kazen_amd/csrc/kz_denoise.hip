@@ -18,9 +18,6 @@
 #include <cmath>
 #include <cstring>
 
-#define KZ_DN_BLOCK 256
-#define KZ_DN_ROW 64                  // pixels of a row per block (one wave), KZ_DN_BLOCK / KZ_DN_ROW rows
-
 __global__ __launch_bounds__(KZ_DN_BLOCK) void kz_dn_prepare(int width, int height, int border, const float4 *__restrict__ film, const float4 *__restrict__ albedo,
                                                              const float4 *__restrict__ normal, const float4 *__restrict__ depth, int demodulate,
                                                              float4 *__restrict__ colour, float4 *__restrict__ normalZ, float4 *__restrict__ albedoP) {
@@ -35,13 +32,6 @@ __global__ __launch_bounds__(KZ_DN_BLOCK) void kz_dn_prepare(int width, int heig
     normalZ[i] = make_float4(n.x, n.y, n.z, z.x);
     albedoP[i] = make_float4(a.x, a.y, a.z, 0.f);
 }
-
-// The a-trous form per step (measured): the LDS-tile kernel for the steps up to KZ_DN_LDS_MAX_STEP, the direct-gather kernel beyond. 0 builds the
-// direct form alone (scripts/denoise_rates.py times the two side by side); the results are the same bits.
-#ifndef KZ_DN_LDS_MAX_STEP
-#define KZ_DN_LDS_MAX_STEP 2
-#endif
-static_assert(KZ_DN_LDS_MAX_STEP == 0 || KZ_DN_LDS_MAX_STEP == 1 || KZ_DN_LDS_MAX_STEP == 2, "the LDS-tile kernel is built for the steps 1 and 2");
 
 // The direct-gather form: lane (x, y) loads its 25 taps from the planes (the rows of a wave's taps are contiguous; L1 / L2 serve the 25-fold reuse)
 template <bool GUIDED>
@@ -137,10 +127,9 @@ __global__ __launch_bounds__(KZ_DN_BLOCK) void kz_dn_finish(int width, int heigh
 }
 
 // ---- host side ----
-// What a call does, from its options: `avail` = the guides there are (the scene's mask / the films given to kz_denoise_films)
-struct KzDnPlan { uint32_t iterations, guides; bool demodulate, guided; float kc[KZ_DENOISE_MAX_ITERATIONS], kn, kz, ka; };
-
-static int dnPlan(const KzDenoiseOpts *opts, uint32_t avail, const char *call, KzDnPlan *plan) {
+// What a call does, from its options (KzDnPlan, kz_denoise.h): `avail` = the guides there are (the scene's mask / the films given to kz_denoise_films);
+// defaultSigmaColor: 1.0 for kz_denoise, 2.0 for kz_denoise_variance (kz_variance.hip)
+int dnPlan(const KzDenoiseOpts *opts, uint32_t avail, const char *call, KzDnPlan *plan, float defaultSigmaColor) {
     static const KzDenoiseOpts defaults = {};
     const KzDenoiseOpts &o = opts ? *opts : defaults;
     if (o.iterations > KZ_DENOISE_MAX_ITERATIONS) return kz_fail(KZ_ERR_INVALID_ARG, "%s: iterations = %u (1 .. %u; 0: the default, 5)", call, o.iterations, KZ_DENOISE_MAX_ITERATIONS);
@@ -149,7 +138,7 @@ static int dnPlan(const KzDenoiseOpts *opts, uint32_t avail, const char *call, K
     if (o.guides & ~avail) return kz_fail(KZ_ERR_INVALID_ARG, "%s: guides = %u is not a subset of the AOVs there are (mask %u)", call, o.guides, avail);
     const float sig[4] = {o.sigmaColor, o.sigmaNormal, o.sigmaDepth, o.sigmaAlbedo};
     static const char *const names[4] = {"sigmaColor", "sigmaNormal", "sigmaDepth", "sigmaAlbedo"};
-    static const float dflt[4] = {1.0f, 0.3f, 0.1f, 0.1f};
+    const float dflt[4] = {defaultSigmaColor, 0.3f, 0.1f, 0.1f};
     float s[4];
     for (int k = 0; k < 4; ++k) {
         if (!(std::isfinite(sig[k]) && sig[k] >= 0.f)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: %s = %g must be finite and > 0 (0: the default, %g)", call, names[k], (double)sig[k], (double)dflt[k]);

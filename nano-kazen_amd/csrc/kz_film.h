@@ -1,6 +1,6 @@
 // kz_film.h - one film of a replica: the running tap sums of every pixel of the frame, [tap][y * width + x], and the film texels resolved from them. A replica
-// keeps four of identical construction - the picture and the albedo, normal and depth feature films (kazen_mi355x_aov.h) -, all fed by kz_film_taps and resolved
-// by kz_film_resolve (kz_film.hip). What a film is made of arrives as plain numbers: nSums = taps x taps x the frame's pixels, nTexels = the frame's texels with
+// keeps five of identical construction - the picture, the albedo, normal and depth feature films (kazen_mi355x_aov.h) and the second-moment film
+// (kazen_mi355x_variance.h) -, all fed by kz_film_taps (the last by its restatement kz_film_taps_moment, kz_film_moment.hip) and resolved by kz_film_resolve (kz_film.hip). What a film is made of arrives as plain numbers: nSums = taps x taps x the frame's pixels, nTexels = the frame's texels with
 // its filter apron (KzDeviceState::filmPixels). Host code only, like kz_own.h: a plain C++ program can exercise it against stand-ins (tests/host_cpp/film_test.cpp).
 #pragma once
 #include "kz_own.h"

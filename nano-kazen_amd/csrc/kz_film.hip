@@ -1,6 +1,7 @@
 // kz_film.hip - the film: deterministic ImageBlock::put (block.cpp:56-96) as HIP kernels for gfx950, the packing / download of tile rects
 // (the device half of the multi-GPU gather), the 8-bit sRGB resolve, and the kz_film_* entry points.
 #include "kz_state.h"
+#include "../../include/kazen_mi355x_variance.h"
 
 #include <algorithm>
 #include <atomic>
@@ -31,8 +32,6 @@
 // The weights are formed block-relative exactly as the reference does (32x32 blocks at multiples of KAZEN_BLOCK_SIZE), so they are bit-identical to
 // ImageBlock::put; only the order of the float additions is the build's own (fixed) one.
 // ============================================================================================
-#define KZ_TAPS_CHUNK1 8                     // samples per staging round with one lane per pixel (32-B pieces of every sample row; round 2's kernel)
-#define KZ_TAPS_CHUNK 16                     // ... with several lanes per pixel: 64-B pieces = whole HBM sectors (profiles/r05h_film_taps)
 // GROUPS lane groups share a pixel: group g carries the tap ROWS [g * R0, g * R0 + R0) of its 64 / GROUPS pixels, R0 = ceil(TAPS / GROUPS). Every accumulator
 // receives the same products in the same (sample) order whatever GROUPS is; what is paid for more groups is the per-sample set-up (validity, footprint, the
 // x weights) once per group. TAPS <= 5 (every default of the reference): two groups - 15 and 10 accumulators instead of 25, 10.5 KB of staging per wave
@@ -199,7 +198,8 @@ int kzFilmEnsure(KzScene *scene, KzFilm &film, size_t filmPixels, bool accumulat
 }
 
 int kzFilmClear(KzDeviceState *ds, hipStream_t stream) {
-    for (KzFilm &film : ds->films) if (const int rc = film.clear(stream)) return rc;      // the picture, then the feature films
+    for (KzFilm &film : ds->films) if (const int rc = film.clear(stream)) return rc;      // the picture, then the feature films, then the second-moment film
+    ds->pictureSamples = ds->momentSamples = 0;
     return KZ_OK;
 }
 
@@ -305,7 +305,7 @@ int kz_tiles_packed_floats(const KzScene *scene, const KzTile *tiles, uint32_t n
 
 int kz_film_download_tiles(KzScene *scene, int device, const KzTile *tiles, uint32_t nTiles, float *packed, size_t nFloats) {
     KzDeviceState *ds; int rc;
-    if ((rc = kzAovRefuseGather(scene, "kz_film_download_tiles")) || (rc = findReplica(scene, device, &ds))) return rc;
+    if ((rc = kzAovRefuseGather(scene, "kz_film_download_tiles")) || (rc = kzVarianceRefuseGather(scene, "kz_film_download_tiles")) || (rc = findReplica(scene, device, &ds))) return rc;
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     return downloadTiles(scene, ds, ds->picture(), tiles, nTiles, packed, nFloats, ds->lastStream);
 }
@@ -372,6 +372,42 @@ int kz_aov_info(KzScene *scene, int device, uint64_t *bytes) {
     if (!bytes) return kz_fail(KZ_ERR_INVALID_ARG, "null bytes");
     if ((rc = findReplica(scene, device, &ds))) return rc;
     *bytes = ds->aovBytes();
+    return KZ_OK;
+}
+
+// ---- the entry points of include/kazen_mi355x_variance.h that only touch replica state (kz_denoise_variance* are kz_variance.hip's) ----
+int kz_scene_set_variance(KzScene *scene, int32_t mode) {
+    if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_variance: null scene");
+    if (mode < 0 || mode > KZ_VARIANCE_ONE_PASS) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_variance: mode %d (0 = off, 1 = on, 2 = on with two tap launches, 3 = on with the one-pass tap kernel)", mode);
+    KzReplicaSet *rs = replicaSet(scene);
+    std::vector<KzDeviceState *> v;
+    if (rs) { std::lock_guard<std::mutex> g(rs->m); v = rs->v; }
+    for (KzDeviceState *ds : v) {                                      // queued work finishes with the sums it was launched with
+        HIP_TRY(hipSetDevice(ds->hipDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        if (!mode) { ds->moment().free(); ds->momentSamples = 0; }
+    }
+    scene->varianceMode = mode;
+    return KZ_OK;
+}
+int kz_scene_variance(const KzScene *scene, int32_t *mode) {
+    if (!scene || !mode) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_variance: null argument");
+    *mode = scene->varianceMode;
+    return KZ_OK;
+}
+int kz_variance_download(KzScene *scene, int device, float *film, size_t nFloats) {
+    if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "kz_variance_download: null scene");
+    if (!scene->varianceMode) return kz_fail(KZ_ERR_STATE, "kz_variance_download: the second-moment film is switched off (kz_scene_set_variance)");
+    KzDeviceState *ds; int rc;
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    return downloadFilm(scene, ds, ds->moment(), false, film, nFloats);
+}
+int kz_variance_info(KzScene *scene, int device, uint64_t *bytes, uint32_t *samples) {
+    KzDeviceState *ds; int rc;
+    if (!bytes && !samples) return kz_fail(KZ_ERR_INVALID_ARG, "kz_variance_info: null bytes and samples");
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    if (bytes) *bytes = ds->moment().bytes();
+    if (samples) *samples = ds->momentSamples;
     return KZ_OK;
 }
 

@@ -203,6 +203,7 @@ struct KzScene {
     std::vector<uint8_t> pendXOn;
     bool hostStale = false;             // tris, nodes, nodes4 and bvh.sahCost do not follow the last edit yet (kzHostSync brings them up to date)
     uint32_t aovMask = 0;               // KZ_AOV_* feature films every render of the scene produces beside the picture (kazen_mi355x_aov.h; kz_scene_set_aovs)
+    int32_t varianceMode = 0;           // KZ_VARIANCE_*: every render keeps a second-moment film beside the picture's (kazen_mi355x_variance.h; kz_scene_set_variance)
     std::mutex editMutex;               // guards the lazy host refit (kzHostSync may be reached from several device threads of kz_render_multi)
     // device replicas, one per GPU the scene is resident on (KzReplicaSet, owned by kz_render.hip; created with the scene)
     void *dev = nullptr;
@@ -219,6 +220,9 @@ int kz_collapse_bvh4(const std::vector<KzNode> &nodes, uint32_t rootRef, std::ve
 // (kzAovRefuse), and every call that is the tile-rect gather itself (kzAovRefuseGather). KZ_OK for a scene without AOVs.
 int kzAovRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call);
 int kzAovRefuseGather(const KzScene *scene, const char *call);
+// ... and the same refusals while the second-moment film is switched on (kazen_mi355x_variance.h). KZ_OK with the switch off.
+int kzVarianceRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call);
+int kzVarianceRefuseGather(const KzScene *scene, const char *call);
 // kz_host.cpp
 int kz_fail(int code, const char *fmt, ...);
 int kzCameraParams(const KzCamera &c, KzParams &p);                     // the camera part of KzParams (pixel beams included)

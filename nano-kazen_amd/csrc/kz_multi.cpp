@@ -34,6 +34,19 @@ int kzAovRefuseGather(const KzScene *scene, const char *call) {
     if (!scene || !scene->aovMask) return KZ_OK;
     return kz_fail(KZ_ERR_UNSUPPORTED, "%s: refused while AOVs are enabled (mask %u): " KZ_NO_AOV_GATHER " - kz_scene_set_aovs(scene, 0) first", call, scene->aovMask);
 }
+// The second-moment film (kazen_mi355x_variance.h) is fed and read like a feature film: the same refusals while it is switched on.
+#define KZ_NO_MOMENT_GATHER "the tile-rect gather of the second-moment film is not built"
+int kzVarianceRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call) {
+    if (!scene || !scene->varianceMode || !opts) return KZ_OK;
+    const char *what = opts->pipeline == 1 ? "KzRenderOpts.pipeline = 1 (the megakernel pipeline feeds no second-moment film)" : opts->dealer ? "a KzTileDealer (" KZ_NO_MOMENT_GATHER ")"
+                     : opts->packedOutput ? "KzRenderOpts.packedOutput = 1 (" KZ_NO_MOMENT_GATHER ")" : nullptr;
+    if (!what) return KZ_OK;
+    return kz_fail(KZ_ERR_UNSUPPORTED, "%s: %s is refused while the second-moment film is on - kz_scene_set_variance(scene, 0) first", call, what);
+}
+int kzVarianceRefuseGather(const KzScene *scene, const char *call) {
+    if (!scene || !scene->varianceMode) return KZ_OK;
+    return kz_fail(KZ_ERR_UNSUPPORTED, "%s: refused while the second-moment film is on: " KZ_NO_MOMENT_GATHER " - kz_scene_set_variance(scene, 0) first", call);
+}
 
 extern "C" {
 
@@ -128,6 +141,7 @@ int kz_render_multi(KzScene *scene, const KzRenderOpts *opts, const int32_t *dev
                     float *deviceMs) {
     if (!scene || !devices || nDevices == 0 || !film) return kz_fail(KZ_ERR_INVALID_ARG, "kz_render_multi: null argument");
     if (const int rc = kzAovRefuseGather(scene, "kz_render_multi")) return rc;
+    if (const int rc = kzVarianceRefuseGather(scene, "kz_render_multi")) return rc;
     const KzParams &P = scene->prm;
     const size_t filmFloats = (size_t)(P.width + 2 * P.border) * (size_t)(P.height + 2 * P.border) * 4;
     if (nFloats != filmFloats) return kz_fail(KZ_ERR_INVALID_ARG, "film buffer must hold %zu floats", filmFloats);

@@ -14,6 +14,7 @@
 #include "kz_integrators.h"
 #include "kz_aov.h"
 #include "kz_state.h"
+#include "../../include/kazen_mi355x_variance.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -288,6 +289,17 @@ static int wfCamera(WfLaunch &L, bool beams) {
 // ORDER: tap sums are read-modify-write per pixel and a pixel's samples must arrive in ascending sample order; with passes in flight the pass before this one,
 // on another stream, touches the same pixels. The AOV stages have an event chain of their own (evAov: recorded behind a pass's AOV tap launches, waited for by
 // the next pass's) - waiting for evFilm[prev], which is recorded at the END of the pass before, would serialise the passes.
+// The film stage of a pass's pixels [pixList, +nPix) on `pst`: the picture's tap launch and, with the second-moment film switched on (kazen_mi355x_variance.h), that
+// film's directly behind it - the same stream, pixel list and sample planes, inside the same evFilm chain - or the one launch that feeds both. Switch off: the
+// picture's launch alone, as before the switch existed.
+#define KZ_VARIANCE_DEFAULT_ONE_PASS 1      // what KZ_VARIANCE_ON means: the faster of the two forms on a C4 pass (2.74 against 2.94 ms of film stage)
+static int filmStages(KzScene *scene, KzDeviceState *ds, hipStream_t pst, const uint32_t *pixList, uint32_t nPix, uint32_t Sp, const float *const plane[5], hipEvent_t waitFilm, int lanes) {
+    const int mode = scene->varianceMode;
+    if (!mode) return kzFilmStage(scene, ds, ds->picture(), false, pst, pixList, nPix, Sp, plane, waitFilm, lanes);
+    const bool onePass = (mode == KZ_VARIANCE_ONE_PASS || (mode == KZ_VARIANCE_ON && KZ_VARIANCE_DEFAULT_ONE_PASS)) && kzFilmMomentOnePassOk(scene->prm);
+    if (!onePass) if (const int rc = kzFilmStage(scene, ds, ds->picture(), false, pst, pixList, nPix, Sp, plane, waitFilm, lanes)) return rc;
+    return kzFilmStageMoment(scene, ds, ds->picture(), ds->moment(), onePass, pst, pixList, nPix, Sp, plane, waitFilm);
+}
 static int filmLanes(const KzTune &tune) { return tune.filmGather == 3 ? 1 : 0; }      // kzFilmStage's lanesPerPixel: KzTuning.filmGather = 3 asks for one lane per pixel
 typedef decltype(&kz_wf_aov<0>) KzAovFn;
 static KzAovFn aovFn(int ext) {                      // ext: 0 / KZ_X_MODELS / KZ_X_ALL
@@ -571,8 +583,8 @@ static int launchHalves(PassRun &r, PassCtx &c, hipStream_t pst, EventPair &ep, 
     if ((rc = wfPass(scene, ds, vb, c.halfStream, pixList + nA, s, Sp, (uint32_t)itemsB, r.tune, r.beams, how.beside[1]))) return rc;
     ds->lastInfo.shadowBeside = 2u;                                   // (kz_last_pass_info: the last pass ran as halves)
     // the halves' pixels are disjoint, so are their tap sums: the two film stages need no order between them
-    if ((rc = kzFilmStage(scene, ds, ds->picture(), false, pst, pixList, nA, Sp, va.plane, nullptr, lanes))) return rc;
-    if ((rc = kzFilmStage(scene, ds, ds->picture(), false, c.halfStream, pixList + nA, nB, Sp, vb.plane, nullptr, lanes))) return rc;
+    if ((rc = filmStages(scene, ds, pst, pixList, nA, Sp, va.plane, nullptr, lanes))) return rc;
+    if ((rc = filmStages(scene, ds, c.halfStream, pixList + nA, nB, Sp, vb.plane, nullptr, lanes))) return rc;
     if ((rc = stageMark(va, pst, 4))) return rc;
     HIP_TRY(hipEventRecord(c.evHalfJoin, c.halfStream)); HIP_TRY(hipStreamWaitEvent(pst, c.evHalfJoin, 0));
     HIP_TRY(hipEventRecord(ep.b, pst)); HIP_TRY(hipGetLastError());
@@ -607,7 +619,7 @@ static int launchWhole(PassRun &r, PassCtx &c, int ci, hipStream_t pst, EventPai
     HIP_TRY(hipEventRecord(ep.b, pst)); HIP_TRY(hipGetLastError());
     // the film stage adds this pass's samples to the running tap sums of its pixels, behind the film stage of the pass before it (another stream's)
     const int prev = (ci + r.pl.nCtx - 1) % r.pl.nCtx;
-    if ((rc = kzFilmStage(scene, ds, ds->picture(), false, pst, pixList, nPixPass, Sp, c.plane, (r.pl.multi && r.pass > 0) ? ds->evFilm[prev] : nullptr, filmLanes(r.tune)))) return rc;
+    if ((rc = filmStages(scene, ds, pst, pixList, nPixPass, Sp, c.plane, (r.pl.multi && r.pass > 0) ? ds->evFilm[prev] : nullptr, filmLanes(r.tune)))) return rc;
     return r.pipeline == 2 ? stageMark(c, pst, 4) : KZ_OK;
 }
 
@@ -682,6 +694,12 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     // outside the pass contexts' budget, cleared unless the call accumulates
     if ((rc = kzFilmEnsure(scene, ds->picture(), ds->filmPixels, opts->accumulate != 0, stream))) return rc;
     for (int f = 0; f < 3; ++f) if ((scene->aovMask & (1u << f)) && (rc = kzFilmEnsure(scene, ds->aov(f), ds->filmPixels, opts->accumulate != 0, stream))) return rc;
+    // ... and the second-moment film's (kazen_mi355x_variance.h). What each of the two films has been given since it was last zeroed is counted per pixel.
+    if (!opts->accumulate) ds->pictureSamples = 0;
+    if (scene->varianceMode) {
+        if (!ds->moment().sums || !opts->accumulate) ds->momentSamples = 0;
+        if ((rc = kzFilmEnsure(scene, ds->moment(), ds->filmPixels, opts->accumulate != 0, stream))) return rc;
+    }
     const KzTileDealer *dealer = opts->dealer;
     if (dealer) {
         if (!dealer->counter || (dealer->takenCap && (!dealer->taken || !dealer->nTaken))) return kz_fail(KZ_ERR_INVALID_ARG, "KzTileDealer: null counter / taken buffer");
@@ -736,6 +754,8 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     if (multi)                                                         // join: everything after this call on `stream` sees the film
         for (int i = 0; i < nCtx; ++i) if (r.inFlight[i]) HIP_TRY(hipStreamWaitEvent(stream, ds->evFilm[i], 0));
     if ((rc = kzFilmResolve(scene, ds->picture(), stream))) return rc;          // the film texels from the tap sums: once per call
+    ds->pictureSamples += s1 - s0;
+    if (scene->varianceMode) ds->momentSamples += s1 - s0;
     HIP_TRY(hipEventRecord(ds->evCallB, stream));
     // what the call leaves for kz_last_pass_info / kz_last_grow_note
     ds->lastDual = multi;
@@ -752,7 +772,7 @@ extern "C" {
 int kz_render(KzScene *scene, const KzRenderOpts *opts) {
     if (!opts) return kz_fail(KZ_ERR_INVALID_ARG, "null opts");
     KzDeviceState *ds; int rc;
-    if ((rc = kzAovRefuse(scene, opts, "kz_render"))) return rc;
+    if ((rc = kzAovRefuse(scene, opts, "kz_render")) || (rc = kzVarianceRefuse(scene, opts, "kz_render"))) return rc;
     // opts->device addresses a replica by HIP device index; a scene resident on ONE device is addressed by any zero-initialised opts
     if ((rc = findReplica(scene, opts->device, &ds))) {
         KzReplicaSet *rs = scene ? replicaSet(scene) : nullptr;
@@ -765,7 +785,7 @@ int kz_render(KzScene *scene, const KzRenderOpts *opts) {
 
 int kz_render_tiles(KzScene *scene, const KzRenderOpts *opts, const KzTile *tiles, uint32_t nTiles, int device, float *film, size_t nFloats) {
     KzDeviceState *ds; int rc;
-    if ((rc = kzAovRefuse(scene, opts, "kz_render_tiles"))) return rc;
+    if ((rc = kzAovRefuse(scene, opts, "kz_render_tiles")) || (rc = kzVarianceRefuse(scene, opts, "kz_render_tiles"))) return rc;
     if ((rc = findReplica(scene, device, &ds))) return rc;
     const size_t full = ds->filmPixels * 4;
     const bool packedOut = opts && opts->packedOutput;

@@ -5,7 +5,9 @@
 //   kz_refit.hip    device side of the edits of a resident scene (kz_refit.h)
 //   kz_film.hip     film reconstruction kernels + their launchers, each taking the film (kz_film.h: KzFilm, the picture or a feature film) it works on, tile packing /
 //                   download, the kz_film_* entry points and those of kazen_mi355x_aov.h that only touch replica state
+//   kz_film_moment.hip  the tap kernels of the second-moment film (include/kazen_mi355x_variance.h) and their launcher, kzFilmStageMoment
 //   kz_denoise.hip  the a-trous denoiser of include/kazen_mi355x_denoise.h: its kernels, the replica's denoise buffers, kz_denoise* entry points
+//   kz_variance.hip the variance-guided form of that filter (include/kazen_mi355x_variance.h): its kernels, kz_denoise_variance* entry points
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
 // Every device buffer, pinned buffer, event and stream named below is a member of one of the four move-only owners of kz_own.h (DevBuf, PinnedBuf, Event, Stream).
@@ -182,9 +184,13 @@ struct KzDeviceState {
     // The films (kz_film.h): [0] the picture - its texels there from the upload, its sums from the first render -, [1 + f] the feature film of AOV f (kazen_mi355x_aov.h:
     // 0 albedo, 1 normal, 2 depth), there from the first render with the AOV enabled. filmPixels: the texels of each. evAov[i]: the AOV tap launches of the pass last
     // run in context i (the chain passes in flight order their AOV stages by, wfPass)
-    KzFilm films[4]; size_t filmPixels = 0; Event evAov[KZ_MAX_PASSES_IN_FLIGHT];
+    // [4] the second-moment film (kazen_mi355x_variance.h): (w r^2, w g^2, w b^2, w) of the samples the picture receives, there from the first render with the switch on.
+    // pictureSamples / momentSamples: samples per pixel the two films have been given since each was last zeroed (the sum of sampleEnd - sampleBegin over renders).
+    KzFilm films[5]; size_t filmPixels = 0; Event evAov[KZ_MAX_PASSES_IN_FLIGHT];
+    uint32_t pictureSamples = 0, momentSamples = 0;
     KzFilm &picture() { return films[0]; }
     KzFilm &aov(int f) { return films[1 + f]; }
+    KzFilm &moment() { return films[4]; }
     size_t aovBytes() const { return films[1].bytes() + films[2].bytes() + films[3].bytes(); }
     DevBuf<uint8_t> srgb;                                        // staging raster of kz_film_to_srgb8 / kz_denoise_to_srgb8 (allocated on first use)
     // The denoiser (kazen_mi355x_denoise.h; kz_denoise.hip), allocated by the first kz_denoise outside the pass contexts' budget: frame-sized planes without an
@@ -248,11 +254,17 @@ int downloadTiles(KzScene *scene, KzDeviceState *ds, KzFilm &film, const KzTile 
 // The film machine (kz_film.hip), each function for the film it is handed: kzFilmEnsure before the passes of a call (KzFilm::ensure with the scene's geometry), kzFilmStage
 // after every pass (ImageBlock::put for the pass's sample records - five planes jx | jy | r | g | b - into the film's running tap sums, launched on `pst` behind `waitFilm`;
 // isSigned: a feature film's values, which may be negative), kzFilmResolve once per call and wherever a feature film is read (the texels from the sums).
+#define KZ_TAPS_CHUNK1 8                     // samples per staging round with one lane per pixel (32-B pieces of every sample row; round 2's kernel)
+#define KZ_TAPS_CHUNK 16                     // ... with several lanes per pixel: 64-B pieces = whole HBM sectors (profiles/r05h_film_taps)
 #define KZ_FILM_GRID 64                      // the canonical tile grid of the resolve = kz_deal_tiles' default tile: the film of one device equals the host merge of its tiles' rects bit for bit
 int kzFilmEnsure(KzScene *scene, KzFilm &film, size_t filmPixels, bool accumulate, hipStream_t stream);
 int kzFilmClear(KzDeviceState *ds, hipStream_t stream);          // every film of the replica: the picture's sums and texels, then each feature film's
 int kzFilmStage(KzScene *scene, KzDeviceState *ds, KzFilm &film, bool isSigned, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *const plane[5], hipEvent_t waitFilm, int lanesPerPixel);
 int kzFilmResolve(KzScene *scene, KzFilm &film, hipStream_t stream);
+// The second-moment film's stage of a pass, on the picture's stream with its pixel list and sample planes: behind the picture's tap launch (onePass = false), or in
+// its place, feeding both films from one read of the planes (onePass = true, filters kzFilmMomentOnePassOk accepts; waits for `waitFilm` as kzFilmStage does)
+bool kzFilmMomentOnePassOk(const KzParams &P);
+int kzFilmStageMoment(KzScene *scene, KzDeviceState *ds, KzFilm &picture, KzFilm &moment, bool onePass, hipStream_t pst, const uint32_t *pixList, uint32_t nPixPass, uint32_t Sp, const float *const plane[5], hipEvent_t waitFilm);
 // The float planes a pass's features go to: three per feature (p[0] albedo, p[1] normal, p[2] depth replicated), `stride` floats apart. They alias the shadow
 // arrays of the pass context (wfAov, kz_render.hip), which are dead between the camera stage and the first shade / ao / mats launch.
 struct KzAovPlanes { float *p[3]; size_t stride; };

@@ -459,6 +459,35 @@ class Scene:
     def denoise_release(self, device=-1):
         abi.check(self.lib, self.lib.kz_denoise_release(self.h, int(device)))
 
+    # ---- the second-moment film and the variance-guided denoiser (include/kazen_mi355x_variance.h)
+    def set_variance(self, on=True):
+        """kz_scene_set_variance: True / False (or a KZ_VARIANCE_* mode: 2 = two tap launches, 3 = the one-pass tap kernel - the same film either way). A film that is
+        switched on covers the samples rendered from then on."""
+        abi.check(self.lib, self.lib.kz_scene_set_variance(self.h, int(on)))
+
+    def variance(self):
+        m = C.c_int32()
+        abi.check(self.lib, self.lib.kz_scene_variance(self.h, C.byref(m)))
+        return int(m.value)
+
+    def moment_film(self, device=None):
+        """kz_variance_download: the second-moment film, (h + 2b, w + 2b, 4) = (w r^2, w g^2, w b^2, w) like film()."""
+        out, ptr, n = self._film_out()
+        abi.check(self.lib, self.lib.kz_variance_download(self.h, -1 if device is None else int(device), ptr, n))
+        return out
+
+    def variance_info(self, device=-1):
+        """kz_variance_info: (bytes the film holds on that replica, samples per pixel it has been given since it was last zeroed)."""
+        b, n = C.c_uint64(), C.c_uint32()
+        abi.check(self.lib, self.lib.kz_variance_info(self.h, int(device), C.byref(b), C.byref(n)))
+        return int(b.value), int(n.value)
+
+    def denoise_variance(self, device=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0, **opts):
+        """kz_denoise_variance: denoise() with a colour tolerance that follows the second-moment film's variance (sigma_color defaults to 2.0 here); the result is read
+        like denoise()'s. Options: denoise_opts' and variance_opts'."""
+        o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
+        abi.check(self.lib, self.lib.kz_denoise_variance(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v)))
+
     def bsdf_query(self, bsdf, wi, wo, acc, s3, uv=None):
         """eval (n,3), pdf (n,), sample (n,8) = weight rgb, wo xyz, alive, pdf(bRec) after sample()."""
         bsdf = np.ascontiguousarray(bsdf, np.int32)
@@ -550,6 +579,33 @@ def denoise_films(film, albedo=None, normal=None, depth=None, border=0, device=0
     abi.check(lib, lib.kz_denoise_films(int(device), cols - 2 * int(border), rows - 2 * int(border), int(border), film.ctypes.data_as(abi.f32p),
                                         *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g], C.byref(o), out.ctypes.data_as(abi.f32p)))
     return out
+
+
+def variance_opts(sigma_variance=0.0, samples=0, flags=0, reserved=0):
+    """A KzVarianceOpts: 0 means the default (sigma 3.0; the replica's sample count)."""
+    return abi.KzVarianceOpts(float(sigma_variance), int(samples), int(flags), int(reserved))
+
+
+def denoise_variance_films(film, moment, albedo=None, normal=None, depth=None, border=0, device=0, lib=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0,
+                           return_variance=False, **opts):
+    """kz_denoise_variance_films: the device's variance-guided denoiser on host films (denoise_films' layout; `moment`: the second-moment film; `samples` must be
+    stated). Returns the denoised film, or (film, v_last of shape (h, w)) with return_variance."""
+    lib = lib or abi.load_library()
+    film = np.ascontiguousarray(film, np.float32)
+    if film.ndim != 3 or film.shape[2] != 4:
+        raise ValueError("a film is (h + 2 border, w + 2 border, 4)")
+    rows, cols = film.shape[0], film.shape[1]
+    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (moment, albedo, normal, depth)]
+    for a in g:
+        if a is not None and a.shape != film.shape:
+            raise ValueError("the moment film and the guide films have the picture's shape")
+    out = np.empty_like(film)
+    var = np.full((max(rows - 2 * int(border), 0), max(cols - 2 * int(border), 0)), np.nan, np.float32) if return_variance else None
+    o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
+    abi.check(lib, lib.kz_denoise_variance_films(int(device), cols - 2 * int(border), rows - 2 * int(border), int(border), film.ctypes.data_as(abi.f32p),
+                                                 *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g], C.byref(o), C.byref(v), out.ctypes.data_as(abi.f32p),
+                                                 None if var is None else var.ctypes.data_as(abi.f32p)))
+    return (out, var) if return_variance else out
 
 
 def hits_to_arrays(hits, n):

@@ -1,5 +1,5 @@
 #!/bin/sh
-# Did the compiled device code stay? Compiles the device side of the six device units of the working tree and of another revision with build.sh's flags
+# Did the compiled device code stay? Compiles the device side of the eight device units of the working tree and of another revision with build.sh's flags
 # (plain and -DKZ_EXPERIMENTS), disassembles the gfx950 code objects and compares them kernel by kernel. Needs no GPU.
 #   scripts/device_code_diff.sh <git-rev>
 # Prints the kernels whose instructions differ - their own, or those of a device function they call (pathLi, matsLi, the texture filters ...) - with the
@@ -20,6 +20,7 @@ FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function"
 one() {
     B=$OUT/$1.$3.$4
     [ "$3" = exp ] && X=-DKZ_EXPERIMENTS || X=
+    [ -f "$2/nano-kazen_amd/csrc/$4.hip" ] || { : > "$B.dis"; : > "$B.sym"; : > "$B.rem"; return 0; }      # (a unit the other revision does not have yet: every kernel of it is new)
     (cd "$2/nano-kazen_amd/csrc" && hipcc $FLAGS $5 $X ${KZ_EXTRA_HIPFLAGS} --cuda-device-only -Rpass-analysis=kernel-resource-usage -c $4.hip -o "$B.bundle" 2> "$B.rem") || { echo "$1 $3 $4: did not compile"; tail -5 "$B.rem"; return 1; }
     "$LLVM/clang-offload-bundler" --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input="$B.bundle" --output="$B.co" 2> /dev/null || cp "$B.bundle" "$B.co"      # (a compiler that does not bundle a lone device object)
     "$LLVM/llvm-objdump" -d --no-show-raw-insn "$B.co" > "$B.dis"
@@ -29,8 +30,8 @@ PIDS=""
 for build in plain exp; do
     for side in this rev; do
         [ $side = this ] && TREE=$ROOT || TREE=$WT
-        for u in kz_render kz_replica kz_film kz_debug; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fgpu-flush-denormals-to-zero -fno-slp-vectorize" & PIDS="$PIDS $!"; done
-        for u in kz_refit kz_denoise; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fno-slp-vectorize" & PIDS="$PIDS $!"; done      # (build.sh's IEEE units: no flush to zero)
+        for u in kz_render kz_replica kz_film kz_film_moment kz_debug; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fgpu-flush-denormals-to-zero -fno-slp-vectorize" & PIDS="$PIDS $!"; done
+        for u in kz_refit kz_denoise kz_variance; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fno-slp-vectorize" & PIDS="$PIDS $!"; done      # (build.sh's IEEE units: no flush to zero)
     done
 done
 FAILED=0
@@ -88,7 +89,7 @@ def demangle(names):
 
 differing = 0
 for build in ("plain", "exp"):
-    for unit in ("kz_render", "kz_replica", "kz_film", "kz_debug", "kz_refit", "kz_denoise"):
+    for unit in ("kz_render", "kz_replica", "kz_film", "kz_film_moment", "kz_debug", "kz_refit", "kz_denoise", "kz_variance"):
         a, b = "%s/this.%s.%s" % (out, build, unit), "%s/rev.%s.%s" % (out, build, unit)
         (fa, ka), (fb, kb) = functions(a), functions(b)
         ra, rb = resources(a + ".rem"), resources(b + ".rem")
@@ -106,7 +107,7 @@ for build in ("plain", "exp"):
         names = demangle(set(why) | kernels | {w[6:] for w in why.values() if w.startswith("calls ")})
         short = lambda n: names.get(n, n).split("(")[0].replace("void ", "")
         bad = sorted(n for n in why if n in kernels)
-        print("%-5s %-10s %3d kernels, %d differ from %s%s" % (build, unit, len(kernels), len(bad), rev, "".join("; device function %s differs" % short(n) for n in sorted(own - kernels))))
+        print("%-5s %-14s %3d kernels, %d differ from %s%s" % (build, unit, len(kernels), len(bad), rev, "".join("; device function %s differs" % short(n) for n in sorted(own - kernels))))
         for n in bad:
             differing += 1
             reason = why[n] if not why[n].startswith("calls ") else "calls " + short(why[n][6:])

@@ -1,18 +1,29 @@
-// kz_denoise.h - the edge-avoiding a-trous filter of include/kazen_mi355x_denoise.h, stated once for the device: what one film texel is worth, what a tap
-// weighs, and what one iteration makes of a pixel. The reference renderer has no denoiser; THIS ARITHMETIC defines the result, and tests/cpu_ref/kz_denoise_ref.cpp
-// restates it independently in plain C++ (same bits: the unit that includes this file is compiled without flush-to-zero and without contraction, build.sh).
+// kz_denoise.h - the edge-avoiding a-trous filter of include/kazen_mi355x_denoise.h and its variance-guided form (include/kazen_mi355x_variance.h), stated once for
+// the device: what one film texel is worth, what a tap weighs, and what one iteration makes of a pixel. The reference renderer has no denoiser; THIS ARITHMETIC
+// defines the result, and tests/cpu_ref/kz_denoise_ref.cpp and kz_variance_ref.cpp restate it independently in plain C++ (same bits: the unit that includes this file
+// is compiled without flush-to-zero and without contraction, build.sh).
 // Every operation below is one fp32 IEEE operation in the order written; dnMax(a, b) is a > b ? a : b (no fmaxf: its NaN rule is not part of the definition).
+// Lines marked VAR are what kz_denoise_variance adds (the template argument VAR); everything else is both calls'.
 //
 //   value of a film texel t:  t.w != 0 ? t.xyz / t.w : 0                               (dnValue; a null film: 0)
 //   planes, frame-sized, no apron:  colour (e.rgb, valid ? 1 : 0) | (n.xyz, z) | (a.rgb, 0)
-//   e_0 = demodulate ? c / dnMax(a, 1e-3f) : c     per channel                           (kz_dn_prepare)
-//   one iteration at a valid pixel p (kz_dn_atrous, dnPixel), taps dy = -2..2 outer, dx = -2..2 inner, q = p + step * (dx, dy) inside the frame and valid:
+//     VAR: the colour plane's fourth float holds v, the variance estimate of the pixel's (demodulated) colour, and a NEGATIVE value (-1) where the pixel is not
+//          valid (dnValid): a tap's v(q) arrives with the 16 bytes the tap loads anyway, and the call needs no plane beyond kz_denoise's
+//   am = dnMax(a, 1e-3f) per channel;  e_0 = demodulate ? c / am : c                       (dnPrepare)
+//     VAR: s = dnValue(moment), n = (float)samples:  var_k = dnMax(s_k - c_k * c_k, 0) / n
+//          v_0 = demodulate ? (var_r / (am_r * am_r) + var_g / (am_g * am_g)) + var_b / (am_b * am_b) : (var_r + var_g) + var_b
+//   one iteration at a valid pixel p (dnAtrous, dnAtrousLds):
+//     VAR: gn = gd = 0; dy = -1..1 outer, dx = -1..1 inner, q = p + (dx, dy) inside the frame and valid: gn += dnK(dy) * dnK(dx) * v(q), gd += dnK(dy) * dnK(dx)   (dnPrefilter)
+//          kv = 1.0f / (sv2 * (gn / gd) + 1e-12f), kc = dnMax(kc, kv) from here on     sv2 = sigmaVariance * sigmaVariance, formed on the host      (dnTolerance)
+//     taps dy = -2..2 outer, dx = -2..2 inner, q = p + step * (dx, dy) inside the frame and valid (dnTap):
 //       dc = dnSq(e(q) - e(p)), dn = dnSq(n(q) - n(p)), da = dnSq(a(q) - a(p))           dnSq(v) = (v.x * v.x + v.y * v.y) + v.z * v.z
 //       m = dnMax(dnMax(z_p, z_q), 1e-20f), t = (z_q - z_p) / m, dz = t * t
 //       arg = ((dc * kc + dn * kn) + dz * kz) + da * ka                                  (colour weights only: arg = dc * kc)
 //       wgt = (h[dy + 2] * h[dx + 2]) * dnExp(-arg)                                      h = {1/16, 1/4, 3/8, 1/4, 1/16}; the products are exact
-//       num.k += wgt * e(q).k (k = r, g, b), den += wgt;     e'(p) = num / den
-//   result = demodulate ? e_last * dnMax(a, 1e-3f) : e_last, weight 1; (0, 0, 0, 0) where the pixel is not valid and in the apron   (kz_dn_finish)
+//       num.k += wgt * e(q).k (k = r, g, b), den += wgt;     VAR: nv += (wgt * wgt) * v(q)
+//     e'(p) = num / den;     VAR: v'(p) = nv / (den * den)
+//   result = demodulate ? e_last * am : e_last, weight 1; (0, 0, 0, 0) where the pixel is not valid and in the apron   (dnFinish)
+//     VAR: v_last of a valid pixel beside it, 0 where the pixel is not valid
 // The constants kc (per iteration: sigmaColor halves), kn, kz, ka = 1.0f / (sigma * sigma) are computed on the host (kz_denoise.hip dnPlan).
 #pragma once
 #include "../../include/kazen_mi355x_denoise.h"
@@ -30,10 +41,6 @@ struct KzDnIter { int width, height, step; float kc, kn, kz, ka; };
 #endif
 static_assert(KZ_DN_LDS_MAX_STEP == 0 || KZ_DN_LDS_MAX_STEP == 1 || KZ_DN_LDS_MAX_STEP == 2, "the LDS-tile kernel is built for the steps 1 and 2");
 
-// Host side, shared by kz_denoise.hip and kz_variance.hip: what a call does, from its options (dnPlan, kz_denoise.hip)
-struct KzDnPlan { uint32_t iterations, guides; bool demodulate, guided; float kc[KZ_DENOISE_MAX_ITERATIONS], kn, kz, ka; };
-int dnPlan(const KzDenoiseOpts *opts, uint32_t avail, const char *call, KzDnPlan *plan, float defaultSigmaColor = 1.0f);
-
 #define KZ_DN_FN __device__ __forceinline__
 KZ_DN_FN float dnMax(float a, float b) { return a > b ? a : b; }
 KZ_DN_FN float dnSq(float x, float y, float z) { return (x * x + y * y) + z * z; }
@@ -50,39 +57,10 @@ KZ_DN_FN float dnExp(float x) {
 }
 // the B3-spline weights: h[|d|] for d = -2..2
 KZ_DN_FN float dnH(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
+// whether a colour plane texel is a valid pixel's
+template <bool VAR> KZ_DN_FN bool dnValid(const float4 &e) { return VAR ? !(e.w < 0.f) : e.w != 0.f; }
 
-// What tap q adds to the sums of pixel p: (wgt * e(q), wgt). ep / eq: colour plane texels, gp / gq: (n.xyz, z), ap / aq: (a.rgb, -).
-template <bool GUIDED>
-KZ_DN_FN void dnTap(const KzDnIter &I, float hh, const float4 &ep, const float4 &eq, const float4 &gp, const float4 &gq, const float4 &ap, const float4 &aq,
-                    float &nr, float &ng, float &nb, float &den) {
-    const float dc = dnSq(eq.x - ep.x, eq.y - ep.y, eq.z - ep.z);
-    float arg = dc * I.kc;
-    if (GUIDED) {
-        const float dn = dnSq(gq.x - gp.x, gq.y - gp.y, gq.z - gp.z);
-        const float da = dnSq(aq.x - ap.x, aq.y - ap.y, aq.z - ap.z);
-        const float m = dnMax(dnMax(gp.w, gq.w), 1e-20f);
-        const float t = (gq.w - gp.w) / m;
-        const float dz = t * t;
-        arg = ((arg + dn * I.kn) + dz * I.kz) + da * I.ka;
-    }
-    const float wgt = hh * dnExp(-arg);
-    nr += wgt * eq.x; ng += wgt * eq.y; nb += wgt * eq.z;
-    den += wgt;
-}
-
-// ---- the variance-guided filter of include/kazen_mi355x_variance.h, stated once for the device. Everything not restated here is the definition above. ----
-// The colour plane's fourth float holds v, the variance estimate of the pixel's (demodulated) colour, and a NEGATIVE value (-1) where the pixel is not valid: a tap's
-// v(q) arrives with the 16 bytes the tap loads anyway, and the call needs no plane beyond kz_denoise's.
-//   s = dnValue(moment), c = dnValue(picture), n = (float)samples:  var_k = dnMax(s_k - c_k * c_k, 0) / n                                  (kz_dn_prepare_var)
-//   v_0 = demodulate ? (var_r / (am_r * am_r) + var_g / (am_g * am_g)) + var_b / (am_b * am_b) : (var_r + var_g) + var_b
-//   one iteration at a valid pixel p (kz_dn_atrous_var[_lds]):
-//       gn = gd = 0; dy = -1..1 outer, dx = -1..1 inner, q = p + (dx, dy) inside the frame and valid: gn += dnK(dy) * dnK(dx) * v(q), gd += dnK(dy) * dnK(dx)   (dnPrefilter)
-//       kv = 1.0f / (sv2 * (gn / gd) + 1e-12f), kcv = dnMax(kc, kv)          sv2 = sigmaVariance * sigmaVariance, formed on the host                 (dnTolerance)
-//       per tap: dnTap's arg with kcv in the place of kc; additionally nv += (wgt * wgt) * v(q)                                                      (dnTapVar)
-//       e'(p) = num / den, v'(p) = nv / (den * den)
-//   result as kz_dn_finish's; v_last of a valid pixel beside it (kz_dn_finish_var)
-KZ_DN_FN bool dnValidVar(const float4 &e) { return !(e.w < 0.f); }
-// the 3 x 3 prefilter's weights: k[|d|] for d = -1..1; the products are exact
+// VAR, the 3 x 3 prefilter's weights: k[|d|] for d = -1..1; the products are exact
 KZ_DN_FN float dnK(int d) { return d == 0 ? 0.5f : 0.25f; }
 KZ_DN_FN void dnPrefilter(int dy, int dx, float vq, float &gn, float &gd) { const float kk = dnK(dy) * dnK(dx); gn += kk * vq; gd += kk; }
 KZ_DN_FN float dnTolerance(float kc, float sv2, float gn, float gd) {
@@ -90,11 +68,14 @@ KZ_DN_FN float dnTolerance(float kc, float sv2, float gn, float gd) {
     const float kv = 1.0f / (sv2 * g + 1e-12f);
     return dnMax(kc, kv);
 }
-template <bool GUIDED>
-KZ_DN_FN void dnTapVar(const KzDnIter &I, float kcv, float hh, const float4 &ep, const float4 &eq, const float4 &gp, const float4 &gq, const float4 &ap, const float4 &aq,
-                       float &nr, float &ng, float &nb, float &den, float &nv) {
+
+// What tap q adds to the sums of pixel p: (wgt * e(q), wgt) and, VAR, wgt^2 * v(q). kc: the iteration's colour constant (I.kc; VAR: dnTolerance's);
+// ep / eq: colour plane texels, gp / gq: (n.xyz, z), ap / aq: (a.rgb, -).
+template <bool GUIDED, bool VAR>
+KZ_DN_FN void dnTap(const KzDnIter &I, float kc, float hh, const float4 &ep, const float4 &eq, const float4 &gp, const float4 &gq, const float4 &ap, const float4 &aq,
+                    float &nr, float &ng, float &nb, float &den, float &nv) {
     const float dc = dnSq(eq.x - ep.x, eq.y - ep.y, eq.z - ep.z);
-    float arg = dc * kcv;
+    float arg = dc * kc;
     if (GUIDED) {
         const float dn = dnSq(gq.x - gp.x, gq.y - gp.y, gq.z - gp.z);
         const float da = dnSq(aq.x - ap.x, aq.y - ap.y, aq.z - ap.z);
@@ -106,5 +87,5 @@ KZ_DN_FN void dnTapVar(const KzDnIter &I, float kcv, float hh, const float4 &ep,
     const float wgt = hh * dnExp(-arg);
     nr += wgt * eq.x; ng += wgt * eq.y; nb += wgt * eq.z;
     den += wgt;
-    nv += (wgt * wgt) * eq.w;
+    if (VAR) nv += (wgt * wgt) * eq.w;
 }

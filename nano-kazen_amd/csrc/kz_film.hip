@@ -375,7 +375,7 @@ int kz_aov_info(KzScene *scene, int device, uint64_t *bytes) {
     return KZ_OK;
 }
 
-// ---- the entry points of include/kazen_mi355x_variance.h that only touch replica state (kz_denoise_variance* are kz_variance.hip's) ----
+// ---- the entry points of include/kazen_mi355x_variance.h that only touch replica state (kz_denoise_variance* are kz_denoise.hip's) ----
 int kz_scene_set_variance(KzScene *scene, int32_t mode) {
     if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_variance: null scene");
     if (mode < 0 || mode > KZ_VARIANCE_ONE_PASS) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_variance: mode %d (0 = off, 1 = on, 2 = on with two tap launches, 3 = on with the one-pass tap kernel)", mode);

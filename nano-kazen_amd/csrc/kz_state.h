@@ -6,8 +6,8 @@
 //   kz_film.hip     film reconstruction kernels + their launchers, each taking the film (kz_film.h: KzFilm, the picture or a feature film) it works on, tile packing /
 //                   download, the kz_film_* entry points and those of kazen_mi355x_aov.h that only touch replica state
 //   kz_film_moment.hip  the tap kernels of the second-moment film (include/kazen_mi355x_variance.h) and their launcher, kzFilmStageMoment
-//   kz_denoise.hip  the a-trous denoiser of include/kazen_mi355x_denoise.h: its kernels, the replica's denoise buffers, kz_denoise* entry points
-//   kz_variance.hip the variance-guided form of that filter (include/kazen_mi355x_variance.h): its kernels, kz_denoise_variance* entry points
+//   kz_denoise.hip  the a-trous denoiser of include/kazen_mi355x_denoise.h and its variance-guided form (include/kazen_mi355x_variance.h): their kernels, the
+//                   replica's denoise buffers, kz_denoise* and kz_denoise_variance* entry points
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
 // Every device buffer, pinned buffer, event and stream named below is a member of one of the four move-only owners of kz_own.h (DevBuf, PinnedBuf, Event, Stream).

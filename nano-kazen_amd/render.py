@@ -566,19 +566,24 @@ def denoise_films(film, albedo=None, normal=None, depth=None, border=0, device=0
     """kz_denoise_films: the device's denoiser on host films of (h + 2 border, w + 2 border, 4) float32 each (albedo / normal / depth may be None: an absent
     guide); needs a device, no scene. Returns the denoised film, same shape."""
     lib = lib or abi.load_library()
-    film = np.ascontiguousarray(film, np.float32)
-    rows, cols = film.shape[0], film.shape[1]
-    if film.ndim != 3 or film.shape[2] != 4:
-        raise ValueError("a film is (h + 2 border, w + 2 border, 4)")
-    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (albedo, normal, depth)]
-    for a in g:
-        if a is not None and a.shape != film.shape:
-            raise ValueError("a guide film has the picture's shape")
+    film, g, frame = _host_films(film, (albedo, normal, depth), border, "a guide film has the picture's shape")
     out = np.empty_like(film)
     o = denoise_opts(**opts)
-    abi.check(lib, lib.kz_denoise_films(int(device), cols - 2 * int(border), rows - 2 * int(border), int(border), film.ctypes.data_as(abi.f32p),
-                                        *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g], C.byref(o), out.ctypes.data_as(abi.f32p)))
+    abi.check(lib, lib.kz_denoise_films(int(device), *frame, film.ctypes.data_as(abi.f32p), *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g],
+                                        C.byref(o), out.ctypes.data_as(abi.f32p)))
     return out
+
+
+def _host_films(film, others, border, shape_error):
+    """The picture and the films that go with it (None: absent) as contiguous float32 arrays of one shape, and the frame (width, height, border) they hold."""
+    film = np.ascontiguousarray(film, np.float32)
+    if film.ndim != 3 or film.shape[2] != 4:
+        raise ValueError("a film is (h + 2 border, w + 2 border, 4)")
+    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in others]
+    for a in g:
+        if a is not None and a.shape != film.shape:
+            raise ValueError(shape_error)
+    return film, g, (film.shape[1] - 2 * int(border), film.shape[0] - 2 * int(border), int(border))
 
 
 def variance_opts(sigma_variance=0.0, samples=0, flags=0, reserved=0):
@@ -591,20 +596,12 @@ def denoise_variance_films(film, moment, albedo=None, normal=None, depth=None, b
     """kz_denoise_variance_films: the device's variance-guided denoiser on host films (denoise_films' layout; `moment`: the second-moment film; `samples` must be
     stated). Returns the denoised film, or (film, v_last of shape (h, w)) with return_variance."""
     lib = lib or abi.load_library()
-    film = np.ascontiguousarray(film, np.float32)
-    if film.ndim != 3 or film.shape[2] != 4:
-        raise ValueError("a film is (h + 2 border, w + 2 border, 4)")
-    rows, cols = film.shape[0], film.shape[1]
-    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (moment, albedo, normal, depth)]
-    for a in g:
-        if a is not None and a.shape != film.shape:
-            raise ValueError("the moment film and the guide films have the picture's shape")
+    film, g, frame = _host_films(film, (moment, albedo, normal, depth), border, "the moment film and the guide films have the picture's shape")
     out = np.empty_like(film)
-    var = np.full((max(rows - 2 * int(border), 0), max(cols - 2 * int(border), 0)), np.nan, np.float32) if return_variance else None
+    var = np.full((max(frame[1], 0), max(frame[0], 0)), np.nan, np.float32) if return_variance else None
     o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
-    abi.check(lib, lib.kz_denoise_variance_films(int(device), cols - 2 * int(border), rows - 2 * int(border), int(border), film.ctypes.data_as(abi.f32p),
-                                                 *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g], C.byref(o), C.byref(v), out.ctypes.data_as(abi.f32p),
-                                                 None if var is None else var.ctypes.data_as(abi.f32p)))
+    abi.check(lib, lib.kz_denoise_variance_films(int(device), *frame, film.ctypes.data_as(abi.f32p), *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g],
+                                                 C.byref(o), C.byref(v), out.ctypes.data_as(abi.f32p), None if var is None else var.ctypes.data_as(abi.f32p)))
     return (out, var) if return_variance else out
 
 

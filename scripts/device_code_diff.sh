@@ -1,10 +1,12 @@
 #!/bin/sh
-# Did the compiled device code stay? Compiles the device side of the eight device units of the working tree and of another revision with build.sh's flags
-# (plain and -DKZ_EXPERIMENTS), disassembles the gfx950 code objects and compares them kernel by kernel. Needs no GPU.
+# Did the compiled device code stay? Compiles the device side of the device units of the working tree and of another revision with build.sh's flags
+# (plain and -DKZ_EXPERIMENTS), disassembles the gfx950 code objects and compares them kernel by kernel. Needs no GPU. (kz_variance: a unit of the revisions
+# before the denoiser's two became one; its kernels and kz_denoise's are compared as one set, by name.)
 #   scripts/device_code_diff.sh <git-rev>
 # Prints the kernels whose instructions differ - their own, or those of a device function they call (pathLi, matsLi, the texture filters ...) - with the
 # kernel_resources.sh row of both sides, and exits non-zero if there is one. Instructions are compared as text without their addresses and encodings; the
-# pc-relative literal behind an s_getpc_b64 is compared as the symbol it points to, so a kernel that only moved (because another one grew) counts as equal.
+# pc-relative literal behind an s_getpc_b64 is compared as the symbol it points to, so a kernel that only moved (because another one grew) counts as equal;
+# so does one that became, or stopped being, the last of its code object (the padding behind it is left out).
 # (The code-object files themselves are no yardstick: two builds of equal instructions differ in a few hundred bytes of notes and hashes.)
 set -e
 [ -n "$1" ] || { echo "usage: $0 <git-rev>"; exit 2; }
@@ -70,6 +72,8 @@ def functions(base):        # name -> (instruction texts, names of the functions
             cur[1].add(target.rsplit("+", 1)[0])
         getpc = text.startswith("s_getpc_b64")
         cur[0].append(text)
+    for text, _ in fns.values():          # the padding behind the last function of a code object is not that function's: a kernel may be the last on one side only
+        while text and text[-1] in ("s_nop 0", "s_code_end", "..."): text.pop()
     kernels = {s[2][:-3] for s in syms if s[2].endswith(".kd")}
     return fns, kernels
 
@@ -87,12 +91,18 @@ def demangle(names):
     names = list(names)
     return dict(zip(names, subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.splitlines())) if names else {}
 
+def side(which, build, units):          # functions, kernels and resource rows of one side's "unit+unit": one set
+    fns, kernels, rows = {}, set(), {}
+    for u in units.split("+"):
+        base = "%s/%s.%s.%s" % (out, which, build, u)
+        f, k = functions(base)
+        fns.update(f); kernels |= k; rows.update(resources(base + ".rem"))
+    return fns, kernels, rows
+
 differing = 0
 for build in ("plain", "exp"):
-    for unit in ("kz_render", "kz_replica", "kz_film", "kz_film_moment", "kz_debug", "kz_refit", "kz_denoise", "kz_variance"):
-        a, b = "%s/this.%s.%s" % (out, build, unit), "%s/rev.%s.%s" % (out, build, unit)
-        (fa, ka), (fb, kb) = functions(a), functions(b)
-        ra, rb = resources(a + ".rem"), resources(b + ".rem")
+    for unit in ("kz_render", "kz_replica", "kz_film", "kz_film_moment", "kz_debug", "kz_refit", "kz_denoise+kz_variance"):
+        (fa, ka, ra), (fb, kb, rb) = side("this", build, unit), side("rev", build, unit)
         own = {n for n in set(fa) | set(fb) if n not in fa or n not in fb or fa[n][0] != fb[n][0]}
         # a kernel also differs through a device function it calls: close over the references
         why = {n: "its own instructions" for n in own}
@@ -107,7 +117,7 @@ for build in ("plain", "exp"):
         names = demangle(set(why) | kernels | {w[6:] for w in why.values() if w.startswith("calls ")})
         short = lambda n: names.get(n, n).split("(")[0].replace("void ", "")
         bad = sorted(n for n in why if n in kernels)
-        print("%-5s %-14s %3d kernels, %d differ from %s%s" % (build, unit, len(kernels), len(bad), rev, "".join("; device function %s differs" % short(n) for n in sorted(own - kernels))))
+        print("%-5s %-22s %3d kernels, %d differ from %s%s" % (build, unit, len(kernels), len(bad), rev, "".join("; device function %s differs" % short(n) for n in sorted(own - kernels))))
         for n in bad:
             differing += 1
             reason = why[n] if not why[n].startswith("calls ") else "calls " + short(why[n][6:])

@@ -220,6 +220,16 @@ class KzVarianceOpts(C.Structure):
     _fields_ = [("sigmaVariance", C.c_float), ("samples", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class KzTemporalView(C.Structure):
+    # include/kazen_mi355x_temporal.h: 96 bytes, a pinhole view - the direction through (sx, sy) is a + sx u + sy v; inv: the inverse of the matrix with columns (u, v, a)
+    _fields_ = [("o", C.c_float * 3), ("a", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("inv", C.c_float * 9), ("reserved", C.c_float * 3)]
+
+
+class KzTemporalOpts(C.Structure):
+    # include/kazen_mi355x_temporal.h: 32 bytes, a zero field means its default
+    _fields_ = [("depthTolerance", C.c_float), ("normalTolerance", C.c_float), ("maxHistory", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
 class KzBvhInfo(C.Structure):
     _fields_ = [("nNodes", C.c_uint32), ("nLeaves", C.c_uint32), ("nTris", C.c_uint32), ("maxDepth", C.c_uint32),
                 ("maxLeafSize", C.c_uint32), ("sahCost", C.c_float), ("buildSeconds", C.c_double)]
@@ -249,6 +259,8 @@ KZ_DENOISE_NO_DEMODULATE, KZ_DENOISE_NO_GUIDES, KZ_DENOISE_MAX_ITERATIONS = 1, 2
 # what include/kazen_mi355x_variance.h declares (checked by tests/test_variance_cpu.py): a second-moment film beside the picture's and the denoiser guided by its variance
 VARIANCE_EXPORTS = ["kz_scene_set_variance", "kz_scene_variance", "kz_variance_download", "kz_variance_info", "kz_denoise_variance", "kz_denoise_variance_films"]
 KZ_VARIANCE_OFF, KZ_VARIANCE_ON, KZ_VARIANCE_TWO_LAUNCHES, KZ_VARIANCE_ONE_PASS = 0, 1, 2, 3
+# what include/kazen_mi355x_temporal.h declares (checked by tests/test_temporal_cpu.py): the denoiser's history, reprojected across camera edits and blended in
+TEMPORAL_EXPORTS = ["kz_temporal_view", "kz_denoise_temporal", "kz_temporal_info", "kz_temporal_reset", "kz_temporal_download", "kz_denoise_temporal_films"]
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead", "kz_debug_shadow_order"]
@@ -368,6 +380,14 @@ def load_library(path=None):
         lib.kz_variance_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), u32p]
         lib.kz_denoise_variance.argtypes = [C.c_void_p, C.c_int, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts)]
         lib.kz_denoise_variance_films.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts), f32p, f32p]
+    if hasattr(lib, "kz_denoise_temporal"):       # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_temporal_view.argtypes = [C.POINTER(KzCamera), C.POINTER(KzTemporalView)]
+        lib.kz_denoise_temporal.argtypes = [C.c_void_p, C.c_int, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts), C.POINTER(KzTemporalOpts)]
+        lib.kz_temporal_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), u32p]
+        lib.kz_temporal_reset.argtypes = [C.c_void_p, C.c_int]
+        lib.kz_temporal_download.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
+        lib.kz_denoise_temporal_films.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts),
+                                                  C.POINTER(KzTemporalOpts), C.POINTER(KzTemporalView), C.POINTER(KzTemporalView), f32p, f32p, f32p, f32p]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

@@ -32,6 +32,17 @@
 // One iteration's constants, by value to the kernel
 struct KzDnIter { int width, height, step; float kc, kn, kz, ka; };
 
+// What kz_denoise_temporal (include/kazen_mi355x_temporal.h, which holds the definition) puts in front of the VAR filter, by value to kz_dn_prepare_temporal:
+// the current view's (o, a, u, v), the history's view (po, pinv), the tolerances as the taps compare them - depthTol, normalTol2 = normalTolerance^2 formed
+// on the host - and (float)maxHistory. The history of a pixel is 36 bytes in three frame-sized planes, (e.rgb, v) | (n.xyz, z) | N, the first two the layout of the
+// colour and the guide plane; in*: the copy the taps read (null: no history, every pixel starts at N = 1), out*: the copy the pixel's record goes to.
+struct KzDnTemporal {
+    float o[3], a[3], u[3], v[3], po[3], pinv[9];
+    float depthTol, normalTol2, maxHistory;
+    const float4 *inE, *inG; const float *inN;
+    float4 *outE, *outG; float *outN;
+};
+
 #define KZ_DN_BLOCK 256
 #define KZ_DN_ROW 64                  // pixels of a row per block (one wave), KZ_DN_BLOCK / KZ_DN_ROW rows
 // The a-trous form per step (measured): the LDS-tile kernel for the steps up to KZ_DN_LDS_MAX_STEP, the direct-gather kernel beyond. 0 builds the

@@ -8,6 +8,8 @@
 //   kz_dn_atrous[_var]    one launch per iteration, one lane per pixel: steps 1 and 2 from an LDS tile with a halo (kz_dn_atrous[_var]_lds), the larger steps by
 //                         direct gather with a wave along a row - every tap of a wave is one contiguous 1 KB load per plane
 //   kz_dn_finish[_var]    per film texel: remodulated colour and weight 1 in a valid frame pixel, (0, 0, 0, 0) elsewhere (the apron too)
+//   kz_dn_prepare_temporal  kz_denoise_temporal (include/kazen_mi355x_temporal.h) alone, in kz_dn_prepare_var's place: the replica's history reprojected into the current
+//                         view and blended into (e_0, v_0), the new history stored; the _var kernels follow unchanged
 // Each of the four is ONE body (dnPrepare, dnAtrous, dnAtrousLds, dnFinish) templated on VAR; the eight kernels are its two instances under the names the profiles
 // know. With VAR the colour plane's .w carries v (negative: not valid) instead of the valid flag, so the planes and the tap loads are the same and the variance-
 // guided call needs no buffer of its own. Each kernel's result is a function of its inputs alone: no atomics, no order between threads, the taps of a pixel summed
@@ -17,6 +19,7 @@
 
 #include "../../include/kazen_mi355x_denoise.h"
 #include "../../include/kazen_mi355x_variance.h"
+#include "../../include/kazen_mi355x_temporal.h"
 #include "kz_state.h"
 #include "kz_denoise.h"
 
@@ -208,6 +211,83 @@ KZ_DN_KERNEL kz_dn_finish_var(int width, int height, int border, const float4 *_
     dnFinish<true>(width, height, border, colour, albedoP, demodulate, out, variance);
 }
 
+// kz_dn_prepare_var with the temporal stage of include/kazen_mi355x_temporal.h (the definition; every line below is one of its lines): this frame's (e_cur, v_cur)
+// blended with the history reprojected from the previous view, into the colour plane, and with (n, z) and the count into the history's other copy. One lane per
+// pixel, a wave along a row: for the small view changes this is for, the 2 x 2 taps of neighbouring lanes fall on neighbouring records, so each of a wave's twelve
+// tap loads (two 16-byte planes and the count, four taps) touches little more than the 1 KB / 256 B its own pixels hold. A pixel's sums are its own lane's, in the
+// stated order; the copy that is read is not written.
+KZ_DN_KERNEL kz_dn_prepare_temporal(int width, int height, int border, const float4 *__restrict__ film, const float4 *__restrict__ moment, const float4 *__restrict__ albedo,
+                                    const float4 *__restrict__ normal, const float4 *__restrict__ depth, int demodulate, float samples, const KzDnTemporal T,
+                                    float4 *__restrict__ colour, float4 *__restrict__ normalZ, float4 *__restrict__ albedoP) {
+    const uint32_t i = blockIdx.x * KZ_DN_BLOCK + threadIdx.x;
+    if (i >= (uint32_t)width * (uint32_t)height) return;
+    const int y = (int)(i / (uint32_t)width), x = (int)(i - (uint32_t)y * (uint32_t)width);
+    const size_t t = (size_t)(y + border) * (size_t)(width + 2 * border) + (size_t)(x + border);      // < (height + 2b)(width + 2b): the films' texels
+    const float4 c = dnValue(film, t), a = dnValue(albedo, t), n = dnValue(normal, t), z = dnValue(depth, t), s = dnValue(moment, t);
+    // (e_cur, v_cur): dnPrepare<true>'s lines
+    const float vr = dnMax(s.x - c.x * c.x, 0.f) / samples, vg = dnMax(s.y - c.y * c.y, 0.f) / samples, vb = dnMax(s.z - c.z * c.z, 0.f) / samples;
+    float4 e = make_float4(c.x, c.y, c.z, (vr + vg) + vb);
+    if (demodulate) {
+        const float ar = dnMax(a.x, 1e-3f); e.x = c.x / ar;
+        const float ag = dnMax(a.y, 1e-3f); e.y = c.y / ag;
+        const float ab = dnMax(a.z, 1e-3f); e.z = c.z / ab;
+        e.w = (vr / (ar * ar) + vg / (ag * ag)) + vb / (ab * ab);
+    }
+    normalZ[i] = make_float4(n.x, n.y, n.z, z.x);
+    albedoP[i] = make_float4(a.x, a.y, a.z, 0.f);
+    if (c.w == 0.f) {                                                   // not valid: no part in the filter (v = -1), an empty record
+        e.w = -1.f;
+        colour[i] = e;
+        T.outE[i] = make_float4(0.f, 0.f, 0.f, 0.f); T.outG[i] = make_float4(0.f, 0.f, 0.f, 0.f); T.outN[i] = 0.f;
+        return;
+    }
+    float count = 1.0f;
+    if (T.inE && z.x > 0.f) {
+        const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
+        const float dx = (T.a[0] + fx * T.u[0]) + fy * T.v[0], dy = (T.a[1] + fx * T.u[1]) + fy * T.v[1], dz = (T.a[2] + fx * T.u[2]) + fy * T.v[2];
+        const float len = sqrtf(dnSq(dx, dy, dz));
+        const float r = z.x / len;
+        const float qx = (T.o[0] + dx * r) - T.po[0], qy = (T.o[1] + dy * r) - T.po[1], qz = (T.o[2] + dz * r) - T.po[2];
+        const float P0 = (T.pinv[0] * qx + T.pinv[1] * qy) + T.pinv[2] * qz, P1 = (T.pinv[3] * qx + T.pinv[4] * qy) + T.pinv[5] * qz,
+                    P2 = (T.pinv[6] * qx + T.pinv[7] * qy) + T.pinv[8] * qz;
+        if (P2 > 0.f) {
+            const float sx = P0 / P2 - 0.5f, sy = P1 / P2 - 0.5f;
+            if (sx >= -1.f && sx < (float)width && sy >= -1.f && sy < (float)height) {      // (so x0, y0 are in -1 .. width - 1, -1 .. height - 1: the int conversions are exact)
+                const float fx0 = floorf(sx), fy0 = floorf(sy), tx = sx - fx0, ty = sy - fy0;
+                const int x0 = (int)fx0, y0 = (int)fy0;
+                const float zp = sqrtf(dnSq(qx, qy, qz)), ztol = T.depthTol * dnMax(zp, 1e-20f);
+                float Wb = 0.f, Er = 0.f, Eg = 0.f, Eb = 0.f, V = 0.f, M = 0.f;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int ty_ = y0 + j;
+                    const bool rowIn = ty_ >= 0 && ty_ < height;
+                    const size_t rowAt = (size_t)(rowIn ? ty_ : y) * (size_t)width;      // (a tap outside the frame loads the pixel's own row / column and is skipped)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const int tx_ = x0 + k;
+                        const bool colIn = tx_ >= 0 && tx_ < width;
+                        const size_t it = rowAt + (size_t)(colIn ? tx_ : x);             // < width * height
+                        const float nh = T.inN[it];
+                        const float4 gh = T.inG[it], eh = T.inE[it];
+                        const float b = (k ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
+                        if (!(rowIn && colIn) || nh == 0.f || fabsf(gh.w - zp) > ztol || dnSq(gh.x - n.x, gh.y - n.y, gh.z - n.z) > T.normalTol2) continue;
+                        Wb += b; Er += b * eh.x; Eg += b * eh.y; Eb += b * eh.z; V += b * eh.w; M += b * nh;
+                    }
+                }
+                if (Wb > 1e-3f) {
+                    const float Nh = M / Wb, Nn1 = Nh + 1.0f, Nn = Nn1 < T.maxHistory ? Nn1 : T.maxHistory;
+                    const float al = 1.0f / Nn, om = 1.0f - al;
+                    e.x = om * (Er / Wb) + al * e.x; e.y = om * (Eg / Wb) + al * e.y; e.z = om * (Eb / Wb) + al * e.z;
+                    e.w = (om * om) * (V / Wb) + (al * al) * e.w;
+                    count = Nn;
+                }
+            }
+        }
+    }
+    colour[i] = e;
+    T.outE[i] = e; T.outG[i] = make_float4(n.x, n.y, n.z, z.x); T.outN[i] = count;
+}
+
 // ---- host side ----
 // What a call does, from its options: `avail` = the guides there are (the scene's mask / the films given to kz_denoise_films);
 // defaultSigmaColor: 1.0 for kz_denoise, 2.0 for kz_denoise_variance
@@ -238,7 +318,49 @@ static int dnPlan(const KzDenoiseOpts *opts, uint32_t avail, const char *call, K
 }
 
 // What kz_denoise_variance adds to a call (null: kz_denoise). `moment`: the second-moment film (null: zeros); `variance`: null or width x height floats.
-struct KzDnVar { float sv2, samples; const float4 *moment; float *variance; };
+// `temporal` (null: kz_denoise_variance): what kz_denoise_temporal puts in front - its prepare kernel takes the place of kz_dn_prepare_var.
+struct KzDnVar { float sv2, samples; const float4 *moment; float *variance; const KzDnTemporal *temporal; };
+
+// KzTemporalOpts, checked, as the kernel takes them (the views and the history's planes are filled in by the caller)
+static int dnTemporalOpts(const KzTemporalOpts *topts, const char *call, KzDnTemporal *T) {
+    static const KzTemporalOpts defaults = {};
+    const KzTemporalOpts &o = topts ? *topts : defaults;
+    if (!(std::isfinite(o.depthTolerance) && o.depthTolerance >= 0.f)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzTemporalOpts.depthTolerance = %g must be finite and > 0 (0: the default, 0.05)", call, (double)o.depthTolerance);
+    if (!(std::isfinite(o.normalTolerance) && o.normalTolerance >= 0.f)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzTemporalOpts.normalTolerance = %g must be finite and > 0 (0: the default, 0.5)", call, (double)o.normalTolerance);
+    if (o.maxHistory > 65535u) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzTemporalOpts.maxHistory = %u (1 .. 65535; 0: the default, 32)", call, o.maxHistory);
+    if (o.flags) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzTemporalOpts.flags = %u must be 0", call, o.flags);
+    for (int k = 0; k < 4; ++k) if (o.reserved[k]) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzTemporalOpts.reserved[%d] = %u must be 0", call, k, o.reserved[k]);
+    const float nt = o.normalTolerance == 0.f ? 0.5f : o.normalTolerance;
+    *T = KzDnTemporal{};
+    T->depthTol = o.depthTolerance == 0.f ? 0.05f : o.depthTolerance;
+    T->normalTol2 = nt * nt;
+    T->maxHistory = (float)(o.maxHistory ? o.maxHistory : 32u);
+    return KZ_OK;
+}
+// the reprojection reads the depth film whatever the weights use: a KzDenoiseOpts.guides without it is refused
+static int dnTemporalGuides(const KzDnPlan &plan, uint32_t avail, const char *call) {
+    if ((avail & KZ_AOV_DEPTH) && !(plan.guides & KZ_AOV_DEPTH)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: guides = %u leaves out KZ_AOV_DEPTH (%u), which the reprojection reads", call, plan.guides, KZ_AOV_DEPTH);
+    return KZ_OK;
+}
+// The view of the camera words in `P` (kzPinholeWords: a thin-lens camera is taken as the pinhole through its lens centre); inv from a double inverse narrowed once
+static int dnViewOf(const KzParams &P, const char *call, KzTemporalView *view) {
+    std::memset(view, 0, sizeof *view);
+    if (!kzPinholeWords(P, view->o, view->a, view->u, view->v))
+        return kz_fail(KZ_ERR_UNSUPPORTED, "%s: the camera's pixel -> direction map is not affine (a sampleToCamera whose divide depends on the sample position, or a toWorld that is not affine) or is not finite", call);
+    const double m[9] = {view->u[0], view->v[0], view->a[0], view->u[1], view->v[1], view->a[1], view->u[2], view->v[2], view->a[2]};      // columns (u, v, a)
+    const double c[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                         m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                         m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};      // the adjugate, row-major
+    const double det = m[0] * c[0] + m[1] * c[3] + m[2] * c[6];
+    bool fin = det != 0.0 && std::isfinite(det);
+    for (int k = 0; k < 9 && fin; ++k) { view->inv[k] = (float)(c[k] / det); fin = std::isfinite(view->inv[k]); }
+    if (!fin) { std::memset(view, 0, sizeof *view); return kz_fail(KZ_ERR_UNSUPPORTED, "%s: the matrix (u, v, a) of the camera's view is singular (determinant %g)", call, det); }
+    return KZ_OK;
+}
+static void dnSetViews(KzDnTemporal *T, const KzTemporalView &cur, const float po[3], const float pinv[9]) {
+    for (int k = 0; k < 3; ++k) { T->o[k] = cur.o[k]; T->a[k] = cur.a[k]; T->u[k] = cur.u[k]; T->v[k] = cur.v[k]; T->po[k] = po[k]; }
+    for (int k = 0; k < 9; ++k) T->pinv[k] = pinv[k];
+}
 
 // KzVarianceOpts, checked: sv2 = sigmaVariance^2 with the default filled in
 static int dnVarianceOpts(const KzVarianceOpts *vopts, const char *call, float *sv2, uint32_t *samples) {
@@ -261,7 +383,8 @@ static int dnRun(const KzDnPlan &plan, const KzDnVar *var, int width, int height
     const int demod = plan.demodulate ? 1 : 0;
     const dim3 gPix((nPix + KZ_DN_BLOCK - 1) / KZ_DN_BLOCK), gTexels((nTexels + KZ_DN_BLOCK - 1) / KZ_DN_BLOCK), b1(KZ_DN_BLOCK);
     albedo = (plan.guides & KZ_AOV_ALBEDO) ? albedo : nullptr; normal = (plan.guides & KZ_AOV_NORMAL) ? normal : nullptr; depth = (plan.guides & KZ_AOV_DEPTH) ? depth : nullptr;
-    if (var) hipLaunchKernelGGL(kz_dn_prepare_var, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, colour[0], normalZ, albedoP);
+    if (var && var->temporal) hipLaunchKernelGGL(kz_dn_prepare_temporal, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, *var->temporal, colour[0], normalZ, albedoP);
+    else if (var) hipLaunchKernelGGL(kz_dn_prepare_var, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, colour[0], normalZ, albedoP);
     else hipLaunchKernelGGL(kz_dn_prepare, gPix, b1, 0, stream, width, height, border, film, albedo, normal, depth, demod, colour[0], normalZ, albedoP);
     HIP_TRY(hipGetLastError());
     const dim3 grid((unsigned)((width + KZ_DN_ROW - 1) / KZ_DN_ROW), (unsigned)((height + KZ_DN_BLOCK / KZ_DN_ROW - 1) / (KZ_DN_BLOCK / KZ_DN_ROW))), blk(KZ_DN_ROW, KZ_DN_BLOCK / KZ_DN_ROW);
@@ -293,11 +416,33 @@ static int dnRun(const KzDnPlan &plan, const KzDnVar *var, int width, int height
     return KZ_OK;
 }
 
+// A history's three planes into the interchange format: per pixel (e.rgb, v), (n.xyz, z), (N, 0, 0, 0)
+static int dnHistoryDownload(const DevBuf<float4> &E, const DevBuf<float4> &G, const DevBuf<float> &N, size_t nPix, float *history) {
+    std::vector<float> e(4 * nPix), g(4 * nPix), n(nPix);
+    int rc;
+    if ((rc = E.download((float4 *)e.data(), nPix)) || (rc = G.download((float4 *)g.data(), nPix)) || (rc = N.download(n.data(), nPix))) return rc;
+    for (size_t i = 0; i < nPix; ++i) {
+        std::memcpy(history + 12 * i, &e[4 * i], 16); std::memcpy(history + 12 * i + 4, &g[4 * i], 16);
+        history[12 * i + 8] = n[i]; history[12 * i + 9] = history[12 * i + 10] = history[12 * i + 11] = 0.f;
+    }
+    return KZ_OK;
+}
+
 // A call on a replica's own films, into its denoise buffers: behind the replica's queued work, with the guides the plan wants (and the moment film) resolved
-static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, KzDnVar *var) {
+// `T` (kz_denoise_temporal alone): its checked options; the views and the replica's history are filled in here, and the history moves on when the call has succeeded
+static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, KzDnVar *var, KzDnTemporal *T = nullptr) {
     const KzParams &P = scene->prm;
     const size_t nPix = (size_t)P.width * (size_t)P.height;
     int rc;
+    KzTemporalView view;
+    bool fresh = true;                                                  // T: nothing stored, or what is stored is stale
+    if (T) {
+        if ((rc = dnViewOf(P, "kz_denoise_temporal", &view))) return rc;
+        fresh = !ds->tpFrames || ds->tpEdits != scene->geometryEdits || ds->tpE[0].cap() != nPix;
+        if (!fresh && ds->tpDemod != plan.demodulate)
+            return kz_fail(KZ_ERR_STATE, "kz_denoise_temporal: this call %s, the history of %u frame(s) holds colours that %s: kz_temporal_reset first", plan.demodulate ? "demodulates" : "does not demodulate",
+                           ds->tpFrames, ds->tpDemod ? "are demodulated" : "are not");
+    }
     HIP_TRY(hipStreamSynchronize(ds->lastStream));                      // the replica's queued work: the films and the sums are final
     if (var && ds->moment().sums && ds->moment().texels) {
         if ((rc = kzFilmResolve(scene, ds->moment(), ds->lastStream))) return rc;
@@ -305,7 +450,7 @@ static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, 
     }
     const float4 *guide[3] = {nullptr, nullptr, nullptr};
     for (int f = 0; f < 3; ++f) {
-        const bool wanted = f == 0 ? (plan.demodulate || (plan.guided && (plan.guides & KZ_AOV_ALBEDO))) : (plan.guided && (plan.guides & (1u << f)));
+        const bool wanted = f == 0 ? (plan.demodulate || (plan.guided && (plan.guides & KZ_AOV_ALBEDO))) : ((plan.guided || T) && (plan.guides & (1u << f)));      // (T: the reprojection reads n and z whatever the weights use)
         KzFilm &film = ds->aov(f);
         if (!wanted || !film.sums || !film.texels) continue;                // (enabled, nothing rendered yet: zeros, as kz_aov_download gives)
         if ((rc = kzFilmResolve(scene, film, ds->lastStream))) return rc;
@@ -315,16 +460,35 @@ static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, 
     for (DevBuf<float4> *b : {&ds->dnColor[0], &ds->dnColor[1], &ds->dnNormalZ, &ds->dnAlbedo})
         if (b->cap() != nPix && (rc = b->regrow(nPix))) return rc;
     if (ds->dnOut.cap() != ds->filmPixels && (rc = ds->dnOut.regrow(ds->filmPixels))) return rc;
+    if (T) {
+        if (fresh) ds->tpFrames = 0;                                    // (from here on a call that fails leaves either the history it found or none)
+        for (int k = 0; k < 2; ++k) {
+            for (DevBuf<float4> *b : {&ds->tpE[k], &ds->tpG[k]}) if (b->cap() != nPix && (rc = b->regrow(nPix))) return rc;
+            if (ds->tpN[k].cap() != nPix && (rc = ds->tpN[k].regrow(nPix))) return rc;
+        }
+        const int in = ds->tpCur, out = in ^ 1;
+        dnSetViews(T, view, ds->tpO, ds->tpInv);
+        if (!fresh && T->maxHistory != 1.0f) { T->inE = ds->tpE[in]; T->inG = ds->tpG[in]; T->inN = ds->tpN[in]; }      // (maxHistory = 1: without history, by definition)
+        T->outE = ds->tpE[out]; T->outG = ds->tpG[out]; T->outN = ds->tpN[out];
+        var->temporal = T;
+    }
     float4 *const colour[2] = {ds->dnColor[0].get(), ds->dnColor[1].get()};
     if ((rc = dnRun(plan, var, P.width, P.height, P.border, ds->picture().texels, guide[0], guide[1], guide[2], colour, ds->dnNormalZ, ds->dnAlbedo, ds->dnOut, ds->lastStream))) return rc;
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     ds->dnValid = true;
+    if (T) {
+        ds->tpCur ^= 1; ds->tpFrames += 1; ds->tpDemod = plan.demodulate; ds->tpEdits = scene->geometryEdits;
+        std::memcpy(ds->tpO, view.o, sizeof ds->tpO); std::memcpy(ds->tpInv, view.inv, sizeof ds->tpInv);
+    }
     return KZ_OK;
 }
 
-// A call on films of the host's: kz_denoise_films, and with `moment` kz_denoise_variance_films (`vopts`, `outVariance`: its alone)
+// What kz_denoise_temporal_films adds to a call on host films: the views and the history in the interchange format (12 floats per pixel), in and out
+struct KzDnHostTemporal { const KzTemporalOpts *topts; const KzTemporalView *current, *previous; const float *historyIn; float *historyOut; };
+
+// A call on films of the host's: kz_denoise_films, with `moment` kz_denoise_variance_films (`vopts`, `outVariance`: its alone), with `ht` kz_denoise_temporal_films
 static int dnFilms(const char *call, int device, int32_t width, int32_t height, int32_t border, const float *film, const float *moment, const float *albedo, const float *normal,
-                   const float *depth, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, float *out, float *outVariance) {
+                   const float *depth, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, float *out, float *outVariance, const KzDnHostTemporal *ht = nullptr) {
     if (width < 1 || height < 1 || border < 0 || border > 64 || (uint64_t)(width + 2 * (int64_t)border) * (uint64_t)(height + 2 * (int64_t)border) >= (1ull << 31))
         return kz_fail(KZ_ERR_INVALID_ARG, "%s: a frame of %d x %d with border %d (at least 1 x 1, border 0 .. 64, fewer than 2^31 texels)", call, width, height, border);
     KzDnPlan plan; KzDnVar var = {}; int rc;
@@ -336,6 +500,8 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
         if (!samples) return kz_fail(KZ_ERR_STATE, "%s: KzVarianceOpts.samples = 0 (there is no replica whose count could stand in: state it)", call);
         var.samples = (float)samples;
     }
+    KzDnTemporal T;
+    if (ht && ((rc = dnTemporalOpts(ht->topts, call, &T)) || (rc = dnTemporalGuides(plan, avail, call)))) return rc;
     if ((rc = kzUseDevice(device))) return rc;
     const size_t nPix = (size_t)width * (size_t)height, nTexels = (size_t)(width + 2 * border) * (size_t)(height + 2 * border);
     DevBuf<float4> films[5], planes[4], result; DevBuf<float> variance;
@@ -348,9 +514,25 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
     if ((rc = result.alloc(nTexels))) return rc;
     if (outVariance && (rc = variance.alloc(nPix))) return rc;
     var.moment = films[4]; var.variance = variance;
+    DevBuf<float4> hE[2], hG[2]; DevBuf<float> hN[2];                   // the history: [0] read (historyIn), [1] written
+    if (ht) {
+        static const float noView[9] = {};
+        dnSetViews(&T, *ht->current, ht->previous ? ht->previous->o : noView, ht->previous ? ht->previous->inv : noView);
+        const bool in = ht->historyIn && T.maxHistory != 1.0f;           // (maxHistory = 1: without history, by definition)
+        for (int k = in ? 0 : 1; k < 2; ++k) if ((rc = hE[k].alloc(nPix)) || (rc = hG[k].alloc(nPix)) || (rc = hN[k].alloc(nPix))) return rc;
+        if (in) {
+            std::vector<float> e(4 * nPix), g(4 * nPix), n(nPix);
+            for (size_t i = 0; i < nPix; ++i) { std::memcpy(&e[4 * i], ht->historyIn + 12 * i, 16); std::memcpy(&g[4 * i], ht->historyIn + 12 * i + 4, 16); n[i] = ht->historyIn[12 * i + 8]; }
+            if ((rc = hE[0].upload((const float4 *)e.data(), nPix)) || (rc = hG[0].upload((const float4 *)g.data(), nPix)) || (rc = hN[0].upload(n.data(), nPix))) return rc;
+            T.inE = hE[0]; T.inG = hG[0]; T.inN = hN[0];
+        }
+        T.outE = hE[1]; T.outG = hG[1]; T.outN = hN[1];
+        var.temporal = &T;
+    }
     float4 *const colour[2] = {planes[0].get(), planes[1].get()};
     if ((rc = dnRun(plan, moment ? &var : nullptr, width, height, border, films[0], films[1], films[2], films[3], colour, planes[2], planes[3], result, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
+    if (ht && ht->historyOut && (rc = dnHistoryDownload(hE[1], hG[1], hN[1], nPix, ht->historyOut))) return rc;
     if (outVariance && (rc = variance.download(outVariance, nPix))) return rc;
     return result.download((float4 *)out, nTexels);
 }
@@ -425,6 +607,70 @@ int kz_denoise_variance_films(int device, int32_t width, int32_t height, int32_t
                               const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, float *out, float *outVariance) {
     if (!film || !moment || !out) return kz_fail(KZ_ERR_INVALID_ARG, "kz_denoise_variance_films: null film");
     return dnFilms("kz_denoise_variance_films", device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance);
+}
+
+// ---- include/kazen_mi355x_temporal.h
+int kz_temporal_view(const KzCamera *camera, KzTemporalView *view) {
+    if (!camera || !view) return kz_fail(KZ_ERR_INVALID_ARG, "kz_temporal_view: null argument");
+    std::memset(view, 0, sizeof *view);
+    if (camera->width < 1 || camera->height < 1) return kz_fail(KZ_ERR_INVALID_ARG, "kz_temporal_view: a frame of %d x %d", camera->width, camera->height);
+    KzParams P{};
+    int rc;
+    if ((rc = kzCameraParams(*camera, P))) return rc;
+    return dnViewOf(P, "kz_temporal_view", view);
+}
+
+int kz_denoise_temporal(KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts) {
+    static const char *const call = "kz_denoise_temporal";
+    if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null scene", call);
+    KzDnPlan plan; KzDnVar var = {}; KzDnTemporal T; KzDeviceState *ds; int rc; uint32_t samples;
+    if ((rc = dnPlan(opts, scene->aovMask, call, &plan, 2.0f)) || (rc = dnVarianceOpts(vopts, call, &var.sv2, &samples)) || (rc = dnTemporalOpts(topts, call, &T)) ||
+        (rc = dnTemporalGuides(plan, scene->aovMask, call))) return rc;
+    if (!(scene->aovMask & KZ_AOV_DEPTH)) return kz_fail(KZ_ERR_STATE, "%s: the depth film is not among the scene's AOVs (mask %u, KZ_AOV_DEPTH = %u): kz_scene_set_aovs, then render", call, scene->aovMask, KZ_AOV_DEPTH);
+    if (!scene->varianceMode) return kz_fail(KZ_ERR_STATE, "%s: the second-moment film is switched off (kz_scene_variance gives 0): kz_scene_set_variance(scene, 1), then render", call);
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    if (!samples) samples = ds->momentSamples;
+    if (!samples) return kz_fail(KZ_ERR_STATE, "%s: KzVarianceOpts.samples = 0 and the replica's second-moment film has been given 0 samples per pixel (the picture's: %u)", call, ds->pictureSamples);
+    if (ds->pictureSamples != ds->momentSamples)
+        return kz_fail(KZ_ERR_STATE, "%s: the picture's film holds %u samples per pixel, the second-moment film %u (switched on late: kz_film_clear, then render both)", call, ds->pictureSamples, ds->momentSamples);
+    var.samples = (float)samples;
+    return dnOnReplica(scene, ds, plan, &var, &T);
+}
+
+int kz_temporal_info(KzScene *scene, int device, uint64_t *bytes, uint32_t *frames) {
+    KzDeviceState *ds; int rc;
+    if (!bytes && !frames) return kz_fail(KZ_ERR_INVALID_ARG, "kz_temporal_info: null bytes and frames");
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    if (bytes) *bytes = ds->tpBytes();
+    if (frames) *frames = ds->tpFrames;
+    return KZ_OK;
+}
+
+int kz_temporal_reset(KzScene *scene, int device) {
+    KzDeviceState *ds; int rc;
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    HIP_TRY(hipStreamSynchronize(ds->lastStream));
+    for (int k = 0; k < 2; ++k) { ds->tpE[k].free(); ds->tpG[k].free(); ds->tpN[k].free(); }
+    ds->tpFrames = 0; ds->tpCur = 0;
+    return KZ_OK;
+}
+
+int kz_temporal_download(KzScene *scene, int device, float *history, size_t nFloats) {
+    KzDeviceState *ds; int rc;
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    if (!ds->tpFrames) return kz_fail(KZ_ERR_STATE, "kz_temporal_download: no kz_denoise_temporal has run on this replica (or its history was reset)");
+    const size_t nPix = ds->tpN[ds->tpCur].cap();
+    if (!history || nFloats != nPix * 12) return kz_fail(KZ_ERR_INVALID_ARG, "kz_temporal_download: history buffer must hold %zu floats", nPix * 12);
+    return dnHistoryDownload(ds->tpE[ds->tpCur], ds->tpG[ds->tpCur], ds->tpN[ds->tpCur], nPix, history);
+}
+
+int kz_denoise_temporal_films(int device, int32_t width, int32_t height, int32_t border, const float *film, const float *moment, const float *albedo, const float *normal, const float *depth,
+                              const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts, const KzTemporalView *current, const KzTemporalView *previous,
+                              const float *historyIn, float *out, float *historyOut, float *outVariance) {
+    if (!film || !moment || !depth || !out) return kz_fail(KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films: null film (the picture, the moment film and the depth film are needed)");
+    if (!current || (historyIn && !previous)) return kz_fail(KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films: null view (the current one, and with a history the one it was stored with)");
+    const KzDnHostTemporal ht = {topts, current, previous, historyIn, historyOut};
+    return dnFilms("kz_denoise_temporal_films", device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance, &ht);
 }
 
 } // extern "C"

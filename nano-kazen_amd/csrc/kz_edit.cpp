@@ -200,6 +200,7 @@ int kz_scene_set_vertices(KzScene *sc, const KzVertexUpdate *u, uint32_t n) {
         if (!lightRows.empty()) kzInvisibleLights(sc);
         sc->hostStale = true;
     }
+    ++sc->geometryEdits;                                       // (no motion vectors: every replica's temporal history is stale from here on)
     return kzEditVertices(sc, u, n, lightRows);
 }
 
@@ -304,6 +305,7 @@ int kz_scene_set_transforms(KzScene *sc, const KzTransformUpdate *u, uint32_t n)
         if (!lightRows.empty()) kzInvisibleLights(sc);
         sc->hostStale = true;
     }
+    ++sc->geometryEdits;
     return kzEditXformCommit(sc, jobs.data(), n, lightRows);
 }
 

@@ -322,27 +322,36 @@ int kzCameraParams(const KzCamera &c, KzParams &p) {
         for (int i = 0; i < 16; ++i) p.s2c[i] = (float)Mi[i];
     }
     {   // pixel beams (kz_wf_beam): only for a pinhole camera whose homogeneous divide does not depend on the sample position and an affine c2w
-        const float *m = p.s2c, *w = p.c2w;
         p.beamOk = 0;
         for (int r = 0; r < 3; ++r) p.beamO[r] = p.beamA[r] = p.beamU[r] = p.beamV[r] = 0.f;      // (a camera without beams carries zeros: an edit leaves no stale ones)
-        const float tiny = 1e-9f * std::fabs(m[15]);          // (a numerically formed inverse leaves 1e-17s where the zeros are: far inside the beams' margins)
-        if (c.type != KZ_CAMERA_THINLENS && std::fabs(m[12]) <= tiny && std::fabs(m[13]) <= tiny && m[15] != 0.f && w[12] == 0.f && w[13] == 0.f && w[14] == 0.f && w[15] != 0.f) {
-            const double rw = m[15];
-            const double A[3] = {m[3] / rw, m[7] / rw, m[11] / rw}, U[3] = {m[0] * (double)p.invW / rw, m[4] * (double)p.invW / rw, m[8] * (double)p.invW / rw},
-                         V[3] = {m[1] * (double)p.invH / rw, m[5] * (double)p.invH / rw, m[9] * (double)p.invH / rw};
-            bool fin = true;
-            for (int r = 0; r < 3; ++r) {
-                p.beamA[r] = (float)(w[4 * r] * A[0] + w[4 * r + 1] * A[1] + w[4 * r + 2] * A[2]);
-                p.beamU[r] = (float)(w[4 * r] * U[0] + w[4 * r + 1] * U[1] + w[4 * r + 2] * U[2]);
-                p.beamV[r] = (float)(w[4 * r] * V[0] + w[4 * r + 1] * V[1] + w[4 * r + 2] * V[2]);
-                p.beamO[r] = w[4 * r + 3] / w[15];
-                fin = fin && std::isfinite(p.beamA[r]) && std::isfinite(p.beamU[r]) && std::isfinite(p.beamV[r]) && std::isfinite(p.beamO[r]);
-            }
-            p.beamOk = fin ? 1 : 0;
+        float O[3], A[3], U[3], V[3];
+        if (c.type != KZ_CAMERA_THINLENS && kzPinholeWords(p, O, A, U, V)) {
+            for (int r = 0; r < 3; ++r) { p.beamO[r] = O[r]; p.beamA[r] = A[r]; p.beamU[r] = U[r]; p.beamV[r] = V[r]; }
+            p.beamOk = 1;
         }
     }
     p.cameraType = c.type; p.apertureRadius = c.apertureRadius; p.focusDistance = c.focusDistance;
     return KZ_OK;
+}
+
+// nearP(sx, sy) = A + sx * U + sy * V in world axes (the 3x3 of c2w applied; sx, sy in pixels), apex O: there when the homogeneous divide of s2c does not depend on
+// the sample position and c2w is affine, and every word is finite. Formed in double and narrowed once.
+bool kzPinholeWords(const KzParams &p, float O[3], float A[3], float U[3], float V[3]) {
+    const float *m = p.s2c, *w = p.c2w;
+    const float tiny = 1e-9f * std::fabs(m[15]);          // (a numerically formed inverse leaves 1e-17s where the zeros are: far inside the beams' margins)
+    if (!(std::fabs(m[12]) <= tiny && std::fabs(m[13]) <= tiny && m[15] != 0.f && w[12] == 0.f && w[13] == 0.f && w[14] == 0.f && w[15] != 0.f)) return false;
+    const double rw = m[15];
+    const double a[3] = {m[3] / rw, m[7] / rw, m[11] / rw}, u[3] = {m[0] * (double)p.invW / rw, m[4] * (double)p.invW / rw, m[8] * (double)p.invW / rw},
+                 v[3] = {m[1] * (double)p.invH / rw, m[5] * (double)p.invH / rw, m[9] * (double)p.invH / rw};
+    bool fin = true;
+    for (int r = 0; r < 3; ++r) {
+        A[r] = (float)(w[4 * r] * a[0] + w[4 * r + 1] * a[1] + w[4 * r + 2] * a[2]);
+        U[r] = (float)(w[4 * r] * u[0] + w[4 * r + 1] * u[1] + w[4 * r + 2] * u[2]);
+        V[r] = (float)(w[4 * r] * v[0] + w[4 * r + 1] * v[1] + w[4 * r + 2] * v[2]);
+        O[r] = w[4 * r + 3] / w[15];
+        fin = fin && std::isfinite(A[r]) && std::isfinite(U[r]) && std::isfinite(V[r]) && std::isfinite(O[r]);
+    }
+    return fin;
 }
 
 namespace {

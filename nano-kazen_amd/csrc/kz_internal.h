@@ -204,7 +204,8 @@ struct KzScene {
     bool hostStale = false;             // tris, nodes, nodes4 and bvh.sahCost do not follow the last edit yet (kzHostSync brings them up to date)
     uint32_t aovMask = 0;               // KZ_AOV_* feature films every render of the scene produces beside the picture (kazen_mi355x_aov.h; kz_scene_set_aovs)
     int32_t varianceMode = 0;           // KZ_VARIANCE_*: every render keeps a second-moment film beside the picture's (kazen_mi355x_variance.h; kz_scene_set_variance)
-    std::mutex editMutex;               // guards the lazy host refit (kzHostSync may be reached from several device threads of kz_render_multi)
+    uint64_t geometryEdits = 0;         // kz_scene_set_vertices / kz_scene_set_transforms calls that changed something: a replica's temporal history (kazen_mi355x_temporal.h) older than the last one is stale
+    std::mutex editMutex;              // guards the lazy host refit (kzHostSync may be reached from several device threads of kz_render_multi)
     // device replicas, one per GPU the scene is resident on (KzReplicaSet, owned by kz_render.hip; created with the scene)
     void *dev = nullptr;
 };
@@ -226,6 +227,7 @@ int kzVarianceRefuseGather(const KzScene *scene, const char *call);
 // kz_host.cpp
 int kz_fail(int code, const char *fmt, ...);
 int kzCameraParams(const KzCamera &c, KzParams &p);                     // the camera part of KzParams (pixel beams included)
+bool kzPinholeWords(const KzParams &p, float O[3], float A[3], float U[3], float V[3]);      // the affine pixel -> near-plane map of p.s2c / p.c2w, whatever the camera's type; false: there is none
 void kzLightCdf(const KzTriShade *shade, uint32_t nF, std::vector<float> &t, float &normalization);   // a light mesh's area CDF (t[0] = 0, nF + 1 entries)
 void kzInvisibleLights(KzScene *sc);                                    // ilTris, ilLo / ilHi, ilGid* and shadowFast from the shading records (and kzEmitterTris)
 void kzEmitterTris(KzScene *sc);                                        // emTris, nEmTris, emLo / emHi from the shading records, the background and the integrator

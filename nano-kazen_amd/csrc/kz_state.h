@@ -198,6 +198,11 @@ struct KzDeviceState {
     // dnValid: dnOut holds the result of a kz_denoise (a snapshot: renders, clears and edits leave it alone).
     DevBuf<float4> dnColor[2], dnNormalZ, dnAlbedo, dnOut; bool dnValid = false;
     size_t dnBytes() const { return dnColor[0].bytes() + dnColor[1].bytes() + dnNormalZ.bytes() + dnAlbedo.bytes() + dnOut.bytes(); }
+    // The temporal history (kazen_mi355x_temporal.h), allocated by the first kz_denoise_temporal, outside the budget too: per frame pixel (e.rgb, v) | (n.xyz, z) | N in
+    // three planes, twice - a call reads copy tpCur and writes the other. tpFrames: calls folded into it since it started (0: nothing stored); tpO / tpInv: the view it
+    // was stored with; tpDemod: whether its colours are demodulated; tpEdits: the scene's geometryEdits then (another value now: stale).
+    DevBuf<float4> tpE[2], tpG[2]; DevBuf<float> tpN[2]; int tpCur = 0; uint32_t tpFrames = 0; bool tpDemod = false; uint64_t tpEdits = 0; float tpO[3] = {}, tpInv[9] = {};
+    size_t tpBytes() const { size_t b = 0; for (int k = 0; k < 2; ++k) b += tpE[k].bytes() + tpG[k].bytes() + tpN[k].bytes(); return b; }
     DevBuf<float4> packDev; DevBuf<KzTileRect> rectsDev;         // kz_film_download_tiles: packed tile rects + their table
     PinnedBuf<float4> packHost;                                  // pinned staging of the same (D2H at link rate)
     // The tile set: pixList = its pixels (tile after tile, 8x8 blocks row-major inside a tile, row-major inside a block), written on the device from the

@@ -488,6 +488,30 @@ class Scene:
         o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
         abi.check(self.lib, self.lib.kz_denoise_variance(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v)))
 
+    # ---- the denoiser's history across camera edits (include/kazen_mi355x_temporal.h)
+    def denoise_temporal(self, device=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0, depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0,
+                         treserved=(0, 0, 0, 0), **opts):
+        """kz_denoise_temporal: denoise_variance() with the replica's history reprojected from the previous call's camera and blended in first; the result is read
+        like denoise()'s. Options: denoise_opts', variance_opts' and temporal_opts'."""
+        o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
+        t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
+        abi.check(self.lib, self.lib.kz_denoise_temporal(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v), C.byref(t)))
+
+    def temporal_info(self, device=-1):
+        """kz_temporal_info: (bytes the history holds on that replica, calls folded into it since it last started)."""
+        b, n = C.c_uint64(), C.c_uint32()
+        abi.check(self.lib, self.lib.kz_temporal_info(self.h, int(device), C.byref(b), C.byref(n)))
+        return int(b.value), int(n.value)
+
+    def temporal_reset(self, device=-1):
+        abi.check(self.lib, self.lib.kz_temporal_reset(self.h, int(device)))
+
+    def temporal_history(self, device=None):
+        """kz_temporal_download: (h, w, 12) = per pixel (e.rgb, v), (n.xyz, z), (N, 0, 0, 0) - what denoise_temporal_films takes as `history`."""
+        out = np.zeros((self.height, self.width, 12), np.float32)
+        abi.check(self.lib, self.lib.kz_temporal_download(self.h, -1 if device is None else int(device), out.ctypes.data_as(abi.f32p), out.size))
+        return out
+
     def bsdf_query(self, bsdf, wi, wo, acc, s3, uv=None):
         """eval (n,3), pdf (n,), sample (n,8) = weight rgb, wo xyz, alive, pdf(bRec) after sample()."""
         bsdf = np.ascontiguousarray(bsdf, np.int32)
@@ -603,6 +627,50 @@ def denoise_variance_films(film, moment, albedo=None, normal=None, depth=None, b
     abi.check(lib, lib.kz_denoise_variance_films(int(device), *frame, film.ctypes.data_as(abi.f32p), *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g],
                                                  C.byref(o), C.byref(v), out.ctypes.data_as(abi.f32p), None if var is None else var.ctypes.data_as(abi.f32p)))
     return (out, var) if return_variance else out
+
+
+def temporal_opts(depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, flags=0, reserved=(0, 0, 0, 0)):
+    """A KzTemporalOpts: 0 means the default (depth tolerance 0.05 relative, normal tolerance 0.5, a history of 32 calls)."""
+    return abi.KzTemporalOpts(float(depth_tolerance), float(normal_tolerance), int(max_history), int(flags), (C.c_uint32 * 4)(*[int(r) for r in reserved]))
+
+
+def temporal_view(camera, lib=None):
+    """kz_temporal_view: the KzTemporalView of a camera given as SceneDescription.camera gives it (a dict). Needs no device."""
+    from .scenes import camera_to_c
+    lib = lib or abi.load_library()
+    cam = dict(camera)
+    if "toWorld" in cam:
+        cam["toWorld"] = np.array(cam["toWorld"], np.float32)
+    c = camera_to_c(cam, abi.KzCamera())
+    view = abi.KzTemporalView()
+    abi.check(lib, lib.kz_temporal_view(C.byref(c), C.byref(view)))
+    view._camera = c                                                    # (keeps what the C camera points to alive with the view)
+    return view
+
+
+def denoise_temporal_films(film, moment, albedo=None, normal=None, depth=None, border=0, device=0, lib=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0,
+                           depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0, treserved=(0, 0, 0, 0), current=None, previous=None, history=None,
+                           return_variance=False, **opts):
+    """kz_denoise_temporal_films: the device's temporal stage and variance-guided denoiser on host films (denoise_variance_films' layout; `depth` and `samples` must be
+    given). current / previous: KzTemporalView of this frame and of `history` ((h, w, 12) as Scene.temporal_history gives it; None: no history).
+    Returns (film, history (h, w, 12)), or (film, history, v_last (h, w)) with return_variance."""
+    lib = lib or abi.load_library()
+    film, g, frame = _host_films(film, (moment, albedo, normal, depth), border, "the moment film and the guide films have the picture's shape")
+    h, w = max(frame[1], 0), max(frame[0], 0)
+    if history is not None:
+        history = np.ascontiguousarray(history, np.float32)
+        if history.shape != (h, w, 12):
+            raise ValueError("a history is (h, w, 12)")
+    out = np.empty_like(film)
+    hist = np.full((h, w, 12), np.nan, np.float32)
+    var = np.full((h, w), np.nan, np.float32) if return_variance else None
+    o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
+    t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
+    p = lambda a: None if a is None else a.ctypes.data_as(abi.f32p)
+    abi.check(lib, lib.kz_denoise_temporal_films(int(device), *frame, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t),
+                                                 None if current is None else C.byref(current), None if previous is None else C.byref(previous), p(history),
+                                                 p(out), p(hist), p(var)))
+    return (out, hist, var) if return_variance else (out, hist)
 
 
 def hits_to_arrays(hits, n):

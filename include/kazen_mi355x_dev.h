@@ -143,7 +143,7 @@ int kz_pass_mode_info(KzScene *scene, int device, KzPassModeInfo *out);
 int kz_last_grow_note(KzScene *scene, char *buf, size_t cap);
 
 /* ---- DEVELOPMENT BUILDS ONLY (a library compiled with -DKZ_EXPERIMENTS: kz_build_flags() & KZ_BUILD_EXPERIMENTS; nano-kazen_amd/csrc/variants/experiments).
- * These seven are process-global state - the product library does not contain them (`nm -D libkazen_mi355x.so | grep kz_debug` is empty), so that nothing behind the
+ * These eight are process-global state - the product library does not contain them (`nm -D libkazen_mi355x.so | grep kz_debug` is empty), so that nothing behind the
  * product ABI depends on state outside the objects the caller holds. The tests that need them load the development variant.
  *   kz_debug_fail_alloc    the nth device allocation made from now on by the calling thread fails with KZ_ERR_OOM (0 = off): a failure in the middle of a call
  *                          releases what the call had allocated.
@@ -171,6 +171,10 @@ void kz_debug_rr_ahead(int on);
  *                          kernels do and as they did before; 1 = into the child whose box holds the longest part of the segment (the default). Which occluder
  *                          an any-hit ray finds first does not change its answer: the films are the same bits either way (tests/test_shadow_order_gpu.py). */
 void kz_debug_shadow_order(int on);
+/*   kz_debug_compact_late  0 = the path_mis passes launched from now on keep every bounce in the pass's own path-state arrays, as they did before; 1 = in front of the
+ *                          first roulette bounce the survivors' state moves to the context's dense set and the later launches run there (the default). The films
+ *                          are the same bits either way (tests/test_late_compact_gpu.py). */
+void kz_debug_compact_late(int on);
 
 /* ---- the pass planner (nano-kazen_amd/csrc/kz_plan.cpp: pure host arithmetic, no GPU, no state) through the ABI: what kz_render would decide for a call.
  * tests/test_plan_cpu.py tabulates it for the BASELINE configs - the table is the documentation of the pass policy. */

@@ -263,7 +263,7 @@ KZ_VARIANCE_OFF, KZ_VARIANCE_ON, KZ_VARIANCE_TWO_LAUNCHES, KZ_VARIANCE_ONE_PASS 
 TEMPORAL_EXPORTS = ["kz_temporal_view", "kz_denoise_temporal", "kz_temporal_info", "kz_temporal_reset", "kz_temporal_download", "kz_denoise_temporal_films"]
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
-DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead", "kz_debug_shadow_order"]
+DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead", "kz_debug_shadow_order", "kz_debug_compact_late"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KZ_LIB_PATH: a development build of the library (scripts/build_variant.sh) instead of the in-tree one; probes only
@@ -280,7 +280,7 @@ class KzError(RuntimeError):
 
 def load_dev_library():
     """The development variant of the library (-DKZ_EXPERIMENTS: the same sources plus the hooks that are process-global state - kz_debug_fail_alloc /
-    fail_device / grow_delay / trace / alias_devices / rr_ahead / shadow_order). Only tests load it; a second copy of the library in one process is a separate world
+    fail_device / grow_delay / trace / alias_devices / rr_ahead / shadow_order / compact_late). Only tests load it; a second copy of the library in one process is a separate world
     (its own device pools, its own replicas)."""
     return load_library(DEV_LIB_PATH)
 

@@ -302,4 +302,7 @@ extern "C" void kz_debug_rr_ahead(int on) { g_kzRrAhead.store(on == 2 ? 2 : on ?
 // kz_debug_shadow_order: whether the any-hit shadow launches descend first into the child that holds most of the segment (kz_render.hip launchTrace reads it per launch)
 std::atomic<int> g_kzShadowOrder{1};
 extern "C" void kz_debug_shadow_order(int on) { g_kzShadowOrder.store(on ? 1 : 0); }
+// kz_debug_compact_late: whether a path_mis pass moves its survivors to the context's dense set in front of the first roulette bounce (kz_render.hip wfPass reads it per pass)
+std::atomic<int> g_kzCompactLate{1};
+extern "C" void kz_debug_compact_late(int on) { g_kzCompactLate.store(on ? 1 : 0); }
 #endif

@@ -109,7 +109,17 @@ static int ctxEnsure(PassCtx &c, size_t want, size_t minItems, double graceMs, h
 }
 
 // kz_wf_trace instantiations by (mode, stats): the launch code picks from this table instead of a ladder of macros
-static decltype(&kz_wf_trace<0, false>) traceFn(int mode, bool stats) {
+static decltype(&kz_wf_trace<0, false>) traceFn(int mode, bool stats, bool late) {
+    // the bounces behind kz_wf_compact (wfMis): the instantiations that take their per-path arrays from the device (modes 0 / 2 / 4: what a bounce loop launches)
+    if (late) {
+        constexpr int L = KZ_MODE_LATE;
+        static const decltype(&kz_wf_trace<0, false>) ltab[5][2] = {{kz_wf_trace<L, false>, kz_wf_trace<L, true>}, {nullptr, nullptr},
+                                            {kz_wf_trace<L + 2, false>, kz_wf_trace<L + 2, true>}, {nullptr, nullptr}, {kz_wf_trace<L + 4, false>, kz_wf_trace<L + 4, true>}};
+#ifdef KZ_EXPERIMENTS
+        if (mode == 4 && !g_kzShadowOrder.load(std::memory_order_relaxed)) return stats ? kz_wf_trace<L + 5, true> : kz_wf_trace<L + 5, false>;
+#endif
+        return ltab[mode][stats ? 1 : 0];
+    }
     static const decltype(&kz_wf_trace<0, false>) tab[5][2] = {{kz_wf_trace<0, false>, kz_wf_trace<0, true>}, {kz_wf_trace<1, false>, kz_wf_trace<1, true>},
                                         {kz_wf_trace<2, false>, kz_wf_trace<2, true>}, {nullptr, nullptr}, {kz_wf_trace<4, false>, kz_wf_trace<4, true>}};
 #ifdef KZ_EXPERIMENTS
@@ -132,9 +142,11 @@ static decltype(&kz_wf_trace_packet<false, false>) packetFn(bool stats, bool fix
 static int extSel(int bsdfExt, int all) { return bsdfExt == 0 ? 0 : (bsdfExt == KZ_X_MODELS ? KZ_X_MODELS : all); }
 static int extCol(int ext) { return ext == 0 ? 0 : (ext == KZ_X_MODELS ? 1 : 2); }
 typedef decltype(&kz_wf_shade<false, 0>) KzShadeFn;
-static KzShadeFn shadeFn(bool stats, int ext) {      // ext: 0 / KZ_X_MODELS / KZ_X_ALL
+static KzShadeFn shadeFn(bool stats, int ext, bool late = false) {      // ext: 0 / KZ_X_MODELS / KZ_X_ALL; late: the bounces behind kz_wf_compact (wfMis)
     static const KzShadeFn tab[2][3] = {{kz_wf_shade<false, 0>, kz_wf_shade<false, KZ_X_MODELS>, kz_wf_shade<false, KZ_X_ALL>}, {kz_wf_shade<true, 0>, kz_wf_shade<true, KZ_X_MODELS>, kz_wf_shade<true, KZ_X_ALL>}};
-    return tab[stats ? 1 : 0][extCol(ext)];
+    constexpr int L = KZ_X_LATE;
+    static const KzShadeFn ltab[2][3] = {{kz_wf_shade<false, L>, kz_wf_shade<false, L | KZ_X_MODELS>, kz_wf_shade<false, L | KZ_X_ALL>}, {kz_wf_shade<true, L>, kz_wf_shade<true, L | KZ_X_MODELS>, kz_wf_shade<true, L | KZ_X_ALL>}};
+    return (late ? ltab : tab)[stats ? 1 : 0][extCol(ext)];
 }
 typedef decltype(&kz_wf_mats<0>) KzMatsFn;
 static KzMatsFn matsFn(int ext) {                    // ext: 0 / KZ_X_MODELS / KZ_X_MATS
@@ -213,13 +225,13 @@ static TraceShape traceShape(const KzParams &P, unsigned gridBlocks, int ldsStac
 }
 // One kz_wf_trace launch: mode 0 / 1 / 2 / 4 on queue q (nullptr: identity) of *cptr (nullptr: cimm) entries, with the defaults a tuning leaves open.
 static void launchTrace(int mode, bool stats, dim3 grid, size_t traceLds, hipStream_t on, const KzParams &P, const KzDevTables &T, const KzWf &W, const uint32_t *q, const uint32_t *cptr,
-                        uint32_t cimm, uint32_t *head, KzTune t, uint32_t *qb, uint32_t *cb) {
+                        uint32_t cimm, uint32_t *head, KzTune t, uint32_t *qb, uint32_t *cb, const KzWfLate *sel = nullptr) {
     if (t.batch <= 0) t.batch = 128;                 // (the least a wave reserves per global atomic: kz_wf_trace asks for more while much is left)
     // idle lanes are refilled once fewer than this many are busy. A refill of the shadow kernel is the dearer one (the invisible-light test of every new
     // ray), so it waits for more idle lanes: same-call sweep, shadow stage 21.7 / 20.9 / 20.9 ms at 40 / 32 / 28 on C3, 20.3 / 20.0 / 20.3 on C4; the
     // closest-hit kernel 32.85 / 33.3 / 34.2 on C4
     if (t.refill <= 0) t.refill = (mode == 2 || mode == 4) ? 32 : 40;
-    hipLaunchKernelGGL(traceFn(mode, stats), grid, dim3(KZ_BLOCK), traceLds, on, P, T, W, q, cptr, cimm, head, t, qb, cb);
+    hipLaunchKernelGGL(traceFn(mode, stats, sel != nullptr), grid, dim3(KZ_BLOCK), traceLds, on, P, T, W, q, cptr, cimm, head, t, qb, cb, sel);      // (sel: the per-path arrays are the ones *sel names - wfMis, behind kz_wf_compact)
 }
 // The shadow rays of queue q: with P.shadowFast the any-hit kernel without the walk-through machinery; the (rare) rays whose segment crosses an
 // invisible-light triangle go to litQ and are walked through by the general kernel. Without it the general kernel takes everything.
@@ -240,6 +252,33 @@ static int ensureOverflow(KzScene *scene, KzDeviceState *ds, PassCtx &c, const K
     return c.ovf.regrow(needOvf);
 }
 
+// The dense set of a pass: a second, small set of the per-path arrays for the late bounces of a path_mis pass (kz_wavefront.h kz_wf_compact; wfMis). It costs no
+// memory: it lies INSIDE the pass's own `hit` array, 16 B per item, which is dead from shade(2)'s last read on if the late bounces move out - their closest-hit
+// launches store into the dense set's hit records - and is not touched at all if they stay (kz_wf_compact decides before it writes; the shadow rays of bounce 2,
+// which may still run beside it, read shA / shB / shL and the shadow queue). An entry is the seven records every bounce needs (ray A / B, hit, throughput, shadow
+// A / B / L), misc and the sampler words where the kernels keep them, and the origin word: 116 - 148 B, so the set holds 16 / 116 = 13.8 % (lean kernels,
+// pmj02bn: C4) to 10.8 % of the pass's items. Measured with kz_debug_trace on passes of 1920 x 1080 x 64 items of the two scenes whose late bounces weigh most
+// (profiles/r20a_compact/README.md): shade(2) queues 9.0 % of C4's items for bounce 3 (11.92 M of 132.7 M) and 10.4 % of C3's (13.86 M; lean, independent:
+// 12.1 % fit). A pass whose survivors do not fit goes on in its own arrays (decided on the device).
+// What the late launches read from the device - which arrays, and the origins - is the pass's one KzWfLate, in the counter block (KzCounts::kLate).
+#define KZ_DENSE_BOUNCE 3                  // the bounce in front of which the compaction runs: the first one that plays the roulette
+struct DenseSet { KzWf D; uint32_t *origin; uint32_t cap; int withMisc, withSampler; };
+static DenseSet denseSetOf(const KzParams &P, const KzWf &W, uint32_t items) {
+    DenseSet s;
+    s.withMisc = (P.bsdfExt || P.regularization) ? 1 : 0;      // (kz_wf_shade's `compact` state has no misc record)
+    s.withSampler = P.samplerType == KZ_SAMPLER_PMJ02BN ? 0 : 1;      // (pmj02bn has no sampler record: wfLoadSampler)
+    const size_t rec = 7 * sizeof(float4) + sizeof(uint32_t) + (s.withMisc ? sizeof(float4) : 0) + (s.withSampler ? sizeof(uint4) : 0);
+    const size_t n = s.cap = (uint32_t)((size_t)items * sizeof(float4) / rec);
+    float4 *f = W.hit.p;
+    s.D = W;                               // (the queues, the counters, the sample sums and the statistics are the pass's)
+    s.D.rayA.p = f; s.D.rayB.p = f + n; s.D.hit.p = f + 2 * n; s.D.thr.p = f + 3 * n; s.D.shA.p = f + 4 * n; s.D.shB.p = f + 5 * n; s.D.shL.p = f + 6 * n;
+    f += 7 * n;
+    s.D.misc.p = f; if (s.withMisc) f += n;                    // (a record the kernels do not keep gets no room, and nobody follows its pointer)
+    s.D.smp = (uint4 *)f; if (s.withSampler) f += n;
+    s.origin = (uint32_t *)f;
+    return s;
+}
+
 // What the launches of one wfPass share: the stream, the kernels' arguments, the grids.
 struct WfLaunch {
     KzDeviceState *ds; PassCtx &c; hipStream_t stream;
@@ -247,13 +286,15 @@ struct WfLaunch {
     const uint32_t *pixList; uint32_t items, Sp, sBegin; bool st;      // st: the counters run
     dim3 blk, gItems, gTrav, gShade, gPacket;
     size_t traceLds, ovfPart;
+    bool dense = false;                                                // this pass compacts its survivors in front of the first roulette bounce (wfPass: path_mis with such a bounce to come)
+    const KzWfLate *sel = nullptr;                                     // set by wfMis behind kz_wf_compact: the launches from there on take their per-path arrays from *sel
     int mark(int kind) { return stageMark(c, stream, kind); }
     // mode 0 / 1 / 2 / 4 of kz_wf_trace on queue q (nullptr: identity) of *cptr (nullptr: cimm) entries
     void trace(int mode, const uint32_t *q, const uint32_t *cptr, uint32_t cimm, uint32_t *head, uint32_t *qb, uint32_t *cb, hipStream_t on = nullptr) const {
         KzTune t = tune;
         const bool side = on != nullptr;                 // (a launch beside the pass's own stream walks its own part of the overflow area)
         if (side) t.ovf = tune.ovf + 2 * ovfPart; else on = stream;
-        launchTrace(mode, st, gTrav, traceLds, on, P, ds->T, W, q, cptr, cimm, head, t, qb, cb);
+        launchTrace(mode, st, gTrav, traceLds, on, P, ds->T, W, q, cptr, cimm, head, t, qb, cb, sel);
     }
 };
 
@@ -356,11 +397,12 @@ static int wfMis(WfLaunch &L, bool beside) {
     L.ds->lastInfo.shadowBeside = beside ? 1u : 0u;      // (what the last pass did: kz_last_pass_info)
     if (beside && ((rc = c.side.ensure(hipStreamNonBlocking)) || (rc = c.evFork.ensure(hipEventDisableTiming)) || (rc = c.evJoin.ensure(hipEventDisableTiming)))) return rc;
     const KzShadeFn shade = shadeFn(L.st, extSel(P.bsdfExt, KZ_X_ALL));
+    const KzShadeFn shadeLate = shadeFn(L.st, extSel(P.bsdfExt, KZ_X_ALL), true);
     const uint32_t *cur = nullptr, *curCount = nullptr;
     for (int iter = 0; iter < P.maxDepth; ++iter) {
         // one kernel per bounce: the path queues ping-pong (W.queue[iter & 1] is written, the other one read)
         uint32_t *nextQ = W.queue[iter & 1], *nextCount = W.counts + KzCounts::quad(iter), *shQ = W.queue[2], *shCount = nextCount + KzCounts::kShadows;
-        hipLaunchKernelGGL(shade, L.gShade, L.blk, 0, stream, P, L.Tsh, W, L.pixList, L.Sp, L.sBegin, iter, cur, curCount, L.items, nextQ, nextCount, shQ, shCount);
+        hipLaunchKernelGGL(L.sel ? shadeLate : shade, L.gShade, L.blk, 0, stream, P, L.Tsh, W, L.pixList, L.Sp, L.sBegin, iter, cur, curCount, L.items, nextQ, nextCount, shQ, shCount, L.sel);
         const bool needExtend = iter < P.maxDepth - 1 || P.bgPresent;
         if ((rc = L.mark(2))) return rc;
         // `beside`: this bounce's shadow rays go to the context's side stream and run beside its closest-hit rays; the next shade
@@ -376,6 +418,16 @@ static int wfMis(WfLaunch &L, bool beside) {
         }
         if (shOn) HIP_TRY(hipEventRecord(c.evJoin, c.side));
         if ((rc = L.mark(3))) return rc;
+        if (iter == KZ_DENSE_BOUNCE - 1 && L.dense) {
+            // Once per pass, in front of the first roulette bounce: the survivors' state goes to the pass's dense set (kz_wf_compact) and every launch from
+            // here on takes its per-path arrays from the device - the dense set, or the pass's own when the survivors did not fit. (The shadow rays of this
+            // bounce, which may still be running beside, read shA / shB / shL and the shadow queue of the pass's own arrays: nothing the kernel touches.)
+            // The stage clock books it under "shade".
+            const DenseSet ds_ = denseSetOf(P, W, L.items);
+            hipLaunchKernelGGL(kz_wf_compact, L.gShade, L.blk, 0, stream, W, ds_.D, ds_.origin, ds_.cap, ds_.withMisc, ds_.withSampler, nextQ, (const uint32_t *)nextCount, (KzWfLate *)(W.counts + KzCounts::kLate));
+            L.sel = (const KzWfLate *)(W.counts + KzCounts::kLate);
+            if ((rc = L.mark(2))) return rc;
+        }
         if (needExtend) {
             L.trace(0, nextQ, nextCount, 0u, nextCount + KzCounts::kBounceHead, nullptr, nullptr);
             if (shOn) HIP_TRY(hipStreamWaitEvent(stream, c.evJoin, 0));          // (the stage clock then shows the pair under "trace_bounce" and nothing under "trace_shadow")
@@ -383,7 +435,22 @@ static int wfMis(WfLaunch &L, bool beside) {
         }
         cur = nextQ; curCount = nextCount;
     }
-    if (P.bgPresent) hipLaunchKernelGGL(kz_wf_final, L.gShade, L.blk, 0, stream, P, L.ds->T, W, cur, curCount);
+    if (P.bgPresent) {
+        if (L.sel) hipLaunchKernelGGL(kz_wf_final_late, L.gShade, L.blk, 0, stream, P, L.ds->T, L.sel, cur, curCount);
+        else hipLaunchKernelGGL(kz_wf_final, L.gShade, L.blk, 0, stream, P, L.ds->T, W, cur, curCount);
+    }
+#ifdef KZ_EXPERIMENTS
+    // kz_debug_trace: how many paths each bounce queued for the next one (a host read of the counters: the pass is waited for) - what the dense set's share is chosen from
+    if (g_kzTrace.load(std::memory_order_relaxed)) {
+        uint32_t h[KzCounts::kLitBase];
+        HIP_TRY(hipMemcpyAsync(h, W.counts, sizeof h, hipMemcpyDeviceToHost, stream)); HIP_TRY(hipStreamSynchronize(stream));
+        std::string line;
+        for (int iter = 0; iter < std::min(P.maxDepth, 8); ++iter) line += " " + std::to_string(h[KzCounts::quad(iter) + KzCounts::kPaths]);
+        const uint32_t late = P.maxDepth >= KZ_DENSE_BOUNCE ? h[KzCounts::quad(KZ_DENSE_BOUNCE - 1) + KzCounts::kPaths] : 0u;
+        KZ_TRACE("path_mis pass of %u items: paths queued by shade(0 ..):%s; late bounces %s (%u paths, dense set of %u)", L.items, line.c_str(),
+                 !L.sel ? "in the pass's arrays: no compaction" : late <= denseSetOf(P, W, L.items).cap ? "compacted" : "in the pass's arrays: the dense set is too small", late, L.sel ? denseSetOf(P, W, L.items).cap : 0u);
+    }
+#endif
     return KZ_OK;
 }
 
@@ -425,6 +492,10 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
     tune.ldsStack = shape.ldsStack;
     L.traceLds = shape.traceLds;
     if ((rc = ensureOverflow(scene, ds, c, tune, stream))) return rc;
+    L.dense = mis && P.maxDepth > KZ_DENSE_BOUNCE;
+#ifdef KZ_EXPERIMENTS
+    if (!g_kzCompactLate.load(std::memory_order_relaxed)) L.dense = false;      // kz_debug_compact_late(0): every bounce in the pass's own arrays
+#endif
     tune.ovf = c.ovf; tune.ovfStride = shape.ovfStride;
     L.tune = tune; L.ovfPart = shape.ovfPart;
     c.stageUsed = 0;

@@ -44,6 +44,9 @@ struct KzWf {
     float *outJx, *outJy, *outR, *outG, *outB;
     unsigned long long *stats;
 };
+// What the launches behind kz_wf_compact (kz_wavefront.h; wfMis) read from the device: the per-path arrays they run on - the context's dense set, or the pass's own -
+// and the pass slot each entry of them came from (null: a slot is its own origin). KzWf itself stays as it is: the kernels of the early bounces take it by value.
+struct KzWfLate { KzWf W; const uint32_t *orig; };
 
 // The queue counters of a pass (PassCtx::counts; the kernels receive pointers into the block, the launch code alone knows its layout).
 //   lower half  one quad per stage: [kPaths] entries of the path queue the stage wrote, [kShadows] entries of its shadow queue, [kBounceHead] / [kShadowHead] the work
@@ -51,9 +54,11 @@ struct KzWf {
 //               the walk-through), word 2 the head of the per-lane / packet camera rays, word 3 the head of the walk-through -, bounce b of a loop has quad b + 1
 //               (ao, which has one bounce, therefore counts its occlusion rays in word 5 and drains them through word 7).
 //   upper half  one pair per bounce: the shadow rays that cross an invisible-light triangle (count, head of their walk-through), pair b + 1 for bounce b;
-//               the last 8 words: the camera rays of pixels whose beam list overflowed (count, head of the packet kernel that takes them).
+//               the last 8 words: the camera rays of pixels whose beam list overflowed (count, head of the packet kernel that takes them); the 64 words in front
+//               of them: the pass's KzWfLate, which kz_wf_compact writes and the launches behind it read (wfMis) - it rides here so that a context has no
+//               allocation of its own for it.
 struct KzCounts {
-    enum : uint32_t { kQuads = 520, kWords = 8 * kQuads, kLitBase = 4 * kQuads, kFallback = kWords - 8 };
+    enum : uint32_t { kQuads = 520, kWords = 8 * kQuads, kLitBase = 4 * kQuads, kFallback = kWords - 8, kLate = kFallback - 64 };
     enum : uint32_t { kPaths = 0, kShadows = 1, kBounceHead = 2, kShadowHead = 3 };
     static constexpr uint32_t kCamera = 0;                                             // the camera stage's quad
     static constexpr uint32_t quad(int bounce) { return 4u * (uint32_t)(bounce + 1); }
@@ -61,7 +66,8 @@ struct KzCounts {
     static constexpr size_t bytes() { return kWords * sizeof(uint32_t); }
 };
 static_assert(KzCounts::quad(KZ_PATH_MATS_MAX_DEPTH - 1) + 4 <= KzCounts::kLitBase && KzCounts::quad(KZ_PATH_MIS_MAX_DEPTH - 1) + 4 <= KzCounts::kLitBase, "the deepest bounce's quad stays in the lower half");
-static_assert(KzCounts::lit(KZ_PATH_MIS_MAX_DEPTH - 1) + 2 <= KzCounts::kFallback, "the deepest bounce's lit pair stays below the fallback pair");
+static_assert(KzCounts::lit(KZ_PATH_MIS_MAX_DEPTH - 1) + 2 <= KzCounts::kLate, "the deepest bounce's lit pair stays below the late record and the fallback pair");
+static_assert(sizeof(KzWfLate) <= (KzCounts::kFallback - KzCounts::kLate) * sizeof(uint32_t) && KzCounts::kLate % 2 == 0, "the late record fits in front of the fallback pair, 8-byte aligned");
 
 struct KzTune { int refill, postpone, batch, travBlocksPerCU, shadeBlocksPerCU, ldsStack, packet, filmGather;
                 uint32_t *ovf; uint32_t ovfStride; };
@@ -83,6 +89,7 @@ int kzPhysicalDevice(int logical);            // kz_debug_alias_devices: the HIP
 extern thread_local int g_failAlloc;          // kz_debug_fail_alloc (kz_replica.hip): kzMalloc counts it down, ctxEnsure (kz_render.hip) hands it to a growing arena
 extern std::atomic<int> g_kzRrAhead;          // kz_debug_rr_ahead (kz_debug.hip): 0 = the shade kernels trace every bounce ray, as before the roulette-ahead test
 extern std::atomic<int> g_kzShadowOrder;      // kz_debug_shadow_order (kz_debug.hip): 0 = the any-hit shadow launches descend in closest-hit order (kz_wf_trace<5>), as before the overlap order
+extern std::atomic<int> g_kzCompactLate;      // kz_debug_compact_late (kz_debug.hip): 0 = path_mis passes keep every bounce on the pass's own slots, as before the late-bounce compaction
 #else
 #define KZ_TRACE(...) do { } while (0)
 static inline int kzPhysicalDevice(int logical) { return logical; }

@@ -94,6 +94,15 @@ __device__ __forceinline__ void wfStoreSampler(const KzParams &P, const KzWf &W,
 __device__ __forceinline__ void wfAddRadiance(const KzWf &W, uint32_t slot, V3 c) {
     unsafeAtomicAdd(W.outR + slot, c.x); unsafeAtomicAdd(W.outG + slot, c.y); unsafeAtomicAdd(W.outB + slot, c.z);
 }
+// The pass slot behind index `slot` of the per-path arrays. Until the first roulette bounce the arrays are the pass's own and a slot is its own origin; the late
+// bounces of a path_mis pass may run on a dense copy of the survivors' state (kz_wf_compact), whose entry i came from slot orig[i]. Two things of a path stay tied
+// to its pass slot: its radiance sums (the film stage reads them per slot, in sample order) and its sampler's identity (pixList[slot / S], sampleBegin + slot % S).
+// LATE is a property of the instantiation: the kernels of the bounces before the compaction neither take the pointer nor contain the test.
+template <bool LATE>
+__device__ __forceinline__ uint32_t wfOrigin(const uint32_t *__restrict__ orig, uint32_t slot) {
+    if (LATE) { if (orig) return orig[slot]; }
+    return slot;
+}
 // The continuation ray of a first hit on an invisible light (isInvisibleLight, walkThroughOrigin: kz_devfn.h) into shA / shB, where kz_wf_trace<1> reads it.
 // The queue push is the caller's: an appender in kz_wf_primary_fix, an atomic in the epilogues of the camera-ray kernels.
 __device__ __forceinline__ void wfStoreWalkThrough(const KzParams &P, const KzWf &W, uint32_t slot, const Its &its, V3 d) {
@@ -232,8 +241,8 @@ __device__ __forceinline__ bool wfEmitterHit(const KzDevTables &T, bool cand, V3
 // Pass A of shade(iter) for one queue entry: hit record -> intersection; a miss, an emitter hit and a one-sided BSDF seen from behind end the
 // path here (integrator.cpp:210-231, 315-327), the Russian roulette of integrator.cpp:237-244 is played. True = the path goes on to the light
 // sample and the BSDF sample (wfShadeSurvivor); `its` is then complete. `compact`: see kz_wf_shade.
-template <bool STATS, int EXT>
-__device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables &T, const KzWf &W, const uint32_t *__restrict__ pixList, uint32_t S, uint32_t sampleBegin,
+template <bool STATS, int EXT, bool LATE>
+__device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables &T, const KzWf &W, const uint32_t *__restrict__ orig, const uint32_t *__restrict__ pixList, uint32_t S, uint32_t sampleBegin,
                                            int iter, bool compact, uint32_t slot, Its &its, uint32_t &modelKey, Counters &cn, KzSst &sst) {
     bool survivor = false;
     const float4 h = kzLoadStream(&W.hit[slot]);
@@ -248,7 +257,7 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
         // miss: black for the primary ray (H5), background after a bounce (integrator.cpp:315-318)
         if (iter > 0 && P.bgPresent) {
             const float4 th = kzLoadStream(&W.thr[slot]);
-            wfAddRadiance(W, slot, mk(th.x, th.y, th.z) * backgroundRadiance(P, T, rd));
+            wfAddRadiance(W, wfOrigin<LATE>(orig, slot), mk(th.x, th.y, th.z) * backgroundRadiance(P, T, rd));
         }
         return false;
     }
@@ -264,7 +273,7 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
         const V3 wi = normalized(its.p - ro);
         float bsdfWeight = 1.f;
         if (iter > 0 && mi.z == 0.f) bsdfWeight = powerHeuristic(mi.x, lightPdfSolidAngle(lr.normalization, its.sh.n, wi, its.p, ro));   // mi.z: EDiscrete (integrator.cpp:329-331)
-        if (emitterFaces(its, wi)) wfAddRadiance(W, slot, emitterTerm(lr, bsdfWeight, mk(th.x, th.y, th.z)));
+        if (emitterFaces(its, wi)) wfAddRadiance(W, wfOrigin<LATE>(orig, slot), emitterTerm(lr, bsdfWeight, mk(th.x, th.y, th.z)));
         return false;
     }
     // A one-sided BSDF seen from below evaluates to 0 for every light sample (no shadow ray, nothing added) and its
@@ -285,8 +294,8 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
         // pass B (at depth 3 and 4 that was 2 of 3 lanes). The survivor's scaled throughput and advanced sampler go back to
         // the path state, where pass B reads them.
         // (wfSampleOf, kept as its own lines at the three sites of kz_wf_shade: see wfShadeSurvivor)
-        const uint32_t pl = slot / S; const uint32_t pxy = pixList[pl];
-        Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, wfPmjDim(P, iter));
+        const uint32_t os = wfOrigin<LATE>(orig, slot); const uint32_t pl = os / S; const uint32_t pxy = pixList[pl];
+        Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (os - pl * S), smp, wfPmjDim(P, iter));
         const float4 th = kzLoadStream(&W.thr[slot]);
         V3 throughput = mk(th.x, th.y, th.z);
         const float etaA = compact ? 1.f : th.w;
@@ -301,8 +310,8 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
         // counters only: the reference draws the roulette sample before it takes the light sample (integrator.cpp:237-247)
         bool alive = true;
         if (iter >= 3) {
-            const uint32_t pl = slot / S; const uint32_t pxy = pixList[pl];
-            Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, wfPmjDim(P, iter));
+            const uint32_t os = wfOrigin<LATE>(orig, slot); const uint32_t pl = os / S; const uint32_t pxy = pixList[pl];
+            Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (os - pl * S), smp, wfPmjDim(P, iter));
             const float4 th = kzLoadStream(&W.thr[slot]);
             const float etaA = compact ? 1.f : th.w;
             float probability;
@@ -315,8 +324,8 @@ __device__ __forceinline__ bool wfClassify(const KzParams &P, const KzDevTables 
 
 // Pass B of shade(iter) for one surviving path: light sample + BSDF eval / pdf + MIS weight -> pending radiance and shadow ray
 // (integrator.cpp:247-295), BSDF sample -> throughput and next ray (:297-313). (The roulette of integrator.cpp:237-244 was played in pass A.)
-template <bool STATS, int EXT>
-__device__ __forceinline__ void wfShadeSurvivor(const KzParams &P, const KzDevTables &T, const KzWf &W, const uint32_t *__restrict__ pixList, uint32_t S, uint32_t sampleBegin,
+template <bool STATS, int EXT, bool LATE>
+__device__ __forceinline__ void wfShadeSurvivor(const KzParams &P, const KzDevTables &T, const KzWf &W, const uint32_t *__restrict__ orig, const uint32_t *__restrict__ pixList, uint32_t S, uint32_t sampleBegin,
                                                 int iter, bool compact, uint32_t slot, const Its &its, bool &pushNext, bool &pushShadow, Counters &cn, KzSst &sst) {
     const float eps = P.traceBias;
     const float4 rb = kzLoadStream(&W.rayB[slot]);
@@ -327,9 +336,10 @@ __device__ __forceinline__ void wfShadeSurvivor(const KzParams &P, const KzDevTa
     float accRough = (iter == 0 || compact) ? 0.f : W.misc[slot].y;
     // (wfSampleOf, kept as its own lines: through the shared function kz_wf_shade's division here takes another copy of the slot - one register of one
     // instruction - and the two sites of wfClassify come out in another order in the counting variants)
-    const uint32_t pl = slot / S;
+    const uint32_t os = wfOrigin<LATE>(orig, slot);
+    const uint32_t pl = os / S;
     const uint32_t pxy = pixList[pl];
-    Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (slot - pl * S), smp, wfPmjDim(P, iter) + (iter >= 3 ? 1u : 0u));
+    Sampler smp; wfLoadSampler(P, W, slot, (int)(pxy & 0xffffu), (int)(pxy >> 16), sampleBegin + (os - pl * S), smp, wfPmjDim(P, iter) + (iter >= 3 ? 1u : 0u));
     KzBSDF bsdf = T.bsdfs[its.bsdf];
     NMap nm; surfaceSetup<EXT>(T, its, bsdf, nm);
     const V3 wiLocal = toLocal(its.sh, -rd);
@@ -435,12 +445,18 @@ struct WfQueuePair {
 // the entries that still need the light sample and the BSDF sample are compacted through LDS (record = slot + frame + uv),
 // and pass B — which carries ~85 % of the kernel's instructions — only ever runs on full waves.
 #define KZ_SV_CAP (2 * KZ_BLOCK)
-template <bool STATS, int EXT>
-__global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_SHADE_WAVES)) void kz_wf_shade(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__ pixList, uint32_t S,
+// EXTL: the content mask EXT of the scene's BSDF rows (kz_devfn.h) and, for the bounces behind kz_wf_compact, KZ_X_LATE: that instantiation's per-path arrays are
+// the ones *sel names (the dense set, or the pass's own when the survivors did not fit) with the origin of their entries. The others never look at `sel`.
+#define KZ_X_LATE 8
+template <bool STATS, int EXTL>
+__global__ __launch_bounds__(KZ_BLOCK, ((EXTL & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_SHADE_WAVES)) void kz_wf_shade(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__ pixList, uint32_t S,
                                                         uint32_t sampleBegin, int iter, const uint32_t *__restrict__ queue,
                                                         const uint32_t *__restrict__ countPtr, uint32_t countImm,
                                                         uint32_t *__restrict__ nextQueue, uint32_t *__restrict__ nextCount,
-                                                        uint32_t *__restrict__ shadowQueue, uint32_t *__restrict__ shadowCount) {
+                                                        uint32_t *__restrict__ shadowQueue, uint32_t *__restrict__ shadowCount, const KzWfLate *__restrict__ sel) {
+    constexpr int EXT = EXTL & KZ_X_ALL; constexpr bool LATE = (EXTL & KZ_X_LATE) != 0;
+    const uint32_t *orig = nullptr;
+    if (LATE) { W = sel->W; orig = sel->orig; }
     constexpr bool NMAPX = (EXT & KZ_X_NMAP) != 0;
     constexpr int SVW = NMAPX ? 19 : 16;                     // words per survivor: slot, p, s, t, n, uv, bsdf row | model key << 24 (+ dpdu: normal maps)
     constexpr uint32_t QCAP = (uint32_t)KZ_WF_QCAP;
@@ -479,7 +495,7 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
         if (more && base + threadIdx.x < count) {
             const uint32_t qi = base + threadIdx.x;
             slot = queue ? queue[qi] : qi;
-            survivor = wfClassify<STATS, EXT>(P, T, W, pixList, S, sampleBegin, iter, compact, slot, its, modelKey, cn, sst);
+            survivor = wfClassify<STATS, EXT, LATE>(P, T, W, orig, pixList, S, sampleBegin, iter, compact, slot, its, modelKey, cn, sst);
         }
         sst.mark(0);                                        // pass A
         {   // compaction of the survivors onto the LDS record stack
@@ -529,7 +545,7 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
             its.sh.n = mk(__uint_as_float(r[10 * KZ_SV_CAP]), __uint_as_float(r[11 * KZ_SV_CAP]), __uint_as_float(r[12 * KZ_SV_CAP]));
             its.uvx = __uint_as_float(r[13 * KZ_SV_CAP]); its.uvy = __uint_as_float(r[14 * KZ_SV_CAP]); its.bsdf = EXT ? (r[15 * KZ_SV_CAP] & 0xFFFFFFu) : r[15 * KZ_SV_CAP];
             if (NMAPX) its.dpdu = mk(__uint_as_float(r[16 * KZ_SV_CAP]), __uint_as_float(r[17 * KZ_SV_CAP]), __uint_as_float(r[18 * KZ_SV_CAP]));
-            wfShadeSurvivor<STATS, EXT>(P, T, W, pixList, S, sampleBegin, iter, compact, slot, its, pushNext, pushShadow, cn, sst);
+            wfShadeSurvivor<STATS, EXT, LATE>(P, T, W, orig, pixList, S, sampleBegin, iter, compact, slot, its, pushNext, pushShadow, cn, sst);
         }
         sst.mark(7);                                        // next-ray stores (and, for lanes without a survivor, nothing)
         apN.push(pushNext, slot); apS.push(pushShadow, slot);
@@ -568,12 +584,17 @@ __global__ __launch_bounds__(KZ_BLOCK, ((EXT & (KZ_X_TEX | KZ_X_NMAP)) ? 3 : KZ_
 #ifndef KZ_TRACE_WAVES
 #define KZ_TRACE_WAVES 8            // waves per SIMD the per-lane traversal is compiled for (64 VGPRs); 7 = 72 VGPRs measured in r02i
 #endif
-template <int MODE, bool STATS>
+// MODEL: MODE and, for the bounces behind kz_wf_compact, KZ_MODE_LATE: that instantiation takes its per-path arrays and their origins from *sel (see kz_wf_shade).
+#define KZ_MODE_LATE 8
+template <int MODEL, bool STATS>
 __global__ __launch_bounds__(KZ_BLOCK) __attribute__((amdgpu_waves_per_eu(STATS ? KZ_TRACE_WAVES - 1 : KZ_TRACE_WAVES, STATS ? KZ_TRACE_WAVES - 1 : KZ_TRACE_WAVES)))
 void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__ queue,
                                                         const uint32_t *__restrict__ countPtr, uint32_t countImm, uint32_t *__restrict__ head, KzTune tune,
-                                                        uint32_t *__restrict__ queueB, uint32_t *__restrict__ countPtrB) {
+                                                        uint32_t *__restrict__ queueB, uint32_t *__restrict__ countPtrB, const KzWfLate *__restrict__ sel) {
     extern __shared__ uint32_t s_stack[];
+    constexpr int MODE = MODEL & 7; constexpr bool LATE = (MODEL & KZ_MODE_LATE) != 0;
+    const uint32_t *orig = nullptr;
+    if (LATE) { W = sel->W; orig = sel->orig; }
     const uint32_t count = countPtr ? *countPtr : countImm;
     constexpr bool FAST = MODE == 4 || MODE == 5;                     // the any-hit shadow kernel; 5 (development builds): with the closest-hit child order
     constexpr bool OVERLAP = MODE == 4;                               // child order of the node step: largest overlap with the segment (below)
@@ -644,6 +665,7 @@ void kz_wf_trace(KzParams P, KzDevTables T, KzWf W, const uint32_t *__restrict__
     auto addPending = [&]() {
         uint32_t s_ = slot; asm volatile("" : "+v"(s_));          // (the three addresses are formed here: hoisted to the refill they were six registers held through the loop)
         if (!FAST) { const float4 l = W.shL[s_]; plR = l.x; plG = l.y; plB = l.z; }
+        if (LATE) s_ = wfOrigin<LATE>(orig, s_);                   // (the sums are the pass slot's)
         unsafeAtomicAdd(W.outR + s_, plR); unsafeAtomicAdd(W.outG + s_, plG); unsafeAtomicAdd(W.outB + s_, plB);
     };
     // the lane's stack ran empty: publish the result (or, for a literal shadow lane, decide / walk through the light)
@@ -1208,6 +1230,45 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_wf_final(KzParams P, KzDevTables 
         const V3 bg = backgroundRadiance(P, T, mk(rb.x, rb.y, rb.z));
         // (wfAddRadiance, kept as its own lines: with the three products formed in front of the three adds this kernel's instructions change order)
         unsafeAtomicAdd(W.outR + slot, th.x * bg.x); unsafeAtomicAdd(W.outG + slot, th.y * bg.y); unsafeAtomicAdd(W.outB + slot, th.z * bg.z);
+    }
+}
+// ... behind kz_wf_compact: the arrays *sel names, the sums of the slot an entry came from (a kernel of its own - kz_wf_final is not a template, and stays as it is)
+__global__ __launch_bounds__(KZ_BLOCK) void kz_wf_final_late(KzParams P, KzDevTables T, const KzWfLate *__restrict__ sel, const uint32_t *__restrict__ queue, const uint32_t *__restrict__ countPtr) {
+    const KzWf W = sel->W;
+    const uint32_t count = *countPtr;
+    for (uint32_t qi = blockIdx.x * KZ_BLOCK + threadIdx.x; qi < count; qi += gridDim.x * KZ_BLOCK) {
+        const uint32_t slot = queue[qi];
+        const float4 h = kzLoadStream(&W.hit[slot]);
+        if (h.x < KZ_INF) continue;
+        const float4 rb = kzLoadStream(&W.rayB[slot]), th = kzLoadStream(&W.thr[slot]);
+        const V3 bg = backgroundRadiance(P, T, mk(rb.x, rb.y, rb.z));
+        const uint32_t os = wfOrigin<true>(sel->orig, slot);
+        unsafeAtomicAdd(W.outR + os, th.x * bg.x); unsafeAtomicAdd(W.outG + os, th.y * bg.y); unsafeAtomicAdd(W.outB + os, th.z * bg.z);
+    }
+}
+
+// ---- compaction in front of the first roulette bounce ----------------------------------------------------------------------
+// By bounce 3 the back faces, the emitters and the roulette (played ahead by shade(2): wfShadeSurvivor) have left about a tenth of a pass's slots alive, scattered
+// over arrays of 16 GB each: every 16-B record a late launch touches costs a whole line and, at that spacing, a page of its own. This kernel walks the path queue
+// that shade(2) wrote and copies the state of entry i's path - what shade(3) and the launches behind it read by slot: the ray, the throughput, misc and the sampler
+// words where the kernels keep them - to index i of a second, small set of the same arrays D (laid inside the pass's hit array: kz_render.hip denseSetOf); origin[i] is the slot it came from (wfOrigin) and the queue becomes the
+// identity. The launches behind it are the late instantiations (KZ_X_LATE, KZ_MODE_LATE, kz_wf_final_late), which take their arrays from *sel: D when the queue fits D's `cap` entries, W itself (origin null)
+// when it does not - the pass then goes on where it is, the decision never leaves the device, and nothing is ever written beyond `cap`.
+// hit, shA, shB and shL are written before they are read in every bounce: nothing of them is copied.
+__global__ __launch_bounds__(KZ_BLOCK) void kz_wf_compact(KzWf W, KzWf D, uint32_t *__restrict__ origin, uint32_t cap, int withMisc, int withSampler,
+                                                          uint32_t *__restrict__ queue, const uint32_t *__restrict__ countPtr, KzWfLate *__restrict__ sel) {
+    const uint32_t count = *countPtr;
+    const bool fits = count <= cap;                                   // uniform over the launch
+    if (blockIdx.x == 0 && threadIdx.x == 0) { sel->W = fits ? D : W; sel->orig = fits ? origin : nullptr; }
+    if (!fits) return;
+    for (uint32_t qi = blockIdx.x * KZ_BLOCK + threadIdx.x; qi < count; qi += gridDim.x * KZ_BLOCK) {
+        const uint32_t slot = kzLoadStream(queue + qi);
+        const float4 a = kzLoadStream(&W.rayA[slot]), b = kzLoadStream(&W.rayB[slot]), th = kzLoadStream(&W.thr[slot]);
+        kzStoreStream(&D.rayA[qi], a); kzStoreStream(&D.rayB[qi], b); kzStoreStream(&D.thr[qi], th);
+        if (withMisc) kzStoreStream(&D.misc[qi], kzLoadStream(&W.misc[slot]));
+        if (withSampler) D.smp[qi] = W.smp[slot];
+        origin[qi] = slot;
+        queue[qi] = qi;
     }
 }
 

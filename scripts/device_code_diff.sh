@@ -6,7 +6,8 @@
 # Prints the kernels whose instructions differ - their own, or those of a device function they call (pathLi, matsLi, the texture filters ...) - with the
 # kernel_resources.sh row of both sides, and exits non-zero if there is one. Instructions are compared as text without their addresses and encodings; the
 # pc-relative literal behind an s_getpc_b64 is compared as the symbol it points to, so a kernel that only moved (because another one grew) counts as equal;
-# so does one that became, or stopped being, the last of its code object (the padding behind it is left out).
+# so does one that became, or stopped being, the last of its code object (the padding behind it is left out). A kernel whose PARAMETER LIST changed has another
+# mangled name on each side: the two are compared as one kernel when its name and template arguments are on both sides exactly once.
 # (The code-object files themselves are no yardstick: two builds of equal instructions differ in a few hundred bytes of notes and hashes.)
 set -e
 [ -n "$1" ] || { echo "usage: $0 <git-rev>"; exit 2; }
@@ -103,6 +104,15 @@ differing = 0
 for build in ("plain", "exp"):
     for unit in ("kz_render", "kz_replica", "kz_film", "kz_film_moment", "kz_debug", "kz_refit", "kz_denoise+kz_variance"):
         (fa, ka, ra), (fb, kb, rb) = side("this", build, unit), side("rev", build, unit)
+        # kernels on one side only, paired by their demangled name without the parameter list: the other revision's takes this tree's mangled name
+        lone = demangle((ka - kb) | (kb - ka))
+        head = lambda n: lone[n].split("(")[0]
+        for n in sorted(kb - ka):
+            twins = [m for m in ka - kb if head(m) == head(n)]
+            if len(twins) == 1 and sum(head(m) == head(n) for m in kb - ka) == 1:
+                m = twins[0]
+                fb[m] = fb.pop(n); kb = (kb - {n}) | {m}
+                if n in rb: rb[m] = rb.pop(n)
         own = {n for n in set(fa) | set(fb) if n not in fa or n not in fb or fa[n][0] != fb[n][0]}
         # a kernel also differs through a device function it calls: close over the references
         why = {n: "its own instructions" for n in own}

@@ -86,7 +86,9 @@ json.dump(out, open(os.path.join(dst, "pmc_sum_over_one_pass.json"), "w"), inden
 samples = bench["roofline"]["samples_per_launch"]
 fetch = sum(v.get("FETCH_SIZE", 0) for v in out.values()); write = sum(v.get("WRITE_SIZE", 0) for v in out.values())
 def group(prefix):
-    ks = [k for k in out if k.startswith(prefix)]
+    # (the launches behind kz_wf_compact are instantiations of their own, mode + 8 = KZ_MODE_LATE: they count with their mode's)
+    late = {"kz_wf_trace<0": "kz_wf_trace<8", "kz_wf_trace<2": "kz_wf_trace<10", "kz_wf_trace<4": "kz_wf_trace<12"}.get(prefix)
+    ks = [k for k in out if k.startswith(prefix) or (late and k.startswith(late))]
     c = defaultdict(float)
     for k in ks:
         for n, v in out[k].items():

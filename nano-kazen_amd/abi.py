@@ -230,6 +230,11 @@ class KzTemporalOpts(C.Structure):
     _fields_ = [("depthTolerance", C.c_float), ("normalTolerance", C.c_float), ("maxHistory", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
+class KzMotionRow(C.Structure):
+    # include/kazen_mi355x_motion.h: 96 bytes - where a point of a mesh was when the history was stored: d (3 x 4) = H C^-1, n (3 x 3) its linear part's inverse transpose
+    _fields_ = [("d", C.c_float * 12), ("n", C.c_float * 9), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class KzBvhInfo(C.Structure):
     _fields_ = [("nNodes", C.c_uint32), ("nLeaves", C.c_uint32), ("nTris", C.c_uint32), ("maxDepth", C.c_uint32),
                 ("maxLeafSize", C.c_uint32), ("sahCost", C.c_float), ("buildSeconds", C.c_double)]
@@ -261,6 +266,9 @@ VARIANCE_EXPORTS = ["kz_scene_set_variance", "kz_scene_variance", "kz_variance_d
 KZ_VARIANCE_OFF, KZ_VARIANCE_ON, KZ_VARIANCE_TWO_LAUNCHES, KZ_VARIANCE_ONE_PASS = 0, 1, 2, 3
 # what include/kazen_mi355x_temporal.h declares (checked by tests/test_temporal_cpu.py): the denoiser's history, reprojected across camera edits and blended in
 TEMPORAL_EXPORTS = ["kz_temporal_view", "kz_denoise_temporal", "kz_temporal_info", "kz_temporal_reset", "kz_temporal_download", "kz_denoise_temporal_films"]
+# what include/kazen_mi355x_motion.h declares (checked by tests/test_motion_cpu.py): the history kept across kz_scene_set_transforms - per-mesh rows and a mesh id per pixel
+MOTION_EXPORTS = ["kz_motion_rows", "kz_motion_ids", "kz_denoise_motion", "kz_denoise_motion_films", "kz_motion_info"]
+KZ_MOTION_STATIC, KZ_MOTION_UNTRACKED, KZ_MOTION_MISS = 1, 2, 0xFFFFFFFF
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead", "kz_debug_shadow_order", "kz_debug_compact_late"]
@@ -388,6 +396,14 @@ def load_library(path=None):
         lib.kz_temporal_download.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
         lib.kz_denoise_temporal_films.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts),
                                                   C.POINTER(KzTemporalOpts), C.POINTER(KzTemporalView), C.POINTER(KzTemporalView), f32p, f32p, f32p, f32p]
+    if hasattr(lib, "kz_denoise_motion"):         # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_motion_rows.argtypes = [f32p, f32p, C.c_uint32, C.POINTER(KzMotionRow)]
+        lib.kz_motion_ids.argtypes = [C.c_void_p, C.c_int, u32p, C.c_size_t]
+        lib.kz_denoise_motion.argtypes = [C.c_void_p, C.c_int, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts), C.POINTER(KzTemporalOpts)]
+        lib.kz_denoise_motion_films.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts),
+                                                C.POINTER(KzTemporalOpts), C.POINTER(KzTemporalView), C.POINTER(KzTemporalView), f32p, u32p, C.POINTER(KzMotionRow), C.c_uint32,
+                                                f32p, f32p, f32p]
+        lib.kz_motion_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), u32p]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

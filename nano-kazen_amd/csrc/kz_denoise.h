@@ -43,6 +43,12 @@ struct KzDnTemporal {
     float4 *outE, *outG; float *outN;
 };
 
+// What kz_denoise_motion (include/kazen_mi355x_motion.h, which holds the definition) adds to KzDnTemporal, by value to kz_dn_prepare_motion: the mesh id of every
+// frame pixel (0xFFFFFFFF: a miss), the rows - where a point of each mesh was when the history was stored - and their number. A struct of its own, not a part of
+// KzDnTemporal: that one is a kernel argument of kz_dn_prepare_temporal, whose code stays what it was.
+struct KzMotionRow;
+struct KzDnMotion { const uint32_t *ids; const KzMotionRow *rows; uint32_t nRows; };
+
 #define KZ_DN_BLOCK 256
 #define KZ_DN_ROW 64                  // pixels of a row per block (one wave), KZ_DN_BLOCK / KZ_DN_ROW rows
 // The a-trous form per step (measured): the LDS-tile kernel for the steps up to KZ_DN_LDS_MAX_STEP, the direct-gather kernel beyond. 0 builds the

@@ -20,6 +20,7 @@
 #include "../../include/kazen_mi355x_denoise.h"
 #include "../../include/kazen_mi355x_variance.h"
 #include "../../include/kazen_mi355x_temporal.h"
+#include "../../include/kazen_mi355x_motion.h"
 #include "kz_state.h"
 #include "kz_denoise.h"
 
@@ -288,6 +289,99 @@ KZ_DN_KERNEL kz_dn_prepare_temporal(int width, int height, int border, const flo
     T.outE[i] = e; T.outG[i] = make_float4(n.x, n.y, n.z, z.x); T.outN[i] = count;
 }
 
+// kz_dn_prepare_temporal with the motion stage of include/kazen_mi355x_motion.h (the definition): restated, not shared - a template over the two would be one more
+// way for kz_dn_prepare_temporal's code to move - plus the pixel's mesh id, that mesh's row and the header's three changes: the point the history's
+// view sees is the row's map of X, the normal the taps compare is the row's map of n(p), and a pixel of an untracked mesh takes no history. A miss and a static
+// row take kz_dn_prepare_temporal's arithmetic to the bit: the multiply is skipped, not done with an identity. A wave's lanes mostly show one mesh, so the row's 96
+// bytes are a plain load that the lanes share; like its model the kernel has no atomics, no LDS, no scratch and no index at or beyond width x height (an id at or
+// beyond M.nRows - the host has refused it - reads no row: a miss).
+KZ_DN_KERNEL kz_dn_prepare_motion(int width, int height, int border, const float4 *__restrict__ film, const float4 *__restrict__ moment, const float4 *__restrict__ albedo,
+                                  const float4 *__restrict__ normal, const float4 *__restrict__ depth, int demodulate, float samples, const KzDnTemporal T, const KzDnMotion M,
+                                  float4 *__restrict__ colour, float4 *__restrict__ normalZ, float4 *__restrict__ albedoP) {
+    const uint32_t i = blockIdx.x * KZ_DN_BLOCK + threadIdx.x;
+    if (i >= (uint32_t)width * (uint32_t)height) return;
+    const int y = (int)(i / (uint32_t)width), x = (int)(i - (uint32_t)y * (uint32_t)width);
+    const size_t t = (size_t)(y + border) * (size_t)(width + 2 * border) + (size_t)(x + border);      // < (height + 2b)(width + 2b): the films' texels
+    const float4 c = dnValue(film, t), a = dnValue(albedo, t), n = dnValue(normal, t), z = dnValue(depth, t), s = dnValue(moment, t);
+    // (e_cur, v_cur): dnPrepare<true>'s lines
+    const float vr = dnMax(s.x - c.x * c.x, 0.f) / samples, vg = dnMax(s.y - c.y * c.y, 0.f) / samples, vb = dnMax(s.z - c.z * c.z, 0.f) / samples;
+    float4 e = make_float4(c.x, c.y, c.z, (vr + vg) + vb);
+    if (demodulate) {
+        const float ar = dnMax(a.x, 1e-3f); e.x = c.x / ar;
+        const float ag = dnMax(a.y, 1e-3f); e.y = c.y / ag;
+        const float ab = dnMax(a.z, 1e-3f); e.z = c.z / ab;
+        e.w = (vr / (ar * ar) + vg / (ag * ag)) + vb / (ab * ab);
+    }
+    normalZ[i] = make_float4(n.x, n.y, n.z, z.x);
+    albedoP[i] = make_float4(a.x, a.y, a.z, 0.f);
+    if (c.w == 0.f) {                                                   // not valid: no part in the filter (v = -1), an empty record
+        e.w = -1.f;
+        colour[i] = e;
+        T.outE[i] = make_float4(0.f, 0.f, 0.f, 0.f); T.outG[i] = make_float4(0.f, 0.f, 0.f, 0.f); T.outN[i] = 0.f;
+        return;
+    }
+    float count = 1.0f;
+    // the pixel's row: flags 0 = moved (d, n are read), STATIC also for a miss, UNTRACKED = no history
+    uint32_t flags = KZ_MOTION_STATIC;
+    const KzMotionRow *row = nullptr;
+    if (T.inE && z.x > 0.f) {
+        const uint32_t m = M.ids[i];
+        if (m < M.nRows) { row = M.rows + m; flags = row->flags; }
+    }
+    if (T.inE && z.x > 0.f && !(flags & KZ_MOTION_UNTRACKED)) {
+        const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
+        const float dx = (T.a[0] + fx * T.u[0]) + fy * T.v[0], dy = (T.a[1] + fx * T.u[1]) + fy * T.v[1], dz = (T.a[2] + fx * T.u[2]) + fy * T.v[2];
+        const float len = sqrtf(dnSq(dx, dy, dz));
+        const float r = z.x / len;
+        float Xx = T.o[0] + dx * r, Xy = T.o[1] + dy * r, Xz = T.o[2] + dz * r;
+        float nx = n.x, ny = n.y, nz = n.z;                             // the normal the taps compare: n(p), or n' of a moved mesh
+        if (!(flags & KZ_MOTION_STATIC)) {
+            const float *d = row->d, *w = row->n;
+            const float px = ((d[0] * Xx + d[1] * Xy) + d[2] * Xz) + d[3], py = ((d[4] * Xx + d[5] * Xy) + d[6] * Xz) + d[7], pz = ((d[8] * Xx + d[9] * Xy) + d[10] * Xz) + d[11];
+            Xx = px; Xy = py; Xz = pz;
+            nx = (w[0] * n.x + w[1] * n.y) + w[2] * n.z; ny = (w[3] * n.x + w[4] * n.y) + w[5] * n.z; nz = (w[6] * n.x + w[7] * n.y) + w[8] * n.z;
+        }
+        const float qx = Xx - T.po[0], qy = Xy - T.po[1], qz = Xz - T.po[2];
+        const float P0 = (T.pinv[0] * qx + T.pinv[1] * qy) + T.pinv[2] * qz, P1 = (T.pinv[3] * qx + T.pinv[4] * qy) + T.pinv[5] * qz,
+                    P2 = (T.pinv[6] * qx + T.pinv[7] * qy) + T.pinv[8] * qz;
+        if (P2 > 0.f) {
+            const float sx = P0 / P2 - 0.5f, sy = P1 / P2 - 0.5f;
+            if (sx >= -1.f && sx < (float)width && sy >= -1.f && sy < (float)height) {      // (so x0, y0 are in -1 .. width - 1, -1 .. height - 1: the int conversions are exact)
+                const float fx0 = floorf(sx), fy0 = floorf(sy), tx = sx - fx0, ty = sy - fy0;
+                const int x0 = (int)fx0, y0 = (int)fy0;
+                const float zp = sqrtf(dnSq(qx, qy, qz)), ztol = T.depthTol * dnMax(zp, 1e-20f);
+                float Wb = 0.f, Er = 0.f, Eg = 0.f, Eb = 0.f, V = 0.f, Mn = 0.f;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int ty_ = y0 + j;
+                    const bool rowIn = ty_ >= 0 && ty_ < height;
+                    const size_t rowAt = (size_t)(rowIn ? ty_ : y) * (size_t)width;      // (a tap outside the frame loads the pixel's own row / column and is skipped)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const int tx_ = x0 + k;
+                        const bool colIn = tx_ >= 0 && tx_ < width;
+                        const size_t it = rowAt + (size_t)(colIn ? tx_ : x);             // < width * height
+                        const float nh = T.inN[it];
+                        const float4 gh = T.inG[it], eh = T.inE[it];
+                        const float b = (k ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
+                        if (!(rowIn && colIn) || nh == 0.f || fabsf(gh.w - zp) > ztol || dnSq(gh.x - nx, gh.y - ny, gh.z - nz) > T.normalTol2) continue;
+                        Wb += b; Er += b * eh.x; Eg += b * eh.y; Eb += b * eh.z; V += b * eh.w; Mn += b * nh;
+                    }
+                }
+                if (Wb > 1e-3f) {
+                    const float Nh = Mn / Wb, Nn1 = Nh + 1.0f, Nn = Nn1 < T.maxHistory ? Nn1 : T.maxHistory;
+                    const float al = 1.0f / Nn, om = 1.0f - al;
+                    e.x = om * (Er / Wb) + al * e.x; e.y = om * (Eg / Wb) + al * e.y; e.z = om * (Eb / Wb) + al * e.z;
+                    e.w = (om * om) * (V / Wb) + (al * al) * e.w;
+                    count = Nn;
+                }
+            }
+        }
+    }
+    colour[i] = e;
+    T.outE[i] = e; T.outG[i] = make_float4(n.x, n.y, n.z, z.x); T.outN[i] = count;
+}
+
 // ---- host side ----
 // What a call does, from its options: `avail` = the guides there are (the scene's mask / the films given to kz_denoise_films);
 // defaultSigmaColor: 1.0 for kz_denoise, 2.0 for kz_denoise_variance
@@ -319,7 +413,8 @@ static int dnPlan(const KzDenoiseOpts *opts, uint32_t avail, const char *call, K
 
 // What kz_denoise_variance adds to a call (null: kz_denoise). `moment`: the second-moment film (null: zeros); `variance`: null or width x height floats.
 // `temporal` (null: kz_denoise_variance): what kz_denoise_temporal puts in front - its prepare kernel takes the place of kz_dn_prepare_var.
-struct KzDnVar { float sv2, samples; const float4 *moment; float *variance; const KzDnTemporal *temporal; };
+// `motion` (with `temporal` alone; null: kz_denoise_temporal): what kz_denoise_motion adds - kz_dn_prepare_motion takes that place.
+struct KzDnVar { float sv2, samples; const float4 *moment; float *variance; const KzDnTemporal *temporal; const KzDnMotion *motion; };
 
 // KzTemporalOpts, checked, as the kernel takes them (the views and the history's planes are filled in by the caller)
 static int dnTemporalOpts(const KzTemporalOpts *topts, const char *call, KzDnTemporal *T) {
@@ -383,7 +478,8 @@ static int dnRun(const KzDnPlan &plan, const KzDnVar *var, int width, int height
     const int demod = plan.demodulate ? 1 : 0;
     const dim3 gPix((nPix + KZ_DN_BLOCK - 1) / KZ_DN_BLOCK), gTexels((nTexels + KZ_DN_BLOCK - 1) / KZ_DN_BLOCK), b1(KZ_DN_BLOCK);
     albedo = (plan.guides & KZ_AOV_ALBEDO) ? albedo : nullptr; normal = (plan.guides & KZ_AOV_NORMAL) ? normal : nullptr; depth = (plan.guides & KZ_AOV_DEPTH) ? depth : nullptr;
-    if (var && var->temporal) hipLaunchKernelGGL(kz_dn_prepare_temporal, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, *var->temporal, colour[0], normalZ, albedoP);
+    if (var && var->temporal && var->motion) hipLaunchKernelGGL(kz_dn_prepare_motion, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, *var->temporal, *var->motion, colour[0], normalZ, albedoP);
+    else if (var && var->temporal) hipLaunchKernelGGL(kz_dn_prepare_temporal, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, *var->temporal, colour[0], normalZ, albedoP);
     else if (var) hipLaunchKernelGGL(kz_dn_prepare_var, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, colour[0], normalZ, albedoP);
     else hipLaunchKernelGGL(kz_dn_prepare, gPix, b1, 0, stream, width, height, border, film, albedo, normal, depth, demod, colour[0], normalZ, albedoP);
     HIP_TRY(hipGetLastError());
@@ -430,18 +526,39 @@ static int dnHistoryDownload(const DevBuf<float4> &E, const DevBuf<float4> &G, c
 
 // A call on a replica's own films, into its denoise buffers: behind the replica's queued work, with the guides the plan wants (and the moment film) resolved
 // `T` (kz_denoise_temporal alone): its checked options; the views and the replica's history are filled in here, and the history moves on when the call has succeeded
-static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, KzDnVar *var, KzDnTemporal *T = nullptr) {
+// `motion` (with T; kz_denoise_motion): the history survives kz_scene_set_transforms - stale only by baseEdits -, and when a mesh has moved since it was stored the
+// call computes this frame's ids and the rows and takes kz_dn_prepare_motion
+static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, KzDnVar *var, KzDnTemporal *T = nullptr, bool motion = false) {
     const KzParams &P = scene->prm;
     const size_t nPix = (size_t)P.width * (size_t)P.height;
+    const char *const call = motion ? "kz_denoise_motion" : "kz_denoise_temporal";
     int rc;
     KzTemporalView view;
+    KzDnMotion M = {};
     bool fresh = true;                                                  // T: nothing stored, or what is stored is stale
     if (T) {
-        if ((rc = dnViewOf(P, "kz_denoise_temporal", &view))) return rc;
-        fresh = !ds->tpFrames || ds->tpEdits != scene->geometryEdits || ds->tpE[0].cap() != nPix;
+        if ((rc = dnViewOf(P, call, &view))) return rc;
+        const bool stale = motion ? ds->tpBaseEdits != scene->baseEdits : ds->tpEdits != scene->geometryEdits;
+        fresh = !ds->tpFrames || stale || ds->tpE[0].cap() != nPix;
         if (!fresh && ds->tpDemod != plan.demodulate)
-            return kz_fail(KZ_ERR_STATE, "kz_denoise_temporal: this call %s, the history of %u frame(s) holds colours that %s: kz_temporal_reset first", plan.demodulate ? "demodulates" : "does not demodulate",
+            return kz_fail(KZ_ERR_STATE, "%s: this call %s, the history of %u frame(s) holds colours that %s: kz_temporal_reset first", call, plan.demodulate ? "demodulates" : "does not demodulate",
                            ds->tpFrames, ds->tpDemod ? "are demodulated" : "are not");
+    }
+    const std::vector<float> &xfNow = kzMeshXf(scene);
+    if (motion) {
+        const uint32_t nMeshes = (uint32_t)scene->meshRows.size();
+        std::vector<KzMotionRow> rows(nMeshes);
+        const bool known = !fresh && ds->tpXf.size() == xfNow.size();    // (a fresh call reads no history: every row static)
+        if ((rc = kz_motion_rows(xfNow.data(), known ? ds->tpXf.data() : xfNow.data(), nMeshes, rows.data()))) return rc;
+        uint32_t counts[3] = {0, 0, 0};
+        for (const KzMotionRow &r : rows) ++counts[(r.flags & KZ_MOTION_STATIC) ? 0 : ((r.flags & KZ_MOTION_UNTRACKED) ? 2 : 1)];
+        std::memcpy(ds->mtCounts, counts, sizeof counts);
+        if (counts[1] + counts[2]) {                                    // something moved: this frame's ids, and the rows
+            if ((rc = kzMotionIds(scene, ds))) return rc;
+            if (ds->mtRows.cap() != nMeshes && (rc = ds->mtRows.regrow(nMeshes))) return rc;
+            if ((rc = ds->mtRows.upload(rows.data(), nMeshes))) return rc;
+            M.ids = ds->mtIds; M.rows = ds->mtRows; M.nRows = nMeshes;
+        }
     }
     HIP_TRY(hipStreamSynchronize(ds->lastStream));                      // the replica's queued work: the films and the sums are final
     if (var && ds->moment().sums && ds->moment().texels) {
@@ -471,6 +588,7 @@ static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, 
         if (!fresh && T->maxHistory != 1.0f) { T->inE = ds->tpE[in]; T->inG = ds->tpG[in]; T->inN = ds->tpN[in]; }      // (maxHistory = 1: without history, by definition)
         T->outE = ds->tpE[out]; T->outG = ds->tpG[out]; T->outN = ds->tpN[out];
         var->temporal = T;
+        if (M.ids && T->inE) var->motion = &M;                          // (without a history to read, kz_dn_prepare_temporal's lines are the motion kernel's)
     }
     float4 *const colour[2] = {ds->dnColor[0].get(), ds->dnColor[1].get()};
     if ((rc = dnRun(plan, var, P.width, P.height, P.border, ds->picture().texels, guide[0], guide[1], guide[2], colour, ds->dnNormalZ, ds->dnAlbedo, ds->dnOut, ds->lastStream))) return rc;
@@ -478,13 +596,16 @@ static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, 
     ds->dnValid = true;
     if (T) {
         ds->tpCur ^= 1; ds->tpFrames += 1; ds->tpDemod = plan.demodulate; ds->tpEdits = scene->geometryEdits;
+        ds->tpBaseEdits = scene->baseEdits; ds->tpXf = xfNow;           // (what kz_denoise_motion's rows are formed from, whichever call stored the history)
         std::memcpy(ds->tpO, view.o, sizeof ds->tpO); std::memcpy(ds->tpInv, view.inv, sizeof ds->tpInv);
     }
     return KZ_OK;
 }
 
 // What kz_denoise_temporal_films adds to a call on host films: the views and the history in the interchange format (12 floats per pixel), in and out
-struct KzDnHostTemporal { const KzTemporalOpts *topts; const KzTemporalView *current, *previous; const float *historyIn; float *historyOut; };
+// (ids non-null: kz_denoise_motion_films - the id plane, the rows and their number, checked by the caller)
+struct KzDnHostTemporal { const KzTemporalOpts *topts; const KzTemporalView *current, *previous; const float *historyIn; float *historyOut;
+                          const uint32_t *ids; const KzMotionRow *rows; uint32_t nRows; };
 
 // A call on films of the host's: kz_denoise_films, with `moment` kz_denoise_variance_films (`vopts`, `outVariance`: its alone), with `ht` kz_denoise_temporal_films
 static int dnFilms(const char *call, int device, int32_t width, int32_t height, int32_t border, const float *film, const float *moment, const float *albedo, const float *normal,
@@ -502,8 +623,12 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
     }
     KzDnTemporal T;
     if (ht && ((rc = dnTemporalOpts(ht->topts, call, &T)) || (rc = dnTemporalGuides(plan, avail, call)))) return rc;
-    if ((rc = kzUseDevice(device))) return rc;
     const size_t nPix = (size_t)width * (size_t)height, nTexels = (size_t)(width + 2 * border) * (size_t)(height + 2 * border);
+    if (ht && ht->ids)                                                  // (the kernel reads no row for such an id; the caller is told before anything is launched)
+        for (size_t i = 0; i < nPix; ++i)
+            if (ht->ids[i] >= ht->nRows && ht->ids[i] != KZ_MOTION_MISS)
+                return kz_fail(KZ_ERR_INVALID_ARG, "%s: pixel (%zu, %zu) names mesh %u, the table has %u rows (a miss is %u)", call, i % (size_t)width, i / (size_t)width, ht->ids[i], ht->nRows, KZ_MOTION_MISS);
+    if ((rc = kzUseDevice(device))) return rc;
     DevBuf<float4> films[5], planes[4], result; DevBuf<float> variance;
     const float *host[5] = {film, albedo, normal, depth, moment};
     for (int k = 0; k < 5; ++k) {
@@ -515,6 +640,7 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
     if (outVariance && (rc = variance.alloc(nPix))) return rc;
     var.moment = films[4]; var.variance = variance;
     DevBuf<float4> hE[2], hG[2]; DevBuf<float> hN[2];                   // the history: [0] read (historyIn), [1] written
+    DevBuf<uint32_t> mIds; DevBuf<KzMotionRow> mRows; KzDnMotion M = {};
     if (ht) {
         static const float noView[9] = {};
         dnSetViews(&T, *ht->current, ht->previous ? ht->previous->o : noView, ht->previous ? ht->previous->inv : noView);
@@ -528,6 +654,12 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
         }
         T.outE = hE[1]; T.outG = hG[1]; T.outN = hN[1];
         var.temporal = &T;
+        if (ht->ids) {
+            if ((rc = mIds.alloc(nPix)) || (rc = mIds.upload(ht->ids, nPix))) return rc;
+            if (ht->nRows && ((rc = mRows.alloc(ht->nRows)) || (rc = mRows.upload(ht->rows, ht->nRows)))) return rc;
+            M.ids = mIds; M.rows = mRows; M.nRows = ht->nRows;
+            var.motion = &M;
+        }
     }
     float4 *const colour[2] = {planes[0].get(), planes[1].get()};
     if ((rc = dnRun(plan, moment ? &var : nullptr, width, height, border, films[0], films[1], films[2], films[3], colour, planes[2], planes[3], result, nullptr))) return rc;
@@ -620,8 +752,8 @@ int kz_temporal_view(const KzCamera *camera, KzTemporalView *view) {
     return dnViewOf(P, "kz_temporal_view", view);
 }
 
-int kz_denoise_temporal(KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts) {
-    static const char *const call = "kz_denoise_temporal";
+// kz_denoise_temporal and, with `motion`, kz_denoise_motion (include/kazen_mi355x_motion.h): one path, the same refusals under the call's own name
+static int dnTemporalCall(const char *call, bool motion, KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts) {
     if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null scene", call);
     KzDnPlan plan; KzDnVar var = {}; KzDnTemporal T; KzDeviceState *ds; int rc; uint32_t samples;
     if ((rc = dnPlan(opts, scene->aovMask, call, &plan, 2.0f)) || (rc = dnVarianceOpts(vopts, call, &var.sv2, &samples)) || (rc = dnTemporalOpts(topts, call, &T)) ||
@@ -634,7 +766,10 @@ int kz_denoise_temporal(KzScene *scene, int device, const KzDenoiseOpts *opts, c
     if (ds->pictureSamples != ds->momentSamples)
         return kz_fail(KZ_ERR_STATE, "%s: the picture's film holds %u samples per pixel, the second-moment film %u (switched on late: kz_film_clear, then render both)", call, ds->pictureSamples, ds->momentSamples);
     var.samples = (float)samples;
-    return dnOnReplica(scene, ds, plan, &var, &T);
+    return dnOnReplica(scene, ds, plan, &var, &T, motion);
+}
+int kz_denoise_temporal(KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts) {
+    return dnTemporalCall("kz_denoise_temporal", false, scene, device, opts, vopts, topts);
 }
 
 int kz_temporal_info(KzScene *scene, int device, uint64_t *bytes, uint32_t *frames) {
@@ -652,6 +787,7 @@ int kz_temporal_reset(KzScene *scene, int device) {
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     for (int k = 0; k < 2; ++k) { ds->tpE[k].free(); ds->tpG[k].free(); ds->tpN[k].free(); }
     ds->tpFrames = 0; ds->tpCur = 0;
+    ds->mtIds.free(); ds->mtRows.free(); ds->mtCounts[0] = ds->mtCounts[1] = ds->mtCounts[2] = 0;      // (kazen_mi355x_motion.h: the id plane and the rows go with the history)
     return KZ_OK;
 }
 
@@ -671,6 +807,34 @@ int kz_denoise_temporal_films(int device, int32_t width, int32_t height, int32_t
     if (!current || (historyIn && !previous)) return kz_fail(KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films: null view (the current one, and with a history the one it was stored with)");
     const KzDnHostTemporal ht = {topts, current, previous, historyIn, historyOut};
     return dnFilms("kz_denoise_temporal_films", device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance, &ht);
+}
+
+// ---- include/kazen_mi355x_motion.h (kz_motion_rows and kz_motion_ids: kz_motion.hip)
+int kz_denoise_motion(KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts) {
+    return dnTemporalCall("kz_denoise_motion", true, scene, device, opts, vopts, topts);
+}
+
+int kz_denoise_motion_films(int device, int32_t width, int32_t height, int32_t border, const float *film, const float *moment, const float *albedo, const float *normal, const float *depth,
+                            const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts, const KzTemporalView *current, const KzTemporalView *previous,
+                            const float *historyIn, const uint32_t *ids, const KzMotionRow *rows, uint32_t nRows, float *out, float *historyOut, float *outVariance) {
+    static const char *const call = "kz_denoise_motion_films";
+    if (!film || !moment || !depth || !out) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null film (the picture, the moment film and the depth film are needed)", call);
+    if (!current || (historyIn && !previous)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null view (the current one, and with a history the one it was stored with)", call);
+    if (!ids || (nRows && !rows)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null ids or rows (the id plane, and %u rows)", call, nRows);
+    for (uint32_t m = 0; m < nRows; ++m)
+        if ((rows[m].flags & ~(KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED)) || rows[m].flags == (KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED) || rows[m].reserved[0] || rows[m].reserved[1])
+            return kz_fail(KZ_ERR_INVALID_ARG, "%s: row %u: flags = %u (0, KZ_MOTION_STATIC or KZ_MOTION_UNTRACKED) or a non-zero reserved word", call, m, rows[m].flags);
+    const KzDnHostTemporal ht = {topts, current, previous, historyIn, historyOut, ids, rows, nRows};
+    return dnFilms(call, device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance, &ht);
+}
+
+int kz_motion_info(KzScene *scene, int device, uint64_t *bytes, uint32_t *counts) {
+    KzDeviceState *ds; int rc;
+    if (!bytes && !counts) return kz_fail(KZ_ERR_INVALID_ARG, "kz_motion_info: null bytes and counts");
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    if (bytes) *bytes = ds->mtBytes();
+    if (counts) std::memcpy(counts, ds->mtCounts, sizeof ds->mtCounts);
+    return KZ_OK;
 }
 
 } // extern "C"

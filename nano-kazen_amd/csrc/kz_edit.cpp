@@ -200,7 +200,12 @@ int kz_scene_set_vertices(KzScene *sc, const KzVertexUpdate *u, uint32_t n) {
         if (!lightRows.empty()) kzInvisibleLights(sc);
         sc->hostStale = true;
     }
-    ++sc->geometryEdits;                                       // (no motion vectors: every replica's temporal history is stale from here on)
+    ++sc->geometryEdits;                                       // (every replica's temporal history is stale from here on: kz_denoise_temporal's ...
+    ++sc->baseEdits;                                           //  ... and kz_denoise_motion's, which follows matrices, not vertices)
+    {
+        std::vector<float> &xf = kzMeshXf(sc);                 // new base data: the mesh's matrix is the identity again
+        for (uint32_t i = 0; i < n; ++i) for (int k = 0; k < 16; ++k) xf[16 * (size_t)u[i].mesh + k] = (k % 5 == 0) ? 1.f : 0.f;
+    }
     return kzEditVertices(sc, u, n, lightRows);
 }
 
@@ -306,6 +311,10 @@ int kz_scene_set_transforms(KzScene *sc, const KzTransformUpdate *u, uint32_t n)
         sc->hostStale = true;
     }
     ++sc->geometryEdits;
+    {
+        std::vector<float> &cur = kzMeshXf(sc);                // the meshes' matrices as they stand (kazen_mi355x_motion.h)
+        for (uint32_t i = 0; i < n; ++i) std::memcpy(&cur[16 * (size_t)u[i].mesh], u[i].toWorld, 16 * sizeof(float));
+    }
     return kzEditXformCommit(sc, jobs.data(), n, lightRows);
 }
 

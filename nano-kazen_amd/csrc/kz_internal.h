@@ -205,10 +205,21 @@ struct KzScene {
     uint32_t aovMask = 0;               // KZ_AOV_* feature films every render of the scene produces beside the picture (kazen_mi355x_aov.h; kz_scene_set_aovs)
     int32_t varianceMode = 0;           // KZ_VARIANCE_*: every render keeps a second-moment film beside the picture's (kazen_mi355x_variance.h; kz_scene_set_variance)
     uint64_t geometryEdits = 0;         // kz_scene_set_vertices / kz_scene_set_transforms calls that changed something: a replica's temporal history (kazen_mi355x_temporal.h) older than the last one is stale
+    // motion vectors (kazen_mi355x_motion.h): per mesh its object-to-world matrix as it stands, 16 floats each - the identity until the mesh's first
+    // kz_scene_set_transforms and again after a kz_scene_set_vertices of it (pendX only holds what the host tables lag behind) - and the number of
+    // kz_scene_set_vertices calls that changed something: kz_denoise_motion's history is stale only when that one moved on
+    std::vector<float> meshXf; uint64_t baseEdits = 0;
     std::mutex editMutex;              // guards the lazy host refit (kzHostSync may be reached from several device threads of kz_render_multi)
     // device replicas, one per GPU the scene is resident on (KzReplicaSet, owned by kz_render.hip; created with the scene)
     void *dev = nullptr;
 };
+
+// scene->meshXf, sized: identities for every mesh no transform has placed yet
+static inline std::vector<float> &kzMeshXf(KzScene *sc) {
+    const size_t n = 16 * sc->meshRows.size();
+    if (sc->meshXf.size() != n) { sc->meshXf.assign(n, 0.f); for (size_t m = 0; m < n; m += 16) for (int k = 0; k < 16; k += 5) sc->meshXf[m + k] = 1.f; }
+    return sc->meshXf;
+}
 
 // kz_bvh.cpp
 struct KzBuildTri { float v[3][3]; uint32_t mesh, prim, gid; };

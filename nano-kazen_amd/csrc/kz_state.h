@@ -8,6 +8,7 @@
 //   kz_film_moment.hip  the tap kernels of the second-moment film (include/kazen_mi355x_variance.h) and their launcher, kzFilmStageMoment
 //   kz_denoise.hip  the a-trous denoiser of include/kazen_mi355x_denoise.h and its variance-guided form (include/kazen_mi355x_variance.h): their kernels, the
 //                   replica's denoise buffers, kz_denoise* and kz_denoise_variance* entry points
+//   kz_motion.hip   include/kazen_mi355x_motion.h beyond the denoiser's unit: the id kernel (which mesh every frame pixel shows) and the host-only row table
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
 // Every device buffer, pinned buffer, event and stream named below is a member of one of the four move-only owners of kz_own.h (DevBuf, PinnedBuf, Event, Stream).
@@ -16,6 +17,7 @@
 #include "kz_internal.h"
 #include "kz_film.h"
 #include "kz_plan.h"
+#include "../../include/kazen_mi355x_motion.h"
 
 #include <atomic>
 #include <chrono>
@@ -210,6 +212,13 @@ struct KzDeviceState {
     // was stored with; tpDemod: whether its colours are demodulated; tpEdits: the scene's geometryEdits then (another value now: stale).
     DevBuf<float4> tpE[2], tpG[2]; DevBuf<float> tpN[2]; int tpCur = 0; uint32_t tpFrames = 0; bool tpDemod = false; uint64_t tpEdits = 0; float tpO[3] = {}, tpInv[9] = {};
     size_t tpBytes() const { size_t b = 0; for (int k = 0; k < 2; ++k) b += tpE[k].bytes() + tpG[k].bytes() + tpN[k].bytes(); return b; }
+    // Motion vectors (kazen_mi355x_motion.h). tpBaseEdits / tpXf: the scene's baseEdits and its meshes' matrices (16 floats each) when the history was stored -
+    // every call that stores a history records them. mtIds: the mesh id of every frame pixel (kz_motion_ids_kernel, kz_motion.hip), mtRows: the row table of the
+    // last kz_denoise_motion that needed one; both allocated on first use, outside the budget, freed by kz_temporal_reset. mtCounts: static / moved / untracked
+    // meshes of the last kz_denoise_motion.
+    uint64_t tpBaseEdits = 0; std::vector<float> tpXf;
+    DevBuf<uint32_t> mtIds; DevBuf<KzMotionRow> mtRows; uint32_t mtCounts[3] = {};
+    size_t mtBytes() const { return mtIds.bytes() + mtRows.bytes(); }
     DevBuf<float4> packDev; DevBuf<KzTileRect> rectsDev;         // kz_film_download_tiles: packed tile rects + their table
     PinnedBuf<float4> packHost;                                  // pinned staging of the same (D2H at link rate)
     // The tile set: pixList = its pixels (tile after tile, 8x8 blocks row-major inside a tile, row-major inside a block), written on the device from the
@@ -256,6 +265,8 @@ static inline KzReplicaSet *replicaSet(const KzScene *scene) { return (KzReplica
 // kz_replica.hip
 int findReplica(const KzScene *scene, int device, KzDeviceState **out);
 int kzEnsureBvh2(KzScene *scene, KzDeviceState *ds);                                                      // the BVH2 table, on first use
+// kz_motion.hip
+int kzMotionIds(KzScene *scene, KzDeviceState *ds);                                                       // ds->mtIds: the mesh id of every frame pixel of the scene as it stands (returns with the device idle)
 int kzEmitterUpload(KzScene *scene, KzDeviceState *ds);                                                   // the emitter triangles, their count and box (upload and every edit of a light)
 int prepareTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32_t nTiles, hipStream_t stream);      // makes `tiles` the replica's tile set
 static inline int requireDevice(KzScene *scene, KzDeviceState **out) { return findReplica(scene, -1, out); }

@@ -512,6 +512,27 @@ class Scene:
         abi.check(self.lib, self.lib.kz_temporal_download(self.h, -1 if device is None else int(device), out.ctypes.data_as(abi.f32p), out.size))
         return out
 
+    # ---- the history kept across set_transforms (include/kazen_mi355x_motion.h)
+    def motion_ids(self, device=None):
+        """kz_motion_ids: (h, w) uint32, the mesh the centre of every frame pixel shows (abi.KZ_MOTION_MISS: none) - for path_mis behind an invisible light."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        abi.check(self.lib, self.lib.kz_motion_ids(self.h, -1 if device is None else int(device), out.ctypes.data_as(abi.u32p), out.size))
+        return out
+
+    def denoise_motion(self, device=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0, depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0,
+                       treserved=(0, 0, 0, 0), **opts):
+        """kz_denoise_motion: denoise_temporal() whose history survives set_transforms - every pixel looks its history up where its mesh was. Options and results as
+        denoise_temporal's; temporal_info / temporal_reset / temporal_history serve both."""
+        o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
+        t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
+        abi.check(self.lib, self.lib.kz_denoise_motion(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v), C.byref(t)))
+
+    def motion_info(self, device=-1):
+        """kz_motion_info: (bytes the id plane and the row table hold on that replica, (static, moved, untracked) meshes of its last denoise_motion)."""
+        b, n = C.c_uint64(), (C.c_uint32 * 3)()
+        abi.check(self.lib, self.lib.kz_motion_info(self.h, int(device), C.byref(b), n))
+        return int(b.value), tuple(int(x) for x in n)
+
     def bsdf_query(self, bsdf, wi, wo, acc, s3, uv=None):
         """eval (n,3), pdf (n,), sample (n,8) = weight rgb, wo xyz, alive, pdf(bRec) after sample()."""
         bsdf = np.ascontiguousarray(bsdf, np.int32)
@@ -670,6 +691,50 @@ def denoise_temporal_films(film, moment, albedo=None, normal=None, depth=None, b
     abi.check(lib, lib.kz_denoise_temporal_films(int(device), *frame, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t),
                                                  None if current is None else C.byref(current), None if previous is None else C.byref(previous), p(history),
                                                  p(out), p(hist), p(var)))
+    return (out, hist, var) if return_variance else (out, hist)
+
+
+def motion_rows(cur, prev, lib=None):
+    """kz_motion_rows: the KzMotionRow table (a ctypes array) of meshes whose object-to-world matrices are `cur` now and were `prev` when the history was stored:
+    (n, 4, 4) arrays, or None for identities (then the other one gives n). Needs no device."""
+    lib = lib or abi.load_library()
+    mats = [None if m is None else np.ascontiguousarray(m, np.float32).reshape(-1, 16) for m in (cur, prev)]
+    n = max([m.shape[0] for m in mats if m is not None] or [0])
+    if any(m is not None and m.shape[0] != n for m in mats):
+        raise ValueError("cur and prev hold one matrix per mesh")
+    rows = (abi.KzMotionRow * max(1, n))()
+    abi.check(lib, lib.kz_motion_rows(*[None if m is None else m.ctypes.data_as(abi.f32p) for m in mats], n, rows))
+    rows.n_rows = n
+    return rows
+
+
+def denoise_motion_films(film, moment, albedo=None, normal=None, depth=None, border=0, device=0, lib=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0,
+                         depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0, treserved=(0, 0, 0, 0), current=None, previous=None, history=None,
+                         ids=None, rows=None, n_rows=None, return_variance=False, **opts):
+    """kz_denoise_motion_films: denoise_temporal_films with the motion stage - ids (h, w) uint32 (abi.KZ_MOTION_MISS: a miss) and rows, a KzMotionRow array as
+    motion_rows gives it (n_rows: its length, when it is not motion_rows'). Returns what denoise_temporal_films returns."""
+    lib = lib or abi.load_library()
+    film, g, frame = _host_films(film, (moment, albedo, normal, depth), border, "the moment film and the guide films have the picture's shape")
+    h, w = max(frame[1], 0), max(frame[0], 0)
+    if history is not None:
+        history = np.ascontiguousarray(history, np.float32)
+        if history.shape != (h, w, 12):
+            raise ValueError("a history is (h, w, 12)")
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, np.uint32)
+        if ids.shape != (h, w):
+            raise ValueError("ids are (h, w)")
+    if n_rows is None:
+        n_rows = 0 if rows is None else getattr(rows, "n_rows", len(rows))
+    out = np.empty_like(film)
+    hist = np.full((h, w, 12), np.nan, np.float32)
+    var = np.full((h, w), np.nan, np.float32) if return_variance else None
+    o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
+    t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
+    p = lambda a: None if a is None else a.ctypes.data_as(abi.f32p)
+    abi.check(lib, lib.kz_denoise_motion_films(int(device), *frame, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t),
+                                               None if current is None else C.byref(current), None if previous is None else C.byref(previous), p(history),
+                                               None if ids is None else ids.ctypes.data_as(abi.u32p), rows, int(n_rows), p(out), p(hist), p(var)))
     return (out, hist, var) if return_variance else (out, hist)
 
 

@@ -33,7 +33,7 @@ PIDS=""
 for build in plain exp; do
     for side in this rev; do
         [ $side = this ] && TREE=$ROOT || TREE=$WT
-        for u in kz_render kz_replica kz_film kz_film_moment kz_debug; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fgpu-flush-denormals-to-zero -fno-slp-vectorize" & PIDS="$PIDS $!"; done
+        for u in kz_render kz_replica kz_film kz_film_moment kz_debug kz_motion; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fgpu-flush-denormals-to-zero -fno-slp-vectorize" & PIDS="$PIDS $!"; done
         for u in kz_refit kz_denoise kz_variance; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fno-slp-vectorize" & PIDS="$PIDS $!"; done      # (build.sh's IEEE units: no flush to zero)
     done
 done
@@ -102,7 +102,7 @@ def side(which, build, units):          # functions, kernels and resource rows o
 
 differing = 0
 for build in ("plain", "exp"):
-    for unit in ("kz_render", "kz_replica", "kz_film", "kz_film_moment", "kz_debug", "kz_refit", "kz_denoise+kz_variance"):
+    for unit in ("kz_render", "kz_replica", "kz_film", "kz_film_moment", "kz_debug", "kz_motion", "kz_refit", "kz_denoise+kz_variance"):
         (fa, ka, ra), (fb, kb, rb) = side("this", build, unit), side("rev", build, unit)
         # kernels on one side only, paired by their demangled name without the parameter list: the other revision's takes this tree's mangled name
         lone = demangle((ka - kb) | (kb - ka))

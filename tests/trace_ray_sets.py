@@ -4,7 +4,11 @@ The kernels a render launches - kz_wf_trace<0|1|2|4>, kz_wf_trace_packet - are r
 brute-force oracle. The sets aim at what a render rarely or never sends: direction components that are exactly zero or next to the 1e-20 stand-in, origins
 that lie bit for bit on the planes of the quantised BVH4 packets with tmin = 0, rays through vertices and edge midpoints, tmax one ulp around the hit, dead
 rays (NaN / inf / zero direction) between live ones, and - for the shadow kernels - segments that end on, stop short of and pass through a light of
-lightPrimaryVisibility == false. test_trace_wf_cpu.py holds every set to what it claims, on the oracle alone."""
+lightPrimaryVisibility == false. test_trace_wf_cpu.py holds every set to what it claims, on the oracle alone.
+
+With deform=..., a case is the scene AFTER an edit (Scene.set_vertices, `deformation` below): the build's topology under refit boxes that no longer form a good
+tree. Scene, oracle, ray sets and reference are then those of the deformed description, and two aimed sets (h), (i) follow the others
+(tests/test_trace_refit_cpu.py, tests/test_trace_refit_gpu.py)."""
 import numpy as np
 
 NODE4 = np.dtype([("p", "<f4", 3), ("scaleX", "<f4"), ("qlo", "<u4", 3), ("qhi", "<u4", 3), ("scaleY", "<f4"), ("scaleZ", "<f4"), ("child", "<u4", 4)])
@@ -247,6 +251,15 @@ def set_outside(name, n, seed):
     return o, d.astype(np.float32), np.full(n, EPS, np.float32), np.full(n, np.inf, np.float32)
 
 
+def set_aimed(name, desc, meshes, n, seed):
+    """Rays from inside the room at uniform points of the triangles of `meshes` as `desc` places them (degenerate triangles included: their points lie on a segment
+    or are one point)."""
+    rng = np.random.default_rng(seed)
+    target = _light_points(rng, desc, meshes, n)
+    o = _inside(rng, name, n, 0.85)
+    return o, _unit(target - o), np.full(n, EPS, np.float32), np.full(n, np.inf, np.float32)
+
+
 def closest_sets(S, name, host_scene, ora, seed=5):
     """{set name: (o, d, tmin, tmax)} of scene `name`, with {set name: extra} beside it. host_scene: a kz.Scene of it (its host copy of the BVH4); ora: its brute-force oracle.
     The sizes are the smallest that fill several waves per set and, together, more rays than one static batch per wave of a one-workgroup launch."""
@@ -376,31 +389,101 @@ def shadow_reference(ora, ora_il, desc, o, d, tmin, tmax, eps=EPS):
     return occluded, walks, crosses
 
 
+# ------------------------------------------------------------------------------------------------ deformations: the same topology under boxes that stopped forming a good tree
+DEFORMS = {"soup": ("scatter", "slivers", "stacked", "nested"), "cornell": ("flattened",), "cornell_il": ("flattened",)}
+SOUP_MESHES, SOUP_LIGHTS = tuple(range(8)), tuple(range(9, 17))       # random_triangles(5000): eight meshes of 625 unshared triangles, the room, eight light quads
+STACKED = (0, 1, 2, 3)                                                # `stacked`: the meshes that end up coincident
+NESTED_FACTORS = (1.0, 0.85, 0.7, 0.55, 0.4, 0.25, 0.1, 0.05)         # `nested`: steps of 0.15 down to 0.1; the eighth mesh keeps a positive factor
+FLAT_POINT = (0.35, -0.6, 0.3)                                        # `flattened`: where mesh 6 collapses to
+REFIT_CLOSEST = (("soup", "scatter"), ("soup", "slivers"), ("soup", "stacked"), ("soup", "nested"), ("cornell", "flattened"))
+REFIT_SHADOW = (("soup", "scatter"), ("cornell_il", "flattened"))
+
+
+def deformation(name, desc, deform, seed=71):
+    """{mesh: (V, N)} of deformation `deform` of scene `name` (Scene.set_vertices' argument): seeded, inside ROOM[name], every mesh named once, N as it is.
+    soup - scatter: inside each soup mesh every triangle moves rigidly so that its centroid lands on the centroid of triangle pi(i), pi a seeded permutation, and
+    the light quads change places along a seeded 8-cycle: a leaf then holds triangles from anywhere in the room and every inner box is about the room's size.
+    slivers: V' = V[perm] inside each soup mesh - triangles whose corners are three random points of the mesh. stacked: meshes 1, 2, 3 take mesh 0's vertices bit
+    for bit - four coincident copies in four subtrees. nested: soup mesh k is scaled about the room's centre by NESTED_FACTORS[k].
+    cornell, cornell_il - flattened: the tall box (mesh 5) gets the floor's y in every vertex, the short box (mesh 6) collapses to FLAT_POINT, the light drops by 0.3."""
+    rng = np.random.default_rng(seed)
+    M = desc.meshes
+    upd = {}
+    if deform == "scatter":
+        for m in SOUP_MESHES:
+            T = np.asarray(M[m]["V"], np.float32).reshape(-1, 3, 3).astype(np.float64)
+            c = T.mean(axis=1)
+            upd[m] = (T + (c[rng.permutation(len(T))] - c)[:, None, :]).astype(np.float32).reshape(-1, 3)
+        order = rng.permutation(len(SOUP_LIGHTS))
+        cent = {m: np.asarray(M[m]["V"], np.float64).mean(axis=0) for m in SOUP_LIGHTS}
+        for i, k in enumerate(order):
+            a, b = SOUP_LIGHTS[k], SOUP_LIGHTS[order[(i + 1) % len(order)]]
+            upd[a] = (np.asarray(M[a]["V"], np.float64) + (cent[b] - cent[a])).astype(np.float32)
+    elif deform == "slivers":
+        for m in SOUP_MESHES:
+            V = np.asarray(M[m]["V"], np.float32)
+            upd[m] = V[rng.permutation(len(V))]
+    elif deform == "stacked":
+        for m in STACKED[1:]:
+            upd[m] = np.asarray(M[STACKED[0]]["V"], np.float32).copy()
+    elif deform == "nested":
+        lo, hi = (np.array(x, np.float64) for x in ROOM[name])
+        c = (lo + hi) / 2
+        for m, f in zip(SOUP_MESHES[1:], NESTED_FACTORS[1:]):              # (factor 1.0 leaves mesh 0 where it is: not named)
+            upd[m] = (c + (np.asarray(M[m]["V"], np.float64) - c) * f).astype(np.float32)
+    elif deform == "flattened":
+        V5 = np.asarray(M[5]["V"], np.float32).copy()
+        V5[:, 1] = np.asarray(M[0]["V"], np.float32)[0, 1]
+        V7 = np.asarray(M[7]["V"], np.float32).copy()
+        V7[:, 1] -= np.float32(0.3)
+        upd = {5: V5, 6: np.tile(np.array(FLAT_POINT, np.float32), (len(M[6]["V"]), 1)), 7: V7}
+    else:
+        raise KeyError(deform)
+    return {m: (np.ascontiguousarray(V, np.float32), M[m]["N"]) if M[m]["N"] is not None else np.ascontiguousarray(V, np.float32) for m, V in upd.items()}
+
+
 # ------------------------------------------------------------------------------------------------ a scene's rays with their reference, made once per process
 _cases = {}
 
 
-def closest_case(kz, O, name, device=None):
-    """{"desc", "scene" (kz.Scene, on `device` if given), "rays" (o, d, tmin, tmax of all sets), "spans", "extra", "ref" (the brute-force hits)} of a closest-hit scene."""
-    key = ("closest", name, device)
+def edited_scene(kz, name, deform, device, lib=None):
+    """The scene built from its description and then, with a deformation, edited in place: the tree keeps the build's topology under refit boxes, desc follows."""
+    desc = scene(kz.scenes, name)
+    sc = kz.Scene(desc, device=device, lib=lib)
+    if deform is not None:
+        sc.set_vertices(deformation(name, sc.desc, deform))
+    return sc
+
+
+def closest_case(kz, O, name, device=None, deform=None):
+    """{"desc", "scene" (kz.Scene, on `device` if given), "rays" (o, d, tmin, tmax of all sets), "spans", "extra", "ref" (the brute-force hits)} of a closest-hit scene.
+    deform: a name of DEFORMS[name] - the scene is built, then deformed with set_vertices; the oracle, the ray sets (set (c) from the REFIT packets) and the
+    reference are those of the deformed description."""
+    key = ("closest", name, device, deform)
     if key not in _cases:
-        desc = scene(kz.scenes, name)
-        sc = kz.Scene(desc, device=device)
+        sc = edited_scene(kz, name, deform, device)
+        desc = sc.desc
         ora = O.OracleScene(desc, brute=True)
         sets, extra = closest_sets(kz.scenes, name, sc, ora)
+        if deform is not None:
+            # the room is large and the soup thin - of the 2 048 rays of set (a) 66 end on the coincident copies of `stacked`, and the boxes of `flattened` are a small
+            # part of their room - so two AIMED sets follow: (h) at the meshes the deformation names where they are now, (i) at where they were before the edit
+            before = scene(kz.scenes, name)
+            moved = sorted(deformation(name, before, deform))
+            sets["h"], sets["i"] = set_aimed(name, desc, moved, 2048, 12), set_aimed(name, before, moved, 1024, 13)
         rays, spans = concat(sets)
         _cases[key] = {"desc": desc, "scene": sc, "ora": ora, "rays": rays, "spans": spans, "extra": extra, "ref": ora.trace_rays(*rays)}
     return _cases[key]
 
 
-def shadow_case(kz, O, name, device=None):
+def shadow_case(kz, O, name, device=None, deform=None):
     """The same for a shadow scene: "ref" = (occluded, walk-throughs, crosses an invisible-light triangle) per segment (shadow_reference)."""
-    key = ("shadow", name, device)
+    key = ("shadow", name, device, deform)
     if key not in _cases:
-        desc = scene(kz.scenes, name)
-        sc = kz.Scene(desc, device=device)
+        sc = edited_scene(kz, name, deform, device)
+        desc = sc.desc
         ora = O.OracleScene(desc, brute=True)
         ora_il = O.OracleScene(only_meshes(kz.scenes, desc, invisible_meshes(desc)), brute=True)
         rays, spans = concat(shadow_sets(kz.scenes, name, desc, ora))
-        _cases[key] = {"desc": desc, "scene": sc, "ora": ora, "rays": rays, "spans": spans, "ref": shadow_reference(ora, ora_il, desc, *rays)}
+        _cases[key] = {"desc": desc, "scene": sc, "ora": ora, "ora_il": ora_il, "rays": rays, "spans": spans, "ref": shadow_reference(ora, ora_il, desc, *rays)}
     return _cases[key]

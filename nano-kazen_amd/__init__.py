@@ -8,3 +8,4 @@ from . import abi, output, scenes, shard, xmlscene     # noqa: F401
 from .render import Scene, denoise_films, denoise_opts, denoise_variance_films, variance_opts      # noqa: F401
 from .render import denoise_temporal_films, temporal_opts, temporal_view      # noqa: F401
 from .render import denoise_motion_films, motion_rows      # noqa: F401
+from .render import denoise_responsive_films, responsive_opts      # noqa: F401

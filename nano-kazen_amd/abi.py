@@ -235,6 +235,11 @@ class KzMotionRow(C.Structure):
     _fields_ = [("d", C.c_float * 12), ("n", C.c_float * 9), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class KzResponsiveOpts(C.Structure):
+    # include/kazen_mi355x_responsive.h: 32 bytes, a zero field means its default
+    _fields_ = [("fastHistory", C.c_uint32), ("clampSigma", C.c_float), ("radius", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
 class KzBvhInfo(C.Structure):
     _fields_ = [("nNodes", C.c_uint32), ("nLeaves", C.c_uint32), ("nTris", C.c_uint32), ("maxDepth", C.c_uint32),
                 ("maxLeafSize", C.c_uint32), ("sahCost", C.c_float), ("buildSeconds", C.c_double)]
@@ -269,6 +274,9 @@ TEMPORAL_EXPORTS = ["kz_temporal_view", "kz_denoise_temporal", "kz_temporal_info
 # what include/kazen_mi355x_motion.h declares (checked by tests/test_motion_cpu.py): the history kept across kz_scene_set_transforms - per-mesh rows and a mesh id per pixel
 MOTION_EXPORTS = ["kz_motion_rows", "kz_motion_ids", "kz_denoise_motion", "kz_denoise_motion_films", "kz_motion_info"]
 KZ_MOTION_STATIC, KZ_MOTION_UNTRACKED, KZ_MOTION_MISS = 1, 2, 0xFFFFFFFF
+# what include/kazen_mi355x_responsive.h declares (checked by tests/test_responsive_cpu.py): a fast history beside the long one, which is clamped to it where the light moved
+RESPONSIVE_EXPORTS = ["kz_denoise_responsive", "kz_denoise_responsive_films", "kz_responsive_download", "kz_responsive_info"]
+KZ_RESPONSIVE_CLAMP_OFF = 1
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead", "kz_debug_shadow_order", "kz_debug_compact_late"]
@@ -404,6 +412,13 @@ def load_library(path=None):
                                                 C.POINTER(KzTemporalOpts), C.POINTER(KzTemporalView), C.POINTER(KzTemporalView), f32p, u32p, C.POINTER(KzMotionRow), C.c_uint32,
                                                 f32p, f32p, f32p]
         lib.kz_motion_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), u32p]
+    if hasattr(lib, "kz_denoise_responsive"):     # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_denoise_responsive.argtypes = [C.c_void_p, C.c_int, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts), C.POINTER(KzTemporalOpts), C.POINTER(KzResponsiveOpts)]
+        lib.kz_denoise_responsive_films.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p, C.POINTER(KzDenoiseOpts), C.POINTER(KzVarianceOpts),
+                                                    C.POINTER(KzTemporalOpts), C.POINTER(KzTemporalView), C.POINTER(KzTemporalView), f32p, u32p, C.POINTER(KzMotionRow), C.c_uint32,
+                                                    f32p, f32p, f32p, C.POINTER(KzResponsiveOpts), f32p, f32p]
+        lib.kz_responsive_download.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
+        lib.kz_responsive_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

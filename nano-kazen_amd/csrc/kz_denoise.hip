@@ -23,6 +23,7 @@
 #include "../../include/kazen_mi355x_motion.h"
 #include "kz_state.h"
 #include "kz_denoise.h"
+#include "kz_responsive.h"
 
 #include <cmath>
 #include <cstring>
@@ -414,7 +415,9 @@ static int dnPlan(const KzDenoiseOpts *opts, uint32_t avail, const char *call, K
 // What kz_denoise_variance adds to a call (null: kz_denoise). `moment`: the second-moment film (null: zeros); `variance`: null or width x height floats.
 // `temporal` (null: kz_denoise_variance): what kz_denoise_temporal puts in front - its prepare kernel takes the place of kz_dn_prepare_var.
 // `motion` (with `temporal` alone; null: kz_denoise_temporal): what kz_denoise_motion adds - kz_dn_prepare_motion takes that place.
-struct KzDnVar { float sv2, samples; const float4 *moment; float *variance; const KzDnTemporal *temporal; const KzDnMotion *motion; };
+// `responsive` (with `temporal` alone; null: one of the calls above): what kz_denoise_responsive adds - the two kernels of kz_responsive.hip take that place, with
+// `motion` or without it (no mesh has moved: every pixel static).
+struct KzDnVar { float sv2, samples; const float4 *moment; float *variance; const KzDnTemporal *temporal; const KzDnMotion *motion; const KzDnResponsive *responsive; };
 
 // KzTemporalOpts, checked, as the kernel takes them (the views and the history's planes are filled in by the caller)
 static int dnTemporalOpts(const KzTemporalOpts *topts, const char *call, KzDnTemporal *T) {
@@ -430,6 +433,29 @@ static int dnTemporalOpts(const KzTemporalOpts *topts, const char *call, KzDnTem
     T->depthTol = o.depthTolerance == 0.f ? 0.05f : o.depthTolerance;
     T->normalTol2 = nt * nt;
     T->maxHistory = (float)(o.maxHistory ? o.maxHistory : 32u);
+    return KZ_OK;
+}
+// KzResponsiveOpts (include/kazen_mi355x_responsive.h), checked, with the defaults in (the fast plane's copies are filled in by the caller)
+static int dnResponsiveOpts(const KzResponsiveOpts *ropts, const char *call, KzDnResponsive *R) {
+    static const KzResponsiveOpts defaults = {};
+    const KzResponsiveOpts &o = ropts ? *ropts : defaults;
+    if (o.fastHistory > 65535u) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzResponsiveOpts.fastHistory = %u (1 .. 65535; 0: the default, 2)", call, o.fastHistory);
+    if (!(std::isfinite(o.clampSigma) && o.clampSigma >= 0.f)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzResponsiveOpts.clampSigma = %g must be finite and > 0 (0: the default, 2)", call, (double)o.clampSigma);
+    if (o.radius > 2u) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzResponsiveOpts.radius = %u (1 or 2; 0: the default, 1)", call, o.radius);
+    if (o.flags & ~KZ_RESPONSIVE_CLAMP_OFF) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzResponsiveOpts.flags = %u has bits outside KZ_RESPONSIVE_CLAMP_OFF", call, o.flags);
+    for (int k = 0; k < 4; ++k) if (o.reserved[k]) return kz_fail(KZ_ERR_INVALID_ARG, "%s: KzResponsiveOpts.reserved[%d] = %u must be 0", call, k, o.reserved[k]);
+    *R = KzDnResponsive{};
+    R->fastHistory = (float)(o.fastHistory ? o.fastHistory : 2u);
+    R->clampSigma = o.clampSigma == 0.f ? 2.0f : o.clampSigma;
+    R->radius = o.radius ? (int)o.radius : 1;
+    R->clampOff = (o.flags & KZ_RESPONSIVE_CLAMP_OFF) != 0;
+    return KZ_OK;
+}
+// A fast plane as it leaves the device: (f.rgb, vf), four zeros where the pixel is not valid (the device marks those with vf = -1, kz_responsive.hip)
+static int dnFastDownload(const DevBuf<float4> &F, size_t nPix, float *fast) {
+    int rc;
+    if ((rc = F.download((float4 *)fast, nPix))) return rc;
+    for (size_t i = 0; i < nPix; ++i) if (fast[4 * i + 3] < 0.f) fast[4 * i] = fast[4 * i + 1] = fast[4 * i + 2] = fast[4 * i + 3] = 0.f;
     return KZ_OK;
 }
 // the reprojection reads the depth film whatever the weights use: a KzDenoiseOpts.guides without it is refused
@@ -478,7 +504,13 @@ static int dnRun(const KzDnPlan &plan, const KzDnVar *var, int width, int height
     const int demod = plan.demodulate ? 1 : 0;
     const dim3 gPix((nPix + KZ_DN_BLOCK - 1) / KZ_DN_BLOCK), gTexels((nTexels + KZ_DN_BLOCK - 1) / KZ_DN_BLOCK), b1(KZ_DN_BLOCK);
     albedo = (plan.guides & KZ_AOV_ALBEDO) ? albedo : nullptr; normal = (plan.guides & KZ_AOV_NORMAL) ? normal : nullptr; depth = (plan.guides & KZ_AOV_DEPTH) ? depth : nullptr;
-    if (var && var->temporal && var->motion) hipLaunchKernelGGL(kz_dn_prepare_motion, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, *var->temporal, *var->motion, colour[0], normalZ, albedoP);
+    if (var && var->temporal && var->responsive) {
+        static const KzDnMotion none = {};
+        int rc;
+        if ((rc = kzDnResponsiveRun(width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, *var->temporal, var->motion ? *var->motion : none,
+                                    *var->responsive, colour[0], normalZ, albedoP, stream))) return rc;
+    }
+    else if (var && var->temporal && var->motion) hipLaunchKernelGGL(kz_dn_prepare_motion, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, *var->temporal, *var->motion, colour[0], normalZ, albedoP);
     else if (var && var->temporal) hipLaunchKernelGGL(kz_dn_prepare_temporal, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, *var->temporal, colour[0], normalZ, albedoP);
     else if (var) hipLaunchKernelGGL(kz_dn_prepare_var, gPix, b1, 0, stream, width, height, border, film, var->moment, albedo, normal, depth, demod, var->samples, colour[0], normalZ, albedoP);
     else hipLaunchKernelGGL(kz_dn_prepare, gPix, b1, 0, stream, width, height, border, film, albedo, normal, depth, demod, colour[0], normalZ, albedoP);
@@ -528,10 +560,12 @@ static int dnHistoryDownload(const DevBuf<float4> &E, const DevBuf<float4> &G, c
 // `T` (kz_denoise_temporal alone): its checked options; the views and the replica's history are filled in here, and the history moves on when the call has succeeded
 // `motion` (with T; kz_denoise_motion): the history survives kz_scene_set_transforms - stale only by baseEdits -, and when a mesh has moved since it was stored the
 // call computes this frame's ids and the rows and takes kz_dn_prepare_motion
-static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, KzDnVar *var, KzDnTemporal *T = nullptr, bool motion = false) {
+// `R` (with T and motion; kz_denoise_responsive): its checked options; the replica's fast plane is filled in here - absent unless it was written with the history the
+// call reads - and moves on with the history
+static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, KzDnVar *var, KzDnTemporal *T = nullptr, bool motion = false, KzDnResponsive *R = nullptr) {
     const KzParams &P = scene->prm;
     const size_t nPix = (size_t)P.width * (size_t)P.height;
-    const char *const call = motion ? "kz_denoise_motion" : "kz_denoise_temporal";
+    const char *const call = R ? "kz_denoise_responsive" : (motion ? "kz_denoise_motion" : "kz_denoise_temporal");
     int rc;
     KzTemporalView view;
     KzDnMotion M = {};
@@ -589,6 +623,12 @@ static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, 
         T->outE = ds->tpE[out]; T->outG = ds->tpG[out]; T->outN = ds->tpN[out];
         var->temporal = T;
         if (M.ids && T->inE) var->motion = &M;                          // (without a history to read, kz_dn_prepare_temporal's lines are the motion kernel's)
+        if (R) {
+            for (int k = 0; k < 2; ++k) if (ds->rsF[k].cap() != nPix) { ds->rsStore = 0; if ((rc = ds->rsF[k].regrow(nPix))) return rc; }
+            if (T->inE && ds->rsStore && ds->rsStore == ds->tpStore) R->inF = ds->rsF[in];      // (written with the history this call reads; otherwise absent)
+            R->outF = ds->rsF[out];
+            var->responsive = R;
+        }
     }
     float4 *const colour[2] = {ds->dnColor[0].get(), ds->dnColor[1].get()};
     if ((rc = dnRun(plan, var, P.width, P.height, P.border, ds->picture().texels, guide[0], guide[1], guide[2], colour, ds->dnNormalZ, ds->dnAlbedo, ds->dnOut, ds->lastStream))) return rc;
@@ -596,6 +636,8 @@ static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, 
     ds->dnValid = true;
     if (T) {
         ds->tpCur ^= 1; ds->tpFrames += 1; ds->tpDemod = plan.demodulate; ds->tpEdits = scene->geometryEdits;
+        ds->tpStore += 1;
+        if (R) ds->rsStore = ds->tpStore;                               // (the fast plane's copy tpCur goes with this store of the history)
         ds->tpBaseEdits = scene->baseEdits; ds->tpXf = xfNow;           // (what kz_denoise_motion's rows are formed from, whichever call stored the history)
         std::memcpy(ds->tpO, view.o, sizeof ds->tpO); std::memcpy(ds->tpInv, view.inv, sizeof ds->tpInv);
     }
@@ -605,7 +647,8 @@ static int dnOnReplica(KzScene *scene, KzDeviceState *ds, const KzDnPlan &plan, 
 // What kz_denoise_temporal_films adds to a call on host films: the views and the history in the interchange format (12 floats per pixel), in and out
 // (ids non-null: kz_denoise_motion_films - the id plane, the rows and their number, checked by the caller)
 struct KzDnHostTemporal { const KzTemporalOpts *topts; const KzTemporalView *current, *previous; const float *historyIn; float *historyOut;
-                          const uint32_t *ids; const KzMotionRow *rows; uint32_t nRows; };
+                          const uint32_t *ids; const KzMotionRow *rows; uint32_t nRows;
+                          const KzDnResponsive *responsive; const float *fastIn; float *fastOut; };      // (responsive non-null: kz_denoise_responsive_films - its checked options, the fast plane in and out)
 
 // A call on films of the host's: kz_denoise_films, with `moment` kz_denoise_variance_films (`vopts`, `outVariance`: its alone), with `ht` kz_denoise_temporal_films
 static int dnFilms(const char *call, int device, int32_t width, int32_t height, int32_t border, const float *film, const float *moment, const float *albedo, const float *normal,
@@ -628,6 +671,10 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
         for (size_t i = 0; i < nPix; ++i)
             if (ht->ids[i] >= ht->nRows && ht->ids[i] != KZ_MOTION_MISS)
                 return kz_fail(KZ_ERR_INVALID_ARG, "%s: pixel (%zu, %zu) names mesh %u, the table has %u rows (a miss is %u)", call, i % (size_t)width, i / (size_t)width, ht->ids[i], ht->nRows, KZ_MOTION_MISS);
+    if (ht && ht->responsive && ht->historyIn)                          // (a negative vf is the device's mark of a pixel that is not valid, kz_responsive.hip: no input may produce one)
+        for (size_t i = 0; i < nPix; ++i)
+            if (ht->historyIn[12 * i + 3] < 0.f || (ht->fastIn && ht->fastIn[4 * i + 3] < 0.f))
+                return kz_fail(KZ_ERR_INVALID_ARG, "%s: pixel (%zu, %zu): a negative variance in the history or in the fast plane", call, i % (size_t)width, i / (size_t)width);
     if ((rc = kzUseDevice(device))) return rc;
     DevBuf<float4> films[5], planes[4], result; DevBuf<float> variance;
     const float *host[5] = {film, albedo, normal, depth, moment};
@@ -641,6 +688,7 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
     var.moment = films[4]; var.variance = variance;
     DevBuf<float4> hE[2], hG[2]; DevBuf<float> hN[2];                   // the history: [0] read (historyIn), [1] written
     DevBuf<uint32_t> mIds; DevBuf<KzMotionRow> mRows; KzDnMotion M = {};
+    DevBuf<float4> hF[2]; KzDnResponsive R = {};                        // the fast plane: [0] read (fastIn), [1] written
     if (ht) {
         static const float noView[9] = {};
         dnSetViews(&T, *ht->current, ht->previous ? ht->previous->o : noView, ht->previous ? ht->previous->inv : noView);
@@ -660,11 +708,22 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
             M.ids = mIds; M.rows = mRows; M.nRows = ht->nRows;
             var.motion = &M;
         }
+        if (ht->responsive) {
+            R = *ht->responsive;
+            if ((rc = hF[1].alloc(nPix))) return rc;
+            if (in && ht->fastIn) {
+                if ((rc = hF[0].alloc(nPix)) || (rc = hF[0].upload((const float4 *)ht->fastIn, nPix))) return rc;
+                R.inF = hF[0];
+            }
+            R.outF = hF[1];
+            var.responsive = &R;
+        }
     }
     float4 *const colour[2] = {planes[0].get(), planes[1].get()};
     if ((rc = dnRun(plan, moment ? &var : nullptr, width, height, border, films[0], films[1], films[2], films[3], colour, planes[2], planes[3], result, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     if (ht && ht->historyOut && (rc = dnHistoryDownload(hE[1], hG[1], hN[1], nPix, ht->historyOut))) return rc;
+    if (ht && ht->responsive && ht->fastOut && (rc = dnFastDownload(hF[1], nPix, ht->fastOut))) return rc;
     if (outVariance && (rc = variance.download(outVariance, nPix))) return rc;
     return result.download((float4 *)out, nTexels);
 }
@@ -753,11 +812,13 @@ int kz_temporal_view(const KzCamera *camera, KzTemporalView *view) {
 }
 
 // kz_denoise_temporal and, with `motion`, kz_denoise_motion (include/kazen_mi355x_motion.h): one path, the same refusals under the call's own name
-static int dnTemporalCall(const char *call, bool motion, KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts) {
+// and, with `responsive`, kz_denoise_responsive (include/kazen_mi355x_responsive.h; `ropts`: its alone)
+static int dnTemporalCall(const char *call, bool motion, KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts,
+                          bool responsive = false, const KzResponsiveOpts *ropts = nullptr) {
     if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null scene", call);
-    KzDnPlan plan; KzDnVar var = {}; KzDnTemporal T; KzDeviceState *ds; int rc; uint32_t samples;
+    KzDnPlan plan; KzDnVar var = {}; KzDnTemporal T; KzDnResponsive R; KzDeviceState *ds; int rc; uint32_t samples;
     if ((rc = dnPlan(opts, scene->aovMask, call, &plan, 2.0f)) || (rc = dnVarianceOpts(vopts, call, &var.sv2, &samples)) || (rc = dnTemporalOpts(topts, call, &T)) ||
-        (rc = dnTemporalGuides(plan, scene->aovMask, call))) return rc;
+        (rc = dnTemporalGuides(plan, scene->aovMask, call)) || (responsive && (rc = dnResponsiveOpts(ropts, call, &R)))) return rc;
     if (!(scene->aovMask & KZ_AOV_DEPTH)) return kz_fail(KZ_ERR_STATE, "%s: the depth film is not among the scene's AOVs (mask %u, KZ_AOV_DEPTH = %u): kz_scene_set_aovs, then render", call, scene->aovMask, KZ_AOV_DEPTH);
     if (!scene->varianceMode) return kz_fail(KZ_ERR_STATE, "%s: the second-moment film is switched off (kz_scene_variance gives 0): kz_scene_set_variance(scene, 1), then render", call);
     if ((rc = findReplica(scene, device, &ds))) return rc;
@@ -766,7 +827,7 @@ static int dnTemporalCall(const char *call, bool motion, KzScene *scene, int dev
     if (ds->pictureSamples != ds->momentSamples)
         return kz_fail(KZ_ERR_STATE, "%s: the picture's film holds %u samples per pixel, the second-moment film %u (switched on late: kz_film_clear, then render both)", call, ds->pictureSamples, ds->momentSamples);
     var.samples = (float)samples;
-    return dnOnReplica(scene, ds, plan, &var, &T, motion);
+    return dnOnReplica(scene, ds, plan, &var, &T, motion, responsive ? &R : nullptr);
 }
 int kz_denoise_temporal(KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts) {
     return dnTemporalCall("kz_denoise_temporal", false, scene, device, opts, vopts, topts);
@@ -788,6 +849,7 @@ int kz_temporal_reset(KzScene *scene, int device) {
     for (int k = 0; k < 2; ++k) { ds->tpE[k].free(); ds->tpG[k].free(); ds->tpN[k].free(); }
     ds->tpFrames = 0; ds->tpCur = 0;
     ds->mtIds.free(); ds->mtRows.free(); ds->mtCounts[0] = ds->mtCounts[1] = ds->mtCounts[2] = 0;      // (kazen_mi355x_motion.h: the id plane and the rows go with the history)
+    ds->rsF[0].free(); ds->rsF[1].free(); ds->rsStore = 0;              // (kazen_mi355x_responsive.h: so does the fast plane)
     return KZ_OK;
 }
 
@@ -834,6 +896,46 @@ int kz_motion_info(KzScene *scene, int device, uint64_t *bytes, uint32_t *counts
     if ((rc = findReplica(scene, device, &ds))) return rc;
     if (bytes) *bytes = ds->mtBytes();
     if (counts) std::memcpy(counts, ds->mtCounts, sizeof ds->mtCounts);
+    return KZ_OK;
+}
+
+// ---- include/kazen_mi355x_responsive.h (the kernels: kz_responsive.hip)
+int kz_denoise_responsive(KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts, const KzResponsiveOpts *ropts) {
+    return dnTemporalCall("kz_denoise_responsive", true, scene, device, opts, vopts, topts, true, ropts);
+}
+
+int kz_denoise_responsive_films(int device, int32_t width, int32_t height, int32_t border, const float *film, const float *moment, const float *albedo, const float *normal, const float *depth,
+                                const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts, const KzTemporalView *current, const KzTemporalView *previous,
+                                const float *historyIn, const uint32_t *ids, const KzMotionRow *rows, uint32_t nRows, float *out, float *historyOut, float *outVariance,
+                                const KzResponsiveOpts *ropts, const float *fastIn, float *fastOut) {
+    static const char *const call = "kz_denoise_responsive_films";
+    if (!film || !moment || !depth || !out) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null film (the picture, the moment film and the depth film are needed)", call);
+    if (!current || (historyIn && !previous)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null view (the current one, and with a history the one it was stored with)", call);
+    if (!ids || (nRows && !rows)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null ids or rows (the id plane, and %u rows)", call, nRows);
+    for (uint32_t m = 0; m < nRows; ++m)
+        if ((rows[m].flags & ~(KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED)) || rows[m].flags == (KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED) || rows[m].reserved[0] || rows[m].reserved[1])
+            return kz_fail(KZ_ERR_INVALID_ARG, "%s: row %u: flags = %u (0, KZ_MOTION_STATIC or KZ_MOTION_UNTRACKED) or a non-zero reserved word", call, m, rows[m].flags);
+    KzDnResponsive R; int rc;
+    if ((rc = dnResponsiveOpts(ropts, call, &R))) return rc;
+    const KzDnHostTemporal ht = {topts, current, previous, historyIn, historyOut, ids, rows, nRows, &R, fastIn, fastOut};
+    return dnFilms(call, device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance, &ht);
+}
+
+int kz_responsive_download(KzScene *scene, int device, float *fast, size_t nFloats) {
+    KzDeviceState *ds; int rc;
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    if (!ds->tpFrames || !ds->rsStore || ds->rsStore != ds->tpStore)
+        return kz_fail(KZ_ERR_STATE, "kz_responsive_download: no kz_denoise_responsive stored this replica's history (none has run, the history was reset, or another call stored it since)");
+    const size_t nPix = ds->rsF[ds->tpCur].cap();
+    if (!fast || nFloats != nPix * 4) return kz_fail(KZ_ERR_INVALID_ARG, "kz_responsive_download: the buffer must hold %zu floats", nPix * 4);
+    return dnFastDownload(ds->rsF[ds->tpCur], nPix, fast);
+}
+
+int kz_responsive_info(KzScene *scene, int device, uint64_t *bytes) {
+    KzDeviceState *ds; int rc;
+    if (!bytes) return kz_fail(KZ_ERR_INVALID_ARG, "kz_responsive_info: null bytes");
+    if ((rc = findReplica(scene, device, &ds))) return rc;
+    *bytes = ds->rsBytes();
     return KZ_OK;
 }
 

@@ -9,6 +9,7 @@
 //   kz_denoise.hip  the a-trous denoiser of include/kazen_mi355x_denoise.h and its variance-guided form (include/kazen_mi355x_variance.h): their kernels, the
 //                   replica's denoise buffers, kz_denoise* and kz_denoise_variance* entry points
 //   kz_motion.hip   include/kazen_mi355x_motion.h beyond the denoiser's unit: the id kernel (which mesh every frame pixel shows) and the host-only row table
+//   kz_responsive.hip  the two kernels of include/kazen_mi355x_responsive.h (the fast history and the clamp) and their launcher; the entry points: kz_denoise.hip
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
 // Every device buffer, pinned buffer, event and stream named below is a member of one of the four move-only owners of kz_own.h (DevBuf, PinnedBuf, Event, Stream).
@@ -219,6 +220,11 @@ struct KzDeviceState {
     uint64_t tpBaseEdits = 0; std::vector<float> tpXf;
     DevBuf<uint32_t> mtIds; DevBuf<KzMotionRow> mtRows; uint32_t mtCounts[3] = {};
     size_t mtBytes() const { return mtIds.bytes() + mtRows.bytes(); }
+    // The fast history (kazen_mi355x_responsive.h): per frame pixel (f.rgb, vf), twice - copy k goes with the history's copy k -, allocated by the first
+    // kz_denoise_responsive, outside the budget, freed by kz_temporal_reset. tpStore counts the stores of the history, whichever call made them; rsStore: the store the
+    // fast plane was written with (0: none) - another value than tpStore: the plane counts as absent.
+    DevBuf<float4> rsF[2]; uint64_t tpStore = 0, rsStore = 0;
+    size_t rsBytes() const { return rsF[0].bytes() + rsF[1].bytes(); }
     DevBuf<float4> packDev; DevBuf<KzTileRect> rectsDev;         // kz_film_download_tiles: packed tile rects + their table
     PinnedBuf<float4> packHost;                                  // pinned staging of the same (D2H at link rate)
     // The tile set: pixList = its pixels (tile after tile, 8x8 blocks row-major inside a tile, row-major inside a block), written on the device from the

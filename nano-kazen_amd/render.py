@@ -533,6 +533,28 @@ class Scene:
         abi.check(self.lib, self.lib.kz_motion_info(self.h, int(device), C.byref(b), n))
         return int(b.value), tuple(int(x) for x in n)
 
+    # ---- a fast history that clamps the long one where the light moved (include/kazen_mi355x_responsive.h)
+    def denoise_responsive(self, device=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0, depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0,
+                           treserved=(0, 0, 0, 0), fast_history=0, clamp_sigma=0.0, radius=0, clamp=True, rflags=None, rreserved=(0, 0, 0, 0), **opts):
+        """kz_denoise_responsive: denoise_motion() with a fast history beside the long one; where the long history's colour leaves the fast one's local mean +- clamp_sigma
+        deviations it is clamped and the pixel re-converges in fast_history calls. Options: denoise_motion's and responsive_opts'; results as denoise_temporal's."""
+        o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
+        t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
+        r = responsive_opts(fast_history, clamp_sigma, radius, clamp, rflags, rreserved)
+        abi.check(self.lib, self.lib.kz_denoise_responsive(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v), C.byref(t), C.byref(r)))
+
+    def responsive_fast(self, device=None):
+        """kz_responsive_download: (h, w, 4) = per pixel (f.rgb, vf), the fast history that goes with temporal_history() - what denoise_responsive_films takes as `fast`."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        abi.check(self.lib, self.lib.kz_responsive_download(self.h, -1 if device is None else int(device), out.ctypes.data_as(abi.f32p), out.size))
+        return out
+
+    def responsive_info(self, device=-1):
+        """kz_responsive_info: bytes the fast planes hold on that replica."""
+        b = C.c_uint64()
+        abi.check(self.lib, self.lib.kz_responsive_info(self.h, int(device), C.byref(b)))
+        return int(b.value)
+
     def bsdf_query(self, bsdf, wi, wo, acc, s3, uv=None):
         """eval (n,3), pdf (n,), sample (n,8) = weight rgb, wo xyz, alive, pdf(bRec) after sample()."""
         bsdf = np.ascontiguousarray(bsdf, np.int32)
@@ -736,6 +758,51 @@ def denoise_motion_films(film, moment, albedo=None, normal=None, depth=None, bor
                                                None if current is None else C.byref(current), None if previous is None else C.byref(previous), p(history),
                                                None if ids is None else ids.ctypes.data_as(abi.u32p), rows, int(n_rows), p(out), p(hist), p(var)))
     return (out, hist, var) if return_variance else (out, hist)
+
+
+def responsive_opts(fast_history=0, clamp_sigma=0.0, radius=0, clamp=True, flags=None, reserved=(0, 0, 0, 0)):
+    """A KzResponsiveOpts: 0 means the default (a fast history of 2 calls, mean +- 2.0 deviations, radius 1: a 3 x 3 window; DESIGN.md 4i has the sweep). clamp=False sets
+    KZ_RESPONSIVE_CLAMP_OFF (`flags` overrides it)."""
+    if flags is None:
+        flags = 0 if clamp else abi.KZ_RESPONSIVE_CLAMP_OFF
+    return abi.KzResponsiveOpts(int(fast_history), float(clamp_sigma), int(radius), int(flags), (C.c_uint32 * 4)(*[int(r) for r in reserved]))
+
+
+def denoise_responsive_films(film, moment, albedo=None, normal=None, depth=None, border=0, device=0, lib=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0,
+                             depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0, treserved=(0, 0, 0, 0), current=None, previous=None, history=None,
+                             ids=None, rows=None, n_rows=None, fast=None, fast_history=0, clamp_sigma=0.0, radius=0, clamp=True, rflags=None, rreserved=(0, 0, 0, 0),
+                             return_variance=False, **opts):
+    """kz_denoise_responsive_films: denoise_motion_films with the fast history - `fast` (h, w, 4) as Scene.responsive_fast gives it (None: absent) and responsive_opts'
+    options. Returns (film, history (h, w, 12), fast (h, w, 4)), or (film, history, fast, v_last (h, w)) with return_variance."""
+    lib = lib or abi.load_library()
+    film, g, frame = _host_films(film, (moment, albedo, normal, depth), border, "the moment film and the guide films have the picture's shape")
+    h, w = max(frame[1], 0), max(frame[0], 0)
+    if history is not None:
+        history = np.ascontiguousarray(history, np.float32)
+        if history.shape != (h, w, 12):
+            raise ValueError("a history is (h, w, 12)")
+    if fast is not None:
+        fast = np.ascontiguousarray(fast, np.float32)
+        if fast.shape != (h, w, 4):
+            raise ValueError("a fast plane is (h, w, 4)")
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, np.uint32)
+        if ids.shape != (h, w):
+            raise ValueError("ids are (h, w)")
+    if n_rows is None:
+        n_rows = 0 if rows is None else getattr(rows, "n_rows", len(rows))
+    out = np.empty_like(film)
+    hist = np.full((h, w, 12), np.nan, np.float32)
+    fout = np.full((h, w, 4), np.nan, np.float32)
+    var = np.full((h, w), np.nan, np.float32) if return_variance else None
+    o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
+    t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
+    r = responsive_opts(fast_history, clamp_sigma, radius, clamp, rflags, rreserved)
+    p = lambda a: None if a is None else a.ctypes.data_as(abi.f32p)
+    abi.check(lib, lib.kz_denoise_responsive_films(int(device), *frame, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t),
+                                                   None if current is None else C.byref(current), None if previous is None else C.byref(previous), p(history),
+                                                   None if ids is None else ids.ctypes.data_as(abi.u32p), rows, int(n_rows), p(out), p(hist), p(var), C.byref(r), p(fast), p(fout)))
+    return (out, hist, fout, var) if return_variance else (out, hist, fout)
 
 
 def hits_to_arrays(hits, n):

@@ -45,7 +45,8 @@ struct KzDnTemporal {
 
 // What kz_denoise_motion (include/kazen_mi355x_motion.h, which holds the definition) adds to KzDnTemporal, by value to kz_dn_prepare_motion: the mesh id of every
 // frame pixel (0xFFFFFFFF: a miss), the rows - where a point of each mesh was when the history was stored - and their number. A struct of its own, not a part of
-// KzDnTemporal: that one is a kernel argument of kz_dn_prepare_temporal, whose code stays what it was.
+// KzDnTemporal: that one is a kernel argument of kz_dn_prepare_temporal, whose argument list stays what it was.
+// (The stage that reads the two, stated once for the three history calls: kz_history.h. This file is the spatial filter's statement.)
 struct KzMotionRow;
 struct KzDnMotion { const uint32_t *ids; const KzMotionRow *rows; uint32_t nRows; };
 
@@ -76,6 +77,24 @@ KZ_DN_FN float dnExp(float x) {
 KZ_DN_FN float dnH(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
 // whether a colour plane texel is a valid pixel's
 template <bool VAR> KZ_DN_FN bool dnValid(const float4 &e) { return VAR ? !(e.w < 0.f) : e.w != 0.f; }
+
+// (e_0, valid | v_0) of a pixel from the values of its texels: c the picture's, a the albedo's, s the moment film's (VAR alone, like `samples`). The pixel that is
+// not valid gets its v = -1 from the caller.
+template <bool VAR> KZ_DN_FN float4 dnCurrent(const float4 &c, const float4 &a, const float4 &s, int demodulate, float samples) {
+    float4 e = make_float4(c.x, c.y, c.z, c.w != 0.f ? 1.f : 0.f);
+    float vr = 0.f, vg = 0.f, vb = 0.f;
+    if (VAR) {
+        vr = dnMax(s.x - c.x * c.x, 0.f) / samples; vg = dnMax(s.y - c.y * c.y, 0.f) / samples; vb = dnMax(s.z - c.z * c.z, 0.f) / samples;
+        e.w = (vr + vg) + vb;
+    }
+    if (demodulate) {
+        const float ar = dnMax(a.x, 1e-3f); e.x = c.x / ar;
+        const float ag = dnMax(a.y, 1e-3f); e.y = c.y / ag;
+        const float ab = dnMax(a.z, 1e-3f); e.z = c.z / ab;
+        if (VAR) e.w = (vr / (ar * ar) + vg / (ag * ag)) + vb / (ab * ab);
+    }
+    return e;
+}
 
 // VAR, the 3 x 3 prefilter's weights: k[|d|] for d = -1..1; the products are exact
 KZ_DN_FN float dnK(int d) { return d == 0 ? 0.5f : 0.25f; }

@@ -8,9 +8,11 @@
 //   kz_dn_atrous[_var]    one launch per iteration, one lane per pixel: steps 1 and 2 from an LDS tile with a halo (kz_dn_atrous[_var]_lds), the larger steps by
 //                         direct gather with a wave along a row - every tap of a wave is one contiguous 1 KB load per plane
 //   kz_dn_finish[_var]    per film texel: remodulated colour and weight 1 in a valid frame pixel, (0, 0, 0, 0) elsewhere (the apron too)
-//   kz_dn_prepare_temporal  kz_denoise_temporal (include/kazen_mi355x_temporal.h) alone, in kz_dn_prepare_var's place: the replica's history reprojected into the current
-//                         view and blended into (e_0, v_0), the new history stored; the _var kernels follow unchanged
-// Each of the four is ONE body (dnPrepare, dnAtrous, dnAtrousLds, dnFinish) templated on VAR; the eight kernels are its two instances under the names the profiles
+//   kz_dn_prepare_temporal, kz_dn_prepare_motion   kz_denoise_temporal (include/kazen_mi355x_temporal.h) and kz_denoise_motion (include/kazen_mi355x_motion.h), in
+//                         kz_dn_prepare_var's place: the replica's history reprojected into the current view and blended into (e_0, v_0), the new history stored;
+//                         the _var kernels follow unchanged. Two instances of the history prepare stage's one body (kz_history.h: dnHistory<MOTION, FAST>); the
+//                         third, kz_denoise_responsive's, is kz_responsive.hip's
+// Each of the first four is ONE body (dnPrepare, dnAtrous, dnAtrousLds, dnFinish) templated on VAR; the eight kernels are its two instances under the names the profiles
 // know. With VAR the colour plane's .w carries v (negative: not valid) instead of the valid flag, so the planes and the tap loads are the same and the variance-
 // guided call needs no buffer of its own. Each kernel's result is a function of its inputs alone: no atomics, no order between threads, the taps of a pixel summed
 // by its own lane in the stated order (kz_denoise.h). This unit is compiled WITHOUT -fgpu-flush-denormals-to-zero (build.sh), so a subnormal weight is the C++
@@ -23,6 +25,7 @@
 #include "../../include/kazen_mi355x_motion.h"
 #include "kz_state.h"
 #include "kz_denoise.h"
+#include "kz_history.h"
 #include "kz_responsive.h"
 
 #include <cmath>
@@ -38,20 +41,10 @@ KZ_DN_FN void dnPrepare(int width, int height, int border, const float4 *__restr
     const int y = (int)(i / (uint32_t)width), x = (int)(i - (uint32_t)y * (uint32_t)width);
     const size_t t = (size_t)(y + border) * (size_t)(width + 2 * border) + (size_t)(x + border);      // < (height + 2b)(width + 2b): the films' texels
     const float4 c = dnValue(film, t), a = dnValue(albedo, t), n = dnValue(normal, t), z = dnValue(depth, t);
-    float4 e = make_float4(c.x, c.y, c.z, c.w != 0.f ? 1.f : 0.f);
-    float vr = 0.f, vg = 0.f, vb = 0.f;
-    if (VAR) {
-        const float4 s = dnValue(moment, t);
-        vr = dnMax(s.x - c.x * c.x, 0.f) / samples; vg = dnMax(s.y - c.y * c.y, 0.f) / samples; vb = dnMax(s.z - c.z * c.z, 0.f) / samples;
-        e.w = (vr + vg) + vb;
-    }
-    if (demodulate) {
-        const float ar = dnMax(a.x, 1e-3f); e.x = c.x / ar;
-        const float ag = dnMax(a.y, 1e-3f); e.y = c.y / ag;
-        const float ab = dnMax(a.z, 1e-3f); e.z = c.z / ab;
-        if (VAR) e.w = (vr / (ar * ar) + vg / (ag * ag)) + vb / (ab * ab);
-    }
-    if (VAR && c.w == 0.f) e.w = -1.f;                                  // not valid
+    float4 s = c;
+    if (VAR) s = dnValue(moment, t);
+    float4 e = dnCurrent<VAR>(c, a, s, demodulate, samples);
+    if (VAR && c.w == 0.f) e.w = -1.f;                                 // not valid
     colour[i] = e;
     normalZ[i] = make_float4(n.x, n.y, n.z, z.x);
     albedoP[i] = make_float4(a.x, a.y, a.z, 0.f);
@@ -213,174 +206,17 @@ KZ_DN_KERNEL kz_dn_finish_var(int width, int height, int border, const float4 *_
     dnFinish<true>(width, height, border, colour, albedoP, demodulate, out, variance);
 }
 
-// kz_dn_prepare_var with the temporal stage of include/kazen_mi355x_temporal.h (the definition; every line below is one of its lines): this frame's (e_cur, v_cur)
-// blended with the history reprojected from the previous view, into the colour plane, and with (n, z) and the count into the history's other copy. One lane per
-// pixel, a wave along a row: for the small view changes this is for, the 2 x 2 taps of neighbouring lanes fall on neighbouring records, so each of a wave's twelve
-// tap loads (two 16-byte planes and the count, four taps) touches little more than the 1 KB / 256 B its own pixels hold. A pixel's sums are its own lane's, in the
-// stated order; the copy that is read is not written.
+// The history prepare stage (kz_history.h: dnHistory, the one body) in kz_dn_prepare_var's place: kz_denoise_temporal's kernel, and kz_denoise_motion's - the same
+// lines plus the pixel's mesh id and that mesh's row (MOTION). kz_denoise_responsive's (MOTION and FAST) is in kz_responsive.hip.
 KZ_DN_KERNEL kz_dn_prepare_temporal(int width, int height, int border, const float4 *__restrict__ film, const float4 *__restrict__ moment, const float4 *__restrict__ albedo,
                                     const float4 *__restrict__ normal, const float4 *__restrict__ depth, int demodulate, float samples, const KzDnTemporal T,
                                     float4 *__restrict__ colour, float4 *__restrict__ normalZ, float4 *__restrict__ albedoP) {
-    const uint32_t i = blockIdx.x * KZ_DN_BLOCK + threadIdx.x;
-    if (i >= (uint32_t)width * (uint32_t)height) return;
-    const int y = (int)(i / (uint32_t)width), x = (int)(i - (uint32_t)y * (uint32_t)width);
-    const size_t t = (size_t)(y + border) * (size_t)(width + 2 * border) + (size_t)(x + border);      // < (height + 2b)(width + 2b): the films' texels
-    const float4 c = dnValue(film, t), a = dnValue(albedo, t), n = dnValue(normal, t), z = dnValue(depth, t), s = dnValue(moment, t);
-    // (e_cur, v_cur): dnPrepare<true>'s lines
-    const float vr = dnMax(s.x - c.x * c.x, 0.f) / samples, vg = dnMax(s.y - c.y * c.y, 0.f) / samples, vb = dnMax(s.z - c.z * c.z, 0.f) / samples;
-    float4 e = make_float4(c.x, c.y, c.z, (vr + vg) + vb);
-    if (demodulate) {
-        const float ar = dnMax(a.x, 1e-3f); e.x = c.x / ar;
-        const float ag = dnMax(a.y, 1e-3f); e.y = c.y / ag;
-        const float ab = dnMax(a.z, 1e-3f); e.z = c.z / ab;
-        e.w = (vr / (ar * ar) + vg / (ag * ag)) + vb / (ab * ab);
-    }
-    normalZ[i] = make_float4(n.x, n.y, n.z, z.x);
-    albedoP[i] = make_float4(a.x, a.y, a.z, 0.f);
-    if (c.w == 0.f) {                                                   // not valid: no part in the filter (v = -1), an empty record
-        e.w = -1.f;
-        colour[i] = e;
-        T.outE[i] = make_float4(0.f, 0.f, 0.f, 0.f); T.outG[i] = make_float4(0.f, 0.f, 0.f, 0.f); T.outN[i] = 0.f;
-        return;
-    }
-    float count = 1.0f;
-    if (T.inE && z.x > 0.f) {
-        const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
-        const float dx = (T.a[0] + fx * T.u[0]) + fy * T.v[0], dy = (T.a[1] + fx * T.u[1]) + fy * T.v[1], dz = (T.a[2] + fx * T.u[2]) + fy * T.v[2];
-        const float len = sqrtf(dnSq(dx, dy, dz));
-        const float r = z.x / len;
-        const float qx = (T.o[0] + dx * r) - T.po[0], qy = (T.o[1] + dy * r) - T.po[1], qz = (T.o[2] + dz * r) - T.po[2];
-        const float P0 = (T.pinv[0] * qx + T.pinv[1] * qy) + T.pinv[2] * qz, P1 = (T.pinv[3] * qx + T.pinv[4] * qy) + T.pinv[5] * qz,
-                    P2 = (T.pinv[6] * qx + T.pinv[7] * qy) + T.pinv[8] * qz;
-        if (P2 > 0.f) {
-            const float sx = P0 / P2 - 0.5f, sy = P1 / P2 - 0.5f;
-            if (sx >= -1.f && sx < (float)width && sy >= -1.f && sy < (float)height) {      // (so x0, y0 are in -1 .. width - 1, -1 .. height - 1: the int conversions are exact)
-                const float fx0 = floorf(sx), fy0 = floorf(sy), tx = sx - fx0, ty = sy - fy0;
-                const int x0 = (int)fx0, y0 = (int)fy0;
-                const float zp = sqrtf(dnSq(qx, qy, qz)), ztol = T.depthTol * dnMax(zp, 1e-20f);
-                float Wb = 0.f, Er = 0.f, Eg = 0.f, Eb = 0.f, V = 0.f, M = 0.f;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int ty_ = y0 + j;
-                    const bool rowIn = ty_ >= 0 && ty_ < height;
-                    const size_t rowAt = (size_t)(rowIn ? ty_ : y) * (size_t)width;      // (a tap outside the frame loads the pixel's own row / column and is skipped)
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int tx_ = x0 + k;
-                        const bool colIn = tx_ >= 0 && tx_ < width;
-                        const size_t it = rowAt + (size_t)(colIn ? tx_ : x);             // < width * height
-                        const float nh = T.inN[it];
-                        const float4 gh = T.inG[it], eh = T.inE[it];
-                        const float b = (k ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
-                        if (!(rowIn && colIn) || nh == 0.f || fabsf(gh.w - zp) > ztol || dnSq(gh.x - n.x, gh.y - n.y, gh.z - n.z) > T.normalTol2) continue;
-                        Wb += b; Er += b * eh.x; Eg += b * eh.y; Eb += b * eh.z; V += b * eh.w; M += b * nh;
-                    }
-                }
-                if (Wb > 1e-3f) {
-                    const float Nh = M / Wb, Nn1 = Nh + 1.0f, Nn = Nn1 < T.maxHistory ? Nn1 : T.maxHistory;
-                    const float al = 1.0f / Nn, om = 1.0f - al;
-                    e.x = om * (Er / Wb) + al * e.x; e.y = om * (Eg / Wb) + al * e.y; e.z = om * (Eb / Wb) + al * e.z;
-                    e.w = (om * om) * (V / Wb) + (al * al) * e.w;
-                    count = Nn;
-                }
-            }
-        }
-    }
-    colour[i] = e;
-    T.outE[i] = e; T.outG[i] = make_float4(n.x, n.y, n.z, z.x); T.outN[i] = count;
+    dnHistory<false, false>(width, height, border, film, moment, albedo, normal, depth, demodulate, samples, T, KzDnMotion{}, KzDnFast{}, colour, normalZ, albedoP);
 }
-
-// kz_dn_prepare_temporal with the motion stage of include/kazen_mi355x_motion.h (the definition): restated, not shared - a template over the two would be one more
-// way for kz_dn_prepare_temporal's code to move - plus the pixel's mesh id, that mesh's row and the header's three changes: the point the history's
-// view sees is the row's map of X, the normal the taps compare is the row's map of n(p), and a pixel of an untracked mesh takes no history. A miss and a static
-// row take kz_dn_prepare_temporal's arithmetic to the bit: the multiply is skipped, not done with an identity. A wave's lanes mostly show one mesh, so the row's 96
-// bytes are a plain load that the lanes share; like its model the kernel has no atomics, no LDS, no scratch and no index at or beyond width x height (an id at or
-// beyond M.nRows - the host has refused it - reads no row: a miss).
 KZ_DN_KERNEL kz_dn_prepare_motion(int width, int height, int border, const float4 *__restrict__ film, const float4 *__restrict__ moment, const float4 *__restrict__ albedo,
                                   const float4 *__restrict__ normal, const float4 *__restrict__ depth, int demodulate, float samples, const KzDnTemporal T, const KzDnMotion M,
                                   float4 *__restrict__ colour, float4 *__restrict__ normalZ, float4 *__restrict__ albedoP) {
-    const uint32_t i = blockIdx.x * KZ_DN_BLOCK + threadIdx.x;
-    if (i >= (uint32_t)width * (uint32_t)height) return;
-    const int y = (int)(i / (uint32_t)width), x = (int)(i - (uint32_t)y * (uint32_t)width);
-    const size_t t = (size_t)(y + border) * (size_t)(width + 2 * border) + (size_t)(x + border);      // < (height + 2b)(width + 2b): the films' texels
-    const float4 c = dnValue(film, t), a = dnValue(albedo, t), n = dnValue(normal, t), z = dnValue(depth, t), s = dnValue(moment, t);
-    // (e_cur, v_cur): dnPrepare<true>'s lines
-    const float vr = dnMax(s.x - c.x * c.x, 0.f) / samples, vg = dnMax(s.y - c.y * c.y, 0.f) / samples, vb = dnMax(s.z - c.z * c.z, 0.f) / samples;
-    float4 e = make_float4(c.x, c.y, c.z, (vr + vg) + vb);
-    if (demodulate) {
-        const float ar = dnMax(a.x, 1e-3f); e.x = c.x / ar;
-        const float ag = dnMax(a.y, 1e-3f); e.y = c.y / ag;
-        const float ab = dnMax(a.z, 1e-3f); e.z = c.z / ab;
-        e.w = (vr / (ar * ar) + vg / (ag * ag)) + vb / (ab * ab);
-    }
-    normalZ[i] = make_float4(n.x, n.y, n.z, z.x);
-    albedoP[i] = make_float4(a.x, a.y, a.z, 0.f);
-    if (c.w == 0.f) {                                                   // not valid: no part in the filter (v = -1), an empty record
-        e.w = -1.f;
-        colour[i] = e;
-        T.outE[i] = make_float4(0.f, 0.f, 0.f, 0.f); T.outG[i] = make_float4(0.f, 0.f, 0.f, 0.f); T.outN[i] = 0.f;
-        return;
-    }
-    float count = 1.0f;
-    // the pixel's row: flags 0 = moved (d, n are read), STATIC also for a miss, UNTRACKED = no history
-    uint32_t flags = KZ_MOTION_STATIC;
-    const KzMotionRow *row = nullptr;
-    if (T.inE && z.x > 0.f) {
-        const uint32_t m = M.ids[i];
-        if (m < M.nRows) { row = M.rows + m; flags = row->flags; }
-    }
-    if (T.inE && z.x > 0.f && !(flags & KZ_MOTION_UNTRACKED)) {
-        const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
-        const float dx = (T.a[0] + fx * T.u[0]) + fy * T.v[0], dy = (T.a[1] + fx * T.u[1]) + fy * T.v[1], dz = (T.a[2] + fx * T.u[2]) + fy * T.v[2];
-        const float len = sqrtf(dnSq(dx, dy, dz));
-        const float r = z.x / len;
-        float Xx = T.o[0] + dx * r, Xy = T.o[1] + dy * r, Xz = T.o[2] + dz * r;
-        float nx = n.x, ny = n.y, nz = n.z;                             // the normal the taps compare: n(p), or n' of a moved mesh
-        if (!(flags & KZ_MOTION_STATIC)) {
-            const float *d = row->d, *w = row->n;
-            const float px = ((d[0] * Xx + d[1] * Xy) + d[2] * Xz) + d[3], py = ((d[4] * Xx + d[5] * Xy) + d[6] * Xz) + d[7], pz = ((d[8] * Xx + d[9] * Xy) + d[10] * Xz) + d[11];
-            Xx = px; Xy = py; Xz = pz;
-            nx = (w[0] * n.x + w[1] * n.y) + w[2] * n.z; ny = (w[3] * n.x + w[4] * n.y) + w[5] * n.z; nz = (w[6] * n.x + w[7] * n.y) + w[8] * n.z;
-        }
-        const float qx = Xx - T.po[0], qy = Xy - T.po[1], qz = Xz - T.po[2];
-        const float P0 = (T.pinv[0] * qx + T.pinv[1] * qy) + T.pinv[2] * qz, P1 = (T.pinv[3] * qx + T.pinv[4] * qy) + T.pinv[5] * qz,
-                    P2 = (T.pinv[6] * qx + T.pinv[7] * qy) + T.pinv[8] * qz;
-        if (P2 > 0.f) {
-            const float sx = P0 / P2 - 0.5f, sy = P1 / P2 - 0.5f;
-            if (sx >= -1.f && sx < (float)width && sy >= -1.f && sy < (float)height) {      // (so x0, y0 are in -1 .. width - 1, -1 .. height - 1: the int conversions are exact)
-                const float fx0 = floorf(sx), fy0 = floorf(sy), tx = sx - fx0, ty = sy - fy0;
-                const int x0 = (int)fx0, y0 = (int)fy0;
-                const float zp = sqrtf(dnSq(qx, qy, qz)), ztol = T.depthTol * dnMax(zp, 1e-20f);
-                float Wb = 0.f, Er = 0.f, Eg = 0.f, Eb = 0.f, V = 0.f, Mn = 0.f;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int ty_ = y0 + j;
-                    const bool rowIn = ty_ >= 0 && ty_ < height;
-                    const size_t rowAt = (size_t)(rowIn ? ty_ : y) * (size_t)width;      // (a tap outside the frame loads the pixel's own row / column and is skipped)
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int tx_ = x0 + k;
-                        const bool colIn = tx_ >= 0 && tx_ < width;
-                        const size_t it = rowAt + (size_t)(colIn ? tx_ : x);             // < width * height
-                        const float nh = T.inN[it];
-                        const float4 gh = T.inG[it], eh = T.inE[it];
-                        const float b = (k ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
-                        if (!(rowIn && colIn) || nh == 0.f || fabsf(gh.w - zp) > ztol || dnSq(gh.x - nx, gh.y - ny, gh.z - nz) > T.normalTol2) continue;
-                        Wb += b; Er += b * eh.x; Eg += b * eh.y; Eb += b * eh.z; V += b * eh.w; Mn += b * nh;
-                    }
-                }
-                if (Wb > 1e-3f) {
-                    const float Nh = Mn / Wb, Nn1 = Nh + 1.0f, Nn = Nn1 < T.maxHistory ? Nn1 : T.maxHistory;
-                    const float al = 1.0f / Nn, om = 1.0f - al;
-                    e.x = om * (Er / Wb) + al * e.x; e.y = om * (Eg / Wb) + al * e.y; e.z = om * (Eb / Wb) + al * e.z;
-                    e.w = (om * om) * (V / Wb) + (al * al) * e.w;
-                    count = Nn;
-                }
-            }
-        }
-    }
-    colour[i] = e;
-    T.outE[i] = e; T.outG[i] = make_float4(n.x, n.y, n.z, z.x); T.outN[i] = count;
+    dnHistory<true, false>(width, height, border, film, moment, albedo, normal, depth, demodulate, samples, T, M, KzDnFast{}, colour, normalZ, albedoP);
 }
 
 // ---- host side ----
@@ -728,6 +564,21 @@ static int dnFilms(const char *call, int device, int32_t width, int32_t height, 
     return result.download((float4 *)out, nTexels);
 }
 
+// What kz_denoise_temporal_films, kz_denoise_motion_films and kz_denoise_responsive_films refuse before anything else, under the call's own name: a null film, a
+// null view and, `motion`, null ids or rows and a row that is not one of the three kinds
+static int dnHistoryFilmsArgs(const char *call, const float *film, const float *moment, const float *depth, const float *out, const KzDnHostTemporal &ht, bool motion) {
+    if (!film || !moment || !depth || !out) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null film (the picture, the moment film and the depth film are needed)", call);
+    if (!ht.current || (ht.historyIn && !ht.previous)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null view (the current one, and with a history the one it was stored with)", call);
+    if (!motion) return KZ_OK;
+    if (!ht.ids || (ht.nRows && !ht.rows)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null ids or rows (the id plane, and %u rows)", call, ht.nRows);
+    for (uint32_t m = 0; m < ht.nRows; ++m) {
+        const KzMotionRow &r = ht.rows[m];
+        if ((r.flags & ~(KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED)) || r.flags == (KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED) || r.reserved[0] || r.reserved[1])
+            return kz_fail(KZ_ERR_INVALID_ARG, "%s: row %u: flags = %u (0, KZ_MOTION_STATIC or KZ_MOTION_UNTRACKED) or a non-zero reserved word", call, m, r.flags);
+    }
+    return KZ_OK;
+}
+
 extern "C" {
 
 int kz_denoise_on(KzScene *scene, int device, const KzDenoiseOpts *opts) {
@@ -780,17 +631,25 @@ int kz_denoise_films(int device, int32_t width, int32_t height, int32_t border, 
     return dnFilms("kz_denoise_films", device, width, height, border, film, nullptr, albedo, normal, depth, opts, nullptr, out, nullptr);
 }
 
+// The replica's side of a variance-guided call, under the call's own name: the second-moment film switched on, the replica, and the sample count the kernels
+// divide by (`samples` 0: the replica's own), which must be the picture's
+static int dnReplicaSamples(const char *call, KzScene *scene, int device, uint32_t samples, KzDeviceState **ds, float *out) {
+    int rc;
+    if (!scene->varianceMode) return kz_fail(KZ_ERR_STATE, "%s: the second-moment film is switched off (kz_scene_variance gives 0): kz_scene_set_variance(scene, 1), then render", call);
+    if ((rc = findReplica(scene, device, ds))) return rc;
+    if (!samples) samples = (*ds)->momentSamples;
+    if (!samples) return kz_fail(KZ_ERR_STATE, "%s: KzVarianceOpts.samples = 0 and the replica's second-moment film has been given 0 samples per pixel (the picture's: %u)", call, (*ds)->pictureSamples);
+    if ((*ds)->pictureSamples != (*ds)->momentSamples)
+        return kz_fail(KZ_ERR_STATE, "%s: the picture's film holds %u samples per pixel, the second-moment film %u (switched on late: kz_film_clear, then render both)", call, (*ds)->pictureSamples, (*ds)->momentSamples);
+    *out = (float)samples;
+    return KZ_OK;
+}
+
 int kz_denoise_variance(KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts) {
     if (!scene) return kz_fail(KZ_ERR_INVALID_ARG, "kz_denoise_variance: null scene");
     KzDnPlan plan; KzDnVar var = {}; KzDeviceState *ds; int rc; uint32_t samples;
-    if ((rc = dnPlan(opts, scene->aovMask, "kz_denoise_variance", &plan, 2.0f)) || (rc = dnVarianceOpts(vopts, "kz_denoise_variance", &var.sv2, &samples))) return rc;
-    if (!scene->varianceMode) return kz_fail(KZ_ERR_STATE, "kz_denoise_variance: the second-moment film is switched off (kz_scene_variance gives 0): kz_scene_set_variance(scene, 1), then render");
-    if ((rc = findReplica(scene, device, &ds))) return rc;
-    if (!samples) samples = ds->momentSamples;
-    if (!samples) return kz_fail(KZ_ERR_STATE, "kz_denoise_variance: KzVarianceOpts.samples = 0 and the replica's second-moment film has been given 0 samples per pixel (the picture's: %u)", ds->pictureSamples);
-    if (ds->pictureSamples != ds->momentSamples)
-        return kz_fail(KZ_ERR_STATE, "kz_denoise_variance: the picture's film holds %u samples per pixel, the second-moment film %u (switched on late: kz_film_clear, then render both)", ds->pictureSamples, ds->momentSamples);
-    var.samples = (float)samples;
+    if ((rc = dnPlan(opts, scene->aovMask, "kz_denoise_variance", &plan, 2.0f)) || (rc = dnVarianceOpts(vopts, "kz_denoise_variance", &var.sv2, &samples)) ||
+        (rc = dnReplicaSamples("kz_denoise_variance", scene, device, samples, &ds, &var.samples))) return rc;
     return dnOnReplica(scene, ds, plan, &var);
 }
 
@@ -820,13 +679,7 @@ static int dnTemporalCall(const char *call, bool motion, KzScene *scene, int dev
     if ((rc = dnPlan(opts, scene->aovMask, call, &plan, 2.0f)) || (rc = dnVarianceOpts(vopts, call, &var.sv2, &samples)) || (rc = dnTemporalOpts(topts, call, &T)) ||
         (rc = dnTemporalGuides(plan, scene->aovMask, call)) || (responsive && (rc = dnResponsiveOpts(ropts, call, &R)))) return rc;
     if (!(scene->aovMask & KZ_AOV_DEPTH)) return kz_fail(KZ_ERR_STATE, "%s: the depth film is not among the scene's AOVs (mask %u, KZ_AOV_DEPTH = %u): kz_scene_set_aovs, then render", call, scene->aovMask, KZ_AOV_DEPTH);
-    if (!scene->varianceMode) return kz_fail(KZ_ERR_STATE, "%s: the second-moment film is switched off (kz_scene_variance gives 0): kz_scene_set_variance(scene, 1), then render", call);
-    if ((rc = findReplica(scene, device, &ds))) return rc;
-    if (!samples) samples = ds->momentSamples;
-    if (!samples) return kz_fail(KZ_ERR_STATE, "%s: KzVarianceOpts.samples = 0 and the replica's second-moment film has been given 0 samples per pixel (the picture's: %u)", call, ds->pictureSamples);
-    if (ds->pictureSamples != ds->momentSamples)
-        return kz_fail(KZ_ERR_STATE, "%s: the picture's film holds %u samples per pixel, the second-moment film %u (switched on late: kz_film_clear, then render both)", call, ds->pictureSamples, ds->momentSamples);
-    var.samples = (float)samples;
+    if ((rc = dnReplicaSamples(call, scene, device, samples, &ds, &var.samples))) return rc;
     return dnOnReplica(scene, ds, plan, &var, &T, motion, responsive ? &R : nullptr);
 }
 int kz_denoise_temporal(KzScene *scene, int device, const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts) {
@@ -865,10 +718,11 @@ int kz_temporal_download(KzScene *scene, int device, float *history, size_t nFlo
 int kz_denoise_temporal_films(int device, int32_t width, int32_t height, int32_t border, const float *film, const float *moment, const float *albedo, const float *normal, const float *depth,
                               const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts, const KzTemporalView *current, const KzTemporalView *previous,
                               const float *historyIn, float *out, float *historyOut, float *outVariance) {
-    if (!film || !moment || !depth || !out) return kz_fail(KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films: null film (the picture, the moment film and the depth film are needed)");
-    if (!current || (historyIn && !previous)) return kz_fail(KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films: null view (the current one, and with a history the one it was stored with)");
+    static const char *const call = "kz_denoise_temporal_films";
     const KzDnHostTemporal ht = {topts, current, previous, historyIn, historyOut};
-    return dnFilms("kz_denoise_temporal_films", device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance, &ht);
+    int rc;
+    if ((rc = dnHistoryFilmsArgs(call, film, moment, depth, out, ht, false))) return rc;
+    return dnFilms(call, device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance, &ht);
 }
 
 // ---- include/kazen_mi355x_motion.h (kz_motion_rows and kz_motion_ids: kz_motion.hip)
@@ -880,13 +734,9 @@ int kz_denoise_motion_films(int device, int32_t width, int32_t height, int32_t b
                             const KzDenoiseOpts *opts, const KzVarianceOpts *vopts, const KzTemporalOpts *topts, const KzTemporalView *current, const KzTemporalView *previous,
                             const float *historyIn, const uint32_t *ids, const KzMotionRow *rows, uint32_t nRows, float *out, float *historyOut, float *outVariance) {
     static const char *const call = "kz_denoise_motion_films";
-    if (!film || !moment || !depth || !out) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null film (the picture, the moment film and the depth film are needed)", call);
-    if (!current || (historyIn && !previous)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null view (the current one, and with a history the one it was stored with)", call);
-    if (!ids || (nRows && !rows)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null ids or rows (the id plane, and %u rows)", call, nRows);
-    for (uint32_t m = 0; m < nRows; ++m)
-        if ((rows[m].flags & ~(KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED)) || rows[m].flags == (KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED) || rows[m].reserved[0] || rows[m].reserved[1])
-            return kz_fail(KZ_ERR_INVALID_ARG, "%s: row %u: flags = %u (0, KZ_MOTION_STATIC or KZ_MOTION_UNTRACKED) or a non-zero reserved word", call, m, rows[m].flags);
     const KzDnHostTemporal ht = {topts, current, previous, historyIn, historyOut, ids, rows, nRows};
+    int rc;
+    if ((rc = dnHistoryFilmsArgs(call, film, moment, depth, out, ht, true))) return rc;
     return dnFilms(call, device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance, &ht);
 }
 
@@ -909,15 +759,9 @@ int kz_denoise_responsive_films(int device, int32_t width, int32_t height, int32
                                 const float *historyIn, const uint32_t *ids, const KzMotionRow *rows, uint32_t nRows, float *out, float *historyOut, float *outVariance,
                                 const KzResponsiveOpts *ropts, const float *fastIn, float *fastOut) {
     static const char *const call = "kz_denoise_responsive_films";
-    if (!film || !moment || !depth || !out) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null film (the picture, the moment film and the depth film are needed)", call);
-    if (!current || (historyIn && !previous)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null view (the current one, and with a history the one it was stored with)", call);
-    if (!ids || (nRows && !rows)) return kz_fail(KZ_ERR_INVALID_ARG, "%s: null ids or rows (the id plane, and %u rows)", call, nRows);
-    for (uint32_t m = 0; m < nRows; ++m)
-        if ((rows[m].flags & ~(KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED)) || rows[m].flags == (KZ_MOTION_STATIC | KZ_MOTION_UNTRACKED) || rows[m].reserved[0] || rows[m].reserved[1])
-            return kz_fail(KZ_ERR_INVALID_ARG, "%s: row %u: flags = %u (0, KZ_MOTION_STATIC or KZ_MOTION_UNTRACKED) or a non-zero reserved word", call, m, rows[m].flags);
     KzDnResponsive R; int rc;
-    if ((rc = dnResponsiveOpts(ropts, call, &R))) return rc;
     const KzDnHostTemporal ht = {topts, current, previous, historyIn, historyOut, ids, rows, nRows, &R, fastIn, fastOut};
+    if ((rc = dnHistoryFilmsArgs(call, film, moment, depth, out, ht, true)) || (rc = dnResponsiveOpts(ropts, call, &R))) return rc;
     return dnFilms(call, device, width, height, border, film, moment, albedo, normal, depth, opts, vopts, out, outVariance, &ht);
 }
 

@@ -1,5 +1,6 @@
 // kz_responsive.h - what kz_denoise.hip (the host path of every denoise call) and kz_responsive.hip (the two kernels of include/kazen_mi355x_responsive.h, which
-// holds the definition) share. Nothing here is an argument of a kernel of kz_denoise.hip: those keep their instructions and their by-value structs.
+// holds the definition) share on the host. Nothing here is an argument of a kernel: what kz_dn_prepare_responsive takes by value (KzDnTemporal, KzDnMotion, KzDnFast)
+// is kz_denoise.h's and kz_history.h's, beside the one body of the stage that the three history kernels instantiate.
 #pragma once
 #include "../../include/kazen_mi355x_responsive.h"
 #include "kz_denoise.h"

@@ -10,6 +10,7 @@
 //                   replica's denoise buffers, kz_denoise* and kz_denoise_variance* entry points
 //   kz_motion.hip   include/kazen_mi355x_motion.h beyond the denoiser's unit: the id kernel (which mesh every frame pixel shows) and the host-only row table
 //   kz_responsive.hip  the two kernels of include/kazen_mi355x_responsive.h (the fast history and the clamp) and their launcher; the entry points: kz_denoise.hip
+//   (kz_history.h   the history prepare stage of the temporal, motion and responsive calls, one body: its three kernels are instances in the two units above)
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
 //   kz_debug.hip    function-level query kernels and known-answer entry points of include/kazen_mi355x_dev.h
 // Every device buffer, pinned buffer, event and stream named below is a member of one of the four move-only owners of kz_own.h (DevBuf, PinnedBuf, Event, Stream).

@@ -489,13 +489,16 @@ class Scene:
         abi.check(self.lib, self.lib.kz_denoise_variance(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v)))
 
     # ---- the denoiser's history across camera edits (include/kazen_mi355x_temporal.h)
+    def _denoise_history(self, entry, device, opts, vargs, targs, rargs=None):
+        """denoise_temporal, denoise_motion and (rargs: responsive_opts' arguments) denoise_responsive: the option structs and the call of `entry`."""
+        structs = [denoise_opts(**opts), variance_opts(*vargs), temporal_opts(*targs)] + ([] if rargs is None else [responsive_opts(*rargs)])
+        abi.check(self.lib, getattr(self.lib, entry)(self.h, -1 if device is None else int(device), *[C.byref(x) for x in structs]))
+
     def denoise_temporal(self, device=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0, depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0,
                          treserved=(0, 0, 0, 0), **opts):
         """kz_denoise_temporal: denoise_variance() with the replica's history reprojected from the previous call's camera and blended in first; the result is read
         like denoise()'s. Options: denoise_opts', variance_opts' and temporal_opts'."""
-        o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
-        t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
-        abi.check(self.lib, self.lib.kz_denoise_temporal(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v), C.byref(t)))
+        self._denoise_history("kz_denoise_temporal", device, opts, (sigma_variance, samples, vflags, vreserved), (depth_tolerance, normal_tolerance, max_history, tflags, treserved))
 
     def temporal_info(self, device=-1):
         """kz_temporal_info: (bytes the history holds on that replica, calls folded into it since it last started)."""
@@ -523,9 +526,7 @@ class Scene:
                        treserved=(0, 0, 0, 0), **opts):
         """kz_denoise_motion: denoise_temporal() whose history survives set_transforms - every pixel looks its history up where its mesh was. Options and results as
         denoise_temporal's; temporal_info / temporal_reset / temporal_history serve both."""
-        o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
-        t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
-        abi.check(self.lib, self.lib.kz_denoise_motion(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v), C.byref(t)))
+        self._denoise_history("kz_denoise_motion", device, opts, (sigma_variance, samples, vflags, vreserved), (depth_tolerance, normal_tolerance, max_history, tflags, treserved))
 
     def motion_info(self, device=-1):
         """kz_motion_info: (bytes the id plane and the row table hold on that replica, (static, moved, untracked) meshes of its last denoise_motion)."""
@@ -538,10 +539,8 @@ class Scene:
                            treserved=(0, 0, 0, 0), fast_history=0, clamp_sigma=0.0, radius=0, clamp=True, rflags=None, rreserved=(0, 0, 0, 0), **opts):
         """kz_denoise_responsive: denoise_motion() with a fast history beside the long one; where the long history's colour leaves the fast one's local mean +- clamp_sigma
         deviations it is clamped and the pixel re-converges in fast_history calls. Options: denoise_motion's and responsive_opts'; results as denoise_temporal's."""
-        o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
-        t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
-        r = responsive_opts(fast_history, clamp_sigma, radius, clamp, rflags, rreserved)
-        abi.check(self.lib, self.lib.kz_denoise_responsive(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v), C.byref(t), C.byref(r)))
+        self._denoise_history("kz_denoise_responsive", device, opts, (sigma_variance, samples, vflags, vreserved), (depth_tolerance, normal_tolerance, max_history, tflags, treserved),
+                              (fast_history, clamp_sigma, radius, clamp, rflags, rreserved))
 
     def responsive_fast(self, device=None):
         """kz_responsive_download: (h, w, 4) = per pixel (f.rgb, vf), the fast history that goes with temporal_history() - what denoise_responsive_films takes as `fast`."""
@@ -691,12 +690,10 @@ def temporal_view(camera, lib=None):
     return view
 
 
-def denoise_temporal_films(film, moment, albedo=None, normal=None, depth=None, border=0, device=0, lib=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0,
-                           depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0, treserved=(0, 0, 0, 0), current=None, previous=None, history=None,
-                           return_variance=False, **opts):
-    """kz_denoise_temporal_films: the device's temporal stage and variance-guided denoiser on host films (denoise_variance_films' layout; `depth` and `samples` must be
-    given). current / previous: KzTemporalView of this frame and of `history` ((h, w, 12) as Scene.temporal_history gives it; None: no history).
-    Returns (film, history (h, w, 12)), or (film, history, v_last (h, w)) with return_variance."""
+def _history_films(entry, film, moment, albedo, normal, depth, border, device, lib, vargs, targs, current, previous, history, return_variance, opts, motion=None,
+                   responsive=None):
+    """What denoise_temporal_films, denoise_motion_films (motion = (ids, rows, n_rows)) and denoise_responsive_films (responsive = (fast, responsive_opts' arguments)
+    as well) share: the shape checks, the output buffers, the option structs and the call of `entry`. Returns (film, history[, fast][, v_last])."""
     lib = lib or abi.load_library()
     film, g, frame = _host_films(film, (moment, albedo, normal, depth), border, "the moment film and the guide films have the picture's shape")
     h, w = max(frame[1], 0), max(frame[0], 0)
@@ -704,16 +701,45 @@ def denoise_temporal_films(film, moment, albedo=None, normal=None, depth=None, b
         history = np.ascontiguousarray(history, np.float32)
         if history.shape != (h, w, 12):
             raise ValueError("a history is (h, w, 12)")
+    fast = responsive[0] if responsive else None
+    if fast is not None:
+        fast = np.ascontiguousarray(fast, np.float32)
+        if fast.shape != (h, w, 4):
+            raise ValueError("a fast plane is (h, w, 4)")
+    if motion:
+        ids, rows, n_rows = motion
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.uint32)
+            if ids.shape != (h, w):
+                raise ValueError("ids are (h, w)")
+        if n_rows is None:
+            n_rows = 0 if rows is None else getattr(rows, "n_rows", len(rows))
     out = np.empty_like(film)
     hist = np.full((h, w, 12), np.nan, np.float32)
+    fout = np.full((h, w, 4), np.nan, np.float32) if responsive else None
     var = np.full((h, w), np.nan, np.float32) if return_variance else None
-    o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
-    t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
+    o, v, t = denoise_opts(**opts), variance_opts(*vargs), temporal_opts(*targs)
     p = lambda a: None if a is None else a.ctypes.data_as(abi.f32p)
-    abi.check(lib, lib.kz_denoise_temporal_films(int(device), *frame, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t),
-                                                 None if current is None else C.byref(current), None if previous is None else C.byref(previous), p(history),
-                                                 p(out), p(hist), p(var)))
-    return (out, hist, var) if return_variance else (out, hist)
+    args = [int(device), *frame, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t), None if current is None else C.byref(current),
+            None if previous is None else C.byref(previous), p(history)]
+    if motion:
+        args += [None if ids is None else ids.ctypes.data_as(abi.u32p), rows, int(n_rows)]
+    args += [p(out), p(hist), p(var)]
+    if responsive:
+        r = responsive_opts(*responsive[1])
+        args += [C.byref(r), p(fast), p(fout)]
+    abi.check(lib, getattr(lib, entry)(*args))
+    return tuple(a for a in (out, hist, fout, var) if a is not None)
+
+
+def denoise_temporal_films(film, moment, albedo=None, normal=None, depth=None, border=0, device=0, lib=None, sigma_variance=0.0, samples=0, vflags=0, vreserved=0,
+                           depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, tflags=0, treserved=(0, 0, 0, 0), current=None, previous=None, history=None,
+                           return_variance=False, **opts):
+    """kz_denoise_temporal_films: the device's temporal stage and variance-guided denoiser on host films (denoise_variance_films' layout; `depth` and `samples` must be
+    given). current / previous: KzTemporalView of this frame and of `history` ((h, w, 12) as Scene.temporal_history gives it; None: no history).
+    Returns (film, history (h, w, 12)), or (film, history, v_last (h, w)) with return_variance."""
+    return _history_films("kz_denoise_temporal_films", film, moment, albedo, normal, depth, border, device, lib, (sigma_variance, samples, vflags, vreserved),
+                          (depth_tolerance, normal_tolerance, max_history, tflags, treserved), current, previous, history, return_variance, opts)
 
 
 def motion_rows(cur, prev, lib=None):
@@ -735,29 +761,8 @@ def denoise_motion_films(film, moment, albedo=None, normal=None, depth=None, bor
                          ids=None, rows=None, n_rows=None, return_variance=False, **opts):
     """kz_denoise_motion_films: denoise_temporal_films with the motion stage - ids (h, w) uint32 (abi.KZ_MOTION_MISS: a miss) and rows, a KzMotionRow array as
     motion_rows gives it (n_rows: its length, when it is not motion_rows'). Returns what denoise_temporal_films returns."""
-    lib = lib or abi.load_library()
-    film, g, frame = _host_films(film, (moment, albedo, normal, depth), border, "the moment film and the guide films have the picture's shape")
-    h, w = max(frame[1], 0), max(frame[0], 0)
-    if history is not None:
-        history = np.ascontiguousarray(history, np.float32)
-        if history.shape != (h, w, 12):
-            raise ValueError("a history is (h, w, 12)")
-    if ids is not None:
-        ids = np.ascontiguousarray(ids, np.uint32)
-        if ids.shape != (h, w):
-            raise ValueError("ids are (h, w)")
-    if n_rows is None:
-        n_rows = 0 if rows is None else getattr(rows, "n_rows", len(rows))
-    out = np.empty_like(film)
-    hist = np.full((h, w, 12), np.nan, np.float32)
-    var = np.full((h, w), np.nan, np.float32) if return_variance else None
-    o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
-    t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
-    p = lambda a: None if a is None else a.ctypes.data_as(abi.f32p)
-    abi.check(lib, lib.kz_denoise_motion_films(int(device), *frame, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t),
-                                               None if current is None else C.byref(current), None if previous is None else C.byref(previous), p(history),
-                                               None if ids is None else ids.ctypes.data_as(abi.u32p), rows, int(n_rows), p(out), p(hist), p(var)))
-    return (out, hist, var) if return_variance else (out, hist)
+    return _history_films("kz_denoise_motion_films", film, moment, albedo, normal, depth, border, device, lib, (sigma_variance, samples, vflags, vreserved),
+                          (depth_tolerance, normal_tolerance, max_history, tflags, treserved), current, previous, history, return_variance, opts, motion=(ids, rows, n_rows))
 
 
 def responsive_opts(fast_history=0, clamp_sigma=0.0, radius=0, clamp=True, flags=None, reserved=(0, 0, 0, 0)):
@@ -774,35 +779,9 @@ def denoise_responsive_films(film, moment, albedo=None, normal=None, depth=None,
                              return_variance=False, **opts):
     """kz_denoise_responsive_films: denoise_motion_films with the fast history - `fast` (h, w, 4) as Scene.responsive_fast gives it (None: absent) and responsive_opts'
     options. Returns (film, history (h, w, 12), fast (h, w, 4)), or (film, history, fast, v_last (h, w)) with return_variance."""
-    lib = lib or abi.load_library()
-    film, g, frame = _host_films(film, (moment, albedo, normal, depth), border, "the moment film and the guide films have the picture's shape")
-    h, w = max(frame[1], 0), max(frame[0], 0)
-    if history is not None:
-        history = np.ascontiguousarray(history, np.float32)
-        if history.shape != (h, w, 12):
-            raise ValueError("a history is (h, w, 12)")
-    if fast is not None:
-        fast = np.ascontiguousarray(fast, np.float32)
-        if fast.shape != (h, w, 4):
-            raise ValueError("a fast plane is (h, w, 4)")
-    if ids is not None:
-        ids = np.ascontiguousarray(ids, np.uint32)
-        if ids.shape != (h, w):
-            raise ValueError("ids are (h, w)")
-    if n_rows is None:
-        n_rows = 0 if rows is None else getattr(rows, "n_rows", len(rows))
-    out = np.empty_like(film)
-    hist = np.full((h, w, 12), np.nan, np.float32)
-    fout = np.full((h, w, 4), np.nan, np.float32)
-    var = np.full((h, w), np.nan, np.float32) if return_variance else None
-    o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
-    t = temporal_opts(depth_tolerance, normal_tolerance, max_history, tflags, treserved)
-    r = responsive_opts(fast_history, clamp_sigma, radius, clamp, rflags, rreserved)
-    p = lambda a: None if a is None else a.ctypes.data_as(abi.f32p)
-    abi.check(lib, lib.kz_denoise_responsive_films(int(device), *frame, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t),
-                                                   None if current is None else C.byref(current), None if previous is None else C.byref(previous), p(history),
-                                                   None if ids is None else ids.ctypes.data_as(abi.u32p), rows, int(n_rows), p(out), p(hist), p(var), C.byref(r), p(fast), p(fout)))
-    return (out, hist, fout, var) if return_variance else (out, hist, fout)
+    return _history_films("kz_denoise_responsive_films", film, moment, albedo, normal, depth, border, device, lib, (sigma_variance, samples, vflags, vreserved),
+                          (depth_tolerance, normal_tolerance, max_history, tflags, treserved), current, previous, history, return_variance, opts, motion=(ids, rows, n_rows),
+                          responsive=(fast, (fast_history, clamp_sigma, radius, clamp, rflags, rreserved)))
 
 
 def hits_to_arrays(hits, n):

@@ -305,3 +305,32 @@ def test_planner_entry_points_check_their_arguments(kz):
     n = C.c_uint32()
     av = (C.c_uint64 * 1)(0)                                                                    # a context that holds nothing: an error, not a loop
     assert lib.kz_plan_schedule(C.byref(q), av, 1, 0, 1000, None, 0, C.byref(n)) != 0
+
+
+def test_history_wrappers_keep_their_signatures(kz):
+    """The three Scene.denoise_* history methods and the three *_films wrappers go through one helper each (render.py: _denoise_history, _history_films): their
+    parameter names, order and defaults are pinned here as they were before the helpers, name by name."""
+    import inspect
+    VAR = [("sigma_variance", 0.0), ("samples", 0), ("vflags", 0), ("vreserved", 0)]
+    TEMPORAL = [("depth_tolerance", 0.0), ("normal_tolerance", 0.0), ("max_history", 0), ("tflags", 0), ("treserved", (0, 0, 0, 0))]
+    RESPONSIVE = [("fast_history", 0), ("clamp_sigma", 0.0), ("radius", 0), ("clamp", True), ("rflags", None), ("rreserved", (0, 0, 0, 0))]
+    FILMS = [("film", inspect.Parameter.empty), ("moment", inspect.Parameter.empty), ("albedo", None), ("normal", None), ("depth", None), ("border", 0), ("device", 0), ("lib", None)]
+    VIEWS = [("current", None), ("previous", None), ("history", None)]
+    MOTION = [("ids", None), ("rows", None), ("n_rows", None)]
+    method = [("self", inspect.Parameter.empty), ("device", None)] + VAR + TEMPORAL
+    films = FILMS + VAR + TEMPORAL + VIEWS
+    table = {
+        kz.Scene.denoise_temporal: method,
+        kz.Scene.denoise_motion: method,
+        kz.Scene.denoise_responsive: method + RESPONSIVE,
+        kz.render.denoise_temporal_films: films + [("return_variance", False)],
+        kz.render.denoise_motion_films: films + MOTION + [("return_variance", False)],
+        kz.render.denoise_responsive_films: films + MOTION + [("fast", None)] + RESPONSIVE + [("return_variance", False)],
+    }
+    for fn, want in table.items():
+        params = list(inspect.signature(fn).parameters.values())
+        assert params[-1].name == "opts" and params[-1].kind is inspect.Parameter.VAR_KEYWORD, fn.__name__
+        assert all(p.kind is inspect.Parameter.POSITIONAL_OR_KEYWORD for p in params[:-1]), fn.__name__
+        assert [(p.name, p.default) for p in params[:-1]] == want, fn.__name__
+        for (_, d), p in zip(want, params):
+            assert type(p.default) is type(d), (fn.__name__, p.name)

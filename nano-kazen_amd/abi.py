@@ -240,6 +240,14 @@ class KzResponsiveOpts(C.Structure):
     _fields_ = [("fastHistory", C.c_uint32), ("clampSigma", C.c_float), ("radius", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
+class KzMatteTexel(C.Structure):
+    _fields_ = [("id", C.c_uint32 * 7), ("count", C.c_uint32 * 7), ("other", C.c_uint32), ("miss", C.c_uint32)]
+
+
+# the same 64 bytes as a numpy record: what Scene.matte() and matte_accumulate_items() hand back
+MATTE_DTYPE = [("id", "<u4", (7,)), ("count", "<u4", (7,)), ("other", "<u4"), ("miss", "<u4")]
+
+
 class KzBvhInfo(C.Structure):
     _fields_ = [("nNodes", C.c_uint32), ("nLeaves", C.c_uint32), ("nTris", C.c_uint32), ("maxDepth", C.c_uint32),
                 ("maxLeafSize", C.c_uint32), ("sahCost", C.c_float), ("buildSeconds", C.c_double)]
@@ -277,6 +285,11 @@ KZ_MOTION_STATIC, KZ_MOTION_UNTRACKED, KZ_MOTION_MISS = 1, 2, 0xFFFFFFFF
 # what include/kazen_mi355x_responsive.h declares (checked by tests/test_responsive_cpu.py): a fast history beside the long one, which is clamped to it where the light moved
 RESPONSIVE_EXPORTS = ["kz_denoise_responsive", "kz_denoise_responsive_films", "kz_responsive_download", "kz_responsive_info"]
 KZ_RESPONSIVE_CLAMP_OFF = 1
+# what include_ext/kazen_mi355x_matte.h declares (checked by tests/test_matte_cpu.py): ID mattes - per pixel (mesh or BSDF-row id, sample count) slots beside the picture
+MATTE_EXPORTS = ["kz_scene_set_mattes", "kz_scene_mattes", "kz_matte_download", "kz_matte_download_on", "kz_matte_layer", "kz_matte_top", "kz_matte_info",
+                 "kz_matte_accumulate_items"]
+KZ_MATTE_MESH, KZ_MATTE_BSDF, KZ_MATTE_ALL, KZ_MATTE_SLOTS, KZ_MATTE_NONE = 1, 2, 3, 7, 0xFFFFFFFF
+MATTE_BITS = {"mesh": KZ_MATTE_MESH, "bsdf": KZ_MATTE_BSDF}
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead", "kz_debug_shadow_order", "kz_debug_compact_late"]
@@ -419,6 +432,15 @@ def load_library(path=None):
                                                     f32p, f32p, f32p, C.POINTER(KzResponsiveOpts), f32p, f32p]
         lib.kz_responsive_download.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
         lib.kz_responsive_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "kz_scene_set_mattes"):       # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_scene_set_mattes.argtypes = [C.c_void_p, C.c_uint32]
+        lib.kz_scene_mattes.argtypes = [C.c_void_p, u32p]
+        lib.kz_matte_download.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(KzMatteTexel), C.c_size_t]
+        lib.kz_matte_download_on.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(KzMatteTexel), C.c_size_t]
+        lib.kz_matte_layer.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, f32p, C.c_size_t]
+        lib.kz_matte_top.argtypes = [C.c_void_p, C.c_int, C.c_uint32, u32p, C.c_size_t]
+        lib.kz_matte_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+        lib.kz_matte_accumulate_items.argtypes = [C.c_void_p, C.c_int, u32p, C.c_uint32, C.c_uint32, u32p, C.POINTER(KzMatteTexel), C.c_uint32]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

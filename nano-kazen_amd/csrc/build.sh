@@ -13,7 +13,7 @@ FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function"
 DEV="--offload-arch=gfx950 -fgpu-flush-denormals-to-zero -fno-slp-vectorize ${KZ_EXTRA_HIPFLAGS}"
 # the translation units compile side by side (kz_state.h says what lives where); every job's exit status is checked and no object of an earlier
 # build can stand in for one that failed to compile now
-DEVICE_UNITS="kz_render kz_replica kz_film kz_film_moment kz_debug kz_motion"
+DEVICE_UNITS="kz_render kz_replica kz_film kz_film_moment kz_debug kz_motion kz_matte"
 # kz_refit.hip (the refit of an edited scene) keeps subnormals: its tables must equal the host's to the bit (kz_refit.h); so does kz_denoise.hip (the
 # a-trous denoiser, plain and variance-guided): its results must equal plain C++ restatements' to the bit, subnormal tap weights included (kz_denoise.h); and so
 # does kz_responsive.hip (the fast history and the clamp of kazen_mi355x_responsive.h), for the same reason

@@ -200,7 +200,7 @@ int kzFilmEnsure(KzScene *scene, KzFilm &film, size_t filmPixels, bool accumulat
 int kzFilmClear(KzDeviceState *ds, hipStream_t stream) {
     for (KzFilm &film : ds->films) if (const int rc = film.clear(stream)) return rc;      // the picture, then the feature films, then the second-moment film
     ds->pictureSamples = ds->momentSamples = 0;
-    return KZ_OK;
+    return kzMatteClear(ds, stream);                                     // (the ID-matte tables, kazen_mi355x_matte.h: nothing where there are none)
 }
 
 // The film stage of one pass (kz_render.hip: launchWhole / launchHalves for the picture, wfAov once per enabled feature film): ImageBlock::put for every sample record
@@ -305,7 +305,8 @@ int kz_tiles_packed_floats(const KzScene *scene, const KzTile *tiles, uint32_t n
 
 int kz_film_download_tiles(KzScene *scene, int device, const KzTile *tiles, uint32_t nTiles, float *packed, size_t nFloats) {
     KzDeviceState *ds; int rc;
-    if ((rc = kzAovRefuseGather(scene, "kz_film_download_tiles")) || (rc = kzVarianceRefuseGather(scene, "kz_film_download_tiles")) || (rc = findReplica(scene, device, &ds))) return rc;
+    if ((rc = kzAovRefuseGather(scene, "kz_film_download_tiles")) || (rc = kzVarianceRefuseGather(scene, "kz_film_download_tiles")) ||
+        (rc = kzMatteRefuseGather(scene, "kz_film_download_tiles")) || (rc = findReplica(scene, device, &ds))) return rc;
     HIP_TRY(hipStreamSynchronize(ds->lastStream));
     return downloadTiles(scene, ds, ds->picture(), tiles, nTiles, packed, nFloats, ds->lastStream);
 }

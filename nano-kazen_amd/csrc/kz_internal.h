@@ -203,6 +203,7 @@ struct KzScene {
     std::vector<uint8_t> pendXOn;
     bool hostStale = false;             // tris, nodes, nodes4 and bvh.sahCost do not follow the last edit yet (kzHostSync brings them up to date)
     uint32_t aovMask = 0;               // KZ_AOV_* feature films every render of the scene produces beside the picture (kazen_mi355x_aov.h; kz_scene_set_aovs)
+    uint32_t matteMask = 0;             // KZ_MATTE_* ID-matte tables every render of the scene feeds beside the picture (kazen_mi355x_matte.h; kz_scene_set_mattes)
     int32_t varianceMode = 0;           // KZ_VARIANCE_*: every render keeps a second-moment film beside the picture's (kazen_mi355x_variance.h; kz_scene_set_variance)
     uint64_t geometryEdits = 0;         // kz_scene_set_vertices / kz_scene_set_transforms calls that changed something: a replica's temporal history (kazen_mi355x_temporal.h) older than the last one is stale
     // motion vectors (kazen_mi355x_motion.h): per mesh its object-to-world matrix as it stands, 16 floats each - the identity until the mesh's first
@@ -235,6 +236,9 @@ int kzAovRefuseGather(const KzScene *scene, const char *call);
 // ... and the same refusals while the second-moment film is switched on (kazen_mi355x_variance.h). KZ_OK with the switch off.
 int kzVarianceRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call);
 int kzVarianceRefuseGather(const KzScene *scene, const char *call);
+// ... and while ID mattes are enabled (kazen_mi355x_matte.h). KZ_OK with the mask 0.
+int kzMatteRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call);
+int kzMatteRefuseGather(const KzScene *scene, const char *call);
 // kz_host.cpp
 int kz_fail(int code, const char *fmt, ...);
 int kzCameraParams(const KzCamera &c, KzParams &p);                     // the camera part of KzParams (pixel beams included)

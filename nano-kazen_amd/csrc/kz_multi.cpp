@@ -47,6 +47,19 @@ int kzVarianceRefuseGather(const KzScene *scene, const char *call) {
     if (!scene || !scene->varianceMode) return KZ_OK;
     return kz_fail(KZ_ERR_UNSUPPORTED, "%s: refused while the second-moment film is on: " KZ_NO_MOMENT_GATHER " - kz_scene_set_variance(scene, 0) first", call);
 }
+// ID mattes (kazen_mi355x_matte.h) are fed by the wavefront pass of one replica and read whole: the same refusals while a key is enabled.
+#define KZ_NO_MATTE_GATHER "the tile-rect gather of mattes is not built"
+int kzMatteRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *call) {
+    if (!scene || !scene->matteMask || !opts) return KZ_OK;
+    const char *what = opts->pipeline == 1 ? "KzRenderOpts.pipeline = 1 (the megakernel pipeline feeds no mattes)" : opts->dealer ? "a KzTileDealer (" KZ_NO_MATTE_GATHER ")"
+                     : opts->packedOutput ? "KzRenderOpts.packedOutput = 1 (" KZ_NO_MATTE_GATHER ")" : nullptr;
+    if (!what) return KZ_OK;
+    return kz_fail(KZ_ERR_UNSUPPORTED, "%s: %s is refused while mattes are enabled (mask %u) - kz_scene_set_mattes(scene, 0) first", call, what, scene->matteMask);
+}
+int kzMatteRefuseGather(const KzScene *scene, const char *call) {
+    if (!scene || !scene->matteMask) return KZ_OK;
+    return kz_fail(KZ_ERR_UNSUPPORTED, "%s: refused while mattes are enabled (mask %u): " KZ_NO_MATTE_GATHER " - kz_scene_set_mattes(scene, 0) first", call, scene->matteMask);
+}
 
 extern "C" {
 
@@ -142,6 +155,7 @@ int kz_render_multi(KzScene *scene, const KzRenderOpts *opts, const int32_t *dev
     if (!scene || !devices || nDevices == 0 || !film) return kz_fail(KZ_ERR_INVALID_ARG, "kz_render_multi: null argument");
     if (const int rc = kzAovRefuseGather(scene, "kz_render_multi")) return rc;
     if (const int rc = kzVarianceRefuseGather(scene, "kz_render_multi")) return rc;
+    if (const int rc = kzMatteRefuseGather(scene, "kz_render_multi")) return rc;
     const KzParams &P = scene->prm;
     const size_t filmFloats = (size_t)(P.width + 2 * P.border) * (size_t)(P.height + 2 * P.border) * 4;
     if (nFloats != filmFloats) return kz_fail(KZ_ERR_INVALID_ARG, "film buffer must hold %zu floats", filmFloats);

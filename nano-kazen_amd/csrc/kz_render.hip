@@ -365,6 +365,13 @@ static int wfAov(KzScene *scene, WfLaunch &L, hipEvent_t waitAov, hipEvent_t rec
     if (recordAov) HIP_TRY(hipEventRecord(recordAov, stream));
     return L.mark(4);                                   // (the stage clock books the AOV launches under "film")
 }
+// The ID mattes' stage of a pass (kazen_mi355x_matte.h; kz_matte.hip), in the same place and for the same reason: the first-hit records are at their own slots of
+// W.hit. It adds no per-item state and reads nothing the AOV stage writes. ORDER: a pixel's record is read-modify-write and its samples are counted in ascending
+// order, so with passes in flight the stage has an event chain of its own (evMatte), exactly as evAov - not evAov's events: that stage may be off.
+static int wfMatte(KzScene *scene, WfLaunch &L, hipEvent_t waitMatte, hipEvent_t recordMatte) {
+    if (const int rc = kzMatteStage(scene, L.ds, L.stream, L.W.hit.p, L.pixList, L.items / L.Sp, L.Sp, waitMatte, recordMatte)) return rc;
+    return L.mark(4);                                   // (booked under "film" too)
+}
 
 //   path_mats  { kz_wf_mats(iter) -> kz_wf_trace<0> } until the path queue is empty or 512 bounces are done; the host reads the survivor count back
 //              after every 4th bounce (one stream synchronisation per 4 bounces), so a pass launches 2 + 2 x (bounces rounded up to 4) kernels after the camera's.
@@ -460,7 +467,7 @@ static int wfMis(WfLaunch &L, bool beside) {
 // The three others see a copy of the parameters that names no invisible light: none of them walks through a light (H6 is path_mis's alone), so a first hit
 // on such a light is kept and an occlusion ray is blocked by it.
 static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t stream, const uint32_t *pixList, uint32_t sBegin, uint32_t Sp, uint32_t items, KzTune tune, bool beams, bool beside,
-                  hipEvent_t waitAov = nullptr, hipEvent_t recordAov = nullptr) {
+                  hipEvent_t waitAov = nullptr, hipEvent_t recordAov = nullptr, hipEvent_t waitMatte = nullptr, hipEvent_t recordMatte = nullptr) {
     int rc;
     WfLaunch L{ds, c, stream};
     const bool mis = scene->prm.integrator == KZ_INTEGRATOR_PATH_MIS;
@@ -503,10 +510,11 @@ static int wfPass(KzScene *scene, KzDeviceState *ds, PassCtx &c, hipStream_t str
     if ((rc = L.mark(-1))) return rc;
     hipLaunchKernelGGL(kz_wf_generate, L.gItems, L.blk, 0, stream, P, ds->T, W, pixList, items, Sp, sBegin);
     if ((rc = L.mark(0))) return rc;
-    if (mis && P.maxDepth <= 0 && !scene->aovMask) return KZ_OK;           // Li returns 0 before the loop contributes anything
+    if (mis && P.maxDepth <= 0 && !scene->aovMask && !scene->matteMask) return KZ_OK;           // Li returns 0 before the loop contributes anything
     if ((rc = wfCamera(L, beams))) return rc;
     if (scene->aovMask && (rc = wfAov(scene, L, waitAov, recordAov))) return rc;
-    if (mis && P.maxDepth <= 0) return KZ_OK;           // (the camera stage ran for the feature films alone)
+    if (scene->matteMask && (rc = wfMatte(scene, L, waitMatte, recordMatte))) return rc;
+    if (mis && P.maxDepth <= 0) return KZ_OK;           // (the camera stage ran for the feature films and the mattes alone)
     if (P.integrator == KZ_INTEGRATOR_NORMALS) {
         //   normals    kz_wf_normals                                                    (no bounce state)
         hipLaunchKernelGGL(kz_wf_normals, L.gShade, L.blk, 0, stream, P, ds->T, W, items);
@@ -676,7 +684,13 @@ static int launchWhole(PassRun &r, PassCtx &c, int ci, hipStream_t pst, EventPai
             recordAov = ds->evAov[ci];
             if (r.pass > 0) waitAov = ds->evAov[(ci + r.pl.nCtx - 1) % r.pl.nCtx];
         }
-        if ((rc = wfPass(scene, ds, c, pst, pixList, s, Sp, items, r.tune, r.beams, beside, waitAov, recordAov))) return rc;
+        hipEvent_t waitMatte = nullptr, recordMatte = nullptr;      // (ID mattes: the same chain, with events of its own)
+        if (scene->matteMask && r.pl.multi) {
+            if ((rc = ds->evMatte[ci].ensure(hipEventDisableTiming))) return rc;
+            recordMatte = ds->evMatte[ci];
+            if (r.pass > 0) waitMatte = ds->evMatte[(ci + r.pl.nCtx - 1) % r.pl.nCtx];
+        }
+        if ((rc = wfPass(scene, ds, c, pst, pixList, s, Sp, items, r.tune, r.beams, beside, waitAov, recordAov, waitMatte, recordMatte))) return rc;
     }
     else {
         const dim3 grid((items + KZ_BLOCK - 1) / KZ_BLOCK), blk(KZ_BLOCK);
@@ -765,6 +779,8 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     // outside the pass contexts' budget, cleared unless the call accumulates
     if ((rc = kzFilmEnsure(scene, ds->picture(), ds->filmPixels, opts->accumulate != 0, stream))) return rc;
     for (int f = 0; f < 3; ++f) if ((scene->aovMask & (1u << f)) && (rc = kzFilmEnsure(scene, ds->aov(f), ds->filmPixels, opts->accumulate != 0, stream))) return rc;
+    // the ID-matte tables (kazen_mi355x_matte.h): outside the budget too, cleared unless the call accumulates
+    if (scene->matteMask && (rc = kzMatteEnsure(scene, ds, opts->accumulate != 0, s1 - s0, stream))) return rc;
     // ... and the second-moment film's (kazen_mi355x_variance.h). What each of the two films has been given since it was last zeroed is counted per pixel.
     if (!opts->accumulate) ds->pictureSamples = 0;
     if (scene->varianceMode) {
@@ -843,7 +859,7 @@ extern "C" {
 int kz_render(KzScene *scene, const KzRenderOpts *opts) {
     if (!opts) return kz_fail(KZ_ERR_INVALID_ARG, "null opts");
     KzDeviceState *ds; int rc;
-    if ((rc = kzAovRefuse(scene, opts, "kz_render")) || (rc = kzVarianceRefuse(scene, opts, "kz_render"))) return rc;
+    if ((rc = kzAovRefuse(scene, opts, "kz_render")) || (rc = kzVarianceRefuse(scene, opts, "kz_render")) || (rc = kzMatteRefuse(scene, opts, "kz_render"))) return rc;
     // opts->device addresses a replica by HIP device index; a scene resident on ONE device is addressed by any zero-initialised opts
     if ((rc = findReplica(scene, opts->device, &ds))) {
         KzReplicaSet *rs = scene ? replicaSet(scene) : nullptr;
@@ -856,7 +872,7 @@ int kz_render(KzScene *scene, const KzRenderOpts *opts) {
 
 int kz_render_tiles(KzScene *scene, const KzRenderOpts *opts, const KzTile *tiles, uint32_t nTiles, int device, float *film, size_t nFloats) {
     KzDeviceState *ds; int rc;
-    if ((rc = kzAovRefuse(scene, opts, "kz_render_tiles")) || (rc = kzVarianceRefuse(scene, opts, "kz_render_tiles"))) return rc;
+    if ((rc = kzAovRefuse(scene, opts, "kz_render_tiles")) || (rc = kzVarianceRefuse(scene, opts, "kz_render_tiles")) || (rc = kzMatteRefuse(scene, opts, "kz_render_tiles"))) return rc;
     if ((rc = findReplica(scene, device, &ds))) return rc;
     const size_t full = ds->filmPixels * 4;
     const bool packedOut = opts && opts->packedOutput;

@@ -9,6 +9,7 @@
 //   kz_denoise.hip  the a-trous denoiser of include/kazen_mi355x_denoise.h and its variance-guided form (include/kazen_mi355x_variance.h): their kernels, the
 //                   replica's denoise buffers, kz_denoise* and kz_denoise_variance* entry points
 //   kz_motion.hip   include/kazen_mi355x_motion.h beyond the denoiser's unit: the id kernel (which mesh every frame pixel shows) and the host-only row table
+//   kz_matte.hip    include_ext/kazen_mi355x_matte.h: the ID-matte tables, the stage of a pass that feeds them (kernels: kz_matte.h), their readers and entry points
 //   kz_responsive.hip  the two kernels of include/kazen_mi355x_responsive.h (the fast history and the clamp) and their launcher; the entry points: kz_denoise.hip
 //   (kz_history.h   the history prepare stage of the temporal, motion and responsive calls, one body: its three kernels are instances in the two units above)
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
@@ -20,6 +21,7 @@
 #include "kz_film.h"
 #include "kz_plan.h"
 #include "../../include/kazen_mi355x_motion.h"
+#include "../../include_ext/kazen_mi355x_matte.h"
 
 #include <atomic>
 #include <chrono>
@@ -203,6 +205,11 @@ struct KzDeviceState {
     KzFilm &aov(int f) { return films[1 + f]; }
     KzFilm &moment() { return films[4]; }
     size_t aovBytes() const { return films[1].bytes() + films[2].bytes() + films[3].bytes(); }
+    // ID mattes (kazen_mi355x_matte.h; kz_matte.hip): per enabled key - [0] mesh, [1] BSDF row - one 64-B record per FRAME pixel, there from the first render with the
+    // key, outside the budget, freed when the key leaves the scene's mask. matteSamples: samples per pixel counted since the table was last zeroed (an upper bound:
+    // the sum of sampleEnd - sampleBegin over renders). evMatte[i]: the matte stage of the pass last run in context i (a chain of its own, as evAov).
+    DevBuf<KzMatteTexel> matte[2]; uint64_t matteSamples[2] = {}; Event evMatte[KZ_MAX_PASSES_IN_FLIGHT];
+    size_t matteBytes() const { return matte[0].bytes() + matte[1].bytes(); }
     DevBuf<uint8_t> srgb;                                        // staging raster of kz_film_to_srgb8 / kz_denoise_to_srgb8 (allocated on first use)
     // The denoiser (kazen_mi355x_denoise.h; kz_denoise.hip), allocated by the first kz_denoise outside the pass contexts' budget: frame-sized planes without an
     // apron - the colour plane (e.rgb, valid) twice, the iterations ping-pong between the two; (n.xyz, z); (a.rgb, -) - and the result, laid out like the film.
@@ -274,6 +281,10 @@ int findReplica(const KzScene *scene, int device, KzDeviceState **out);
 int kzEnsureBvh2(KzScene *scene, KzDeviceState *ds);                                                      // the BVH2 table, on first use
 // kz_motion.hip
 int kzMotionIds(KzScene *scene, KzDeviceState *ds);                                                       // ds->mtIds: the mesh id of every frame pixel of the scene as it stands (returns with the device idle)
+// kz_matte.hip: the tables of the enabled keys before the passes of a call, every table zeroed, and the matte stage of one pass (items nPix x S, pixel-major, first hits at `hit`)
+int kzMatteEnsure(KzScene *scene, KzDeviceState *ds, bool accumulate, uint32_t nSamples, hipStream_t stream);
+int kzMatteClear(KzDeviceState *ds, hipStream_t stream);
+int kzMatteStage(KzScene *scene, KzDeviceState *ds, hipStream_t stream, const float4 *hit, const uint32_t *pixList, uint32_t nPix, uint32_t S, hipEvent_t wait, hipEvent_t record);
 int kzEmitterUpload(KzScene *scene, KzDeviceState *ds);                                                   // the emitter triangles, their count and box (upload and every edit of a light)
 int prepareTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32_t nTiles, hipStream_t stream);      // makes `tiles` the replica's tile set
 static inline int requireDevice(KzScene *scene, KzDeviceState **out) { return findReplica(scene, -1, out); }

@@ -428,6 +428,73 @@ class Scene:
         abi.check(self.lib, self.lib.kz_aov_samples(self.h, n, pxy.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(abi.u32p), out.ctypes.data_as(abi.f32p)))
         return out
 
+    # ---- ID mattes beside the picture (include_ext/kazen_mi355x_matte.h)
+    @staticmethod
+    def _matte_mask(names):
+        if isinstance(names, int):
+            return int(names)
+        if isinstance(names, str):
+            names = [names]
+        mask = 0
+        for n in names or ():
+            if n not in abi.MATTE_BITS:
+                raise ValueError("unknown matte key %r (known: %s)" % (n, ", ".join(sorted(abi.MATTE_BITS))))
+            mask |= abi.MATTE_BITS[n]
+        return mask
+
+    def set_mattes(self, names):
+        """kz_scene_set_mattes: `names` = any of "mesh", "bsdf" (or the bit mask itself; () / 0 switches the mattes off). A key that leaves the mask loses its
+        tables; one that enters starts from zero."""
+        abi.check(self.lib, self.lib.kz_scene_set_mattes(self.h, self._matte_mask(names)))
+
+    def mattes(self):
+        m = C.c_uint32()
+        abi.check(self.lib, self.lib.kz_scene_mattes(self.h, C.byref(m)))
+        return [n for n, b in abi.MATTE_BITS.items() if m.value & b]
+
+    def matte(self, key, device=None):
+        """kz_matte_download[_on]: the key's table, (h, w) records of abi.MATTE_DTYPE (id[7], count[7], other, miss), every record ranked: count descending,
+        ties to the lower id, free slots last."""
+        out = np.zeros((self.height, self.width), abi.MATTE_DTYPE)
+        ptr = out.ctypes.data_as(C.POINTER(abi.KzMatteTexel))
+        if device is None:
+            abi.check(self.lib, self.lib.kz_matte_download(self.h, self._matte_mask(key), ptr, out.size))
+        else:
+            abi.check(self.lib, self.lib.kz_matte_download_on(self.h, int(device), self._matte_mask(key), ptr, out.size))
+        return out
+
+    def matte_layer(self, key, id, device=None):
+        """kz_matte_layer: (h, w) float32, the coverage of `id`: its count over the pixel's samples (0 where it has no slot or the pixel no samples)."""
+        out = np.zeros((self.height, self.width), np.float32)
+        abi.check(self.lib, self.lib.kz_matte_layer(self.h, -1 if device is None else int(device), self._matte_mask(key), int(id), out.ctypes.data_as(abi.f32p), out.size))
+        return out
+
+    def matte_top(self, key, device=None):
+        """kz_matte_top: (h, w) uint32, the id with the largest count of every pixel (abi.KZ_MATTE_NONE: the misses are at least as many, or no samples)."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        abi.check(self.lib, self.lib.kz_matte_top(self.h, -1 if device is None else int(device), self._matte_mask(key), out.ctypes.data_as(abi.u32p), out.size))
+        return out
+
+    def matte_info(self, device=-1):
+        """kz_matte_info: bytes the matte tables hold on that replica."""
+        b = C.c_uint64()
+        abi.check(self.lib, self.lib.kz_matte_info(self.h, int(device), C.byref(b)))
+        return int(b.value)
+
+    def matte_accumulate_items(self, keys, pix_list, tables=None, device=None, form=0):
+        """kz_matte_accumulate_items, the test surface: the product kernel on the (nPix, S) key plane `keys` (abi.KZ_MATTE_NONE = a miss) of the pixels `pix_list`
+        (x | y << 16), starting from the records `tables` (nPix of abi.MATTE_DTYPE; None: zeros). Returns the unranked records. form: 0 as a render picks,
+        1 one lane per pixel, 2 one wave per pixel."""
+        keys = np.ascontiguousarray(keys, np.uint32)
+        pix_list = np.ascontiguousarray(pix_list, np.uint32)
+        n_pix, S = keys.shape
+        out = np.zeros(n_pix, abi.MATTE_DTYPE) if tables is None else np.ascontiguousarray(tables, abi.MATTE_DTYPE).copy()
+        if out.shape != (n_pix,) or pix_list.shape != (n_pix,):
+            raise ValueError("keys (nPix, S), pix_list (nPix,), tables (nPix,)")
+        abi.check(self.lib, self.lib.kz_matte_accumulate_items(self.h, -1 if device is None else int(device), keys.ctypes.data_as(abi.u32p), n_pix, S,
+                                                               pix_list.ctypes.data_as(abi.u32p), out.ctypes.data_as(C.POINTER(abi.KzMatteTexel)), int(form)))
+        return out
+
     # ---- the picture denoised on the device, guided by its feature films (include/kazen_mi355x_denoise.h)
     def denoise(self, device=None, **opts):
         """kz_denoise[_on]: filters the replica's picture with the enabled feature films as guides; the result stays on the device (denoised_film,

@@ -848,10 +848,19 @@ def _film_cases(S):
         "textured": lambda: S.textured_scene(128, 80, 8),
         "sphere_env": lambda: S.sphere_env(96, 96, 8),
         "random_triangles_pmj": lambda: S.random_triangles(20000, 192, 108, 16, sampler="pmj02bn", seed=1),
+        "cornell_stratified": lambda: S.cornell_box(96, 80, 10, sampler="stratified", seed=1),            # rounds to 16 spp
+        "glass_correlated_thinlens": lambda: _glass_thinlens(S),
     }
 
 
-@pytest.mark.parametrize("name", ["cornell_pmj", "cornell_independent_ragged", "hero_kiss", "materials", "textured", "sphere_env", "random_triangles_pmj"])
+def _glass_thinlens(S):
+    d = S.glass_scene(96, 96, 12, sampler="correlated")
+    d.camera.update(type="thinlens", apertureRadius=0.1, focusDistance=3.5)
+    return d
+
+
+@pytest.mark.parametrize("name", ["cornell_pmj", "cornell_independent_ragged", "hero_kiss", "materials", "textured", "sphere_env", "random_triangles_pmj", "cornell_stratified",
+                                  "glass_correlated_thinlens"])
 def test_whole_films_equal_the_oracle_bit_for_bit(gpu_lib, kz, O, name):
     """Every sample's radiance has been the oracle's to the last bit since round 4, and the filter weights are ImageBlock::put's by construction; what kept the FILMS apart
     was the order of the float additions (H10: the reference's own depends on its thread timing). Round 6 fixes that order on the device - per pixel and tap in sample order,

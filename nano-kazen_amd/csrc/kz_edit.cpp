@@ -18,22 +18,6 @@
 
 namespace {
 
-// the shading records of mesh m from its vertex data (kz_scene_create: p from V, n from N through the face's vertex indices)
-void applyMesh(KzScene *sc, uint32_t m, const float *V, const float *N) {
-    const KzMeshRow &row = sc->meshRows[m];
-    for (uint32_t f = 0; f < row.nF; ++f) {
-        const uint32_t g = row.triOffset + f;
-        KzTriShade &s = sc->shade[g];
-        for (int v = 0; v < 3; ++v) {
-            const size_t i = sc->triVtx[3 * (size_t)g + v];
-            for (int a = 0; a < 3; ++a) {
-                s.p[3 * v + a] = V[3 * i + a];
-                if (N) s.n[3 * v + a] = N[3 * i + a];
-            }
-        }
-    }
-}
-
 // the breadth-first levels of the BVH2 (the device refits one level per launch, deepest first)
 void computeLevels(KzScene *sc) {
     if (!sc->levelStart.empty() || sc->nodes.empty()) return;
@@ -45,26 +29,29 @@ void computeLevels(KzScene *sc) {
     sc->levelStart.push_back((uint32_t)sc->nodes.size());
 }
 
+// gives a vector's memory back (clear() would keep it)
+template <class T> void release(std::vector<T> &v) { std::vector<T>().swap(v); }
+
 // A mesh's base data for its first transform: what an edit has set and the shading records do not hold yet (pendV / pendN), else a copy out of the shading
-// records through the faces' vertex indices (exact; a vertex no face names is never read again and stays 0). The caller holds editMutex.
+// records (kzShadeToMesh). The caller holds editMutex.
 void captureBase(KzScene *sc, uint32_t m) {
     const size_t nMeshes = sc->meshRows.size();
     if (sc->baseV.size() != nMeshes) { sc->baseV.resize(nMeshes); sc->baseN.resize(nMeshes); sc->pendX.resize(nMeshes); sc->pendXOn.assign(nMeshes, 0); }
     if (sc->pendV.size() != nMeshes) { sc->pendV.resize(nMeshes); sc->pendN.resize(nMeshes); }
     if (!sc->baseV[m].empty() || !sc->meshNV[m]) return;
-    const KzMeshRow &row = sc->meshRows[m];
-    const bool hasN = (row.flags & 1u) != 0;
     if (!sc->pendV[m].empty()) { sc->baseV[m] = sc->pendV[m]; sc->baseN[m] = sc->pendN[m]; return; }
-    sc->baseV[m].assign(3 * (size_t)sc->meshNV[m], 0.f);
-    if (hasN) sc->baseN[m].assign(3 * (size_t)sc->meshNV[m], 0.f);
-    for (uint32_t f = 0; f < row.nF; ++f) {
-        const uint32_t g = row.triOffset + f;
-        const KzTriShade &t = sc->shade[g];
-        for (int v = 0; v < 3; ++v) {
-            const size_t i = sc->triVtx[3 * (size_t)g + v];
-            for (int a = 0; a < 3; ++a) { sc->baseV[m][3 * i + a] = t.p[3 * v + a]; if (hasN) sc->baseN[m][3 * i + a] = t.n[3 * v + a]; }
-        }
-    }
+    kzShadeToMesh(sc, m, sc->baseV[m], sc->baseN[m]);
+}
+
+// What a batch of edits names, for batchIndex's texts: one of them, how the scene came by them, several of them.
+struct BatchNoun { const char *one, *has, *many; };
+const BatchNoun MESHES = {"mesh", "has", "meshes"}, BSDF_ROWS = {"row", "was created with", "BSDF rows"}, LIGHTS = {"light", "was created with", "lights"};
+// Update i of `call`'s batch names `index` of the scene's `count`: in range, and not named by an earlier update of the batch (seen: one byte per index, marked here).
+int batchIndex(const char *call, const BatchNoun &w, uint32_t i, uint32_t index, uint32_t count, std::vector<uint8_t> &seen) {
+    if (index >= count) return kz_fail(KZ_ERR_INVALID_ARG, "%s: update %u names %s %u, the scene %s %u %s", call, i, w.one, index, w.has, count, w.many);
+    if (seen[index]) return kz_fail(KZ_ERR_INVALID_ARG, "%s: %s %u is listed twice in one batch", call, w.one, index);
+    seen[index] = 1;
+    return KZ_OK;
 }
 
 // base data of mesh m under x (kz_xform.h); false when a transformed coordinate is not finite
@@ -77,9 +64,9 @@ bool transformMesh(const KzScene *sc, uint32_t m, const KzXform &x, std::vector<
     return fin;
 }
 
-// the rows a light mesh's new positions move: its shading records, its CDF (the caller re-forms the invisible-light rows once per batch)
+// the rows a light mesh's new positions move: its shading records, its CDF (the caller brings the tables derived from the lights up to date once per batch: kzLightTables)
 void applyLightMesh(KzScene *sc, uint32_t m, const float *V, const float *N) {
-    applyMesh(sc, m, V, N);
+    kzMeshToShade(sc, m, V, N);
     KzLightRow &lr = sc->lightRows[(size_t)sc->meshRows[m].light];
     std::vector<float> t;
     kzLightCdf(&sc->shade[lr.triOffset], lr.nF, t, lr.normalization);
@@ -94,20 +81,17 @@ void kzHostSync(KzScene *sc) {
     if (!sc->hostStale) return;
     for (size_t m = 0; m < sc->pendV.size(); ++m) {
         if (sc->pendV[m].empty()) continue;
-        applyMesh(sc, (uint32_t)m, sc->pendV[m].data(), sc->pendN[m].empty() ? nullptr : sc->pendN[m].data());
-        std::vector<float>().swap(sc->pendV[m]); std::vector<float>().swap(sc->pendN[m]);
+        kzMeshToShade(sc, (uint32_t)m, sc->pendV[m].data(), sc->pendN[m].empty() ? nullptr : sc->pendN[m].data());
+        release(sc->pendV[m]); release(sc->pendN[m]);
     }
     for (size_t m = 0; m < sc->pendXOn.size(); ++m) {   // (kz_scene_set_transforms of a mesh that is no light: its base data under the matrix, by the arithmetic the replicas used)
         if (!sc->pendXOn[m]) continue;
         std::vector<float> V, N;
         transformMesh(sc, (uint32_t)m, sc->pendX[m], V, N);
-        applyMesh(sc, (uint32_t)m, V.data(), N.empty() ? nullptr : N.data());
+        kzMeshToShade(sc, (uint32_t)m, V.data(), N.empty() ? nullptr : N.data());
         sc->pendXOn[m] = 0;
     }
-    for (KzTri &t : sc->tris) {                         // p0, e1 = v1 - v0, e2 = v2 - v0 (kz_bvh.cpp: the leaf triangles)
-        const float *p = sc->shade[t.gid].p;
-        for (int a = 0; a < 3; ++a) { t.p0[a] = p[a]; t.e1[a] = p[3 + a] - p[a]; t.e2[a] = p[6 + a] - p[a]; }
-    }
+    for (KzTri &t : sc->tris) t = kzLeafTri(sc->shade[t.gid], t.gid);      // (mesh and prim are the shading record's, as the build took them)
     const size_t N = sc->nodes.size();
     if (N) {
         std::vector<KzBox> exact(2 * N);                // unpadded child boxes, children before parents (breadth-first numbering)
@@ -161,9 +145,7 @@ int kz_scene_set_vertices(KzScene *sc, const KzVertexUpdate *u, uint32_t n) {
     std::vector<uint8_t> seen(nMeshes, 0);
     for (uint32_t i = 0; i < n; ++i) {
         const KzVertexUpdate &x = u[i];
-        if (x.mesh >= nMeshes) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_vertices: update %u names mesh %u, the scene has %u meshes", i, x.mesh, nMeshes);
-        if (seen[x.mesh]) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_vertices: mesh %u is listed twice in one batch", x.mesh);
-        seen[x.mesh] = 1;
+        if (int rc = batchIndex("kz_scene_set_vertices", MESHES, i, x.mesh, nMeshes, seen)) return rc;
         if (x.nV != sc->meshNV[x.mesh]) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_vertices: mesh %u has %u vertices, the update gives %u (the topology is fixed)", x.mesh, sc->meshNV[x.mesh], x.nV);
         if (!x.V) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_vertices: mesh %u: V is null", x.mesh);
         const bool hasN = (sc->meshRows[x.mesh].flags & 1u) != 0;
@@ -186,18 +168,18 @@ int kz_scene_set_vertices(KzScene *sc, const KzVertexUpdate *u, uint32_t n) {
             const KzVertexUpdate &x = u[i];
             const int32_t light = sc->meshRows[x.mesh].light;
             if (!sc->baseV.empty()) {                   // new base data: the host's copy is taken again by the mesh's next transform (every replica's follows in kzEditVertices), its transform goes
-                std::vector<float>().swap(sc->baseV[x.mesh]); std::vector<float>().swap(sc->baseN[x.mesh]); sc->pendXOn[x.mesh] = 0;
+                release(sc->baseV[x.mesh]); release(sc->baseN[x.mesh]); sc->pendXOn[x.mesh] = 0;
             }
             if (light < 0) {
                 sc->pendV[x.mesh].assign(x.V, x.V + 3 * (size_t)x.nV);
                 if (x.N) sc->pendN[x.mesh].assign(x.N, x.N + 3 * (size_t)x.nV); else sc->pendN[x.mesh].clear();
                 continue;
             }
-            std::vector<float>().swap(sc->pendV[x.mesh]); std::vector<float>().swap(sc->pendN[x.mesh]);
+            release(sc->pendV[x.mesh]); release(sc->pendN[x.mesh]);
             applyLightMesh(sc, x.mesh, x.V, x.N);
             lightRows.push_back((uint32_t)light);
         }
-        if (!lightRows.empty()) kzInvisibleLights(sc);
+        if (!lightRows.empty()) kzLightTables(sc);
         sc->hostStale = true;
     }
     ++sc->geometryEdits;                                       // (every replica's temporal history is stale from here on: kz_denoise_temporal's ...
@@ -215,14 +197,12 @@ int kz_scene_set_bsdfs(KzScene *sc, const KzBsdfUpdate *u, uint32_t n) {
     std::vector<uint8_t> seen(sc->nDescBsdfs, 0);
     std::vector<uint32_t> rows;
     for (uint32_t i = 0; i < n; ++i) {
-        if (u[i].row >= sc->nDescBsdfs) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_bsdfs: update %u names row %u, the scene was created with %u BSDF rows", i, u[i].row, sc->nDescBsdfs);
-        if (seen[u[i].row]) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_bsdfs: row %u is listed twice in one batch", u[i].row);
-        seen[u[i].row] = 1;
+        if (int rc = batchIndex("kz_scene_set_bsdfs", BSDF_ROWS, i, u[i].row, sc->nDescBsdfs, seen)) return rc;
         table[u[i].row] = u[i].bsdf;
         rows.push_back(u[i].row);
     }
-    int rc = kzCheckBsdfs("kz_scene_set_bsdfs: ", table.data(), sc->nDescBsdfs, (uint32_t)sc->texProgs.size(), sc->prm.integrator);
-    if (rc != KZ_OK) return rc;
+    int rc = kzCheckBsdfs(table.data(), sc->nDescBsdfs, (uint32_t)sc->texProgs.size(), sc->prm.integrator);
+    if (rc != KZ_OK) return kzFailedIn("kz_scene_set_bsdfs", rc);
     if (!n) return KZ_OK;
     if ((rc = kzEditWait(sc)) != KZ_OK) return rc;
     for (uint32_t r : rows) { kzResolveBsdf(table[r]); sc->bsdfs[r] = table[r]; }
@@ -234,10 +214,10 @@ int kz_scene_set_bsdfs(KzScene *sc, const KzBsdfUpdate *u, uint32_t n) {
 
 int kz_scene_set_lights(KzScene *sc, const KzLightUpdate *u, uint32_t n) {
     if (!sc || (n && !u)) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_lights: null argument");
-    std::vector<int32_t> which(sc->nDescLights, -1);
+    std::vector<uint8_t> seen(sc->nDescLights, 0);
+    std::vector<int32_t> which(sc->nDescLights, -1);       // per light of the description: the update that names it
     for (uint32_t i = 0; i < n; ++i) {
-        if (u[i].light >= sc->nDescLights) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_lights: update %u names light %u, the scene was created with %u lights", i, u[i].light, sc->nDescLights);
-        if (which[u[i].light] >= 0) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_lights: light %u is listed twice in one batch", u[i].light);
+        if (int rc = batchIndex("kz_scene_set_lights", LIGHTS, i, u[i].light, sc->nDescLights, seen)) return rc;
         which[u[i].light] = (int32_t)i;
     }
     if (!n) return KZ_OK;
@@ -247,13 +227,9 @@ int kz_scene_set_lights(KzScene *sc, const KzLightUpdate *u, uint32_t n) {
         std::lock_guard<std::mutex> g(sc->editMutex);
         for (size_t l = 0; l < sc->lightRows.size(); ++l) {
             const int32_t i = which[sc->lightDesc[l]];
-            if (i < 0) continue;
-            const KzLight &kl = u[i].value;
-            KzLightRow &lr = sc->lightRows[l];
-            for (int a = 0; a < 3; ++a) lr.radiance[a] = kl.intensity * kl.color[a];
-            lr.primaryVisibility = kl.primaryVisibility ? 1 : 0;
+            if (i >= 0) kzLightRowValue(sc->lightRows[l], u[i].value);
         }
-        kzInvisibleLights(sc);                           // (the shading records of light meshes follow every edit at once: nothing to sync first)
+        kzLightTables(sc);                          // (the shading records of light meshes follow every edit at once: nothing to sync first)
     }
     return kzEditLightRows(sc);
 }
@@ -263,9 +239,7 @@ int kz_scene_set_transforms(KzScene *sc, const KzTransformUpdate *u, uint32_t n)
     const uint32_t nMeshes = (uint32_t)sc->meshRows.size();
     std::vector<uint8_t> seen(nMeshes, 0);
     for (uint32_t i = 0; i < n; ++i) {
-        if (u[i].mesh >= nMeshes) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: update %u names mesh %u, the scene has %u meshes", i, u[i].mesh, nMeshes);
-        if (seen[u[i].mesh]) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: mesh %u is listed twice in one batch", u[i].mesh);
-        seen[u[i].mesh] = 1;
+        if (int rc = batchIndex("kz_scene_set_transforms", MESHES, i, u[i].mesh, nMeshes, seen)) return rc;
         for (int k = 0; k < 16; ++k)
             if (!kzFinite(u[i].toWorld[k])) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_set_transforms: mesh %u: matrix entry %d is not finite (%g)", u[i].mesh, k, u[i].toWorld[k]);
     }
@@ -301,13 +275,13 @@ int kz_scene_set_transforms(KzScene *sc, const KzTransformUpdate *u, uint32_t n)
         std::lock_guard<std::mutex> g(sc->editMutex);
         for (uint32_t i = 0; i < n; ++i) {
             const uint32_t m = u[i].mesh;
-            std::vector<float>().swap(sc->pendV[m]); std::vector<float>().swap(sc->pendN[m]);
+            release(sc->pendV[m]); release(sc->pendN[m]);
             if (sc->meshRows[m].light < 0) { sc->pendX[m] = xf[i]; sc->pendXOn[m] = 1; continue; }
             sc->pendXOn[m] = 0;
             applyLightMesh(sc, m, lightV[i].data(), lightN[i].empty() ? nullptr : lightN[i].data());
             lightRows.push_back((uint32_t)sc->meshRows[m].light);
         }
-        if (!lightRows.empty()) kzInvisibleLights(sc);
+        if (!lightRows.empty()) kzLightTables(sc);
         sc->hostStale = true;
     }
     ++sc->geometryEdits;

@@ -12,6 +12,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 
 static thread_local char g_err[512] = "";
 
@@ -20,6 +21,11 @@ int kz_fail(int code, const char *fmt, ...) {
     std::vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
     return code;
+}
+// the refusal of a check that create and an edit share, as the edit reports it: "<call>: <the check's text>"
+int kzFailedIn(const char *call, int code) {
+    const std::string text = g_err;
+    return kz_fail(code, "%s: %s", call, text.c_str());
 }
 
 namespace {
@@ -181,6 +187,72 @@ void kzLightCdf(const KzTriShade *shade, uint32_t nF, std::vector<float> &t, flo
     }
     normalization = dpdfNormalize(t, 0, nullptr);
 }
+// what a light row takes from its KzLight (light.cpp:13)
+void kzLightRowValue(KzLightRow &lr, const KzLight &kl) {
+    for (int a = 0; a < 3; ++a) lr.radiance[a] = kl.intensity * kl.color[a];
+    lr.primaryVisibility = kl.primaryVisibility ? 1 : 0;
+}
+// A shading record's positions and normals from its mesh's vertex data: p from V and n from N (null: n stays) through the face's three vertex indices.
+static void faceToShade(KzTriShade &s, const uint32_t *idx, const float *V, const float *N) {
+    for (int v = 0; v < 3; ++v) {
+        const size_t i = idx[v];
+        for (int a = 0; a < 3; ++a) {
+            s.p[3 * v + a] = V[3 * i + a];
+            if (N) s.n[3 * v + a] = N[3 * i + a];
+        }
+    }
+}
+// The shading records of mesh m follow its vertex data (create forms them face by face with the same function) ...
+void kzMeshToShade(KzScene *sc, uint32_t m, const float *V, const float *N) {
+    const KzMeshRow &row = sc->meshRows[m];
+    for (uint32_t g = row.triOffset; g < row.triOffset + row.nF; ++g) faceToShade(sc->shade[g], &sc->triVtx[3 * (size_t)g], V, N);
+}
+// ... and the inverse: the mesh's vertex data out of its shading records (exact; a vertex no face names is never read again and stays 0; N only of a mesh with normals)
+void kzShadeToMesh(const KzScene *sc, uint32_t m, std::vector<float> &V, std::vector<float> &N) {
+    const KzMeshRow &row = sc->meshRows[m];
+    const bool hasN = (row.flags & 1u) != 0;
+    V.assign(3 * (size_t)sc->meshNV[m], 0.f);
+    if (hasN) N.assign(3 * (size_t)sc->meshNV[m], 0.f);
+    for (uint32_t f = 0; f < row.nF; ++f) {
+        const uint32_t g = row.triOffset + f;
+        const KzTriShade &s = sc->shade[g];
+        for (int v = 0; v < 3; ++v) {
+            const size_t i = sc->triVtx[3 * (size_t)g + v];
+            for (int a = 0; a < 3; ++a) { V[3 * i + a] = s.p[3 * v + a]; if (hasN) N[3 * i + a] = s.n[3 * v + a]; }
+        }
+    }
+}
+
+// ---- the tables derived from the lights: formed from the light rows and the shading records of their meshes -----------------------------------
+// the leaf-triangle form of a shading record: p0, e1 = v1 - v0, e2 = v2 - v0 (kz_bvh.cpp forms the same from a KzBuildTri)
+KzTri kzLeafTri(const KzTriShade &s, uint32_t gid) {
+    KzTri t;
+    for (int a = 0; a < 3; ++a) { t.p0[a] = s.p[a]; t.e1[a] = s.p[3 + a] - s.p[a]; t.e2[a] = s.p[6 + a] - s.p[a]; }
+    t.mesh = s.mesh; t.prim = s.prim; t.gid = gid;
+    return t;
+}
+
+namespace {
+
+// The invisible-light box's padding, of the box's largest coordinate or extent, on every axis. The box only gates the brute-force triangle tests
+// (invisibleLightOnSegment, kz_devfn.h), so a wider box changes no answer, but it must not be NARROWER than the triangle test: a segment that ends (or starts)
+// exactly on a light has its Moeller-Trumbore t a few ulps to either side of the distance to the light's plane, and with the BVH boxes' padding (4e-7 of the
+// coordinate: an ulp or two of t) the gate closed in front of such a hit - the any-hit kernel then kept the ray and was blocked by the invisible light itself
+// (tests/test_shadow_order_gpu.py: segments with tmin == tmax at a hit on a light that hangs flat at y = 0.2). Ten times that. Not more: every shadow ray that
+// ends inside the padded box runs the triangle loop, and the rays towards a light end 1e-3 in front of it (1e-4 cost C4 2 % of its shadow kernel's instructions).
+const float IL_BOX_PAD = 4e-6f;
+// The emitter box's padding, per axis of that axis' largest coordinate: the padding of the BVH boxes.
+const float EM_BOX_PAD = 4e-7f;
+
+// a light mesh's triangles behind `out`, in the leaf-triangle form, and the box lo / hi grown by their vertices
+void appendLightTris(const KzScene *sc, const KzLightRow &lr, std::vector<KzTri> &out, float lo[3], float hi[3]) {
+    for (uint32_t f = 0; f < lr.nF; ++f) {
+        const KzTriShade &s = sc->shade[lr.triOffset + f];
+        for (int a = 0; a < 3; ++a)
+            for (int v = 0; v < 3; ++v) { lo[a] = std::min(lo[a], s.p[3 * v + a]); hi[a] = std::max(hi[a], s.p[3 * v + a]); }
+        out.push_back(kzLeafTri(s, lr.triOffset + f));
+    }
+}
 
 // invisible-light triangles for the exact any-hit shadow test
 void kzInvisibleLights(KzScene *sc) {
@@ -193,37 +265,21 @@ void kzInvisibleLights(KzScene *sc) {
         if (lr.primaryVisibility) continue;
         p.anyInvisibleLight = 1;
         if (lr.nF) { ilGidLo = std::min(ilGidLo, lr.triOffset); ilGidHi = std::max(ilGidHi, lr.triOffset + lr.nF - 1); }
-        for (uint32_t f = 0; f < lr.nF; ++f) {
-            const KzTriShade &s = sc->shade[lr.triOffset + f];
-            KzTri t; std::memset(&t, 0, sizeof t);
-            for (int a = 0; a < 3; ++a) {
-                t.p0[a] = s.p[a]; t.e1[a] = s.p[3 + a] - s.p[a]; t.e2[a] = s.p[6 + a] - s.p[a];
-                for (int v = 0; v < 3; ++v) { p.ilLo[a] = std::min(p.ilLo[a], s.p[3 * v + a]); p.ilHi[a] = std::max(p.ilHi[a], s.p[3 * v + a]); }
-            }
-            t.mesh = lr.mesh; t.prim = f; t.gid = lr.triOffset + f;
-            sc->ilTris.push_back(t);
-        }
+        appendLightTris(sc, lr, sc->ilTris, p.ilLo, p.ilHi);
     }
     if (sc->ilTris.size() > 64) { p.shadowFast = 0; sc->ilTris.clear(); }      // big emissive meshes: literal closest-hit loop
     p.nIlTris = (uint32_t)sc->ilTris.size();
     p.ilGidLo = ilGidLo <= ilGidHi ? ilGidLo : 1u; p.ilGidSpan = ilGidLo <= ilGidHi ? ilGidHi - ilGidLo : 0u;
-    // Padding. The box only gates the brute-force triangle tests (invisibleLightOnSegment, kz_devfn.h), so a wider box changes no answer, but it must not be
-    // NARROWER than the triangle test: a segment that ends (or starts) exactly on a light has its Moeller-Trumbore t a few ulps to either side of the distance
-    // to the light's plane, and with the BVH boxes' padding (4e-7 of the coordinate: an ulp or two of t) the gate closed in front of such a hit - the any-hit
-    // kernel then kept the ray and was blocked by the invisible light itself (tests/test_shadow_order_gpu.py: segments with tmin == tmax at a hit on a light
-    // that hangs flat at y = 0.2). Ten times that, of the box's largest coordinate or extent, on every axis. Not more: every shadow ray that ends inside the
-    // padded box runs the triangle loop, and the rays towards a light end 1e-3 in front of it (1e-4 cost C4 2 % of its shadow kernel's instructions).
     float m = 0.f;
     for (int a = 0; a < 3; ++a) m = std::max(m, std::max(std::max(std::fabs(p.ilLo[a]), std::fabs(p.ilHi[a])), p.ilHi[a] - p.ilLo[a]));
     for (int a = 0; a < 3; ++a)
-        if (std::isfinite(m)) { float e = m * 4e-6f + 1e-30f; p.ilLo[a] -= e; p.ilHi[a] += e; }
-    kzEmitterTris(sc);
+        if (std::isfinite(m)) { float e = m * IL_BOX_PAD + 1e-30f; p.ilLo[a] -= e; p.ilHi[a] += e; }
 }
 
 // Emitter triangles for the roulette-ahead test of kz_wf_shade (kz_wavefront.h wfShadeSurvivor): the triangles of EVERY light mesh - a bounce ray that hits a
-// light adds its radiance whatever the light's primary visibility, which concerns the first hit only (H6) - in the leaf-triangle form, and their box with the
-// padding of the BVH boxes. The test is off (KZ_EM_OFF, no rows) for more than KZ_EM_MAX triangles, for a scene with a background (a miss then adds
-// radiance) and for the integrators other than path_mis. No lights and no background: an empty table, no bounce ray of an ended path can add anything.
+// light adds its radiance whatever the light's primary visibility, which concerns the first hit only (H6) - in the leaf-triangle form, and their box. The test
+// is off (KZ_EM_OFF, no rows) for more than KZ_EM_MAX triangles, for a scene with a background (a miss then adds radiance) and for the integrators other than
+// path_mis. No lights and no background: an empty table, no bounce ray of an ended path can add anything.
 void kzEmitterTris(KzScene *sc) {
     const KzParams &p = sc->prm;
     sc->emTris.clear();
@@ -231,21 +287,11 @@ void kzEmitterTris(KzScene *sc) {
     size_t total = 0;
     for (const KzLightRow &lr : sc->lightRows) total += lr.nF;
     const bool on = total <= KZ_EM_MAX && !p.bgPresent && p.integrator == KZ_INTEGRATOR_PATH_MIS;
-    if (on) for (const KzLightRow &lr : sc->lightRows)
-        for (uint32_t f = 0; f < lr.nF; ++f) {
-            const KzTriShade &s = sc->shade[lr.triOffset + f];
-            KzTri t; std::memset(&t, 0, sizeof t);
-            for (int a = 0; a < 3; ++a) {
-                t.p0[a] = s.p[a]; t.e1[a] = s.p[3 + a] - s.p[a]; t.e2[a] = s.p[6 + a] - s.p[a];
-                for (int v = 0; v < 3; ++v) { sc->emLo[a] = std::min(sc->emLo[a], s.p[3 * v + a]); sc->emHi[a] = std::max(sc->emHi[a], s.p[3 * v + a]); }
-            }
-            t.mesh = lr.mesh; t.prim = f; t.gid = lr.triOffset + f;
-            sc->emTris.push_back(t);
-        }
+    if (on) for (const KzLightRow &lr : sc->lightRows) appendLightTris(sc, lr, sc->emTris, sc->emLo, sc->emHi);
     sc->nEmTris = on ? (uint32_t)sc->emTris.size() : KZ_EM_OFF;
-    for (int a = 0; a < 3; ++a) {        // same padding as BVH boxes
+    for (int a = 0; a < 3; ++a) {
         float m = std::max(std::fabs(sc->emLo[a]), std::fabs(sc->emHi[a]));
-        if (std::isfinite(m)) { float e = m * 4e-7f + 1e-30f; sc->emLo[a] -= e; sc->emHi[a] += e; }
+        if (std::isfinite(m)) { float e = m * EM_BOX_PAD + 1e-30f; sc->emLo[a] -= e; sc->emHi[a] += e; }
     }
     KzTri h; std::memset(&h, 0, sizeof h);          // the header row (kz_internal.h)
     for (int a = 0; a < 3; ++a) { h.p0[a] = sc->emLo[a]; h.e1[a] = sc->emHi[a]; }
@@ -253,30 +299,38 @@ void kzEmitterTris(KzScene *sc) {
     sc->emTris.push_back(h);
 }
 
-// The checks of a whole BSDF row table (kz_scene_create: the description's rows; kz_scene_set_bsdfs: the scene's rows with a batch applied). `who` is put in
-// front of every message ("" or "kz_scene_set_bsdfs: ").
-int kzCheckBsdfs(const char *who, const KzBSDF *rows, uint32_t n, uint32_t nTextures, int32_t integ) {
+} // namespace
+
+// Every table derived from the lights, brought up to date: after create knows the integrator and the background, and after each edit that moves or toggles a light.
+void kzLightTables(KzScene *sc) {
+    kzInvisibleLights(sc);
+    kzEmitterTris(sc);
+}
+
+// The checks of a whole BSDF row table (kz_scene_create: the description's rows; kz_scene_set_bsdfs: the scene's rows with a batch applied, and
+// its name in front of the text: kzFailedIn).
+int kzCheckBsdfs(const KzBSDF *rows, uint32_t n, uint32_t nTextures, int32_t integ) {
     for (uint32_t i = 0; i < n; ++i) {
         const KzBSDF &b = rows[i];
         if (b.type < KZ_BSDF_DIFFUSE || b.type > KZ_BSDF_NORMALMAP)
-            return kz_fail(KZ_ERR_UNSUPPORTED, "%sbsdf %u has type %d (supported: diffuse, kazenstandard, mirror, dielectric, ggx, roughconductor, roughplastic, roughdielectric, normalmap)", who, i, b.type);
+            return kz_fail(KZ_ERR_UNSUPPORTED, "bsdf %u has type %d (supported: diffuse, kazenstandard, mirror, dielectric, ggx, roughconductor, roughplastic, roughdielectric, normalmap)", i, b.type);
         const int32_t ids[4] = {b.albedoTex, b.roughnessTex, b.metallicTex, b.normalTex};
-        for (int32_t id : ids) if (id < 0 || id > (int32_t)nTextures) return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u: texture id %d out of range (0 = constant, 1..%u)", who, i, id, nTextures);
+        for (int32_t id : ids) if (id < 0 || id > (int32_t)nTextures) return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u: texture id %d out of range (0 = constant, 1..%u)", i, id, nTextures);
         // which rows read a Texture child: diffuse/lambertian + ggx "albedo" (bsdf.cpp:259-262, :672-675), kiss (bsdf.cpp:1375-1390)
         const bool takesAlbedo = b.type == KZ_BSDF_DIFFUSE || b.type == KZ_BSDF_GGX || b.type == KZ_BSDF_KAZENSTANDARD;
         if ((b.albedoTex && !takesAlbedo) || ((b.roughnessTex || b.metallicTex) && b.type != KZ_BSDF_KAZENSTANDARD) || (b.normalTex && b.type != KZ_BSDF_NORMALMAP))
-            return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u (type %d): a texture id is set on a parameter this model does not read through a texture", who, i, b.type);
+            return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u (type %d): a texture id is set on a parameter this model does not read through a texture", i, b.type);
         const bool rough = b.type == KZ_BSDF_ROUGHCONDUCTOR || b.type == KZ_BSDF_ROUGHPLASTIC || b.type == KZ_BSDF_ROUGHDIELECTRIC;
         if ((b.alphaResolved != 0 && b.alphaResolved != 1) || (b.alphaResolved && !rough))
-            return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u (type %d): alphaResolved = %d (0 or 1, and only roughconductor / roughplastic / roughdielectric rows have a resolved alpha)", who, i, b.type, b.alphaResolved);
+            return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u (type %d): alphaResolved = %d (0 or 1, and only roughconductor / roughplastic / roughdielectric rows have a resolved alpha)", i, b.type, b.alphaResolved);
         // path_mats hands the BSDF a record whose intersection is default-constructed (integrator.cpp:168-170): a normal map would read a frame that
         // was never set (LAB_NOTES H16)
         if (b.type == KZ_BSDF_NORMALMAP && integ == KZ_INTEGRATOR_PATH_MATS)
-            return kz_fail(KZ_ERR_UNSUPPORTED, "%sbsdf %u is a normalmap: path_mats does not support normal maps (its BSDF record carries no intersection frame)", who, i);
+            return kz_fail(KZ_ERR_UNSUPPORTED, "bsdf %u is a normalmap: path_mats does not support normal maps (its BSDF record carries no intersection frame)", i);
         if (b.type == KZ_BSDF_NORMALMAP) {                  // bsdf.cpp:391-404: one texture child + one nested BSDF
-            if (b.normalTex == 0) return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u: normalmap without a normal texture", who, i);
+            if (b.normalTex == 0) return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u: normalmap without a normal texture", i);
             if (b.nested < 0 || b.nested >= (int32_t)n || rows[b.nested].type == KZ_BSDF_NORMALMAP)
-                return kz_fail(KZ_ERR_INVALID_ARG, "%sbsdf %u: normalmap needs a nested BSDF row that is not itself a normalmap (got %d)", who, i, b.nested);
+                return kz_fail(KZ_ERR_INVALID_ARG, "bsdf %u: normalmap needs a nested BSDF row that is not itself a normalmap (got %d)", i, b.nested);
         }
     }
     return KZ_OK;
@@ -302,8 +356,12 @@ int32_t kzBsdfExt(const std::vector<KzBSDF> &rows) {
 
 // ---- camera (camera.cpp:35-68). Eigen is not available: the 4x4 product and inverse are formed in
 // double and narrowed once, unless the caller hands over Eigen's own m_sampleToCamera.
-int kzCameraParams(const KzCamera &c, KzParams &p) {
+static int checkCameraType(const KzCamera &c) {
     if (c.type != KZ_CAMERA_PERSPECTIVE && c.type != KZ_CAMERA_THINLENS) return kz_fail(KZ_ERR_UNSUPPORTED, "camera type %d is not supported (\"perspective\", \"thinlens\")", c.type);
+    return KZ_OK;
+}
+int kzCameraParams(const KzCamera &c, KzParams &p) {
+    if (int rc = checkCameraType(c)) return rc;       // (create has asked already, in front of its other checks; an edited camera is asked here)
     p.width = c.width; p.height = c.height;
     p.invW = 1.0f / (float)c.width; p.invH = 1.0f / (float)c.height;
     p.nearClip = c.nearClip; p.farClip = c.farClip;
@@ -354,7 +412,240 @@ bool kzPinholeWords(const KzParams &p, float O[3], float A[3], float U[3], float
     return fin;
 }
 
+// ---- kz_scene_create, stage by stage ---------------------------------------------------------------------------------------------------------------
+// Each stage reads the description, fills its part of the scene and refuses what it cannot take. The stages run in the order in which a description that is
+// wrong in two ways has always been answered (tests/test_scene_create_cpu.py holds it), which is why a later stage's checks of the description alone - the
+// background's texture, the pmj02bn tables - stand in their stage and not in front with checkDescription's.
 namespace {
+
+// what can be refused before there is a scene: plugin types outside the hot path are an error, never a silent fallback
+int checkDescription(const KzSceneDesc *d) {
+    if (d->abiVersion != KZ_ABI_VERSION) return kz_fail(KZ_ERR_INVALID_ARG, "ABI version %u, library is %u", d->abiVersion, KZ_ABI_VERSION);
+    if (int rc = checkCameraType(d->camera)) return rc;
+    const int32_t integ = d->integrator.type;
+    if (integ != KZ_INTEGRATOR_PATH_MIS && integ != KZ_INTEGRATOR_NORMALS && integ != KZ_INTEGRATOR_AO && integ != KZ_INTEGRATOR_PATH_MATS)
+        return kz_fail(KZ_ERR_UNSUPPORTED, "integrator type %d is not on the hot path (\"path_mis\", \"normals\", \"ao\", \"path_mats\")", integ);
+    if (d->sampler.type < KZ_SAMPLER_INDEPENDENT || d->sampler.type > KZ_SAMPLER_CORRELATED)
+        return kz_fail(KZ_ERR_UNSUPPORTED, "sampler type %d is not supported (\"independent\", \"pmj02bn\", \"stratified\", \"correlated\")", d->sampler.type);
+    if (d->sampler.type == KZ_SAMPLER_STRATIFIED && (d->sampler.resolution < 1 || d->sampler.resolution > 256)) return kz_fail(KZ_ERR_INVALID_ARG, "stratified resolution %d", d->sampler.resolution);
+    if (d->sampler.sampleCount > 65536) return kz_fail(KZ_ERR_UNSUPPORTED, "sampleCount %u (limit 65536)", d->sampler.sampleCount);
+    if (d->camera.rfilter.type < KZ_FILTER_GAUSSIAN || d->camera.rfilter.type > KZ_FILTER_BOX) return kz_fail(KZ_ERR_UNSUPPORTED, "rfilter type %d", d->camera.rfilter.type);
+    if (d->camera.width <= 0 || d->camera.height <= 0 || d->camera.width > 65535 || d->camera.height > 65535) return kz_fail(KZ_ERR_INVALID_ARG, "image size %dx%d", d->camera.width, d->camera.height);
+    if (d->sampler.sampleCount == 0) return kz_fail(KZ_ERR_INVALID_ARG, "sampleCount is 0");
+    if (!(d->camera.rfilter.radius > 0.f) || d->camera.rfilter.radius > 4.0f) return kz_fail(KZ_ERR_UNSUPPORTED, "filter radius %g (supported: (0, 4])", d->camera.rfilter.radius);
+    if ((d->nMeshes && !d->meshes) || (d->nBsdfs && !d->bsdfs) || (d->nLights && !d->lights)) return kz_fail(KZ_ERR_INVALID_ARG, "null table with non-zero count");
+    if ((d->nTextures && !d->textures) || (d->nImages && !d->images)) return kz_fail(KZ_ERR_INVALID_ARG, "null texture/image table with non-zero count");
+    return kzCheckBsdfs(d->bsdfs, d->nBsdfs, d->nTextures, integ);
+}
+
+// BSDF rows, and meshes into shading records, mesh rows and light rows; (mesh, face) order = Embree geomID / primID order (accel.cpp:40-55)
+int geometry(const KzSceneDesc *d, KzScene *sc) {
+    sc->bsdfs.assign(d->bsdfs, d->bsdfs + d->nBsdfs);
+    for (KzBSDF &b : sc->bsdfs) kzResolveBsdf(b);         // (the rough models' alpha, formed once)
+    sc->nDescBsdfs = d->nBsdfs; sc->nDescLights = d->nLights;
+    int defaultBsdf = -1;
+    size_t totalF = 0;
+    for (uint32_t m = 0; m < d->nMeshes; ++m) totalF += d->meshes[m].nF;
+    if (totalF >= (1ull << 28)) return kz_fail(KZ_ERR_UNSUPPORTED, "%zu triangles (limit 2^28)", totalF);
+    sc->shade.reserve(totalF); sc->triVtx.reserve(3 * totalF);
+    uint32_t gid = 0;
+    for (uint32_t m = 0; m < d->nMeshes; ++m) {
+        const KzMesh &km = d->meshes[m];
+        if (!km.V || !km.F) return kz_fail(KZ_ERR_INVALID_ARG, "mesh %u has no V/F", m);
+        if (km.bsdf >= (int)d->nBsdfs || km.light >= (int)d->nLights || km.bsdf < -1 || km.light < -1) return kz_fail(KZ_ERR_INVALID_ARG, "mesh %u: bsdf/light index out of range", m);
+        KzMeshRow row; std::memset(&row, 0, sizeof row);
+        row.bsdf = km.bsdf;
+        if (km.bsdf < 0) {      // Mesh::activate instantiates a default Diffuse (mesh.cpp:25-28, albedo 0.5 bsdf.cpp:23)
+            if (defaultBsdf < 0) {
+                KzBSDF b; std::memset(&b, 0, sizeof b);
+                b.type = KZ_BSDF_DIFFUSE; b.albedo[0] = b.albedo[1] = b.albedo[2] = 0.5f;
+                defaultBsdf = (int)sc->bsdfs.size(); sc->bsdfs.push_back(b);
+            }
+            row.bsdf = defaultBsdf;
+        }
+        row.light = km.light >= 0 ? (int32_t)sc->lightRows.size() : -1;      // the row pushed below
+        row.flags = (km.N ? 1u : 0u) | (km.UV ? 2u : 0u);
+        row.triOffset = gid; row.nF = km.nF;
+        for (uint32_t f = 0; f < km.nF; ++f, ++gid) {
+            const uint32_t idx[3] = {km.F[3 * f], km.F[3 * f + 1], km.F[3 * f + 2]};
+            KzTriShade s; std::memset(&s, 0, sizeof s);
+            s.mesh = m; s.prim = f; s.bsdf = (uint32_t)row.bsdf; s.lightFlags = ((uint32_t)(row.light + 1) << 2) | row.flags;
+            for (int v = 0; v < 3; ++v) {
+                if (idx[v] >= km.nV) return kz_fail(KZ_ERR_INVALID_ARG, "mesh %u face %u: vertex index %u >= %u", m, f, idx[v], km.nV);
+                if (km.UV) { s.uv[2 * v] = km.UV[2 * (size_t)idx[v]]; s.uv[2 * v + 1] = km.UV[2 * (size_t)idx[v] + 1]; }
+            }
+            faceToShade(s, idx, km.V, km.N);              // (as an edit of the mesh forms them again: kzMeshToShade)
+            sc->shade.push_back(s);
+            sc->triVtx.insert(sc->triVtx.end(), idx, idx + 3);
+        }
+        sc->meshRows.push_back(row);
+        sc->meshNV.push_back(km.nV);
+        // ---- light rows + area CDF (scene.cpp:42-46, mesh.cpp:24-45, dpdf.h:35-37,77-89)
+        if (km.light >= 0) {
+            KzLightRow lr; std::memset(&lr, 0, sizeof lr);
+            kzLightRowValue(lr, d->lights[km.light]);
+            while (sc->cdf.size() & 3u) sc->cdf.push_back(2.0f);            // every light's table starts on a 16-B boundary (cdfSample reads short tables as float4s)
+            lr.mesh = m; lr.triOffset = row.triOffset; lr.nF = km.nF; lr.cdfOffset = (uint32_t)sc->cdf.size(); lr.hasN = km.N ? 1u : 0u;
+            std::vector<float> t;
+            kzLightCdf(&sc->shade[row.triOffset], km.nF, t, lr.normalization);
+            sc->cdf.insert(sc->cdf.end(), t.begin(), t.end());
+            sc->lightRows.push_back(lr);
+            sc->lightDesc.push_back((uint32_t)km.light);
+        }
+    }
+    sc->cdf.insert(sc->cdf.end(), 8, 2.0f);          // padding: the device reads eight entries of a short table at once (cdfSample)
+    KzParams &p = sc->prm;
+    p.bsdfExt = kzBsdfExt(sc->bsdfs);                // (over the default row too)
+    p.nLights = (uint32_t)sc->lightRows.size();      // scene.h:45-56
+    p.lightPickPdf = p.nLights ? 1.f / (float)p.nLights : 0.f;
+    p.lightPickScale = (p.nLights && (p.nLights & (p.nLights - 1)) == 0) ? (float)p.nLights : 0.f;
+    return KZ_OK;
+}
+
+// the BVH2 over the shading records' triangles, its BVH4 collapse and the words the traversal kernels start from
+int acceleration(const KzSceneDesc *, KzScene *sc) {
+    std::vector<KzBuildTri> bt(sc->shade.size());
+    for (size_t g = 0; g < bt.size(); ++g) {
+        const KzTriShade &s = sc->shade[g];
+        std::memcpy(bt[g].v, s.p, sizeof s.p);
+        bt[g].mesh = s.mesh; bt[g].prim = s.prim; bt[g].gid = (uint32_t)g;
+    }
+    KzParams &p = sc->prm;
+    std::string berr;
+    uint32_t rootRef = 0xFFFFFFFFu;
+    int rc = kz_build_bvh(bt, sc->nodes, sc->tris, rootRef, sc->bvh, berr);
+    if (rc != KZ_OK) return kz_fail(rc, "BVH build: %s", berr.c_str());
+    p.rootRef = rootRef;
+    int sb = 1; uint32_t r4 = rootRef;
+    rc = kz_collapse_bvh4(sc->nodes, rootRef, sc->nodes4, r4, sb, &sc->slotSrc);
+    if (rc != KZ_OK) return kz_fail(rc, "BVH4 collapse failed");
+    // (the kernels address a packet as table base + a 32-bit byte offset, kz_devfn.h kzNode4Ptr)
+    if (sc->nodes4.size() > (size_t(1) << 26)) return kz_fail(KZ_ERR_UNSUPPORTED, "scene too large: %zu BVH4 packets (limit 2^26 = 4 GB of packets)", sc->nodes4.size());
+    p.rootRef4 = r4; p.stackBound4 = sb;
+    p.stackDepth = (int32_t)std::max<uint32_t>(2u, sc->bvh.maxDepth + 1);
+    return KZ_OK;
+}
+
+// the camera words, and its film filter's table (block.cpp:13-21)
+int cameraAndFilter(const KzSceneDesc *d, KzScene *sc) {
+    KzParams &p = sc->prm;
+    if (int rc = kzCameraParams(d->camera, p)) return rc;
+    const KzFilter &rf = sc->rfilter = d->camera.rfilter;
+    p.filterRadius = rf.radius;
+    p.border = (int)std::ceil(rf.radius - 0.5f);
+    for (int i = 0; i < KZ_FILTER_RESOLUTION; ++i) sc->filter[i] = filterEval(rf, (rf.radius * i) / KZ_FILTER_RESOLUTION);
+    sc->filter[KZ_FILTER_RESOLUTION] = 0.0f;
+    p.lookupFactor = KZ_FILTER_RESOLUTION / rf.radius;
+    // source pixels px that can reach film pixel fx satisfy px-(fx-border) in (-r-0.5, r+0.5]
+    p.tapLo = (int)std::floor(-rf.radius - 0.5f) + 1;
+    p.tapHi = (int)std::floor(rf.radius + 0.5f);
+    if (p.tapHi - p.tapLo + 1 > KZ_MAX_FILTER_TAPS) return kz_fail(KZ_ERR_UNSUPPORTED, "filter radius %g needs too many taps", rf.radius);
+    return KZ_OK;
+}
+
+// integrator.cpp:187-193. normals / ao / path_mats read no properties (integrator.cpp:13, :40, :139): maxDepth is then 1 for normals and ao (the camera ray
+// is traced) and the 512-bounce cap of path_mats (LAB_NOTES H15); traceBias is unused by them
+int integrator(const KzSceneDesc *d, KzScene *sc) {
+    KzParams &p = sc->prm;
+    const int32_t integ = d->integrator.type;
+    p.integrator = integ;
+    if (integ == KZ_INTEGRATOR_PATH_MIS) {
+        p.maxDepth = std::min(KZ_PATH_MIS_MAX_DEPTH, d->integrator.maxDepth);
+        p.traceBias = d->integrator.traceBias;
+        p.regularization = d->integrator.regularization ? 1 : 0;
+        p.accumulatedRoughness = d->integrator.accumulatedRoughness;
+    } else {
+        p.maxDepth = integ == KZ_INTEGRATOR_PATH_MATS ? KZ_PATH_MATS_MAX_DEPTH : 1;
+        p.traceBias = 1e-5f; p.regularization = 0; p.accumulatedRoughness = 0.f;
+    }
+    return KZ_OK;
+}
+
+// texture.cpp:121-126. The nested texture by DIRECTION (texture.cpp:20-22, 66-80, texture.h:13): constant -> colour, image -> environment lookup,
+// colorramp / blend -> 0
+int background(const KzSceneDesc *d, KzScene *sc) {
+    KzParams &p = sc->prm;
+    p.bgPresent = d->background.present ? 1 : 0;
+    p.bgImage = -1; p.bgIntensity = d->background.intensity;
+    float col[3] = {d->background.color[0], d->background.color[1], d->background.color[2]};
+    if (d->background.present && d->background.texture != 0) {
+        const int32_t t = d->background.texture - 1;
+        if (t < 0 || (uint32_t)t >= d->nTextures) return kz_fail(KZ_ERR_INVALID_ARG, "background texture id %d out of range", d->background.texture);
+        const KzTexture &k = d->textures[t];
+        if (k.type == KZ_TEX_CONSTANT) { col[0] = k.color[0]; col[1] = k.color[1]; col[2] = k.color[2]; }
+        else if (k.type == KZ_TEX_IMAGE) {
+            if (k.image < 0 || (uint32_t)k.image >= d->nImages) return kz_fail(KZ_ERR_INVALID_ARG, "background image index %d out of range", k.image);
+            if (k.filter != KZ_TEXFILTER_BILINEAR && k.filter != KZ_TEXFILTER_BICUBIC) return kz_fail(KZ_ERR_INVALID_ARG, "background texture: filter %d", k.filter);
+            p.bgImage = k.image; p.bgFilter = k.filter; col[0] = col[1] = col[2] = 0.f;
+        } else col[0] = col[1] = col[2] = 0.f;
+    }
+    for (int a = 0; a < 3; ++a) p.bgRadiance[a] = d->background.present ? d->background.intensity * col[a] : 0.f;
+    return KZ_OK;
+}
+
+int sampler(const KzSceneDesc *d, KzScene *sc) {
+    KzParams &p = sc->prm;
+    p.samplerType = d->sampler.type;
+    p.seed = d->sampler.seed;
+    p.sampleCount = d->sampler.sampleCount;
+    p.resX = p.resY = 1;
+    if (d->sampler.type == KZ_SAMPLER_STRATIFIED) {                       // Stratified ctor, sampler.cpp:84-92
+        int res = d->sampler.resolution;
+        while ((uint32_t)(res * res) < p.sampleCount) res++;
+        p.resX = p.resY = res; p.sampleCount = (uint32_t)(res * res);
+    }
+    if (d->sampler.type == KZ_SAMPLER_CORRELATED) {                       // Correlated ctor, sampler.cpp:179-187
+        int r1 = (int)std::sqrt((double)p.sampleCount);
+        int r0 = (int)((p.sampleCount + r1 - 1) / r1);
+        p.resX = r0; p.resY = r1; p.sampleCount = (uint32_t)(r0 * r1);
+    }
+    if (d->sampler.type == KZ_SAMPLER_PMJ02BN) {
+        if (!d->sampler.pmj02bnSamples || !d->sampler.blueNoise) return kz_fail(KZ_ERR_INVALID_ARG, "pmj02bn sampler without its tables");
+        if (p.sampleCount > KZ_PMJ02BN_SAMPLES) p.sampleCount = KZ_PMJ02BN_SAMPLES;               // sampler.cpp:284-287
+        // the device reads both tables as the floats the reference's accessors return: the conversions (pmj02table.h:28-29 in double then
+        // narrowed; bluenoise.h:22 an fp32 division) are done here, once, with the same IEEE operations
+        const size_t nPmj = (size_t)KZ_PMJ02BN_SETS * KZ_PMJ02BN_SAMPLES * 2, nBn = (size_t)KZ_BLUENOISE_TEXTURES * KZ_BLUENOISE_RES * KZ_BLUENOISE_RES;
+        sc->pmj.resize(nPmj); sc->bn.resize(nBn);
+        for (size_t i = 0; i < nPmj; ++i) sc->pmj[i] = (float)((double)d->sampler.pmj02bnSamples[i] * 0x1p-32);
+        for (size_t i = 0; i < nBn; ++i) sc->bn[i] = (float)d->sampler.blueNoise[i] / 65535.f;
+        // PMJ02BN constructor: sort set 0 into a tile x tile x spp pixel table (sampler.cpp:291-309)
+        uint32_t spp = p.sampleCount;
+        int tile = pmjPixelTile(spp);
+        p.pixelTileSize = tile;
+        sc->pixelSamples.assign((size_t)tile * tile * spp * 2, 0.f);
+        std::vector<uint32_t> nStored((size_t)tile * tile, 0);
+        for (int i = 0; i < KZ_PMJ02BN_SAMPLES; ++i) {
+            float x = sc->pmj[2 * (size_t)i], y = sc->pmj[2 * (size_t)i + 1];
+            x *= tile; y *= tile;
+            int ix = (int)x, iy = (int)y;
+            if (ix >= tile || iy >= tile) return kz_fail(KZ_ERR_INVALID_ARG, "pmj02bn table entry %d rounds to 1.0f (the reference would index out of range)", i);
+            size_t po = (size_t)ix + (size_t)iy * tile;
+            if (nStored[po] == spp) continue;
+            size_t so = po * spp + nStored[po];
+            sc->pixelSamples[2 * so] = x - std::floor(x);
+            sc->pixelSamples[2 * so + 1] = y - std::floor(y);
+            ++nStored[po];
+        }
+    } else {
+        // pcg32::advance(sampleIndex*65536) as an affine map state' = mult*state + inc*plus (pcg32.h:145-166)
+        sc->jump.resize(p.sampleCount);
+        for (uint32_t s = 0; s < p.sampleCount; ++s) {
+            uint64_t cur_mult = PCG32_MULT, cur_plus = 1u, acc_mult = 1u, acc_plus = 0u;
+            uint64_t delta = (uint64_t)s * 65536ull;
+            while (delta > 0) {
+                if (delta & 1) { acc_mult *= cur_mult; acc_plus = acc_plus * cur_mult + cur_plus; }
+                cur_plus = (cur_mult + 1) * cur_plus;
+                cur_mult *= cur_mult;
+                delta /= 2;
+            }
+            sc->jump[s].mult = acc_mult; sc->jump[s].plus = acc_plus;
+        }
+    }
+    p.sppPow2 = (p.sampleCount & (p.sampleCount - 1)) == 0 ? 1 : 0;
+    p.invSpp = 1.0f / (float)p.sampleCount;
+    return KZ_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -388,226 +679,23 @@ int kz_build_flags(void) {
 int kz_scene_create(const KzSceneDesc *d, KzScene **out) {
     if (!d || !out) return kz_fail(KZ_ERR_INVALID_ARG, "kz_scene_create: null argument");
     *out = nullptr;
-    if (d->abiVersion != KZ_ABI_VERSION) return kz_fail(KZ_ERR_INVALID_ARG, "ABI version %u, library is %u", d->abiVersion, KZ_ABI_VERSION);
-    // plugin types outside the hot path are an error, never a silent fallback
-    if (d->camera.type != KZ_CAMERA_PERSPECTIVE && d->camera.type != KZ_CAMERA_THINLENS) return kz_fail(KZ_ERR_UNSUPPORTED, "camera type %d is not supported (\"perspective\", \"thinlens\")", d->camera.type);
-    const int32_t integ = d->integrator.type;
-    if (integ != KZ_INTEGRATOR_PATH_MIS && integ != KZ_INTEGRATOR_NORMALS && integ != KZ_INTEGRATOR_AO && integ != KZ_INTEGRATOR_PATH_MATS)
-        return kz_fail(KZ_ERR_UNSUPPORTED, "integrator type %d is not on the hot path (\"path_mis\", \"normals\", \"ao\", \"path_mats\")", integ);
-    if (d->sampler.type < KZ_SAMPLER_INDEPENDENT || d->sampler.type > KZ_SAMPLER_CORRELATED)
-        return kz_fail(KZ_ERR_UNSUPPORTED, "sampler type %d is not supported (\"independent\", \"pmj02bn\", \"stratified\", \"correlated\")", d->sampler.type);
-    if (d->sampler.type == KZ_SAMPLER_STRATIFIED && (d->sampler.resolution < 1 || d->sampler.resolution > 256)) return kz_fail(KZ_ERR_INVALID_ARG, "stratified resolution %d", d->sampler.resolution);
-    if (d->sampler.sampleCount > 65536) return kz_fail(KZ_ERR_UNSUPPORTED, "sampleCount %u (limit 65536)", d->sampler.sampleCount);
-    if (d->camera.rfilter.type < KZ_FILTER_GAUSSIAN || d->camera.rfilter.type > KZ_FILTER_BOX) return kz_fail(KZ_ERR_UNSUPPORTED, "rfilter type %d", d->camera.rfilter.type);
-    if (d->camera.width <= 0 || d->camera.height <= 0 || d->camera.width > 65535 || d->camera.height > 65535) return kz_fail(KZ_ERR_INVALID_ARG, "image size %dx%d", d->camera.width, d->camera.height);
-    if (d->sampler.sampleCount == 0) return kz_fail(KZ_ERR_INVALID_ARG, "sampleCount is 0");
-    if (!(d->camera.rfilter.radius > 0.f) || d->camera.rfilter.radius > 4.0f) return kz_fail(KZ_ERR_UNSUPPORTED, "filter radius %g (supported: (0, 4])", d->camera.rfilter.radius);
-    if ((d->nMeshes && !d->meshes) || (d->nBsdfs && !d->bsdfs) || (d->nLights && !d->lights)) return kz_fail(KZ_ERR_INVALID_ARG, "null table with non-zero count");
-    if ((d->nTextures && !d->textures) || (d->nImages && !d->images)) return kz_fail(KZ_ERR_INVALID_ARG, "null texture/image table with non-zero count");
-    { const int brc = kzCheckBsdfs("", d->bsdfs, d->nBsdfs, d->nTextures, integ); if (brc != KZ_OK) return brc; }
-
-    KzScene *sc = new KzScene();
+    int rc = checkDescription(d);
+    if (rc != KZ_OK) return rc;
+    std::unique_ptr<KzScene> sc(new KzScene());           // (a stage that refuses takes the scene with it)
     std::memset(&sc->prm, 0, sizeof sc->prm);
-    sc->bsdfs.assign(d->bsdfs, d->bsdfs + d->nBsdfs);
-    for (KzBSDF &b : sc->bsdfs) kzResolveBsdf(b);         // (the rough models' alpha, formed once)
-    sc->nDescBsdfs = d->nBsdfs; sc->nDescLights = d->nLights;
-    { int trc = flattenTextures(d, sc); if (trc != KZ_OK) { delete sc; return trc; } }
-    int defaultBsdf = -1;
-
-    // ---- geometry: (mesh, face) order = Embree geomID / primID order (accel.cpp:40-55)
-    std::vector<KzBuildTri> bt;
-    size_t totalF = 0;
-    for (uint32_t m = 0; m < d->nMeshes; ++m) totalF += d->meshes[m].nF;
-    if (totalF >= (1ull << 28)) { delete sc; return kz_fail(KZ_ERR_UNSUPPORTED, "%zu triangles (limit 2^28)", totalF); }
-    bt.reserve(totalF); sc->shade.reserve(totalF); sc->triVtx.reserve(3 * totalF);
-    uint32_t gid = 0;
-    for (uint32_t m = 0; m < d->nMeshes; ++m) {
-        const KzMesh &km = d->meshes[m];
-        if (!km.V || !km.F) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "mesh %u has no V/F", m); }
-        if (km.bsdf >= (int)d->nBsdfs || km.light >= (int)d->nLights || km.bsdf < -1 || km.light < -1) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "mesh %u: bsdf/light index out of range", m); }
-        KzMeshRow row; std::memset(&row, 0, sizeof row);
-        row.bsdf = km.bsdf; row.light = -1;
-        if (km.bsdf < 0) {      // Mesh::activate instantiates a default Diffuse (mesh.cpp:25-28, albedo 0.5 bsdf.cpp:23)
-            if (defaultBsdf < 0) {
-                KzBSDF b; std::memset(&b, 0, sizeof b);
-                b.type = KZ_BSDF_DIFFUSE; b.albedo[0] = b.albedo[1] = b.albedo[2] = 0.5f;
-                defaultBsdf = (int)sc->bsdfs.size(); sc->bsdfs.push_back(b);
-            }
-            row.bsdf = defaultBsdf;
-        }
-        row.flags = (km.N ? 1u : 0u) | (km.UV ? 2u : 0u);
-        row.triOffset = gid; row.nF = km.nF;
-        const int32_t lightRow = km.light >= 0 ? (int32_t)sc->lightRows.size() : -1;      // the row pushed below
-        for (uint32_t f = 0; f < km.nF; ++f, ++gid) {
-            uint32_t idx[3] = {km.F[3 * f], km.F[3 * f + 1], km.F[3 * f + 2]};
-            KzBuildTri t; t.mesh = m; t.prim = f; t.gid = gid;
-            KzTriShade s; std::memset(&s, 0, sizeof s);
-            s.mesh = m; s.prim = f; s.bsdf = (uint32_t)row.bsdf; s.lightFlags = ((uint32_t)(lightRow + 1) << 2) | row.flags;
-            for (int v = 0; v < 3; ++v) {
-                if (idx[v] >= km.nV) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "mesh %u face %u: vertex index %u >= %u", m, f, idx[v], km.nV); }
-                for (int a = 0; a < 3; ++a) {
-                    t.v[v][a] = km.V[3 * (size_t)idx[v] + a];
-                    s.p[3 * v + a] = t.v[v][a];
-                    if (km.N) s.n[3 * v + a] = km.N[3 * (size_t)idx[v] + a];
-                }
-                if (km.UV) { s.uv[2 * v] = km.UV[2 * (size_t)idx[v]]; s.uv[2 * v + 1] = km.UV[2 * (size_t)idx[v] + 1]; }
-            }
-            bt.push_back(t); sc->shade.push_back(s);
-            sc->triVtx.insert(sc->triVtx.end(), idx, idx + 3);
-        }
-        // ---- light rows + area CDF (scene.cpp:42-46, mesh.cpp:24-45, dpdf.h:35-37,77-89)
-        if (km.light >= 0) {
-            const KzLight &kl = d->lights[km.light];
-            KzLightRow lr; std::memset(&lr, 0, sizeof lr);
-            for (int a = 0; a < 3; ++a) lr.radiance[a] = kl.intensity * kl.color[a];
-            lr.primaryVisibility = kl.primaryVisibility ? 1 : 0;
-            while (sc->cdf.size() & 3u) sc->cdf.push_back(2.0f);            // every light's table starts on a 16-B boundary (cdfSample reads short tables as float4s)
-            lr.mesh = m; lr.triOffset = row.triOffset; lr.nF = km.nF; lr.cdfOffset = (uint32_t)sc->cdf.size(); lr.hasN = km.N ? 1u : 0u;
-            std::vector<float> t;
-            kzLightCdf(&sc->shade[row.triOffset], km.nF, t, lr.normalization);
-            sc->cdf.insert(sc->cdf.end(), t.begin(), t.end());
-            row.light = (int32_t)sc->lightRows.size();
-            sc->lightRows.push_back(lr);
-            sc->lightDesc.push_back((uint32_t)km.light);
-        }
-        sc->meshRows.push_back(row);
-        sc->meshNV.push_back(km.nV);
-    }
-    sc->cdf.insert(sc->cdf.end(), 8, 2.0f);          // padding: the device reads eight entries of a short table at once (cdfSample)
-    std::string berr;
-    uint32_t rootRef = 0xFFFFFFFFu;
-    int rc = kz_build_bvh(bt, sc->nodes, sc->tris, rootRef, sc->bvh, berr);
-    if (rc != KZ_OK) { delete sc; return kz_fail(rc, "BVH build: %s", berr.c_str()); }
-
-    KzParams &p = sc->prm;
-    p.rootRef = rootRef;
-    { int sb = 1; uint32_t r4 = rootRef;
-      rc = kz_collapse_bvh4(sc->nodes, rootRef, sc->nodes4, r4, sb, &sc->slotSrc);
-      if (rc != KZ_OK) { delete sc; return kz_fail(rc, "BVH4 collapse failed"); }
-      // (the kernels address a packet as table base + a 32-bit byte offset, kz_devfn.h kzNode4Ptr)
-      if (sc->nodes4.size() > (size_t(1) << 26)) { delete sc; return kz_fail(KZ_ERR_UNSUPPORTED, "scene too large: %zu BVH4 packets (limit 2^26 = 4 GB of packets)", sc->nodes4.size()); }
-      p.rootRef4 = r4; p.stackBound4 = sb; }
-    p.stackDepth = (int32_t)std::max<uint32_t>(2u, sc->bvh.maxDepth + 1);
-    p.bsdfExt = kzBsdfExt(sc->bsdfs);
-    kzInvisibleLights(sc);
-    const KzCamera &c = d->camera;
-    if ((rc = kzCameraParams(c, p)) != KZ_OK) { delete sc; return rc; }
-    sc->rfilter = c.rfilter;
-    // ---- film filter table (block.cpp:13-21)
-    const KzFilter &rf = c.rfilter;
-    p.filterRadius = rf.radius;
-    p.border = (int)std::ceil(rf.radius - 0.5f);
-    for (int i = 0; i < KZ_FILTER_RESOLUTION; ++i) sc->filter[i] = filterEval(rf, (rf.radius * i) / KZ_FILTER_RESOLUTION);
-    sc->filter[KZ_FILTER_RESOLUTION] = 0.0f;
-    p.lookupFactor = KZ_FILTER_RESOLUTION / rf.radius;
-    // source pixels px that can reach film pixel fx satisfy px-(fx-border) in (-r-0.5, r+0.5]
-    p.tapLo = (int)std::floor(-rf.radius - 0.5f) + 1;
-    p.tapHi = (int)std::floor(rf.radius + 0.5f);
-    if (p.tapHi - p.tapLo + 1 > KZ_MAX_FILTER_TAPS) { delete sc; return kz_fail(KZ_ERR_UNSUPPORTED, "filter radius %g needs too many taps", rf.radius); }
-    // ---- integrator (integrator.cpp:187-193). normals / ao / path_mats read no properties (integrator.cpp:13, :40, :139): maxDepth is then 1 for
-    // normals and ao (the camera ray is traced) and the 512-bounce cap of path_mats (LAB_NOTES H15); traceBias is unused by them
-    p.integrator = integ;
-    if (integ == KZ_INTEGRATOR_PATH_MIS) {
-        p.maxDepth = std::min(KZ_PATH_MIS_MAX_DEPTH, d->integrator.maxDepth);
-        p.traceBias = d->integrator.traceBias;
-        p.regularization = d->integrator.regularization ? 1 : 0;
-        p.accumulatedRoughness = d->integrator.accumulatedRoughness;
-    } else {
-        p.maxDepth = integ == KZ_INTEGRATOR_PATH_MATS ? KZ_PATH_MATS_MAX_DEPTH : 1;
-        p.traceBias = 1e-5f; p.regularization = 0; p.accumulatedRoughness = 0.f;
-    }
-    // ---- lights / background (scene.h:45-56, texture.cpp:121-126)
-    p.nLights = (uint32_t)sc->lightRows.size();
-    p.lightPickPdf = p.nLights ? 1.f / (float)p.nLights : 0.f;
-    p.lightPickScale = (p.nLights && (p.nLights & (p.nLights - 1)) == 0) ? (float)p.nLights : 0.f;
-    p.bgPresent = d->background.present ? 1 : 0;
-    p.bgImage = -1; p.bgIntensity = d->background.intensity;
-    {
-        // the nested texture by DIRECTION (texture.cpp:20-22, 66-80, texture.h:13): constant -> colour, image -> environment lookup,
-        // colorramp / blend -> 0
-        float col[3] = {d->background.color[0], d->background.color[1], d->background.color[2]};
-        if (d->background.present && d->background.texture != 0) {
-            const int32_t t = d->background.texture - 1;
-            if (t < 0 || (uint32_t)t >= d->nTextures) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "background texture id %d out of range", d->background.texture); }
-            const KzTexture &k = d->textures[t];
-            if (k.type == KZ_TEX_CONSTANT) { col[0] = k.color[0]; col[1] = k.color[1]; col[2] = k.color[2]; }
-            else if (k.type == KZ_TEX_IMAGE) {
-                if (k.image < 0 || (uint32_t)k.image >= d->nImages) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "background image index %d out of range", k.image); }
-                if (k.filter != KZ_TEXFILTER_BILINEAR && k.filter != KZ_TEXFILTER_BICUBIC) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "background texture: filter %d", k.filter); }
-                p.bgImage = k.image; p.bgFilter = k.filter; col[0] = col[1] = col[2] = 0.f;
-            } else col[0] = col[1] = col[2] = 0.f;
-        }
-        for (int a = 0; a < 3; ++a) p.bgRadiance[a] = d->background.present ? d->background.intensity * col[a] : 0.f;
-    }
-    kzEmitterTris(sc);                   // (again, now that the integrator and the background are known)
-    // ---- sampler
-    p.samplerType = d->sampler.type;
-    p.seed = d->sampler.seed;
-    p.sampleCount = d->sampler.sampleCount;
-    p.resX = p.resY = 1;
-    if (d->sampler.type == KZ_SAMPLER_STRATIFIED) {                       // Stratified ctor, sampler.cpp:84-92
-        int res = d->sampler.resolution;
-        while ((uint32_t)(res * res) < p.sampleCount) res++;
-        p.resX = p.resY = res; p.sampleCount = (uint32_t)(res * res);
-    }
-    if (d->sampler.type == KZ_SAMPLER_CORRELATED) {                       // Correlated ctor, sampler.cpp:179-187
-        int r1 = (int)std::sqrt((double)p.sampleCount);
-        int r0 = (int)((p.sampleCount + r1 - 1) / r1);
-        p.resX = r0; p.resY = r1; p.sampleCount = (uint32_t)(r0 * r1);
-    }
-    if (d->sampler.type == KZ_SAMPLER_PMJ02BN) {
-        if (!d->sampler.pmj02bnSamples || !d->sampler.blueNoise) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "pmj02bn sampler without its tables"); }
-        if (p.sampleCount > KZ_PMJ02BN_SAMPLES) p.sampleCount = KZ_PMJ02BN_SAMPLES;               // sampler.cpp:284-287
-        // the device reads both tables as the floats the reference's accessors return: the conversions (pmj02table.h:28-29 in double then
-        // narrowed; bluenoise.h:22 an fp32 division) are done here, once, with the same IEEE operations
-        const size_t nPmj = (size_t)KZ_PMJ02BN_SETS * KZ_PMJ02BN_SAMPLES * 2, nBn = (size_t)KZ_BLUENOISE_TEXTURES * KZ_BLUENOISE_RES * KZ_BLUENOISE_RES;
-        sc->pmj.resize(nPmj); sc->bn.resize(nBn);
-        for (size_t i = 0; i < nPmj; ++i) sc->pmj[i] = (float)((double)d->sampler.pmj02bnSamples[i] * 0x1p-32);
-        for (size_t i = 0; i < nBn; ++i) sc->bn[i] = (float)d->sampler.blueNoise[i] / 65535.f;
-        // PMJ02BN constructor: sort set 0 into a tile x tile x spp pixel table (sampler.cpp:291-309)
-        uint32_t spp = p.sampleCount;
-        int tile = pmjPixelTile(spp);
-        p.pixelTileSize = tile;
-        sc->pixelSamples.assign((size_t)tile * tile * spp * 2, 0.f);
-        std::vector<uint32_t> nStored((size_t)tile * tile, 0);
-        for (int i = 0; i < KZ_PMJ02BN_SAMPLES; ++i) {
-            float x = sc->pmj[2 * (size_t)i], y = sc->pmj[2 * (size_t)i + 1];
-            x *= tile; y *= tile;
-            int ix = (int)x, iy = (int)y;
-            if (ix >= tile || iy >= tile) { delete sc; return kz_fail(KZ_ERR_INVALID_ARG, "pmj02bn table entry %d rounds to 1.0f (the reference would index out of range)", i); }
-            size_t po = (size_t)ix + (size_t)iy * tile;
-            if (nStored[po] == spp) continue;
-            size_t so = po * spp + nStored[po];
-            sc->pixelSamples[2 * so] = x - std::floor(x);
-            sc->pixelSamples[2 * so + 1] = y - std::floor(y);
-            ++nStored[po];
-        }
-    } else {
-        // pcg32::advance(sampleIndex*65536) as an affine map state' = mult*state + inc*plus (pcg32.h:145-166)
-        sc->jump.resize(p.sampleCount);
-        for (uint32_t s = 0; s < p.sampleCount; ++s) {
-            uint64_t cur_mult = PCG32_MULT, cur_plus = 1u, acc_mult = 1u, acc_plus = 0u;
-            uint64_t delta = (uint64_t)s * 65536ull;
-            while (delta > 0) {
-                if (delta & 1) { acc_mult *= cur_mult; acc_plus = acc_plus * cur_mult + cur_plus; }
-                cur_plus = (cur_mult + 1) * cur_plus;
-                cur_mult *= cur_mult;
-                delta /= 2;
-            }
-            sc->jump[s].mult = acc_mult; sc->jump[s].plus = acc_plus;
-        }
-    }
-    p.sppPow2 = (p.sampleCount & (p.sampleCount - 1)) == 0 ? 1 : 0;
-    p.invSpp = 1.0f / (float)p.sampleCount;
-    kz_device_init(sc);
-    *out = sc;
+    static int (*const stages[])(const KzSceneDesc *, KzScene *) = {flattenTextures, geometry, acceleration, cameraAndFilter, integrator, background, sampler};
+    for (auto stage : stages)
+        if ((rc = stage(d, sc.get())) != KZ_OK) return rc;
+    kzLightTables(sc.get());                              // (once, now that the integrator and the background are known: the emitter rows depend on both)
+    kz_device_init(sc.get());
+    *out = sc.release();
     return KZ_OK;
 }
 
 void kz_scene_destroy(KzScene *scene) {
     if (!scene) return;
+    const std::unique_ptr<KzScene> owner(scene);          // (freed behind its replicas)
     kz_device_release(scene);
-    delete scene;
 }
 
 int kz_scene_bvh_info(const KzScene *scene, KzBvhInfo *out) {

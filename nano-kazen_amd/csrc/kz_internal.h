@@ -241,12 +241,17 @@ int kzMatteRefuse(const KzScene *scene, const KzRenderOpts *opts, const char *ca
 int kzMatteRefuseGather(const KzScene *scene, const char *call);
 // kz_host.cpp
 int kz_fail(int code, const char *fmt, ...);
+int kzFailedIn(const char *call, int code);                             // the last error with "<call>: " in front: a shared check's refusal as an edit reports it
 int kzCameraParams(const KzCamera &c, KzParams &p);                     // the camera part of KzParams (pixel beams included)
 bool kzPinholeWords(const KzParams &p, float O[3], float A[3], float U[3], float V[3]);      // the affine pixel -> near-plane map of p.s2c / p.c2w, whatever the camera's type; false: there is none
+// ... what kz_scene_create and the edits of kz_edit.cpp both form, each stated once
+KzTri kzLeafTri(const KzTriShade &s, uint32_t gid);                     // the leaf-triangle form of a shading record
+void kzMeshToShade(KzScene *sc, uint32_t m, const float *V, const float *N);                          // mesh m's shading records (p, n) from its vertex data through triVtx
+void kzShadeToMesh(const KzScene *sc, uint32_t m, std::vector<float> &V, std::vector<float> &N);      // the inverse: vertex data out of the shading records
+void kzLightRowValue(KzLightRow &lr, const KzLight &kl);                // a light row's radiance and primaryVisibility
 void kzLightCdf(const KzTriShade *shade, uint32_t nF, std::vector<float> &t, float &normalization);   // a light mesh's area CDF (t[0] = 0, nF + 1 entries)
-void kzInvisibleLights(KzScene *sc);                                    // ilTris, ilLo / ilHi, ilGid* and shadowFast from the shading records (and kzEmitterTris)
-void kzEmitterTris(KzScene *sc);                                        // emTris, nEmTris, emLo / emHi from the shading records, the background and the integrator
-int kzCheckBsdfs(const char *who, const KzBSDF *rows, uint32_t n, uint32_t nTextures, int32_t integrator);   // the checks of a whole BSDF row table (kz_scene_create, kz_scene_set_bsdfs)
+void kzLightTables(KzScene *sc);                                        // every table derived from the lights: ilTris, ilLo / ilHi, ilGid*, shadowFast; emTris, nEmTris, emLo / emHi
+int kzCheckBsdfs(const KzBSDF *rows, uint32_t n, uint32_t nTextures, int32_t integrator);   // the checks of a whole BSDF row table (kz_scene_create, kz_scene_set_bsdfs)
 void kzResolveBsdf(KzBSDF &b);                                          // a row as the kernels read it (the rough models' alpha)
 int32_t kzBsdfExt(const std::vector<KzBSDF> &rows);                     // KzParams::bsdfExt of a row table
 

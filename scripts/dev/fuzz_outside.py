@@ -1,4 +1,4 @@
-"""The samples of one fuzz scene whose HIP radiance lies outside the oracle's tie bracket (tests/test_gpu_parity.py tie_bracket), with the BSDF of the
+"""The samples of one fuzz scene whose HIP radiance lies outside the oracle's tie bracket (tests/checks.py tie_bracket), with the BSDF of the
 first hit: python scripts/dev/fuzz_outside.py <seed>"""
 import importlib, os, sys
 import numpy as np
@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 kz = importlib.import_module("nano-kazen_amd")
 import oracle as O
-from test_gpu_parity import _fuzz_scene
+from film_cases import _fuzz_scene
 seed = int(sys.argv[1])
 d = _fuzz_scene(kz.scenes, seed)
 sc = kz.Scene(d, device=0); ora = O.OracleScene(d)

@@ -1,4 +1,4 @@
-"""A wider randomized parity sweep than the CI suite carries (tests/test_gpu_parity.py::_fuzz_scene, other seeds): HIP film vs the CPU oracle, megakernel == wavefront bit
+"""A wider randomized parity sweep than the CI suite carries (tests/film_cases.py _fuzz_scene, other seeds): HIP film vs the CPU oracle, megakernel == wavefront bit
 for bit, counting == product kernels, one stream / shadow rays beside / pass halves, tile sets / sample ranges / dealer == one shot. Run through gpurun when GPU minutes are to spare:
     python scripts/dev/fuzz_sweep.py [first_seed] [n_scenes] [--rich]"""
 import importlib, os, sys, time
@@ -7,9 +7,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 kz = importlib.import_module("nano-kazen_amd")
 import oracle as O
-from test_gpu_parity import _fuzz_scene, tie_bracket
+from checks import tie_bracket
+from film_cases import _fuzz_scene
 
-rich = "--rich" in sys.argv                 # bicubic lookups and environment backgrounds on top (tests/test_gpu_parity.py _fuzz_scene)
+rich = "--rich" in sys.argv                 # bicubic lookups and environment backgrounds on top (tests/film_cases.py _fuzz_scene)
 argv = [a for a in sys.argv if a != "--rich"]
 first, n = (int(argv[1]) if len(argv) > 1 else 5000), (int(argv[2]) if len(argv) > 2 else 60)
 bad = []
@@ -27,7 +28,7 @@ for seed in range(first, first + n):
     bits = np.array_equal(film, ora.render_canonical(threads=0))           # round 6: the whole film in the build's fixed summation order (ties of the reference's shadow loop aside)
     note = ""
     if not ok and np.allclose(film[..., 3], fc[..., 3], rtol=1e-4, atol=1e-5):
-        # the reference's shadow tie (tests/test_gpu_parity.py tie_bracket): inside the oracle's bracket is parity
+        # the reference's shadow tie (tests/checks.py tie_bracket): inside the oracle's bracket is parity
         outside, n_tie = tie_bracket(ora, sc, d)
         ok = outside < 1e-4 and n_tie > 0
         note = " [literal L2 fails; %d tie samples, share of samples outside the tie bracket %.1e]" % (n_tie, outside)

@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 kz = importlib.import_module("nano-kazen_amd")
 import oracle as O
-from test_gpu_parity import _fuzz_scene
+from film_cases import _fuzz_scene
 seed = int(sys.argv[1])
 def cmp(d, tag):
     sc = kz.Scene(d, device=0); o = O.OracleScene(d)

@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 kz = importlib.import_module("nano-kazen_amd")
 import oracle as O
-from test_gpu_parity import _fuzz_scene
+from film_cases import _fuzz_scene
 first, n = (int(sys.argv[1]) if len(sys.argv) > 1 else 5000), (int(sys.argv[2]) if len(sys.argv) > 2 else 40)
 tot = eq = 0
 worst = []

@@ -18,11 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 kz = importlib.import_module("nano-kazen_amd")
 import oracle as O      # noqa: E402
-from test_aov_cpu import AovRef, aov_ref_lib      # noqa: E402
-from test_denoise_cpu import GUIDES, frame_rgb      # noqa: E402
-from test_motion_cpu import motion_ref_lib, ref_denoise_motion, ref_ids, static_rows, translate      # noqa: E402
-from test_temporal_cpu import temporal_ref_lib      # noqa: E402
-from test_variance_cpu import MomentRef      # noqa: E402
+from cpu_refs import AovRef, MomentRef, lib, ref_denoise_motion, ref_ids      # noqa: E402
+from film_cases import GUIDES, frame_rgb, static_rows, translate      # noqa: E402
 
 SHORT_BOX = 6                                                         # scenes.cornell_box: the short box (metallic, roughness 0.3); 5 is the tall one (dielectric grey, roughness 0.5)
 
@@ -43,7 +40,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20a_motion"))
     a = ap.parse_args()
     tmp = tempfile.mkdtemp()
-    mref, tref, aref = motion_ref_lib(tmp), temporal_ref_lib(tmp), aov_ref_lib(tmp)
+    mref, tref, aref = lib("motion", tmp), lib("temporal", tmp), lib("aov", tmp)
     n_meshes = len(kz.scenes.cornell_box(96, 72, 4).meshes)
     at = lambda f: translate((-a.step * f, 0.0, 0.5 * a.step * f)).astype(np.float32)
     mats = np.tile(np.eye(4, dtype=np.float32), (n_meshes, 1, 1))

@@ -4,7 +4,7 @@ canonical films, 96 x 72, frames of 4 spp from the sample ranges [4f, 4f + 4). T
                      against 1024 spp (static) or 256 spp from the last camera (orbit)
     mover 6 / 5      DESIGN.md 4h's: Cornell, eight frames, the short or the tall box slid by 0.04 per frame; frame 8 against 1024 spp of the last pose, the whole
                      frame and the mover's pixels
-    light step       Cornell, a camera at rest, eight frames, then the lamp turns from white 15 to orange 12 (tests/test_responsive_cpu.py NEW_LIGHT) and eight more
+    light step       Cornell, a camera at rest, eight frames, then the lamp turns from white 15 to orange 12 (tests/film_cases.py NEW_LIGHT) and eight more
                      frames follow; frames 9, 12 and 16 against 1024 spp of the new lighting
 Per sequence the MSE over the noisy frame's MSE for the responsive chain, the kz_motion_ref chain and the frame alone; for the orbits and the movers also the share of
 eligible pixels (N_l > fastHistory) that the clamp changed in the last frame, from the same call with KZ_RESPONSIVE_CLAMP_OFF. --sweep runs every sequence over
@@ -23,11 +23,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 kz = importlib.import_module("nano-kazen_amd")
 import oracle as O      # noqa: E402
-from test_aov_cpu import aov_ref_lib      # noqa: E402
-from test_denoise_cpu import frame_rgb      # noqa: E402
-from test_motion_cpu import static_rows, translate      # noqa: E402
-from test_responsive_cpu import chains, light_step, reference_frames, responsive_ref_lib      # noqa: E402
-from test_temporal_cpu import _orbit      # noqa: E402
+from cpu_refs import lib      # noqa: E402
+from film_cases import _orbit, chains, frame_rgb, light_step, reference_frames, static_rows, translate      # noqa: E402
 
 MAKE = {"cornell": kz.scenes.cornell_box, "materials": kz.scenes.materials_scene, "textured": kz.scenes.textured_scene}
 
@@ -105,7 +102,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r21a_responsive"))
     a = ap.parse_args()
     tmp = tempfile.mkdtemp()
-    L, aov_lib = responsive_ref_lib(tmp), aov_ref_lib(tmp)
+    L, aov_lib = lib("responsive", tmp), lib("aov", tmp)
     seqs = sequences(L, aov_lib)
     os.makedirs(a.out, exist_ok=True)
     base = measure(L, seqs)

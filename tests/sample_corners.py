@@ -172,7 +172,7 @@ def film_of_samples(rows_per_sample, pxy, w=W, h=H):
     return film
 
 
-def differing(a, b):
+def differing_words(a, b):
     """Indices (rows of the first axis pair) where two float32 arrays differ in a bit: two NaNs count as equal, +0 and -0 do not."""
     a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
     assert a.shape == b.shape, (a.shape, b.shape)
@@ -191,7 +191,7 @@ def _head(case, ora, what):
 def report(case, ora, begin, end, got, want, what, limit=4):
     """What a failing film comparison says: for (the first `limit` of) the texels that differ, the pixel, the sample index or range, sampler, count and seed, the
     device's texel, the oracle's, and the oracle's render_samples row of the range's first sample with its jitter."""
-    bad = differing(got, want).any(axis=2)
+    bad = differing_words(got, want).any(axis=2)
     ys, xs = np.nonzero(bad)
     lines = [_head(case, ora, what) + ": %d of %d texels differ over samples [%d, %d)" % (len(xs), bad.size, begin, end)]
     for x, y in list(zip(xs, ys))[:limit]:
@@ -204,7 +204,7 @@ def report(case, ora, begin, end, got, want, what, limit=4):
 
 def report_samples(case, ora, pxy, k, got, want, what, limit=4):
     """The same for a render_samples comparison: the rows that differ, with pixel, sample index, sampler, count and seed."""
-    bad = np.nonzero(differing(got, want).any(axis=1))[0]
+    bad = np.nonzero(differing_words(got, want).any(axis=1))[0]
     lines = [_head(case, ora, what) + ": %d of %d samples differ at index %d" % (len(bad), len(pxy), k)]
     for i in bad[:limit]:
         x, y = int(pxy[i, 0]), int(pxy[i, 1])

@@ -6,52 +6,18 @@ import copy
 import numpy as np
 import pytest
 
-from test_aov_cpu import AOVS, H, SPP, W, AovRef, aov_ref_lib, grid_of, octant_scene, with_integrator
+from checks import same_bits_strict
+from cpu_refs import AovRef, lib
+from film_cases import AOVS, FILTERS, H, SCHEDULES, SPP, W, _looks_at_the_light, _thinlens, _visible, _with_filter, grid_of, octant_scene, with_integrator
 
 pytestmark = pytest.mark.gpu
 
 INTEGRATORS = ("path_mis", "normals", "ao", "path_mats")
-FILTERS = {"gaussian r=2": {"type": "gaussian", "radius": 2.0, "stddev": 0.5, "B": 1 / 3.0, "C": 1 / 3.0},
-           "box r=0.5": {"type": "box", "radius": 0.5, "stddev": 0.5, "B": 1 / 3.0, "C": 1 / 3.0},
-           "mitchell r=2": {"type": "mitchell", "radius": 2.0, "stddev": 0.5, "B": 1 / 3.0, "C": 1 / 3.0},
-           "gaussian r=3": {"type": "gaussian", "radius": 3.0, "stddev": 0.75, "B": 1 / 3.0, "C": 1 / 3.0}}      # 7 taps: the 4-group tap kernel
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and bool((a.view(np.uint32) == b.view(np.uint32)).all())
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return aov_ref_lib(tmp_path_factory.mktemp("kza"))
-
-
-def _visible(desc):
-    d = copy.deepcopy(desc)
-    for m in d.meshes:
-        if m["light"] is not None:
-            m["light"] = dict(m["light"], lightPrimaryVisibility=True)
-    return d
-
-
-def _thinlens(desc):
-    d = copy.deepcopy(desc)
-    d.camera.update(type="thinlens", apertureRadius=0.1, focusDistance=3.5)
-    return d
-
-
-def _looks_at_the_light(kz):
-    """The Cornell box seen from below its ceiling light, which is invisible to camera rays: path_mis walks through it to the ceiling 0.01 behind it."""
-    d = kz.scenes.cornell_box(W, H, SPP)
-    d.camera.update(fov=50.0, toWorld=kz.scenes.look_at((0.05, -0.2, 0.7), (0, 0.99, 0), (0, 0, -1)))
-    return d
-
-
-def _with_filter(desc, rf):
-    d = copy.deepcopy(desc)
-    d.camera["rfilter"] = dict(rf)
-    return d
+    return lib("aov", tmp_path_factory.mktemp("kza"))
 
 
 _films = {}
@@ -90,7 +56,7 @@ def test_samples_have_the_references_bits(gpu_lib, kz, ref, name):
     assert not bad.any(), (name, int(bad.sum()), g[bad][:3], c[bad][:3])
     assert np.isfinite(g).all() and (g[:, 9] == 1).any() and g[:, 2:5].max() > 0 and g[:, 8].max() > 0
     sc.set_aovs(AOVS)                                                 # it works whatever the mask is
-    assert same_bits(sc.aov_samples(pxy[:4096], idx[:4096]), g[:4096])
+    assert same_bits_strict(sc.aov_samples(pxy[:4096], idx[:4096]), g[:4096])
     if name == "materials":
         assert (g[:, 2:5] == 1).all(axis=1).any()                     # the models without a diffuse colour are white
     if name == "textured":
@@ -106,7 +72,7 @@ def test_an_invisible_light_is_walked_through_by_path_mis_only(gpu_lib, kz, ref)
     assert on_light.sum() > 1000
     assert (mis[on_light][:, 2:5] == np.float32(0.73)).all()          # the ceiling behind it
     assert (mis[on_light][:, 8] < 0.05).all() and (nrm[on_light][:, 8] > 0.5).all()      # depth from the restart origin (the stated limitation) / from the camera
-    assert same_bits(mis[~on_light], nrm[~on_light])
+    assert same_bits_strict(mis[~on_light], nrm[~on_light])
 
 
 # ---------------------------------------------------------------- films
@@ -125,9 +91,6 @@ def test_films_equal_the_reference(gpu_lib, kz, ref, scene, filt):
     assert sc.aov("normal").min() < 0                                 # signed values survive the film
     dz = sc.aov("depth")
     assert np.array_equal(dz[..., 0], dz[..., 1]) and np.array_equal(dz[..., 0], dz[..., 2])
-
-
-SCHEDULES = [{}, {"tune": {"sppPerPass": 4}}, {"passes_in_flight": 2, "pass_items": 1024 * SPP}, {"pass_halves": 2}, {"shadow_beside": 2}]
 
 
 @pytest.mark.parametrize("integ", INTEGRATORS)

@@ -2,70 +2,14 @@
 CPU restatement (tests/cpu_ref/kz_denoise_ref.cpp) the GPU tests compare against - checked here against a float64 numpy restatement and on inputs whose answer
 is known - and what the filter is worth on the oracle's own films."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-REF_SRC = os.path.join(HERE, "cpu_ref", "kz_denoise_ref.cpp")
-GUIDES = ("albedo", "normal", "depth")
-
-# ---------------------------------------------------------------- the CPU reference (also imported by test_denoise_gpu.py)
-_ref = {}
-
-
-def denoise_ref_lib(tmpdir):
-    """Compiles the CPU reference with the oracle's flags into `tmpdir` once per process."""
-    if "lib" not in _ref:
-        out = os.path.join(str(tmpdir), "libkz_denoise_ref.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), "-o", out, REF_SRC])
-        L = C.CDLL(out)
-        f32p = C.POINTER(C.c_float)
-        L.kzd_denoise.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, C.c_void_p, f32p]
-        _ref["lib"] = L
-    return _ref["lib"]
-
-
-def ref_denoise(L, kz, film, albedo=None, normal=None, depth=None, border=0, **opts):
-    """The reference's film of four films (guides may be None); options as kz.denoise_opts takes them."""
-    f32p = C.POINTER(C.c_float)
-    film = np.ascontiguousarray(film, np.float32)
-    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (albedo, normal, depth)]
-    out = np.full(film.shape, np.nan, np.float32)
-    o = kz.denoise_opts(**opts)
-    rc = L.kzd_denoise(film.shape[1] - 2 * border, film.shape[0] - 2 * border, border, film.ctypes.data_as(f32p),
-                       *[None if a is None else a.ctypes.data_as(f32p) for a in g], C.byref(o), out.ctypes.data_as(f32p))
-    assert rc == 0, "the reference refused the options"
-    return out
-
-
-def synthetic_films(w, h, b, seed):
-    """Films a renderer could have made, with every awkward texel the definition names: lognormal colour times a filter weight, about 5 % of the frame's pixels
-    with weight 0 (their rgb left non-zero: it must not count), normals constant on pieces of the frame (unit, signed), a depth with zeros, an albedo with channels
-    that are exactly 0 (demodulation divides by max(a, 1e-3)), and a non-zero apron in every film (it must not count either)."""
-    rng = np.random.default_rng(seed)
-    rows, cols = h + 2 * b, w + 2 * b
-
-    def film_of(values):
-        wgt = rng.uniform(0.5, 4.0, (rows, cols, 1)).astype(np.float32)
-        return np.concatenate([values.astype(np.float32) * wgt, wgt], axis=2)
-
-    yy, xx = np.mgrid[0:rows, 0:cols]
-    piece = ((yy // 7) * 3 + (xx // 9)) % 5
-    normals = rng.normal(size=(5, 3))
-    normals /= np.linalg.norm(normals, axis=1, keepdims=True)
-    colour = film_of(rng.lognormal(-1.0, 1.0, (rows, cols, 3)))
-    colour[rng.random((rows, cols)) < 0.05, 3] = 0.0
-    normal = film_of(normals[piece])
-    z = rng.uniform(1.0, 9.0, (rows, cols, 1)) * (rng.random((rows, cols, 1)) > 0.1)
-    depth = film_of(np.repeat(z, 3, axis=2))
-    alb = rng.uniform(0.05, 0.95, (5, 3))[(piece + xx // 4) % 5] * (rng.random((rows, cols, 3)) > 0.15)
-    albedo = film_of(alb)
-    return colour, albedo, normal, depth
+from checks import c_layout, header_surface, refused
+from cpu_refs import AovRef, lib, ref_denoise
+from film_cases import BAD_OPTS, GUIDES, frame_rgb, synthetic_films
 
 
 def np_denoise(film, albedo=None, normal=None, depth=None, border=0, iterations=5, demodulate=True, use_guides=True, sigmas=(1.0, 0.3, 0.1, 0.1)):
@@ -114,60 +58,25 @@ def np_denoise(film, albedo=None, normal=None, depth=None, border=0, iterations=
     return out
 
 
-def frame_rgb(film, b):
-    f = film[b:film.shape[0] - b, b:film.shape[1] - b] if b else film
-    return np.where(f[..., 3:] != 0, f[..., :3] / np.where(f[..., 3:] == 0, 1, f[..., 3:]), 0)
-
-
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return denoise_ref_lib(tmp_path_factory.mktemp("kzd"))
+    return lib("denoise", tmp_path_factory.mktemp("kzd"))
 
 
 # ---------------------------------------------------------------- ABI
 def test_header_declarations_are_exported(kz):
     a = kz.abi
-    lib = a.load_library()
-    src = open(os.path.join(ROOT, "include", "kazen_mi355x_denoise.h")).read()
-    declared = set(re.findall(r"^(?:int|void|const char \*)\s*\*?(kz_[a-z0-9_]+)\s*\(", src, re.M))
-    assert declared == set(a.DENOISE_EXPORTS) and len(a.DENOISE_EXPORTS) == 7, declared ^ set(a.DENOISE_EXPORTS)
-    exported = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.LIB_PATH], text=True)))
-    assert declared <= exported, declared - exported
-    if os.path.exists(a.DEV_LIB_PATH):
-        dev = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.DEV_LIB_PATH], text=True)))
-        assert declared <= dev, declared - dev
-    for sym in declared:
-        assert getattr(lib, sym) is not None
     # a surface of its own: disjoint from the other lists, and nothing added to the existing headers
-    assert not (declared & (set(a.EXPORTS) | set(a.PRODUCT_EXPORTS) | set(a.EDIT_EXPORTS) | set(a.AOV_EXPORTS)))
-    for name in ("kazen_mi355x.h", "kazen_mi355x_dev.h", "kazen_mi355x_edit.h", "kazen_mi355x_aov.h"):
-        assert "kz_denoise" not in open(os.path.join(ROOT, "include", name)).read().lower(), name
-    assert lib.kz_abi_version() == a.KZ_ABI_VERSION == 6
+    _, src = header_surface(kz, "include/kazen_mi355x_denoise.h", a.DENOISE_EXPORTS, 7, [a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS],
+                            ["include/kazen_mi355x.h", "include/kazen_mi355x_dev.h", "include/kazen_mi355x_edit.h", "include/kazen_mi355x_aov.h"], ["kz_denoise"])
     for n, v in (("KZ_DENOISE_NO_DEMODULATE", a.KZ_DENOISE_NO_DEMODULATE), ("KZ_DENOISE_NO_GUIDES", a.KZ_DENOISE_NO_GUIDES), ("KZ_DENOISE_MAX_ITERATIONS", a.KZ_DENOISE_MAX_ITERATIONS)):
         assert int(re.search(r"#define %s\s+(\d+)u" % n, src).group(1)) == v
 
 
 def test_opts_struct_is_32_bytes(kz, tmp_path):
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "kazen_mi355x_denoise.h"\nint main(void){printf("%zu %zu %zu\\n", sizeof(KzDenoiseOpts), '
-                   'offsetof(KzDenoiseOpts, flags), offsetof(KzDenoiseOpts, sigmaDepth));return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    assert subprocess.check_output([str(exe)], text=True).split() == ["32", "8", "24"]
+    assert c_layout(tmp_path, "kazen_mi355x_denoise.h", ["sizeof(KzDenoiseOpts)", "offsetof(KzDenoiseOpts, flags)", "offsetof(KzDenoiseOpts, sigmaDepth)"]) == ["32", "8", "24"]
     o = kz.abi.KzDenoiseOpts
     assert C.sizeof(o) == 32 and o.flags.offset == 8 and o.sigmaDepth.offset == 24
-
-
-BAD_OPTS = [{"iterations": 9}, {"iterations": 1 << 31}, {"sigma_color": -1.0}, {"sigma_normal": float("nan")}, {"sigma_depth": float("inf")}, {"sigma_albedo": -1e-30},
-            {"flags": 4}, {"flags": 1 << 31}, {"reserved": 1}]
-
-
-def _refused(kz, fn, code, *words):
-    with pytest.raises(kz.abi.KzError) as e:
-        fn()
-    assert e.value.code == code, str(e.value)
-    for w in words:
-        assert w in str(e.value), (w, str(e.value))
 
 
 def test_refusals_without_a_device(kz):
@@ -175,29 +84,29 @@ def test_refusals_without_a_device(kz):
     sc = kz.Scene(kz.scenes.cornell_box(16, 16, 2))
     # bad options are refused before a replica is looked for, and the message names the call
     for bad in BAD_OPTS:
-        _refused(kz, lambda: sc.denoise(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise")
+        refused(kz, lambda: sc.denoise(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise")
     for g in ("albedo", 7, 8):
-        _refused(kz, lambda: sc.denoise(guides=g), a.KZ_ERR_INVALID_ARG, "kz_denoise", "guides")      # the scene's mask is 0
+        refused(kz, lambda: sc.denoise(guides=g), a.KZ_ERR_INVALID_ARG, "kz_denoise", "guides")      # the scene's mask is 0
     sc.set_aovs(["albedo", "depth"])
-    _refused(kz, lambda: sc.denoise(guides="normal"), a.KZ_ERR_INVALID_ARG, "kz_denoise", "guides")
+    refused(kz, lambda: sc.denoise(guides="normal"), a.KZ_ERR_INVALID_ARG, "kz_denoise", "guides")
     # good options: the scene is on no device, the existing error
     for good in ({}, {"guides": "albedo"}, {"iterations": 8, "sigma_color": 2.0, "flags": 3}):
-        _refused(kz, lambda: sc.denoise(**good), a.KZ_ERR_STATE, "kz_scene_upload")
-    _refused(kz, lambda: sc.denoise(device=0), a.KZ_ERR_STATE)
-    _refused(kz, sc.denoised_film, a.KZ_ERR_STATE)
-    _refused(kz, sc.denoised_srgb8, a.KZ_ERR_STATE)
-    _refused(kz, sc.denoise_info, a.KZ_ERR_STATE)
-    _refused(kz, sc.denoise_release, a.KZ_ERR_STATE)
+        refused(kz, lambda: sc.denoise(**good), a.KZ_ERR_STATE, "kz_scene_upload")
+    refused(kz, lambda: sc.denoise(device=0), a.KZ_ERR_STATE)
+    refused(kz, sc.denoised_film, a.KZ_ERR_STATE)
+    refused(kz, sc.denoised_srgb8, a.KZ_ERR_STATE)
+    refused(kz, sc.denoise_info, a.KZ_ERR_STATE)
+    refused(kz, sc.denoise_release, a.KZ_ERR_STATE)
     lib = a.load_library()
     assert lib.kz_denoise(None, None) == a.KZ_ERR_INVALID_ARG
     # the test surface checks its arguments and options first, then asks for the device
     film = np.ones((5, 7, 4), np.float32)
     for bad in BAD_OPTS:
-        _refused(kz, lambda: kz.denoise_films(film, **bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_films")
-    _refused(kz, lambda: kz.denoise_films(film, guides="normal"), a.KZ_ERR_INVALID_ARG, "kz_denoise_films", "guides")      # no normal film given
-    _refused(kz, lambda: kz.denoise_films(film, border=3), a.KZ_ERR_INVALID_ARG, "kz_denoise_films")                     # nothing left of the frame
+        refused(kz, lambda: kz.denoise_films(film, **bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_films")
+    refused(kz, lambda: kz.denoise_films(film, guides="normal"), a.KZ_ERR_INVALID_ARG, "kz_denoise_films", "guides")      # no normal film given
+    refused(kz, lambda: kz.denoise_films(film, border=3), a.KZ_ERR_INVALID_ARG, "kz_denoise_films")                     # nothing left of the frame
     if lib.kz_device_count() == 0:
-        _refused(kz, lambda: kz.denoise_films(film), a.KZ_ERR_NO_DEVICE)
+        refused(kz, lambda: kz.denoise_films(film), a.KZ_ERR_NO_DEVICE)
 
 
 # ---------------------------------------------------------------- the reference itself
@@ -298,14 +207,13 @@ QUALITY = {"cornell": 0.5, "materials": 1.0, "textured": 1.0}
 def test_quality_on_the_oracles_films(kz, O, ref, tmp_path_factory, scene):
     """4 spp against 1024 spp at 96 x 72, default options, the oracle's canonical film and the AOV reference's feature films: the mean squared error of the
     frame's rgb values after the filter over the one before it. Deterministic; the ratios are recorded in DESIGN.md 4e."""
-    from test_aov_cpu import AovRef, aov_ref_lib
     make = {"cornell": kz.scenes.cornell_box, "materials": kz.scenes.materials_scene, "textured": kz.scenes.textured_scene}[scene]
     noisy_desc, clean_desc = make(96, 72, 4), make(96, 72, 1024)
     ora = O.OracleScene(noisy_desc)
     noisy = ora.render_canonical(threads=0)
     clean = O.OracleScene(clean_desc).render_canonical(threads=0)
     b = (noisy.shape[0] - 72) // 2
-    aov = AovRef(aov_ref_lib(tmp_path_factory.mktemp("kza")), noisy_desc)
+    aov = AovRef(lib("aov", tmp_path_factory.mktemp("kza")), noisy_desc)
     films = [aov.film(a) for a in GUIDES]
     out = ref_denoise(ref, kz, noisy, *films, border=b)
     want = frame_rgb(clean, b).astype(np.float64)

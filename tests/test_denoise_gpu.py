@@ -6,7 +6,9 @@ import copy
 import numpy as np
 import pytest
 
-from test_denoise_cpu import BAD_OPTS, GUIDES, denoise_ref_lib, ref_denoise, synthetic_films
+from checks import differing, same_bits_strict
+from cpu_refs import lib, ref_denoise
+from film_cases import BAD_OPTS, GUIDES, synthetic_films
 
 pytestmark = pytest.mark.gpu
 
@@ -15,19 +17,9 @@ FILTERS = {"gaussian r=2": {"type": "gaussian", "radius": 2.0, "stddev": 0.5, "B
            "box r=0.5": {"type": "box", "radius": 0.5, "stddev": 0.5, "B": 1 / 3.0, "C": 1 / 3.0}}
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and bool((a.view(np.uint32) == b.view(np.uint32)).all())
-
-
-def differing(a, b):
-    bad = (np.ascontiguousarray(a, np.float32).view(np.uint32) != np.ascontiguousarray(b, np.float32).view(np.uint32)).any(axis=2)
-    return int(bad.sum()), np.argwhere(bad)[:3].tolist()
-
-
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return denoise_ref_lib(tmp_path_factory.mktemp("kzd"))
+    return lib("denoise", tmp_path_factory.mktemp("kzd"))
 
 
 # ---------------------------------------------------------------- the device code on host films
@@ -40,9 +32,9 @@ def test_films_entry_has_the_references_bits(gpu_lib, kz, ref, frame):
         for it in (1, 5, 8):
             got = kz.denoise_films(*films, border=b, iterations=it)
             want = ref_denoise(ref, kz, *films, border=b, iterations=it)
-            assert same_bits(got, want), (frame, b, it, differing(got, want))
+            assert same_bits_strict(got, want), (frame, b, it, differing(got, want, per_pixel=True))
             assert np.isfinite(got).all() and (w * h < 20 or (0 < (got[..., 3] == 1).sum() < w * h))      # some pixels are out, and stay out
-        assert same_bits(kz.denoise_films(*films, border=b), ref_denoise(ref, kz, *films, border=b, iterations=5))      # the default
+        assert same_bits_strict(kz.denoise_films(*films, border=b), ref_denoise(ref, kz, *films, border=b, iterations=5))      # the default
 
 
 @pytest.mark.parametrize("demodulate", [True, False])
@@ -53,16 +45,16 @@ def test_every_guide_subset(gpu_lib, kz, ref, subset, demodulate):
     given = [f if subset & (1 << k) else None for k, f in enumerate((albedo, normal, depth))]
     got = kz.denoise_films(colour, *given, border=b, demodulate=demodulate)
     want = ref_denoise(ref, kz, colour, *given, border=b, demodulate=demodulate)
-    assert same_bits(got, want), (subset, demodulate, differing(got, want))
+    assert same_bits_strict(got, want), (subset, demodulate, differing(got, want, per_pixel=True))
     if subset:
         # the same subset named by `guides` with every film given, and colour weights alone with the subset's demodulation
-        assert same_bits(kz.denoise_films(colour, albedo, normal, depth, border=b, demodulate=demodulate, guides=subset), want)
+        assert same_bits_strict(kz.denoise_films(colour, albedo, normal, depth, border=b, demodulate=demodulate, guides=subset), want)
         flat = kz.denoise_films(colour, *given, border=b, demodulate=demodulate, use_guides=False)
-        assert same_bits(flat, ref_denoise(ref, kz, colour, *given, border=b, demodulate=demodulate, use_guides=False))
-        assert not same_bits(flat, want)
+        assert same_bits_strict(flat, ref_denoise(ref, kz, colour, *given, border=b, demodulate=demodulate, use_guides=False))
+        assert not same_bits_strict(flat, want)
     # other sigmas than the defaults
     sig = dict(sigma_color=0.4, sigma_normal=0.7, sigma_depth=0.25, sigma_albedo=0.05, iterations=3)
-    assert same_bits(kz.denoise_films(colour, *given, border=b, demodulate=demodulate, **sig), ref_denoise(ref, kz, colour, *given, border=b, demodulate=demodulate, **sig))
+    assert same_bits_strict(kz.denoise_films(colour, *given, border=b, demodulate=demodulate, **sig), ref_denoise(ref, kz, colour, *given, border=b, demodulate=demodulate, **sig))
 
 
 # ---------------------------------------------------------------- a scene's own films
@@ -87,17 +79,17 @@ def test_scene_denoise_equals_the_reference(gpu_lib, kz, ref, scene, filt):
     sc.denoise()
     got = sc.denoised_film()
     want = ref_denoise(ref, kz, *films, border=sc.border)
-    assert same_bits(got, want), (scene, filt, differing(got, want))
-    assert same_bits(kz.denoise_films(*films, border=sc.border), want)
+    assert same_bits_strict(got, want), (scene, filt, differing(got, want, per_pixel=True))
+    assert same_bits_strict(kz.denoise_films(*films, border=sc.border), want)
     b = sc.border
     inner = got[b:got.shape[0] - b, b:got.shape[1] - b] if b else got
     assert (inner[..., 3] == 1).all() and inner[..., :3].max() > 0.1 and np.isfinite(got).all()
     if b:
         assert not got[:b].any() and not got[:, :b].any() and not got[-b:].any() and not got[:, -b:].any()
-    assert not same_bits(got[..., :3], sc.film()[..., :3] / np.where(films[0][..., 3:] == 0, 1, films[0][..., 3:]))      # it filtered
+    assert not same_bits_strict(got[..., :3], sc.film()[..., :3] / np.where(films[0][..., 3:] == 0, 1, films[0][..., 3:]))      # it filtered
     # a subset of the mask, and options
     sc.denoise(guides=["normal", "depth"], iterations=3, sigma_color=0.5)
-    assert same_bits(sc.denoised_film(), ref_denoise(ref, kz, films[0], None, films[2], films[3], border=b, iterations=3, sigma_color=0.5))
+    assert same_bits_strict(sc.denoised_film(), ref_denoise(ref, kz, films[0], None, films[2], films[3], border=b, iterations=3, sigma_color=0.5))
 
 
 # ---------------------------------------------------------------- lifecycle
@@ -122,21 +114,21 @@ def test_lifecycle(gpu_lib, kz, ref):
     assert sc.denoise_info() == 4 * W * H * 16 + (H + 2 * b) * (W + 2 * b) * 16      # the documented count
     # the picture's film and the AOV films do not notice
     for x, y in zip(before, _four_films(sc)):
-        assert same_bits(x, y)
+        assert same_bits_strict(x, y)
     # a render after a denoise gives the film it gives without one; the snapshot is left alone by it, by a clear and by an edit
     sc.render(sample_begin=0, sample_end=4)
     fresh = kz.Scene(d, device=0)
     fresh.set_aovs(GUIDES)
     fresh.render(sample_begin=0, sample_end=4)
     for x, y in zip(_four_films(sc), _four_films(fresh)):
-        assert same_bits(x, y)
-    assert same_bits(sc.denoised_film(), snap)
+        assert same_bits_strict(x, y)
+    assert same_bits_strict(sc.denoised_film(), snap)
     sc.film_clear()
     sc.sync()
-    assert not sc.film().any() and same_bits(sc.denoised_film(), snap)
+    assert not sc.film().any() and same_bits_strict(sc.denoised_film(), snap)
     sc.set_camera({"fov": 45.0})
-    assert same_bits(sc.denoised_film(), snap)
-    assert same_bits(snap, ref_denoise(ref, kz, *before, border=b))
+    assert same_bits_strict(sc.denoised_film(), snap)
+    assert same_bits_strict(snap, ref_denoise(ref, kz, *before, border=b))
     # the next denoise replaces it: of the cleared film, nothing
     sc.denoise()
     assert not sc.denoised_film().any()
@@ -147,12 +139,12 @@ def test_lifecycle(gpu_lib, kz, ref):
     assert e.value.code == a.KZ_ERR_STATE
     sc.render()                                                       # (the moved camera's picture)
     sc.denoise(iterations=2)
-    assert same_bits(sc.denoised_film(), ref_denoise(ref, kz, *_four_films(sc), border=b, iterations=2))
+    assert same_bits_strict(sc.denoised_film(), ref_denoise(ref, kz, *_four_films(sc), border=b, iterations=2))
     # a scene without AOVs: colour weights alone
     plain = kz.Scene(d, device=0)
     plain.render()
     plain.denoise()
-    assert same_bits(plain.denoised_film(), ref_denoise(ref, kz, plain.film(), border=b))
+    assert same_bits_strict(plain.denoised_film(), ref_denoise(ref, kz, plain.film(), border=b))
 
 
 def test_static_tiles_over_half_the_frame(gpu_lib, kz, ref):
@@ -167,10 +159,10 @@ def test_static_tiles_over_half_the_frame(gpu_lib, kz, ref):
     sc.denoise()
     got = sc.denoised_film()
     want = ref_denoise(ref, kz, *films, border=b)
-    assert same_bits(got, want), differing(got, want)
+    assert same_bits_strict(got, want), differing(got, want, per_pixel=True)
     assert (got[b:b + H, b:b + W // 2, 3] == 1).all() and got[b:b + H, b:b + W // 2, :3].max() > 0.1      # inside the tiles
     assert not got[:, b + W // 2 + b:].any()                                                               # outside, past the filter's strip
-    assert same_bits(got[..., 3], (films[0][..., 3] != 0) & (want[..., 3] == 1))
+    assert same_bits_strict(got[..., 3], (films[0][..., 3] != 0) & (want[..., 3] == 1))
 
 
 # ---------------------------------------------------------------- the raster
@@ -211,7 +203,7 @@ def test_refusals_with_a_device(gpu_lib, kz):
     for bad in BAD_OPTS:
         refused(lambda: kz.denoise_films(film, border=sc.border, **bad), "kz_denoise_films")
     refused(lambda: kz.denoise_films(film, border=sc.border, guides="albedo"), "kz_denoise_films", "guides")
-    assert same_bits(sc.denoised_film(), snap)                        # a refused call leaves the last result alone
+    assert same_bits_strict(sc.denoised_film(), snap)                        # a refused call leaves the last result alone
     with pytest.raises(a.KzError) as e:
         sc.denoise(device=3)
     assert e.value.code == a.KZ_ERR_STATE

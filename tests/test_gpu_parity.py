@@ -11,6 +11,9 @@ import os
 import numpy as np
 import pytest
 
+from checks import same_bits, tie_bracket
+from film_cases import _fuzz_scene
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 L2_TOL = 1e-3
@@ -347,97 +350,7 @@ def test_full_size_c4_properties(gpu_lib, kz):
     assert l2(rg, rc) < L2_TOL
 
 
-def same_bits(a, b):
-    """Equal to the last bit (two NaNs count as equal, +0 and -0 do not)."""
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
-
-
 # ---------------------------------------------------------------- randomized differential test
-def _fuzz_scene(S, seed, rich=False):
-    """A random small scene: triangle soup + room, random BSDF plugins on every mesh, random visible / invisible lights (some stacked so
-    shadow rays cross them), random camera / sampler / filter / integrator settings. rich: the same scene with (from a second generator, so the plain scene
-    of a seed does not change) bicubic image lookups and an environment image, colour ramp or constant behind the background (scripts/dev/fuzz_sweep.py --rich)."""
-    rng = np.random.default_rng(seed)
-    d = S.random_triangles(int(rng.integers(50, 3000)), int(rng.integers(24, 72)), int(rng.integers(24, 56)), 4, sampler="independent", s_edge=float(rng.uniform(0.05, 0.4)))
-    makers = [lambda: S.diffuse(tuple(rng.uniform(0.1, 0.9, 3))),
-              lambda: S.kazenstandard(tuple(rng.uniform(0.1, 0.9, 3)), float(rng.uniform(0, 1)), float(rng.integers(0, 2)), float(rng.uniform(0, 0.8)),
-                                      float(rng.uniform(0, 1)), float(rng.uniform(0, 1)), float(rng.uniform(0, 1)), float(rng.uniform(0, 1)), float(rng.uniform(0, 1)), float(rng.uniform(0, 1))),
-              lambda: S.mirror(), lambda: S.dielectric(float(rng.uniform(1.2, 1.8)), 1.0), lambda: S.ggx(tuple(rng.uniform(0.2, 0.9, 3)), float(rng.uniform(0.05, 0.9)), float(rng.uniform(0, 0.5))),
-              lambda: S.roughconductor(float(rng.uniform(0.05, 0.6)), str(rng.choice(["Au", "Cu", "Cr"]))), lambda: S.roughplastic(float(rng.uniform(0.05, 0.6)), kd=tuple(rng.uniform(0.1, 0.6, 3))),
-              lambda: S.roughdielectric(float(rng.uniform(0.05, 0.6)))]
-    if seed % 3 == 0:                                                            # every third scene: texture trees and normal maps too (8f rank 4)
-        chk, noise, gray, nrm = S._test_images()
-        t_noise, t_gray = S.imagetexture(noise, float(rng.uniform(0.5, 4)), "srgb"), S.imagetexture(gray, float(rng.uniform(0.5, 4)), "linear")
-        t_nrm = S.imagetexture(nrm, float(rng.uniform(0.5, 3)), "linear")
-        makers += [lambda: S.lambertian(S.blend(t_gray, S.constanttexture(tuple(rng.uniform(0, 1, 3))), t_noise)),
-                   lambda: S.kazenstandard(t_noise, S.colorramp(t_gray, 0.1, 0.9), t_gray, clearcoat=float(rng.uniform(0, 1))),
-                   lambda: S.normalmap(t_nrm, makers[int(rng.integers(0, 8))]()), lambda: S.ggx(S.imagetexture(chk, 3.0, "srgb"), float(rng.uniform(0.1, 0.8)))]
-    for m in d.meshes:
-        if m["light"]:
-            m["light"]["lightPrimaryVisibility"] = bool(rng.integers(0, 2))
-            m["light"]["intensity"] = float(rng.uniform(5, 40))
-        elif rng.random() < 0.85:
-            m["bsdf"] = makers[int(rng.integers(0, len(makers)))]()
-        else:
-            m["bsdf"] = None                                                    # default diffuse (mesh.cpp:25-28)
-        if rng.random() < 0.2:
-            m["N"] = None                                                       # no vertex normals (H4)
-    # an extra light hanging in the room below the ceiling lights: shadow rays to the ceiling cross it
-    q = S.quad((-0.5, 0.6, 1.2), (-0.5, 0.6, 2.2), (0.5, 0.6, 2.2), (0.5, 0.6, 1.2), flip=True)
-    d.add_mesh(q[0], q[3], q[1], q[2], bsdf=S.diffuse((0, 0, 0)), light=S.area((1, 0.8, 0.6), float(rng.uniform(2, 10)), bool(rng.integers(0, 2))))
-    d.sampler = {"type": str(rng.choice(["independent", "pmj02bn", "stratified", "correlated"])), "sampleCount": int(rng.integers(1, 12)), "seed": int(rng.integers(0, 100))}
-    d.integrator.update(maxDepth=int(rng.integers(1, 9)), traceBias=float(rng.choice([1e-3, 1e-4, 5e-3])), regularization=bool(rng.integers(0, 2)),
-                        accumulatedRoughness=float(rng.uniform(0.1, 0.9)))
-    d.camera["rfilter"] = [{"type": "gaussian", "radius": 2.0, "stddev": 0.5}, {"type": "tent"}, {"type": "box"}, {"type": "mitchell", "radius": 2.0, "B": 1 / 3, "C": 1 / 3},
-                           {"type": "gaussian", "radius": 3.5, "stddev": 1.0}][int(rng.integers(0, 5))]
-    if rng.random() < 0.4:
-        d.camera.update(type="thinlens", apertureRadius=float(rng.uniform(0, 0.2)), focusDistance=float(rng.uniform(1, 4)))
-    if rng.random() < 0.5:
-        d.background = {"color": tuple(rng.uniform(0, 1, 3)), "intensity": float(rng.uniform(0, 2))}
-    if rich:
-        r2 = np.random.default_rng(1_000_003 * (seed + 1))
-
-        def walk(node):
-            if isinstance(node, dict):
-                if node.get("type") == "imagetexture" and r2.random() < 0.5:
-                    node["filter"] = "bicubic"
-                for v in node.values():
-                    walk(v)
-        for m in d.meshes:
-            walk(m["bsdf"])
-        k = r2.random()
-        if k < 0.6:
-            env = r2.random((int(r2.integers(2, 9)), int(r2.integers(3, 17)), 3)).astype(np.float32) * float(r2.uniform(0.2, 3))
-            tex = S.imagetexture(env, 1.0, "linear", "bicubic" if r2.random() < 0.3 else "bilinear")
-            d.background = {"texture": tex if k < 0.45 else S.colorramp(tex, 0.1, 0.9), "intensity": float(r2.uniform(0.2, 2))}
-    return d
-
-
-def tie_bracket(ora, sc, desc, tol=1e-3):
-    """The reference's shadow loop has a built-in tie (integrator.cpp:262-278): after walking through an invisible light the far end becomes maxt - t
-    while the origin moved on by t + eps, so the remaining segment ends exactly ON the sampled light and whether a VISIBLE sampled light then
-    occludes itself is decided by the last bit of everything upstream - in the reference as in any restatement of it. Where the upstream
-    arithmetic is only equal to an ulp (libm sin / cos on the lens or in a BSDF sample) the oracle and the HIP path decide some of these ties
-    differently; both are roundings of the same reference. The oracle renders the two extreme resolutions (every tie occluded / none) and every
-    rounding must lie between them SAMPLE by sample (a pixel would not do: filters with negative lobes are not monotone). Returns
-    (share of HIP samples outside the bracket by more than tol, number of samples with an open bracket). A closed bracket is the literal oracle's
-    value, so the first number is the usual per-sample parity there."""
-    w, h, n = desc.camera["width"], desc.camera["height"], sc.sample_count
-    yy, xx, ii = np.meshgrid(np.arange(h), np.arange(w), np.arange(n), indexing="ij")
-    pxy = np.stack([xx.ravel(), yy.ravel()], 1).astype(np.int32)
-    idx = ii.ravel().astype(np.uint32)
-    g = sc.render_samples(pxy, idx)[:, 2:5]
-    c = ora.render_samples(pxy, idx)[:, 2:5]
-    ora.set_tie_mode(+1); lo = ora.render_samples(pxy, idx)[:, 2:5]
-    ora.set_tie_mode(-1); hi = ora.render_samples(pxy, idx)[:, 2:5]
-    ora.set_tie_mode(0)
-    slack = tol * (1.0 + np.abs(hi))
-    assert (lo <= c + slack).all() and (c <= hi + slack).all()
-    outside = ~((g >= lo - slack) & (g <= hi + slack)).all(axis=1)
-    return float(outside.mean()), int(((hi - lo) > slack).any(axis=1).sum())
-
-
 @pytest.mark.parametrize("seed", list(range(15)))
 def test_randomized_scenes_match_oracle(gpu_lib, kz, O, seed):
     desc = _fuzz_scene(kz.scenes, 1000 + seed)

@@ -1,97 +1,23 @@
 """normals / ao / path_mats without a GPU: the C ABI accepts the three tags (and still refuses whitted), the Python and XML plumbing, the C++ mirror's
 describe() rows, and sanity checks of the test-only CPU reference (tests/cpu_ref/kz_integrators_ref.cpp) the GPU tests compare against."""
-import copy
-import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from cpu_refs import RefScene, lib
+from film_cases import INTEGRATORS, with_integrator
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-REF_SRC = os.path.join(HERE, "cpu_ref", "kz_integrators_ref.cpp")
 MINI = os.path.join(HERE, "golden", "xml", "mini.xml")
 LIBDIR = os.path.join(ROOT, "nano-kazen_amd", "csrc")
-INTEGRATORS = ("normals", "ao", "path_mats")
-
-
-# ---------------------------------------------------------------- the CPU reference (also imported by test_integrators_gpu.py)
-_ref = {}
-
-
-def ref_lib(tmpdir):
-    """Compiles the CPU reference with the oracle's flags into `tmpdir` once per process."""
-    if "lib" not in _ref:
-        out = os.path.join(str(tmpdir), "libkz_integrators_ref.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "include"),
-                               "-o", out, REF_SRC])
-        L = C.CDLL(out)
-        import oracle
-        abi = oracle.abi
-        L.kzo_last_error.restype = C.c_char_p
-        L.kzo_scene_create.argtypes = [C.POINTER(abi.KzSceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.kzo_scene_destroy.argtypes = [C.c_void_p]
-        L.kzo_scene_destroy.restype = None
-        L.kzo_film_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.kzi_render_samples.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_int32), abi.u32p, abi.f32p]
-        L.kzi_render_samples.restype = None
-        L.kzi_render_canonical.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, abi.f32p]
-        L.kzi_mats_depth.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32]
-        _ref["lib"] = L
-    return _ref["lib"]
-
-
-class RefScene:
-    """A scene of the CPU reference: created through the oracle's kzo_scene_create with the path_mis tag, rendered with the integrator named here."""
-
-    def __init__(self, L, desc, integrator=None):
-        import oracle
-        self.L, self.abi = L, oracle.abi
-        self.integ = desc.integrator["type"] if integrator is None else integrator
-        d = copy.copy(desc)
-        d.integrator = dict(desc.integrator, type="path_mis")
-        self._c = d.to_c()
-        h = C.c_void_p()
-        rc = L.kzo_scene_create(C.byref(self._c), 0, C.byref(h))
-        if rc != 0:
-            raise self.abi.KzError(rc, L.kzo_last_error().decode())
-        self.h = h
-        w, hh, b = C.c_int(), C.c_int(), C.c_int()
-        L.kzo_film_dims(self.h, C.byref(w), C.byref(hh), C.byref(b))
-        self.width, self.height, self.border = w.value, hh.value, b.value
-        self.tag = {"path_mis": 0, "normals": 1, "ao": 2, "path_mats": 3}[self.integ]
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.kzo_scene_destroy(self.h)
-
-    def render_samples(self, pxy, idx):
-        pxy = np.ascontiguousarray(pxy, np.int32)
-        idx = np.ascontiguousarray(idx, np.uint32)
-        out = np.zeros((idx.shape[0], 5), np.float32)
-        self.L.kzi_render_samples(self.h, self.tag, idx.shape[0], pxy.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(self.abi.u32p),
-                                  out.ctypes.data_as(self.abi.f32p))
-        return out
-
-    def render_canonical(self, s0=0, s1=0, threads=16, grid=64):
-        film = np.zeros((self.height + 2 * self.border, self.width + 2 * self.border, 4), np.float32)
-        assert self.L.kzi_render_canonical(self.h, self.tag, s0, s1, threads, grid, film.ctypes.data_as(self.abi.f32p)) == 0
-        return film
-
-    def mats_depth(self, px, py, idx):
-        return int(self.L.kzi_mats_depth(self.h, px, py, idx))
-
-
-def with_integrator(desc, name):
-    d = copy.copy(desc)
-    d.integrator = dict(desc.integrator, type=name)
-    return d
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return ref_lib(tmp_path_factory.mktemp("kzi"))
+    return lib("integrators", tmp_path_factory.mktemp("kzi"))
 
 
 def _scene_grid(desc):

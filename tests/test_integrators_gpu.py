@@ -5,19 +5,16 @@ import copy
 import numpy as np
 import pytest
 
-from test_integrators_cpu import INTEGRATORS, RefScene, ref_lib, with_integrator
+from checks import same_bits
+from cpu_refs import RefScene, lib
+from film_cases import INTEGRATORS, with_integrator
 
 pytestmark = pytest.mark.gpu
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
-
-
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return ref_lib(tmp_path_factory.mktemp("kzi"))
+    return lib("integrators", tmp_path_factory.mktemp("kzi"))
 
 
 def _visible(desc):

@@ -2,118 +2,16 @@
 test-only CPU reference (tests/cpu_ref/kz_matte_ref.cpp) the GPU tests compare against - its rule on hand-written sequences with the expected records written out,
 its tables of two scenes against a numpy restatement of the rule over its own per-sample keys, and its rank, layer and top against numpy."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_aov_cpu import AovRef, aov_ref_lib, grid_of, with_integrator
+from checks import c_layout, header_surface, refused
+from cpu_refs import AovRef, MatteRef, lib, ref_accumulate, ref_layer, ref_rank, ref_top
+from film_cases import KEYS, NONE, grid_of, looks_at_the_light, record, with_integrator
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-REF_SRC = os.path.join(HERE, "cpu_ref", "kz_matte_ref.cpp")
-KEYS = ("mesh", "bsdf")
-NONE = 0xFFFFFFFF
 W, H, SPP = 24, 18, 16
-
-# ---------------------------------------------------------------- the CPU reference (also imported by test_matte_gpu.py)
-_ref = {}
-
-
-def matte_ref_lib(tmpdir):
-    """Compiles the CPU reference with the oracle's flags into `tmpdir` once per process."""
-    if "lib" not in _ref:
-        out = os.path.join(str(tmpdir), "libkz_matte_ref.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", out, REF_SRC])
-        L = C.CDLL(out)
-        import oracle
-        abi = oracle.abi
-        L.kzo_last_error.restype = C.c_char_p
-        L.kzo_scene_create.argtypes = [C.POINTER(abi.KzSceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.kzo_scene_destroy.argtypes = [C.c_void_p]
-        L.kzo_scene_destroy.restype = None
-        L.kzo_film_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.kzm_samples.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_int32), abi.u32p, abi.u32p]
-        L.kzm_samples.restype = None
-        L.kzm_table.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.kzm_accumulate.argtypes = [abi.u32p, C.c_uint32, C.c_uint32, C.c_void_p]
-        L.kzm_accumulate.restype = None
-        L.kzm_rank.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-        L.kzm_rank.restype = None
-        L.kzm_layer.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, abi.f32p]
-        L.kzm_layer.restype = None
-        L.kzm_top.argtypes = [C.c_void_p, C.c_size_t, abi.u32p]
-        L.kzm_top.restype = None
-        _ref["lib"] = L
-    return _ref["lib"]
-
-
-class MatteRef(AovRef):
-    """A scene of the CPU reference (AovRef: the oracle's scene, the integrator as a tag) with the matte entry points."""
-
-    def __init__(self, L, desc, dtype, integrator=None):
-        super().__init__(L, desc, integrator)
-        self.dtype = dtype
-
-    def samples(self, pxy, idx):
-        """(n, 3) uint32: mesh | bsdf row | hit."""
-        pxy = np.ascontiguousarray(pxy, np.int32)
-        idx = np.ascontiguousarray(idx, np.uint32)
-        out = np.zeros((idx.shape[0], 3), np.uint32)
-        self.L.kzm_samples(self.h, self.tag, idx.shape[0], pxy.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(self.abi.u32p), out.ctypes.data_as(self.abi.u32p))
-        return out
-
-    def table(self, key, s0, s1, start=None, rect=None):
-        """The (h, w) table of `key` after the samples [s0, s1) of `rect` (x0, y0, w, h; None: the frame) on top of `start` (None: zeros). Unranked."""
-        t = np.zeros((self.height, self.width), self.dtype) if start is None else np.ascontiguousarray(start, self.dtype).copy()
-        x0, y0, w, h = rect or (0, 0, self.width, self.height)
-        assert self.L.kzm_table(self.h, self.tag, {"mesh": 1, "bsdf": 2}[key], s0, s1, x0, y0, w, h, t.ctypes.data) == 0
-        return t
-
-
-def ref_accumulate(L, dtype, keys, start=None):
-    keys = np.ascontiguousarray(keys, np.uint32)
-    t = np.zeros(keys.shape[0], dtype) if start is None else np.ascontiguousarray(start, dtype).copy()
-    L.kzm_accumulate(keys.ctypes.data_as(C.POINTER(C.c_uint32)), keys.shape[0], keys.shape[1], t.ctypes.data)
-    return t
-
-
-def ref_rank(L, t):
-    t = np.ascontiguousarray(t)
-    out = np.zeros_like(t)
-    L.kzm_rank(t.ctypes.data, t.size, out.ctypes.data)
-    return out
-
-
-def ref_layer(L, t, id):
-    t = np.ascontiguousarray(t)
-    out = np.zeros(t.shape, np.float32)
-    L.kzm_layer(t.ctypes.data, t.size, id, out.ctypes.data_as(C.POINTER(C.c_float)))
-    return out
-
-
-def ref_top(L, t):
-    t = np.ascontiguousarray(t)
-    out = np.zeros(t.shape, np.uint32)
-    L.kzm_top(t.ctypes.data, t.size, out.ctypes.data_as(C.POINTER(C.c_uint32)))
-    return out
-
-
-def record(dtype, ids=(), counts=(), other=0, miss=0):
-    r = np.zeros((), dtype)
-    r["id"][:len(ids)] = ids
-    r["count"][:len(counts)] = counts
-    r["other"], r["miss"] = other, miss
-    return r
-
-
-def looks_at_the_light(kz, w=W, h=H, spp=SPP):
-    """The Cornell box seen from below its ceiling light, which is invisible to camera rays (tests/test_aov_gpu.py has the same view): path_mis walks through it."""
-    d = kz.scenes.cornell_box(w, h, spp)
-    d.camera.update(fov=50.0, toWorld=kz.scenes.look_at((0.05, -0.2, 0.7), (0, 0.99, 0), (0, 0, -1)))
-    return d
 
 
 def np_rule(keys, start=None):
@@ -139,27 +37,16 @@ def np_record(dtype, state):
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return matte_ref_lib(tmp_path_factory.mktemp("kzm"))
+    return lib("matte", tmp_path_factory.mktemp("kzm"))
 
 
 # ---------------------------------------------------------------- ABI
 def test_header_declarations_are_exported(kz):
     a = kz.abi
-    lib = a.load_library()
-    src = open(os.path.join(ROOT, "include_ext", "kazen_mi355x_matte.h")).read()
-    declared = set(re.findall(r"^(?:int|void|const char \*)\s*\*?(kz_[a-z0-9_]+)\s*\(", src, re.M))
-    assert declared == set(a.MATTE_EXPORTS) and len(a.MATTE_EXPORTS) == 8, declared ^ set(a.MATTE_EXPORTS)
-    exported = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.LIB_PATH], text=True)))
-    assert declared <= exported, declared - exported
-    if os.path.exists(a.DEV_LIB_PATH):
-        dev = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.DEV_LIB_PATH], text=True)))
-        assert declared <= dev, declared - dev
-    # a surface of its own: nothing added to the other lists or to the other headers
-    for other in (a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS, a.VARIANCE_EXPORTS, a.TEMPORAL_EXPORTS, a.MOTION_EXPORTS, a.RESPONSIVE_EXPORTS, a.DEV_ONLY_EXPORTS):
-        assert not (declared & set(other))
-    for name in os.listdir(os.path.join(ROOT, "include")):              # (the header lives beside include/, whose set of files an older test pins)
-        assert "matte" not in open(os.path.join(ROOT, "include", name)).read().lower(), name
-    assert lib.kz_abi_version() == a.KZ_ABI_VERSION == 6
+    # a surface of its own: nothing added to the other lists or to the other headers (the header lives beside include/, whose set of files an older test pins)
+    _, src = header_surface(kz, "include_ext/kazen_mi355x_matte.h", a.MATTE_EXPORTS, 8,
+                            [a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS, a.VARIANCE_EXPORTS, a.TEMPORAL_EXPORTS, a.MOTION_EXPORTS, a.RESPONSIVE_EXPORTS,
+                             a.DEV_ONLY_EXPORTS], ["include"], ["matte"], resolve=False)
     consts = {n: int(re.search(r"#define %s\s+(0x[0-9A-Fa-f]+|\d+)u?" % n, src).group(1), 0) for n in ("KZ_MATTE_MESH", "KZ_MATTE_BSDF", "KZ_MATTE_ALL", "KZ_MATTE_SLOTS", "KZ_MATTE_NONE")}
     assert consts == {"KZ_MATTE_MESH": a.KZ_MATTE_MESH, "KZ_MATTE_BSDF": a.KZ_MATTE_BSDF, "KZ_MATTE_ALL": a.KZ_MATTE_ALL, "KZ_MATTE_SLOTS": a.KZ_MATTE_SLOTS, "KZ_MATTE_NONE": a.KZ_MATTE_NONE}
     assert (a.KZ_MATTE_MESH, a.KZ_MATTE_BSDF, a.KZ_MATTE_NONE) == (1, 2, a.KZ_MOTION_MISS)
@@ -167,24 +54,12 @@ def test_header_declarations_are_exported(kz):
 
 def test_texel_is_64_bytes_as_gcc_sees_it(kz, tmp_path):
     a = kz.abi
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "kazen_mi355x_matte.h"\nint main(void){printf("%zu %zu %zu %zu\\n", sizeof(KzMatteTexel), '
-                   "offsetof(KzMatteTexel, count), offsetof(KzMatteTexel, other), offsetof(KzMatteTexel, miss));return 0;}\n")
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include_ext"), str(src), "-o", str(exe)])
-    assert subprocess.check_output([str(exe)], text=True).split() == ["64", "28", "56", "60"]
+    assert c_layout(tmp_path, "kazen_mi355x_matte.h", ["sizeof(KzMatteTexel)", "offsetof(KzMatteTexel, count)", "offsetof(KzMatteTexel, other)", "offsetof(KzMatteTexel, miss)"],
+                    include="include_ext") == ["64", "28", "56", "60"]
     assert C.sizeof(a.KzMatteTexel) == 64 and np.dtype(a.MATTE_DTYPE).itemsize == 64
     assert (a.KzMatteTexel.count.offset, a.KzMatteTexel.other.offset, a.KzMatteTexel.miss.offset) == (28, 56, 60)
     d = np.dtype(a.MATTE_DTYPE)
     assert (d.fields["count"][1], d.fields["other"][1], d.fields["miss"][1]) == (28, 56, 60)
-
-
-def _refused(kz, fn, code, *words):
-    with pytest.raises(kz.abi.KzError) as e:
-        fn()
-    assert e.value.code == code, str(e.value)
-    for w in words:
-        assert w in str(e.value), (w, str(e.value))
 
 
 def test_refusals_without_a_device(kz):
@@ -192,7 +67,7 @@ def test_refusals_without_a_device(kz):
     sc = kz.Scene(kz.scenes.cornell_box(16, 16, 2))
     assert sc.mattes() == []
     for bad in (4, 7, 1 << 31):
-        _refused(kz, lambda: sc.set_mattes(bad), a.KZ_ERR_INVALID_ARG, "kz_scene_set_mattes")
+        refused(kz, lambda: sc.set_mattes(bad), a.KZ_ERR_INVALID_ARG, "kz_scene_set_mattes")
     assert sc.mattes() == []
     sc.set_mattes(["mesh", "bsdf"])                                    # (a scene on no device: the mask alone)
     assert sc.mattes() == ["mesh", "bsdf"]
@@ -202,28 +77,28 @@ def test_refusals_without_a_device(kz):
         sc.set_mattes(["object"])
     # exactly one enabled bit
     for bad in (0, 1, 3, 4):
-        _refused(kz, lambda: sc.matte(bad), a.KZ_ERR_INVALID_ARG, "kz_matte_download")
-        _refused(kz, lambda: sc.matte_layer(bad, 0), a.KZ_ERR_INVALID_ARG, "kz_matte_layer")
-        _refused(kz, lambda: sc.matte_top(bad), a.KZ_ERR_INVALID_ARG, "kz_matte_top")
-    _refused(kz, lambda: sc.matte_layer("bsdf", NONE), a.KZ_ERR_INVALID_ARG, "kz_matte_layer")
-    _refused(kz, lambda: sc.matte("bsdf"), a.KZ_ERR_STATE)             # one enabled bit, but no device
+        refused(kz, lambda: sc.matte(bad), a.KZ_ERR_INVALID_ARG, "kz_matte_download")
+        refused(kz, lambda: sc.matte_layer(bad, 0), a.KZ_ERR_INVALID_ARG, "kz_matte_layer")
+        refused(kz, lambda: sc.matte_top(bad), a.KZ_ERR_INVALID_ARG, "kz_matte_top")
+    refused(kz, lambda: sc.matte_layer("bsdf", NONE), a.KZ_ERR_INVALID_ARG, "kz_matte_layer")
+    refused(kz, lambda: sc.matte("bsdf"), a.KZ_ERR_STATE)             # one enabled bit, but no device
     tiles = [(0, 0, 16, 16)]
     counter = np.zeros(2, np.uint32)
-    _refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_UNSUPPORTED, "kz_render", "pipeline = 1", "mattes")
-    _refused(kz, lambda: sc.render_multi([0]), a.KZ_ERR_UNSUPPORTED, "kz_render_multi", "mattes")
-    _refused(kz, lambda: sc.render_dealt(tiles, counter, device=0), a.KZ_ERR_UNSUPPORTED, "kz_render_tiles", "KzTileDealer", "mattes")
-    _refused(kz, lambda: sc.render_tiles(tiles, device=0, packed=True), a.KZ_ERR_UNSUPPORTED, "kz_render_tiles", "packedOutput", "mattes")
-    _refused(kz, lambda: sc.film_tiles(tiles, device=0), a.KZ_ERR_UNSUPPORTED, "kz_film_download_tiles", "mattes")
+    refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_UNSUPPORTED, "kz_render", "pipeline = 1", "mattes")
+    refused(kz, lambda: sc.render_multi([0]), a.KZ_ERR_UNSUPPORTED, "kz_render_multi", "mattes")
+    refused(kz, lambda: sc.render_dealt(tiles, counter, device=0), a.KZ_ERR_UNSUPPORTED, "kz_render_tiles", "KzTileDealer", "mattes")
+    refused(kz, lambda: sc.render_tiles(tiles, device=0, packed=True), a.KZ_ERR_UNSUPPORTED, "kz_render_tiles", "packedOutput", "mattes")
+    refused(kz, lambda: sc.film_tiles(tiles, device=0), a.KZ_ERR_UNSUPPORTED, "kz_film_download_tiles", "mattes")
     # the test surface checks its arguments before it looks for a device
     k = np.zeros((2, 3), np.uint32)
-    _refused(kz, lambda: sc.matte_accumulate_items(k, [0, 1], form=3), a.KZ_ERR_INVALID_ARG, "kz_matte_accumulate_items")
-    _refused(kz, lambda: sc.matte_accumulate_items(np.zeros((2, 0), np.uint32), [0, 1]), a.KZ_ERR_INVALID_ARG, "kz_matte_accumulate_items")
+    refused(kz, lambda: sc.matte_accumulate_items(k, [0, 1], form=3), a.KZ_ERR_INVALID_ARG, "kz_matte_accumulate_items")
+    refused(kz, lambda: sc.matte_accumulate_items(np.zeros((2, 0), np.uint32), [0, 1]), a.KZ_ERR_INVALID_ARG, "kz_matte_accumulate_items")
     # with the mask 0 the same calls get as far as they got before: the scene is on no device
     sc.set_mattes(())
     assert sc.mattes() == []
-    _refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_STATE)
-    _refused(kz, lambda: sc.film_tiles(tiles, device=0), a.KZ_ERR_STATE)
-    _refused(kz, lambda: sc.render_tiles(tiles, device=0, packed=True), a.KZ_ERR_STATE)
+    refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_STATE)
+    refused(kz, lambda: sc.film_tiles(tiles, device=0), a.KZ_ERR_STATE)
+    refused(kz, lambda: sc.render_tiles(tiles, device=0, packed=True), a.KZ_ERR_STATE)
 
 
 # ---------------------------------------------------------------- the rule, on hand-written sequences
@@ -289,7 +164,7 @@ def test_reference_tables_are_the_rule_over_its_own_samples(kz, ref, ref_scenes,
 @pytest.mark.parametrize("name", ["cornell", "invisible light"])
 def test_a_samples_hit_is_the_feature_films_hit(kz, ref, ref_scenes, tmp_path_factory, name):
     d, r, pxy, idx, s = ref_scenes[name]
-    a = AovRef(aov_ref_lib(tmp_path_factory.mktemp("kza")), d).samples(pxy, idx)
+    a = AovRef(lib("aov", tmp_path_factory.mktemp("kza")), d).samples(pxy, idx)
     assert np.array_equal(s[:, 2], a[:, 9].astype(np.uint32))
 
 

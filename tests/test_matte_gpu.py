@@ -4,8 +4,8 @@ exactly; rendered tables against the reference's, exactly, whatever the schedule
 import numpy as np
 import pytest
 
-from test_aov_cpu import with_integrator
-from test_matte_cpu import KEYS, NONE, MatteRef, looks_at_the_light, matte_ref_lib, record, ref_accumulate, ref_layer, ref_rank, ref_top
+from cpu_refs import MatteRef, lib, ref_accumulate, ref_layer, ref_rank, ref_top
+from film_cases import KEYS, NONE, looks_at_the_light, record, with_integrator
 
 pytestmark = pytest.mark.gpu
 
@@ -16,7 +16,7 @@ SMAX = 130
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return matte_ref_lib(tmp_path_factory.mktemp("kzm"))
+    return lib("matte", tmp_path_factory.mktemp("kzm"))
 
 
 @pytest.fixture(scope="module")

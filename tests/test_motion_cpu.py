@@ -3,143 +3,35 @@ in double, the refusals that need no device, and the test-only CPU reference (te
 the temporal reference where the two must agree to the bit, on a plane that slides by a known number of pixels, and, for the ids, against a brute-force loop over the
 scene's triangles."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_aov_cpu import AovRef
-from test_denoise_cpu import BAD_OPTS, synthetic_films
-from test_temporal_cpu import BAD_TOPTS, camera_of, random_history, ref_denoise_temporal, view_arrays
-from test_variance_cpu import BAD_VOPTS, synthetic_moment
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-REF_SRC = os.path.join(HERE, "cpu_ref", "kz_motion_ref.cpp")
-MISS = 0xFFFFFFFF
-
-# ---------------------------------------------------------------- the CPU reference (also imported by test_motion_gpu.py)
-_ref = {}
-
-
-def motion_ref_lib(tmpdir):
-    """Compiles the CPU reference with the oracle's flags into `tmpdir` once per process: temporal_ref_lib's entries (kzt_denoise among them) plus kzm_denoise, kzm_ids."""
-    if "lib" not in _ref:
-        out = os.path.join(str(tmpdir), "libkz_motion_ref.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", out, REF_SRC])
-        L = C.CDLL(out)
-        import oracle
-        abi = oracle.abi
-        f32p, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
-        L.kzo_last_error.restype = C.c_char_p
-        L.kzo_scene_create.argtypes = [C.POINTER(abi.KzSceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.kzo_scene_destroy.argtypes = [C.c_void_p]
-        L.kzo_scene_destroy.restype = None
-        L.kzo_film_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.kzt_denoise.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, f32p, f32p]
-        L.kzm_denoise.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, u32p, C.c_void_p, C.c_uint32,
-                                  f32p, f32p, f32p]
-        L.kzm_ids.argtypes = [C.c_void_p, C.c_int, u32p]
-        L.kzm_ids.restype = None
-        _ref["lib"] = L
-    return _ref["lib"]
-
-
-def ref_denoise_motion(L, kz, film, moment, albedo=None, normal=None, depth=None, border=0, samples=4, sigma_variance=0.0, current=None, previous=None, history=None,
-                       ids=None, rows=None, n_rows=None, depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, **opts):
-    """The reference's (film, history (h, w, 12), v_last): ref_denoise_temporal's arguments plus ids (h, w) and rows (a KzMotionRow array as kz.motion_rows gives it)."""
-    f32p = C.POINTER(C.c_float)
-    film = np.ascontiguousarray(film, np.float32)
-    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (moment, albedo, normal, depth)]
-    h, w = film.shape[0] - 2 * border, film.shape[1] - 2 * border
-    history = None if history is None else np.ascontiguousarray(history, np.float32).reshape(h, w, 12)
-    ids = np.ascontiguousarray(ids, np.uint32).reshape(h, w)
-    n_rows = getattr(rows, "n_rows", len(rows)) if n_rows is None else n_rows
-    out, hist, var = np.full(film.shape, np.nan, np.float32), np.full((h, w, 12), np.nan, np.float32), np.full((h, w), np.nan, np.float32)
-    o, v, t = kz.denoise_opts(**opts), kz.variance_opts(sigma_variance, samples), kz.temporal_opts(depth_tolerance, normal_tolerance, max_history)
-    p = lambda a: None if a is None else a.ctypes.data_as(f32p)
-    rc = L.kzm_denoise(w, h, border, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t), None if current is None else C.byref(current),
-                       None if previous is None else C.byref(previous), p(history), ids.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rows), n_rows, p(out), p(hist), p(var))
-    assert rc == 0, "the reference refused the call (%d)" % rc
-    return out, hist, var
-
-
-def ref_ids(L, desc):
-    """The reference's ids (h, w) of a description: the oracle's camera ray at every pixel centre, its closest hit and, for path_mis, its walk-through."""
-    r = AovRef(L, desc)
-    ids = np.zeros((r.height, r.width), np.uint32)
-    L.kzm_ids(r.h, r.tag, ids.ctypes.data_as(C.POINTER(C.c_uint32)))
-    return ids
-
-
-def translate(t):
-    m = np.eye(4)
-    m[:3, 3] = t
-    return m
-
-
-def rotate(axis, angle):
-    """Rodrigues: the 4 x 4 of a turn by `angle` about `axis` through the origin."""
-    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    m = np.eye(4)
-    m[:3, :3] = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
-    return m
-
-
-def static_rows(kz, n):
-    return kz.motion_rows(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)), None)
-
-
-def random_ids(w, h, n_meshes, seed, misses=0.15):
-    rng = np.random.default_rng(seed)
-    ids = rng.integers(0, n_meshes, (h, w)).astype(np.uint32)
-    ids[rng.random((h, w)) < misses] = MISS
-    return ids
+from checks import c_layout, header_surface, refused, same_bits_strict
+from cpu_refs import lib, ref_denoise_motion, ref_denoise_temporal, ref_ids
+from film_cases import (BAD_OPTS, BAD_TOPTS, BAD_VOPTS, MISS, camera_of, random_history, random_ids, rotate, sliding_plane, static_rows, synthetic_films, synthetic_moment,
+                        translate, view_arrays)
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return motion_ref_lib(tmp_path_factory.mktemp("kzm"))
-
-
-bits = lambda x: np.ascontiguousarray(x, np.float32).view(np.uint32)
+    return lib("motion", tmp_path_factory.mktemp("kzm"))
 
 
 # ---------------------------------------------------------------- 1. ABI
 def test_header_declarations_are_exported(kz):
     a = kz.abi
-    lib = a.load_library()
-    src = open(os.path.join(ROOT, "include", "kazen_mi355x_motion.h")).read()
-    declared = set(re.findall(r"^(?:int|void|const char \*)\s*\*?(kz_[a-z0-9_]+)\s*\(", src, re.M))
-    assert declared == set(a.MOTION_EXPORTS) and len(a.MOTION_EXPORTS) == 5, declared ^ set(a.MOTION_EXPORTS)
-    exported = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.LIB_PATH], text=True)))
-    assert declared <= exported, declared - exported
-    if os.path.exists(a.DEV_LIB_PATH):
-        dev = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.DEV_LIB_PATH], text=True)))
-        assert declared <= dev, declared - dev
-    for sym in declared:
-        assert getattr(lib, sym) is not None
     # a surface of its own: disjoint from every other list, and nothing added to the existing headers
-    for other in (a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS, a.VARIANCE_EXPORTS, a.TEMPORAL_EXPORTS):
-        assert not (declared & set(other)), declared & set(other)
-    for name in ("kazen_mi355x.h", "kazen_mi355x_dev.h", "kazen_mi355x_edit.h", "kazen_mi355x_aov.h", "kazen_mi355x_denoise.h", "kazen_mi355x_variance.h", "kazen_mi355x_temporal.h"):
-        text = open(os.path.join(ROOT, "include", name)).read().lower()
-        for word in ("kz_motion", "kz_denoise_motion", "kzmotion"):
-            assert word not in text, (name, word)
-    assert lib.kz_abi_version() == a.KZ_ABI_VERSION == 6
+    header_surface(kz, "include/kazen_mi355x_motion.h", a.MOTION_EXPORTS, 5,
+                   [a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS, a.VARIANCE_EXPORTS, a.TEMPORAL_EXPORTS],
+                   ["include/kazen_mi355x.h", "include/kazen_mi355x_dev.h", "include/kazen_mi355x_edit.h", "include/kazen_mi355x_aov.h", "include/kazen_mi355x_denoise.h",
+                    "include/kazen_mi355x_variance.h", "include/kazen_mi355x_temporal.h"], ["kz_motion", "kz_denoise_motion", "kzmotion"])
     assert (a.KZ_MOTION_STATIC, a.KZ_MOTION_UNTRACKED, a.KZ_MOTION_MISS) == (1, 2, MISS)
 
 
 def test_struct_sizes(kz, tmp_path):
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "kazen_mi355x_motion.h"\nint main(void){printf("%zu %zu %zu %zu %u %u %u\\n", sizeof(KzMotionRow), '
-                   'offsetof(KzMotionRow, n), offsetof(KzMotionRow, flags), offsetof(KzMotionRow, reserved), KZ_MOTION_STATIC, KZ_MOTION_UNTRACKED, KZ_MOTION_MISS);return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    assert subprocess.check_output([str(exe)], text=True).split() == ["96", "48", "84", "88", "1", "2", str(MISS)]
+    assert c_layout(tmp_path, "kazen_mi355x_motion.h", ["sizeof(KzMotionRow)", "offsetof(KzMotionRow, n)", "offsetof(KzMotionRow, flags)", "offsetof(KzMotionRow, reserved)",
+                                                        "KZ_MOTION_STATIC", "KZ_MOTION_UNTRACKED", "KZ_MOTION_MISS"]) == ["96", "48", "84", "88", "1", "2", str(MISS)]
     r = kz.abi.KzMotionRow
     assert C.sizeof(r) == 96 and (r.d.offset, r.n.offset, r.flags.offset, r.reserved.offset) == (0, 48, 84, 88)
 
@@ -210,14 +102,6 @@ def test_rows_against_numpy(kz):
 
 
 # ---------------------------------------------------------------- 3. refusals
-def _refused(kz, fn, code, *words):
-    with pytest.raises(kz.abi.KzError) as e:
-        fn()
-    assert e.value.code == code, str(e.value)
-    for w in words:
-        assert w in str(e.value), (w, str(e.value))
-
-
 def test_refusals_without_a_device(kz):
     a = kz.abi
     lib = a.load_library()
@@ -226,15 +110,15 @@ def test_refusals_without_a_device(kz):
     assert lib.kz_motion_ids(None, -1, None, 0) == a.KZ_ERR_INVALID_ARG
     # kz_denoise_motion: kz_denoise_temporal's refusals in its order, under its own name
     for bad in BAD_OPTS + BAD_VOPTS + BAD_TOPTS:
-        _refused(kz, lambda: sc.denoise_motion(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion")
-    _refused(kz, sc.denoise_motion, a.KZ_ERR_STATE, "kz_denoise_motion", "KZ_AOV_DEPTH", "mask 0")
+        refused(kz, lambda: sc.denoise_motion(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion")
+    refused(kz, sc.denoise_motion, a.KZ_ERR_STATE, "kz_denoise_motion", "KZ_AOV_DEPTH", "mask 0")
     sc.set_aovs(["albedo", "normal", "depth"])
-    _refused(kz, sc.denoise_motion, a.KZ_ERR_STATE, "kz_denoise_motion", "switched off")
-    _refused(kz, lambda: sc.denoise_motion(guides=["albedo", "normal"]), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion", "KZ_AOV_DEPTH")
+    refused(kz, sc.denoise_motion, a.KZ_ERR_STATE, "kz_denoise_motion", "switched off")
+    refused(kz, lambda: sc.denoise_motion(guides=["albedo", "normal"]), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion", "KZ_AOV_DEPTH")
     sc.set_variance(True)
-    _refused(kz, sc.denoise_motion, a.KZ_ERR_STATE, "kz_scene_upload")      # the scene is on no device
+    refused(kz, sc.denoise_motion, a.KZ_ERR_STATE, "kz_scene_upload")      # the scene is on no device
     for fn in (sc.motion_ids, sc.motion_info):
-        _refused(kz, fn, a.KZ_ERR_STATE, "kz_scene_upload")
+        refused(kz, fn, a.KZ_ERR_STATE, "kz_scene_upload")
     # the test surface: arguments, options, ids and rows first, then the device
     film = np.ones((5, 7, 4), np.float32)
     view = kz.temporal_view(camera_of(kz, 7, 5, (0, 0, 0), (0, 0, 1)))
@@ -242,24 +126,24 @@ def test_refusals_without_a_device(kz):
     ids = random_ids(7, 5, 4, seed=1)
     ok = dict(depth=film, samples=4, current=view, ids=ids, rows=rows)
     for bad in BAD_OPTS + BAD_VOPTS + BAD_TOPTS:
-        _refused(kz, lambda: kz.denoise_motion_films(film, film, **ok, **bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films")
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, samples=4, current=view, ids=ids, rows=rows), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "depth")
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, depth=film, samples=4, ids=ids, rows=rows), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "view")
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, depth=film, samples=4, current=view, rows=rows), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "ids")
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, depth=film, samples=4, current=view, ids=ids, n_rows=4), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "rows")
+        refused(kz, lambda: kz.denoise_motion_films(film, film, **ok, **bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, samples=4, current=view, ids=ids, rows=rows), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "depth")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, depth=film, samples=4, ids=ids, rows=rows), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "view")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, depth=film, samples=4, current=view, rows=rows), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "ids")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, depth=film, samples=4, current=view, ids=ids, n_rows=4), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "rows")
     out_of_range = ids.copy()
     out_of_range[3, 2] = 4
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, ids=out_of_range)), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "pixel (2, 3)", "mesh 4", "4 rows")
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, ids=ids), n_rows=3), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "3 rows")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, ids=out_of_range)), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "pixel (2, 3)", "mesh 4", "4 rows")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, ids=ids), n_rows=3), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "3 rows")
     both = static_rows(kz, 4)
     both[2].flags = 3
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, rows=both)), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "row 2")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, rows=both)), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "row 2")
     both[2].flags = 4
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, rows=both)), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "row 2")
-    _refused(kz, lambda: kz.denoise_motion_films(film, film, depth=film, current=view, ids=ids, rows=rows), a.KZ_ERR_STATE, "kz_denoise_motion_films", "samples = 0")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, rows=both)), a.KZ_ERR_INVALID_ARG, "kz_denoise_motion_films", "row 2")
+    refused(kz, lambda: kz.denoise_motion_films(film, film, depth=film, current=view, ids=ids, rows=rows), a.KZ_ERR_STATE, "kz_denoise_motion_films", "samples = 0")
     if lib.kz_device_count() == 0:
-        _refused(kz, lambda: kz.denoise_motion_films(film, film, **ok), a.KZ_ERR_NO_DEVICE)
-        _refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, ids=np.full((5, 7), MISS, np.uint32)), n_rows=0), a.KZ_ERR_NO_DEVICE)      # only misses: no row is needed
+        refused(kz, lambda: kz.denoise_motion_films(film, film, **ok), a.KZ_ERR_NO_DEVICE)
+        refused(kz, lambda: kz.denoise_motion_films(film, film, **dict(ok, ids=np.full((5, 7), MISS, np.uint32)), n_rows=0), a.KZ_ERR_NO_DEVICE)      # only misses: no row is needed
 
 
 # ---------------------------------------------------------------- 4. identity
@@ -283,51 +167,15 @@ def test_static_rows_give_the_temporal_references_bits(kz, ref, frame, border):
             want = ref_denoise_temporal(ref, kz, *films, border=b, samples=4, current=cur, previous=prev, history=history, **kw)
             got = ref_denoise_motion(ref, kz, *films, border=b, samples=4, current=cur, previous=prev, history=history, ids=ids, rows=rows, **kw)
             for g, x, what in zip(got, want, ("film", "history", "variance")):
-                assert np.array_equal(bits(g), bits(x)), (frame, b, what, kw)
+                assert same_bits_strict(g, x), (frame, b, what, kw)
         own = want[1]
     # only misses and no row at all: the same
     got = ref_denoise_motion(ref, kz, *films, border=b, samples=4, current=cur, previous=prev, history=own, ids=np.full((h, w), MISS, np.uint32), rows=rows, n_rows=0, iterations=1)
     want = ref_denoise_temporal(ref, kz, *films, border=b, samples=4, current=cur, previous=prev, history=own, iterations=1)
-    assert all(np.array_equal(bits(g), bits(x)) for g, x in zip(got, want))
+    assert all(same_bits_strict(g, x) for g, x in zip(got, want))
 
 
 # ---------------------------------------------------------------- 5. a plane that slides
-def sliding_plane(kz, w=64, h=48, D=4.0, shift_pixels=3):
-    """test_two_views_of_a_plane's setting with the camera at rest: a quad (mesh 0) in the plane z = D, its silhouette the pixel columns 10 .. 49 and rows 8 .. 39 of
-    frame 1, painted with a linear ramp in ITS OWN coordinates, albedo 1, normal (0, 0, -1), nothing around it (pixels that are not valid, ids a miss). Frame 2: the
-    quad translated along x in its plane by the footprint of `shift_pixels` pixels and lit 0.8 times as brightly. Returns (view, films1, ids1, films2, ids2, rows of
-    frame 2, the world shift)."""
-    view = kz.temporal_view(camera_of(kz, w, h, (0, 0, 0), (0, 0, 1), fov=40.0))
-    o, a, u, v, _ = view_arrays(view)
-    pix = D * np.linalg.norm(u) / a[2]                                # a pixel's footprint on the plane
-    shift = shift_pixels * pix * u / np.linalg.norm(u)                # along the image's x axis: + shift_pixels columns
-    yy, xx = np.mgrid[0:h, 0:w]
-    d = a + (xx[..., None] + 0.5) * u + (yy[..., None] + 0.5) * v
-    X = o + d * ((D - o[2]) / d[..., 2])[..., None]
-    extent = D * np.tan(np.radians(20.0)) + (shift_pixels + 1) * pix
-    gx, gy = np.array([0.45, -0.3, 0.2]) / extent, np.array([0.04, 0.15, -0.25]) / extent
-    one = np.ones((h, w, 1), np.float32)
-    film = lambda val, mask: np.where(mask[..., None], np.concatenate([np.broadcast_to(np.asarray(val, np.float32), (h, w, 3)), one], axis=2), np.float32(0)).astype(np.float32)
-    depth = np.repeat(np.linalg.norm(X - o, axis=2)[..., None], 3, axis=2)
-
-    def frame(offset, gain, mask):
-        obj = X - offset                                              # the quad's own coordinates of what each pixel shows
-        ramp = gain * (0.5 + obj[..., :1] * gx + obj[..., 1:2] * gy)
-        assert ramp.min() >= 0.0 and ramp.max() <= 1.0
-        colour = film(ramp, mask)
-        c32 = colour[..., :3]
-        return (colour, film(c32 * c32, mask), film(1.0, mask), film((0.0, 0.0, -1.0), mask), film(depth, mask)), np.where(mask, 0, MISS).astype(np.uint32)
-
-    mask1 = np.zeros((h, w), bool)
-    mask1[8:40, 10:50] = True
-    mask2 = np.zeros((h, w), bool)
-    mask2[8:40, 10 + shift_pixels:50 + shift_pixels] = True
-    films1, ids1 = frame(np.zeros(3), 1.0, mask1)
-    films2, ids2 = frame(shift, 0.8, mask2)
-    rows = kz.motion_rows(translate(shift).astype(np.float32)[None], None)
-    return view, films1, ids1, films2, ids2, rows, shift
-
-
 def test_a_plane_that_slides(kz, ref):
     w, h, k = 64, 48, 3
     view, films1, ids1, films2, ids2, rows, shift = sliding_plane(kz, w, h, shift_pixels=k)
@@ -358,12 +206,12 @@ def test_a_plane_that_slides(kz, ref):
     # the same films through the temporal reference, and with the row STATIC: those pixels blend with the wrong neighbour - the quad's point k pixels away
     _, histt, _ = ref_denoise_temporal(ref, kz, *films2, current=view, previous=view, history=hist1, **kw)
     _, hists, _ = ref_denoise_motion(ref, kz, *films2, current=view, previous=view, history=hist1, ids=ids2, rows=static_rows(kz, 1), **kw)
-    assert np.array_equal(bits(histt), bits(hists))
+    assert same_bits_strict(histt, hists)
     wrong = 0.5 * hist1[..., :3].astype(np.float64) + 0.5 * films2[0][..., :3].astype(np.float64)
     both = inside & (xx >= 12) & (xx <= 47)                           # ... where the pixel itself lies inside frame 1's silhouette too
     assert (histt[..., 8][both] == 2).all() and np.abs(histt[..., :3] - wrong)[both].max() < 1e-6
     assert np.abs(histt[..., :3].astype(np.float64) - e)[both].min() > 1e-4      # (the ramp changes by more than that over 3 pixels in every channel)
-    assert not np.array_equal(bits(histt), bits(hist2))
+    assert not same_bits_strict(histt, hist2)
     # an UNTRACKED row: no history anywhere on the quad
     lost = static_rows(kz, 1)
     lost[0].flags = kz.abi.KZ_MOTION_UNTRACKED

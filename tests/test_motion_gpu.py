@@ -7,23 +7,17 @@ import copy
 import numpy as np
 import pytest
 
-from test_aov_cpu import H, SPP, W
-from test_aov_gpu import _looks_at_the_light, _thinlens, same_bits
-from test_denoise_cpu import GUIDES, synthetic_films
-from test_motion_cpu import MISS, motion_ref_lib, random_ids, ref_denoise_motion, ref_ids, rotate, static_rows, translate
-from test_temporal_cpu import _orbit, random_history
-from test_temporal_gpu import view_pairs
-from test_variance_cpu import synthetic_moment
-from test_variance_gpu import differing
+from checks import differing, same_bits_strict
+from cpu_refs import lib, ref_denoise_motion, ref_ids
+from film_cases import (GUIDES, H, MISS, SHORT_BOX, SPP, W, _looks_at_the_light, _orbit, _thinlens, random_history, random_ids, rotate, row_tables, synthetic_films,
+                        synthetic_moment, translate, view_pairs)
 
 pytestmark = pytest.mark.gpu
-
-SHORT_BOX = 6                                                         # the short box of scenes.cornell_box: floor, ceiling, back, left, right, tall box, SHORT BOX, light
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return motion_ref_lib(tmp_path_factory.mktemp("kzm"))
+    return lib("motion", tmp_path_factory.mktemp("kzm"))
 
 
 # ---------------------------------------------------------------- the ids
@@ -76,28 +70,12 @@ def test_ids_of_ragged_frames(gpu_lib, kz, ref, frame):
 
 
 # ---------------------------------------------------------------- the films entry
-def row_tables(kz, w):
-    """Tables of 4 rows over a frame whose synthetic depths are 1 .. 9 (view_pairs' cameras: fov 50 at the origin, looking down +z): all STATIC; every mesh translated
-    by 0.3 of a pixel's footprint at distance 5; every mesh turned about the camera by the angle of 40 pixels; all UNTRACKED; one of each."""
-    pix = 2.0 * np.tan(np.radians(25.0)) / w
-    I = np.eye(4)
-    T, R = translate((0.3 * pix * 5.0, -0.2 * pix * 5.0, 0.0)), rotate((0, 1, 0), 40 * pix)
-    f32 = lambda ms: np.stack(ms).astype(np.float32)
-    tables = {"static": kz.motion_rows(f32([I] * 4), None), "translated": kz.motion_rows(f32([T] * 4), None), "rotated": kz.motion_rows(f32([R] * 4), None),
-              "untracked": kz.motion_rows(f32([T] * 4), None), "mixed": kz.motion_rows(f32([I, T, R, T]), None)}
-    for r in tables["untracked"]:
-        r.flags = kz.abi.KZ_MOTION_UNTRACKED
-    tables["mixed"][3].flags = kz.abi.KZ_MOTION_UNTRACKED
-    assert [r.flags for r in tables["mixed"]] == [1, 0, 0, 2] and [r.flags for r in tables["rotated"]] == [0] * 4
-    return tables
-
-
 def check(kz, ref, films, b, cur, prev, history, ids, rows, tag, **kw):
     got, gh, gv = kz.denoise_motion_films(*films, border=b, samples=4, current=cur, previous=prev, history=history, ids=ids, rows=rows, return_variance=True, **kw)
     want, wh, wv = ref_denoise_motion(ref, kz, *films, border=b, samples=4, current=cur, previous=prev, history=history, ids=ids, rows=rows, **kw)
-    assert same_bits(got, want), (tag, kw, "film", differing(got, want))
-    assert same_bits(gh, wh), (tag, kw, "history", differing(gh, wh))
-    assert same_bits(gv, wv), (tag, kw, "variance", differing(gv, wv))
+    assert same_bits_strict(got, want), (tag, kw, "film", differing(got, want))
+    assert same_bits_strict(gh, wh), (tag, kw, "history", differing(gh, wh))
+    assert same_bits_strict(gv, wv), (tag, kw, "variance", differing(gv, wv))
     return wh
 
 
@@ -155,14 +133,14 @@ def test_identities_on_the_device(gpu_lib, kz):
         for kw in (dict(), dict(iterations=3, demodulate=False, sigma_variance=1.5, depth_tolerance=20.0, normal_tolerance=3.0)):
             want = kz.denoise_temporal_films(*films, border=b, samples=8, current=cur, previous=prev, history=history, return_variance=True, **kw)
             got = kz.denoise_motion_films(*films, border=b, samples=8, current=cur, previous=prev, history=history, ids=ids, rows=tables["static"], return_variance=True, **kw)
-            assert all(same_bits(g, x) for g, x in zip(got, want)), (history is None, kw)
+            assert all(same_bits_strict(g, x) for g, x in zip(got, want)), (history is None, kw)
             if history is not None:
                 other = kz.denoise_motion_films(*films, border=b, samples=8, current=cur, previous=prev, history=history, ids=ids, rows=tables["mixed"], return_variance=True, **kw)
-                assert not same_bits(other[1], want[1])               # (the rows matter)
+                assert not same_bits_strict(other[1], want[1])               # (the rows matter)
             want, wv = kz.denoise_variance_films(*films, border=b, samples=8, return_variance=True, **{k: v for k, v in kw.items() if "tolerance" not in k})
             got, hist1, gv = kz.denoise_motion_films(*films, border=b, samples=8, current=cur, previous=prev, history=history, ids=ids, rows=tables["mixed"], max_history=1,
                                                      return_variance=True, **kw)
-            assert same_bits(got, want) and same_bits(gv, wv) and set(np.unique(hist1[..., 8])) == {0.0, 1.0}
+            assert same_bits_strict(got, want) and same_bits_strict(gv, wv) and set(np.unique(hist1[..., 8])) == {0.0, 1.0}
 
 
 # ---------------------------------------------------------------- a replica across transform edits
@@ -209,12 +187,12 @@ def test_replica_chain_equals_the_reference_chain(gpu_lib, kz, ref):
         want, history, _ = ref_denoise_motion(ref, kz, *films, border=b, samples=SPP, current=view, previous=prev, history=history, ids=ids, rows=rows)
         prev, prev_mats = view, mats.copy()
         got, gh = sc.denoised_film(), sc.temporal_history()
-        assert same_bits(got, want), (f, differing(got, want))
-        assert same_bits(gh, history), (f, differing(gh, history))
+        assert same_bits_strict(got, want), (f, differing(got, want))
+        assert same_bits_strict(gh, history), (f, differing(gh, history))
         assert sc.temporal_info() == (2 * W * H * 36, f + 1)
         assert old.temporal_info() == (2 * W * H * 36, 1)             # kz_denoise_temporal: afresh after every transform
         for x, y in zip(films, _films(sc)):                           # the films do not notice
-            assert same_bits(x, y)
+            assert same_bits_strict(x, y)
         if f:
             assert sc.motion_info() == (W * H * 4 + n_meshes * 96, (n_meshes - 1, 1, 0))
             assert rows[SHORT_BOX].flags == 0

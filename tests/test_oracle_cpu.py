@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from film_cases import _fuzz_scene
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -382,7 +384,6 @@ def test_shadow_tie_modes_bracket_the_literal_loop(O, kz):
     """integrator.cpp:262-278: once a shadow ray has walked through an invisible light its far end (maxt - t, origin moved by t + eps) lies exactly
     on the sampled light - the reference's own tie. The oracle's two tie modes (tests only) decide every tie one way; the literal loop lies between
     them, they differ only where visible lights are sampled through invisible ones, and the scene without invisible lights has no tie at all."""
-    from test_gpu_parity import _fuzz_scene
     desc = _fuzz_scene(kz.scenes, 5084)
     ora = O.OracleScene(desc)
     c = ora.rgb(ora.render(threads=0))

@@ -6,7 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_host_mirror import exe, python_twin       # noqa: F401  (the compiled C++ test program, the scene it builds)
+from host_mirror_program import exe, python_twin       # noqa: F401  (the compiled C++ test program, the scene it builds)
 
 
 def _gradient():

@@ -4,174 +4,43 @@ identities say the two agree to the bit, on a case whose every figure is a dyadi
 oracle's films: a lamp that changes colour under a camera at rest (scripts/responsive_quality.py runs the same sequences at length)."""
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_aov_cpu import AovRef, aov_ref_lib
-from test_denoise_cpu import BAD_OPTS, GUIDES, frame_rgb, synthetic_films
-from test_motion_cpu import MISS, random_ids, ref_denoise_motion, ref_ids, static_rows
-from test_motion_gpu import row_tables
-from test_temporal_cpu import BAD_TOPTS, camera_of, random_history, view_arrays
-from test_variance_cpu import BAD_VOPTS, MomentRef, synthetic_moment
+from checks import c_layout, header_surface, refused, same_bits_strict
+from cpu_refs import lib, ref_denoise_motion, ref_denoise_responsive
+from film_cases import (BAD_OPTS, BAD_ROPTS, BAD_TOPTS, BAD_VOPTS, FRAMES, camera_of, chains, light_step, mse_ratio, plane_films, plane_history, quality_inputs, random_fast,
+                        random_history, random_ids, reference_frames, row_tables, static_rows, synthetic_films, synthetic_moment)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-REF_SRC = os.path.join(HERE, "cpu_ref", "kz_responsive_ref.cpp")
-FRAMES = [(1, 1), (7, 5), (65, 3), (130, 9)]                          # one pixel; more rows than a block; more columns than a block; several blocks on both axes
-BAD_ROPTS = [{"fast_history": 65536}, {"clamp_sigma": -1.0}, {"clamp_sigma": float("nan")}, {"clamp_sigma": float("inf")}, {"radius": 3}, {"rflags": 2}, {"rflags": 1 << 31},
-             {"rreserved": (0, 0, 1, 0)}, {"rreserved": (7, 0, 0, 0)}]
-
-# ---------------------------------------------------------------- the CPU reference (also imported by test_responsive_gpu.py and scripts/responsive_quality.py)
-_ref = {}
-
-
-def responsive_ref_lib(tmpdir):
-    """Compiles the CPU reference with the oracle's flags into `tmpdir` once per process: motion_ref_lib's entries (kzt_denoise, kzm_denoise, kzm_ids, the oracle's
-    canonical films) plus kzr_denoise."""
-    if "lib" not in _ref:
-        out = os.path.join(str(tmpdir), "libkz_responsive_ref.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", out, REF_SRC])
-        L = C.CDLL(out)
-        import oracle
-        abi = oracle.abi
-        f32p, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
-        L.kzo_last_error.restype = C.c_char_p
-        L.kzo_scene_create.argtypes = [C.POINTER(abi.KzSceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.kzo_scene_destroy.argtypes = [C.c_void_p]
-        L.kzo_scene_destroy.restype = None
-        L.kzo_film_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.kzv_render_canonical.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, f32p]
-        L.kzi_render_canonical.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, f32p]
-        L.kzt_denoise.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, f32p, f32p]
-        L.kzm_denoise.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, u32p, C.c_void_p, C.c_uint32,
-                                  f32p, f32p, f32p]
-        L.kzm_ids.argtypes = [C.c_void_p, C.c_int, u32p]
-        L.kzm_ids.restype = None
-        L.kzr_denoise.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, u32p, C.c_void_p, C.c_uint32,
-                                  f32p, f32p, f32p, C.c_void_p, f32p, f32p]
-        _ref["lib"] = L
-    return _ref["lib"]
-
-
-def ref_denoise_responsive(L, kz, film, moment, albedo=None, normal=None, depth=None, border=0, samples=4, sigma_variance=0.0, current=None, previous=None, history=None,
-                           ids=None, rows=None, n_rows=None, depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, fast=None, fast_history=0, clamp_sigma=0.0, radius=0,
-                           clamp=True, **opts):
-    """The reference's (film, history (h, w, 12), fast (h, w, 4), v_last): ref_denoise_motion's arguments plus the fast plane (None: absent) and responsive_opts'."""
-    f32p = C.POINTER(C.c_float)
-    film = np.ascontiguousarray(film, np.float32)
-    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (moment, albedo, normal, depth)]
-    h, w = film.shape[0] - 2 * border, film.shape[1] - 2 * border
-    history = None if history is None else np.ascontiguousarray(history, np.float32).reshape(h, w, 12)
-    fast = None if fast is None else np.ascontiguousarray(fast, np.float32).reshape(h, w, 4)
-    ids = np.ascontiguousarray(ids, np.uint32).reshape(h, w)
-    n_rows = getattr(rows, "n_rows", len(rows)) if n_rows is None else n_rows
-    out, hist, var = np.full(film.shape, np.nan, np.float32), np.full((h, w, 12), np.nan, np.float32), np.full((h, w), np.nan, np.float32)
-    fout = np.full((h, w, 4), np.nan, np.float32)
-    o, v, t = kz.denoise_opts(**opts), kz.variance_opts(sigma_variance, samples), kz.temporal_opts(depth_tolerance, normal_tolerance, max_history)
-    r = kz.responsive_opts(fast_history, clamp_sigma, radius, clamp)
-    p = lambda a: None if a is None else a.ctypes.data_as(f32p)
-    rc = L.kzr_denoise(w, h, border, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t), None if current is None else C.byref(current),
-                       None if previous is None else C.byref(previous), p(history), ids.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rows), n_rows, p(out), p(hist), p(var),
-                       C.byref(r), p(fast), p(fout))
-    assert rc == 0, "the reference refused the call (%d)" % rc
-    return out, hist, fout, var
-
-
-def random_fast(history, seed):
-    """A fast plane nobody rendered, to go with `history` (h, w, 12): lognormal colours and variances, zeros where the history is empty."""
-    rng = np.random.default_rng(seed)
-    h, w = history.shape[:2]
-    fast = np.zeros((h, w, 4), np.float32)
-    fast[..., :3] = rng.lognormal(-1.0, 1.0, (h, w, 3))
-    fast[..., 3] = rng.lognormal(-3.0, 2.0, (h, w))
-    fast[history[..., 8] == 0] = 0.0
-    return fast
-
-
-def plane_films(kz, w, h, colour, D=4.0):
-    """A frame of ONE valid surface: the plane z = D seen by a camera at the origin, every pixel valid with the colour given (a scalar or (h, w, 3)), a second
-    moment of exactly colour^2 - zero variance -, albedo 1, normal (0, 0, -1). Returns (view, (film, moment, albedo, normal, depth), the depth per pixel)."""
-    view = kz.temporal_view(camera_of(kz, w, h, (0, 0, 0), (0, 0, 1), fov=40.0))
-    o, a, u, v, _ = view_arrays(view)
-    yy, xx = np.mgrid[0:h, 0:w]
-    d = a + (xx[..., None] + 0.5) * u + (yy[..., None] + 0.5) * v
-    X = o + d * ((D - o[2]) / d[..., 2])[..., None]
-    z = np.linalg.norm(X - o, axis=2).astype(np.float32)
-    one = np.ones((h, w, 1), np.float32)
-    film = lambda val: np.concatenate([np.broadcast_to(np.asarray(val, np.float32), (h, w, 3)), one], axis=2).astype(np.float32)
-    c = film(colour)
-    return view, (c, film(c[..., :3] * c[..., :3]), film(1.0), film((0.0, 0.0, -1.0)), film(z[..., None])), z
-
-
-def plane_history(z, colour, count, v=0.0):
-    """The history of plane_films' surface: colour (a scalar or (h, w, 3)), variance v and count N everywhere."""
-    h, w = z.shape
-    hist = np.zeros((h, w, 12), np.float32)
-    hist[..., :3] = np.broadcast_to(np.asarray(colour, np.float32), (h, w, 3))
-    hist[..., 3], hist[..., 6], hist[..., 7], hist[..., 8] = v, -1.0, z, count
-    return hist
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return responsive_ref_lib(tmp_path_factory.mktemp("kzr"))
-
-
-bits = lambda x: np.ascontiguousarray(x, np.float32).view(np.uint32)
-same = lambda x, y: np.array_equal(bits(x), bits(y))
+    return lib("responsive", tmp_path_factory.mktemp("kzr"))
 
 
 # ---------------------------------------------------------------- 1. ABI
 def test_header_declarations_are_exported(kz):
     a = kz.abi
-    lib = a.load_library()
-    src = open(os.path.join(ROOT, "include", "kazen_mi355x_responsive.h")).read()
-    declared = set(re.findall(r"^(?:int|void|const char \*)\s*\*?(kz_[a-z0-9_]+)\s*\(", src, re.M))
-    assert declared == set(a.RESPONSIVE_EXPORTS) and len(a.RESPONSIVE_EXPORTS) == 4, declared ^ set(a.RESPONSIVE_EXPORTS)
-    exported = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.LIB_PATH], text=True)))
-    assert declared <= exported, declared - exported
-    assert os.path.exists(a.DEV_LIB_PATH)
-    dev = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.DEV_LIB_PATH], text=True)))
-    assert declared <= dev, declared - dev
-    for sym in declared:
-        assert getattr(lib, sym) is not None
     # a surface of its own: disjoint from every other list, and nothing added to the older headers
-    for other in (a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS, a.VARIANCE_EXPORTS, a.TEMPORAL_EXPORTS, a.MOTION_EXPORTS, a.DEV_ONLY_EXPORTS):
-        assert not (declared & set(other)), declared & set(other)
     older = sorted(n for n in os.listdir(os.path.join(ROOT, "include")) if n != "kazen_mi355x_responsive.h")
     assert len(older) == 8, older
-    for name in older:
-        text = open(os.path.join(ROOT, "include", name)).read().lower()
-        for word in ("kz_responsive", "kz_denoise_responsive", "kzresponsive"):
-            assert word not in text, (name, word)
-    assert lib.kz_abi_version() == a.KZ_ABI_VERSION == 6
+    header_surface(kz, "include/kazen_mi355x_responsive.h", a.RESPONSIVE_EXPORTS, 4,
+                   [a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS, a.VARIANCE_EXPORTS, a.TEMPORAL_EXPORTS, a.MOTION_EXPORTS, a.DEV_ONLY_EXPORTS],
+                   ["include/" + n for n in older], ["kz_responsive", "kz_denoise_responsive", "kzresponsive"], dev_required=True)
     assert a.KZ_RESPONSIVE_CLAMP_OFF == 1
 
 
 def test_opts_struct_is_32_bytes(kz, tmp_path):
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "kazen_mi355x_responsive.h"\nint main(void){printf("%zu %zu %zu %zu %zu %u\\n", sizeof(KzResponsiveOpts), '
-                   'offsetof(KzResponsiveOpts, clampSigma), offsetof(KzResponsiveOpts, radius), offsetof(KzResponsiveOpts, flags), offsetof(KzResponsiveOpts, reserved), '
-                   'KZ_RESPONSIVE_CLAMP_OFF);return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    assert subprocess.check_output([str(exe)], text=True).split() == ["32", "4", "8", "12", "16", "1"]
+    assert c_layout(tmp_path, "kazen_mi355x_responsive.h", ["sizeof(KzResponsiveOpts)", "offsetof(KzResponsiveOpts, clampSigma)", "offsetof(KzResponsiveOpts, radius)",
+                                                            "offsetof(KzResponsiveOpts, flags)", "offsetof(KzResponsiveOpts, reserved)", "KZ_RESPONSIVE_CLAMP_OFF"]) == ["32", "4", "8", "12", "16", "1"]
     r = kz.abi.KzResponsiveOpts
     assert C.sizeof(r) == 32 and (r.fastHistory.offset, r.clampSigma.offset, r.radius.offset, r.flags.offset, r.reserved.offset) == (0, 4, 8, 12, 16)
 
 
 # ---------------------------------------------------------------- 2. refusals
-def _refused(kz, fn, code, *words):
-    with pytest.raises(kz.abi.KzError) as e:
-        fn()
-    assert e.value.code == code, str(e.value)
-    for w in words:
-        assert w in str(e.value), (w, str(e.value))
-
-
 def test_refusals_without_a_device(kz):
     a = kz.abi
     lib = a.load_library()
@@ -180,19 +49,19 @@ def test_refusals_without_a_device(kz):
     assert lib.kz_responsive_info(sc.h, -1, None) == a.KZ_ERR_INVALID_ARG
     # kz_denoise_responsive: kz_denoise_motion's refusals under its own name, and its own options', one bad field at a time - before the replica is looked up
     for bad in BAD_OPTS + BAD_VOPTS + BAD_TOPTS:
-        _refused(kz, lambda: sc.denoise_responsive(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_responsive")
+        refused(kz, lambda: sc.denoise_responsive(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_responsive")
     for bad in BAD_ROPTS:
-        _refused(kz, lambda: sc.denoise_responsive(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_responsive", "KzResponsiveOpts")
-    _refused(kz, sc.denoise_responsive, a.KZ_ERR_STATE, "kz_denoise_responsive", "KZ_AOV_DEPTH", "mask 0")
+        refused(kz, lambda: sc.denoise_responsive(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_responsive", "KzResponsiveOpts")
+    refused(kz, sc.denoise_responsive, a.KZ_ERR_STATE, "kz_denoise_responsive", "KZ_AOV_DEPTH", "mask 0")
     sc.set_aovs(["albedo", "normal", "depth"])
-    _refused(kz, sc.denoise_responsive, a.KZ_ERR_STATE, "kz_denoise_responsive", "switched off")
-    _refused(kz, lambda: sc.denoise_responsive(guides=["albedo", "normal"]), a.KZ_ERR_INVALID_ARG, "kz_denoise_responsive", "KZ_AOV_DEPTH")
+    refused(kz, sc.denoise_responsive, a.KZ_ERR_STATE, "kz_denoise_responsive", "switched off")
+    refused(kz, lambda: sc.denoise_responsive(guides=["albedo", "normal"]), a.KZ_ERR_INVALID_ARG, "kz_denoise_responsive", "KZ_AOV_DEPTH")
     sc.set_variance(True)
     for bad in BAD_ROPTS:                                             # (still before the replica)
-        _refused(kz, lambda: sc.denoise_responsive(**bad), a.KZ_ERR_INVALID_ARG, "KzResponsiveOpts")
-    _refused(kz, sc.denoise_responsive, a.KZ_ERR_STATE, "kz_scene_upload")      # the scene is on no device
+        refused(kz, lambda: sc.denoise_responsive(**bad), a.KZ_ERR_INVALID_ARG, "KzResponsiveOpts")
+    refused(kz, sc.denoise_responsive, a.KZ_ERR_STATE, "kz_scene_upload")      # the scene is on no device
     for fn in (sc.responsive_fast, sc.responsive_info):
-        _refused(kz, fn, a.KZ_ERR_STATE, "kz_scene_upload")
+        refused(kz, fn, a.KZ_ERR_STATE, "kz_scene_upload")
     # the test surface: arguments, options, ids and rows first, then the device
     film = np.ones((5, 7, 4), np.float32)
     view = kz.temporal_view(camera_of(kz, 7, 5, (0, 0, 0), (0, 0, 1)))
@@ -200,22 +69,22 @@ def test_refusals_without_a_device(kz):
     ok = dict(depth=film, samples=4, current=view, ids=ids, rows=rows)
     name = "kz_denoise_responsive_films"
     for bad in BAD_OPTS + BAD_VOPTS + BAD_TOPTS + BAD_ROPTS:
-        _refused(kz, lambda: kz.denoise_responsive_films(film, film, **ok, **bad), a.KZ_ERR_INVALID_ARG, name)
-    _refused(kz, lambda: kz.denoise_responsive_films(film, film, samples=4, current=view, ids=ids, rows=rows), a.KZ_ERR_INVALID_ARG, name, "depth")
-    _refused(kz, lambda: kz.denoise_responsive_films(film, film, depth=film, samples=4, ids=ids, rows=rows), a.KZ_ERR_INVALID_ARG, name, "view")
-    _refused(kz, lambda: kz.denoise_responsive_films(film, film, depth=film, samples=4, current=view, rows=rows), a.KZ_ERR_INVALID_ARG, name, "ids")
+        refused(kz, lambda: kz.denoise_responsive_films(film, film, **ok, **bad), a.KZ_ERR_INVALID_ARG, name)
+    refused(kz, lambda: kz.denoise_responsive_films(film, film, samples=4, current=view, ids=ids, rows=rows), a.KZ_ERR_INVALID_ARG, name, "depth")
+    refused(kz, lambda: kz.denoise_responsive_films(film, film, depth=film, samples=4, ids=ids, rows=rows), a.KZ_ERR_INVALID_ARG, name, "view")
+    refused(kz, lambda: kz.denoise_responsive_films(film, film, depth=film, samples=4, current=view, rows=rows), a.KZ_ERR_INVALID_ARG, name, "ids")
     out_of_range = ids.copy()
     out_of_range[3, 2] = 4
-    _refused(kz, lambda: kz.denoise_responsive_films(film, film, **dict(ok, ids=out_of_range)), a.KZ_ERR_INVALID_ARG, name, "pixel (2, 3)", "mesh 4", "4 rows")
+    refused(kz, lambda: kz.denoise_responsive_films(film, film, **dict(ok, ids=out_of_range)), a.KZ_ERR_INVALID_ARG, name, "pixel (2, 3)", "mesh 4", "4 rows")
     both = static_rows(kz, 4)
     both[2].flags = 3
-    _refused(kz, lambda: kz.denoise_responsive_films(film, film, **dict(ok, rows=both)), a.KZ_ERR_INVALID_ARG, name, "row 2")
+    refused(kz, lambda: kz.denoise_responsive_films(film, film, **dict(ok, rows=both)), a.KZ_ERR_INVALID_ARG, name, "row 2")
     negative = random_history(7, 5, seed=2, holes=0.0)
     negative[1, 4, 3] = -0.5
-    _refused(kz, lambda: kz.denoise_responsive_films(film, film, **ok, previous=view, history=negative), a.KZ_ERR_INVALID_ARG, name, "pixel (4, 1)", "negative variance")
-    _refused(kz, lambda: kz.denoise_responsive_films(film, film, depth=film, current=view, ids=ids, rows=rows), a.KZ_ERR_STATE, name, "samples = 0")
+    refused(kz, lambda: kz.denoise_responsive_films(film, film, **ok, previous=view, history=negative), a.KZ_ERR_INVALID_ARG, name, "pixel (4, 1)", "negative variance")
+    refused(kz, lambda: kz.denoise_responsive_films(film, film, depth=film, current=view, ids=ids, rows=rows), a.KZ_ERR_STATE, name, "samples = 0")
     if lib.kz_device_count() == 0:
-        _refused(kz, lambda: kz.denoise_responsive_films(film, film, **ok), a.KZ_ERR_NO_DEVICE)
+        refused(kz, lambda: kz.denoise_responsive_films(film, film, **ok), a.KZ_ERR_NO_DEVICE)
 
 
 # ---------------------------------------------------------------- 3. the identities
@@ -243,28 +112,28 @@ def test_identities_on_the_reference(kz, ref, frame, border):
         # 1. CLAMP_OFF, whatever the other options and the fast plane
         for f, more in ((fast, dict(fast_history=2, clamp_sigma=0.5, radius=1)), (None, dict()), (fast, dict(fast_history=40))):
             got = ref_denoise_responsive(ref, kz, *films, history=junk, fast=f, clamp=False, **more, **kw)
-            assert same(got[0], want[0]) and same(got[1], want[1]) and same(got[3], want[2]), (frame, b, tname, more)
+            assert same_bits_strict(got[0], want[0]) and same_bits_strict(got[1], want[1]) and same_bits_strict(got[3], want[2]), (frame, b, tname, more)
         # ... and the clamp itself does something on this input (the random history's counts reach 40)
         on = ref_denoise_responsive(ref, kz, *films, history=junk, fast=fast, fast_history=2, clamp_sigma=0.5, radius=1, **kw)
         clamped += int((on[1][..., 8] != want[1][..., 8]).sum())
         # 2. no history: kz_motion_ref's bits (which are kz_variance_ref's there), a fast plane given is ignored; and no N_l above fastHistory
         first = ref_denoise_motion(ref, kz, *films, **dict(kw, previous=None))
         got = ref_denoise_responsive(ref, kz, *films, fast=fast, **dict(kw, previous=None))
-        assert same(got[0], first[0]) and same(got[1], first[1]) and same(got[3], first[2]), (frame, b, tname)
+        assert same_bits_strict(got[0], first[0]) and same_bits_strict(got[1], first[1]) and same_bits_strict(got[3], first[2]), (frame, b, tname)
         valid = first[1][..., 8] > 0
-        assert same(got[2][..., :3][valid], first[1][..., :3][valid]) and same(got[2][..., 3][valid], first[1][..., 3][valid]) and not got[2][~valid].any()
+        assert same_bits_strict(got[2][..., :3][valid], first[1][..., :3][valid]) and same_bits_strict(got[2][..., 3][valid], first[1][..., 3][valid]) and not got[2][~valid].any()
         got = ref_denoise_responsive(ref, kz, *films, history=junk, fast=fast, fast_history=40, clamp_sigma=0.01, **kw)      # (N_l <= maxHistory = 32 < 40)
-        assert same(got[0], want[0]) and same(got[1], want[1]) and same(got[3], want[2]), (frame, b, tname)
+        assert same_bits_strict(got[0], want[0]) and same_bits_strict(got[1], want[1]) and same_bits_strict(got[3], want[2]), (frame, b, tname)
         got = ref_denoise_responsive(ref, kz, *films, history=junk, fast=fast, max_history=1, clamp_sigma=0.01, **kw)         # (maxHistory = 1: without history)
         one = ref_denoise_motion(ref, kz, *films, history=junk, max_history=1, **kw)
-        assert same(got[0], one[0]) and same(got[1], one[1])
+        assert same_bits_strict(got[0], one[0]) and same_bits_strict(got[1], one[1])
         # 3. the fast plane absent, fastHistory >= maxHistory: f == e_l, vf == v_l
         for fh, mh in ((32, 0), (7, 7), (65535, 32)):
             long_ = ref_denoise_motion(ref, kz, *films, history=junk, max_history=mh, **kw)
             got = ref_denoise_responsive(ref, kz, *films, history=junk, fast=None, fast_history=fh, max_history=mh, **kw)
             valid = long_[1][..., 8] > 0
-            assert same(got[2][valid], long_[1][..., :4][valid]) and not got[2][~valid].any(), (frame, b, tname, fh)
-            assert same(got[1], long_[1])
+            assert same_bits_strict(got[2][valid], long_[1][..., :4][valid]) and not got[2][~valid].any(), (frame, b, tname, fh)
+            assert same_bits_strict(got[1], long_[1])
     assert clamped > 0 or w * h < 4, frame
 
 
@@ -285,13 +154,13 @@ def test_exact_dyadic_case(kz, ref, radius):
     assert (rh[..., :3] == np.float32(0.625)).all() and (rh[..., 8] == 4).all() and (rh[..., 3] == 0).all()
     for y, x in ((0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1)):    # the corners by name: cnt = (radius + 1)^2
         assert rh[y, x, 0] == np.float32(0.625) and rh[y, x, 8] == 4
-    assert same(rh[..., 4:8], mh[..., 4:8])                           # (n, z) as the film has them
+    assert same_bits_strict(rh[..., 4:8], mh[..., 4:8])                           # (n, z) as the film has them
     # with the clamp off the same call stores kz_motion_ref's history and the same fast plane
     _, oh, ofast, _ = ref_denoise_responsive(ref, kz, *films, fast=None, fast_history=4, radius=radius, clamp=False, **kw)
-    assert same(oh, mh) and same(ofast, fast)
+    assert same_bits_strict(oh, mh) and same_bits_strict(ofast, fast)
     # fastHistory = 32 = N_l: the condition N_l > fastHistory fails, nothing is clamped
     _, eh, efast, _ = ref_denoise_responsive(ref, kz, *films, fast=None, fast_history=32, radius=radius, **kw)
-    assert same(eh, mh) and same(efast[..., :3], mh[..., :3])
+    assert same_bits_strict(eh, mh) and same_bits_strict(efast[..., :3], mh[..., :3])
 
 
 # ---------------------------------------------------------------- 5. a step edge in the fast plane
@@ -324,7 +193,7 @@ def test_a_step_edge_widens_the_bounds(kz, ref, radius):
     assert rel.max() < 1e-6, float(rel.max())
     N = rh[..., 8]
     at_edge = slice(edge - 1, edge + 1)
-    assert (N[:, at_edge] == 32).all() and same(rh[:, at_edge, :4], mh[:, at_edge, :4])      # the bounds widened: e_l kept
+    assert (N[:, at_edge] == 32).all() and same_bits_strict(rh[:, at_edge, :4], mh[:, at_edge, :4])      # the bounds widened: e_l kept
     away = 2 * (2 * radius + 1)
     far = np.ones(w, bool)
     far[edge - away:edge + away] = False
@@ -333,58 +202,6 @@ def test_a_step_edge_widens_the_bounds(kz, ref, radius):
 
 
 # ---------------------------------------------------------------- 6. what it is worth
-LAMP = 7                                                              # scenes.cornell_box: the ceiling light
-NEW_LIGHT = dict(color=(1.0, 0.45, 0.2), intensity=12.0)              # the light step: from white 15 to a dimmer orange - a change of colour, not only of level
-
-
-def reference_frames(kz, L, aov_lib, descs):
-    """Per frame f the reference's inputs of descs[f] (96 x 72), 4 spp from the sample range [4f, 4f + 4): (noisy, moment, [guides], border, view, ids)."""
-    out = []
-    for f, d in enumerate(descs):
-        mr = MomentRef(L, d)
-        out.append((mr.film(4 * f, 4 * f + 4), mr.moment_film(4 * f, 4 * f + 4), [AovRef(aov_lib, d).film(g, 4 * f, 4 * f + 4) for g in GUIDES], mr.border,
-                    kz.temporal_view(d.camera), ref_ids(L, d)))
-    return out
-
-
-def light_step(kz, spp, f, at=8):
-    """Cornell at 96 x 72 as frame f of the light step sees it: from frame `at` on the lamp is NEW_LIGHT."""
-    d = kz.scenes.cornell_box(96, 72, spp)
-    if f >= at:
-        d.meshes[LAMP] = dict(d.meshes[LAMP], light=kz.scenes.area(NEW_LIGHT["color"], NEW_LIGHT["intensity"], False))
-    return d
-
-
-def chains(kz, L, frames, rows_of=None, which=("responsive", "motion", "alone"), **ropts):
-    """The chains over `frames` (reference_frames' tuples): per frame the pictures of "responsive", "motion" (the kz_motion_ref chain) and "alone" (the frame
-    without a history); the responsive chain's histories; and per frame (eligible, clamped): the pixels of the responsive call with N_l > fastHistory and those of
-    them the clamp changed, from the same call with CLAMP_OFF. rows_of(f): the frame's row table (default: Cornell's eight meshes, static)."""
-    pics, hists, counts = {k: [] for k in which}, [], []
-    hr = hm = fast = prev = None
-    for f, (noisy, moment, guides, b, view, ids) in enumerate(frames):
-        rows = rows_of(f) if rows_of else static_rows(kz, 8)
-        kw = dict(border=b, samples=4, current=view, previous=prev, ids=ids, rows=rows)
-        if "responsive" in which:
-            off = ref_denoise_responsive(L, kz, noisy, moment, *guides, history=hr, fast=fast, **dict(ropts, clamp=False), **kw)[1]
-            out, hr, fast, _ = ref_denoise_responsive(L, kz, noisy, moment, *guides, history=hr, fast=fast, **ropts, **kw)
-            pics["responsive"].append(out)
-            hists.append(hr)
-            counts.append((int((off[..., 8] > (ropts.get("fast_history") or 2)).sum()), int((bits(off[..., :4]) != bits(hr[..., :4])).any(axis=2).sum())))
-        if "motion" in which:
-            out, hm, _ = ref_denoise_motion(L, kz, noisy, moment, *guides, history=hm, **kw)
-            pics["motion"].append(out)
-        if "alone" in which:
-            pics["alone"].append(ref_denoise_motion(L, kz, noisy, moment, *guides, **dict(kw, previous=None))[0])
-        prev = view
-    return pics, hists, counts
-
-
-def mse_ratio(pic, noisy, clean, b):
-    want = frame_rgb(clean, b).astype(np.float64)
-    mse = lambda x: float(((frame_rgb(x, b).astype(np.float64) - want) ** 2).mean())
-    return mse(pic) / mse(noisy)
-
-
 def test_quality_on_the_light_step(kz, O, ref, tmp_path_factory):
     """scripts/responsive_quality.py's light step at the defaults: Cornell, 96 x 72, a camera at rest, eight frames of 4 spp, then the lamp turns from white 15 to orange
     12 and eight more frames follow; MSE over the noisy frame's against 1024 spp of the new lighting. At frame 12 the responsive chain is strictly below the
@@ -392,8 +209,7 @@ def test_quality_on_the_light_step(kz, O, ref, tmp_path_factory):
 
     Measured at the defaults (fastHistory 2, clampSigma 2, radius 1; this test's print): frame 9: responsive 5.9576, motion chain 10.7178, frame alone 0.1269; frame 12:
     0.2524, 5.3180, 0.0965; frame 16: 0.0790, 4.9172, 0.1686; static Cornell, frame 8: 0.0708, 0.0707, 0.1471."""
-    from test_variance_cpu import _quality_inputs
-    aov_lib = aov_ref_lib(tmp_path_factory.mktemp("kza"))
+    aov_lib = lib("aov", tmp_path_factory.mktemp("kza"))
     frames = reference_frames(kz, ref, aov_lib, [light_step(kz, 4, f) for f in range(16)])
     clean = O.OracleScene(light_step(kz, 1024, 8)).render_canonical(threads=0)
     pics, hists, _ = chains(kz, ref, frames)
@@ -404,7 +220,7 @@ def test_quality_on_the_light_step(kz, O, ref, tmp_path_factory):
         print("light step, frame %2d: MSE ratio responsive %.4f, motion chain %.4f, frame alone %.4f; longest history %d" % (
             f, at[f]["responsive"], at[f]["motion"], at[f]["alone"], int(hists[f - 1][..., 8].max())))
     # the static sequence: the first eight frames are it
-    still, _ = _quality_inputs(kz, O, ref, tmp_path_factory, "cornell")
+    still, _ = quality_inputs(kz, O, ref, tmp_path_factory, "cornell")
     static = {k: mse_ratio(v[7], frames[7][0], still, b) for k, v in pics.items()}
     print("static cornell, frame 8: MSE ratio responsive %.4f, motion chain %.4f, frame alone %.4f" % (static["responsive"], static["motion"], static["alone"]))
     assert at[12]["responsive"] < at[12]["motion"], at[12]

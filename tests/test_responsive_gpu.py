@@ -7,15 +7,10 @@ import copy
 import numpy as np
 import pytest
 
-from test_aov_gpu import same_bits
-from test_denoise_cpu import GUIDES, synthetic_films
-from test_motion_cpu import MISS, random_ids, ref_denoise_motion, rotate, translate
-from test_motion_gpu import SHORT_BOX, row_tables
-from test_responsive_cpu import FRAMES, LAMP, NEW_LIGHT, random_fast, ref_denoise_responsive, responsive_ref_lib
-from test_temporal_cpu import _orbit, random_history
-from test_temporal_gpu import view_pairs
-from test_variance_cpu import synthetic_moment
-from test_variance_gpu import differing
+from checks import differing, same_bits_strict
+from cpu_refs import lib, ref_denoise_motion, ref_denoise_responsive
+from film_cases import (FRAMES, GUIDES, LAMP, MISS, NEW_LIGHT, SHORT_BOX, _orbit, random_fast, random_history, random_ids, rotate, row_tables, synthetic_films, synthetic_moment,
+                        translate, view_pairs)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,16 +19,16 @@ W, H, SPP = 96, 72, 1
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return responsive_ref_lib(tmp_path_factory.mktemp("kzr"))
+    return lib("responsive", tmp_path_factory.mktemp("kzr"))
 
 
 def check(kz, ref, films, b, cur, prev, history, fast, ids, rows, tag, **kw):
     got, gh, gf, gv = kz.denoise_responsive_films(*films, border=b, samples=4, current=cur, previous=prev, history=history, fast=fast, ids=ids, rows=rows, return_variance=True, **kw)
     want, wh, wf, wv = ref_denoise_responsive(ref, kz, *films, border=b, samples=4, current=cur, previous=prev, history=history, fast=fast, ids=ids, rows=rows, **kw)
-    assert same_bits(got, want), (tag, kw, "film", differing(got, want))
-    assert same_bits(gh, wh), (tag, kw, "history", differing(gh, wh))
-    assert same_bits(gv, wv), (tag, kw, "variance", differing(gv, wv))
-    assert same_bits(gf, wf), (tag, kw, "fast", differing(gf, wf))
+    assert same_bits_strict(got, want), (tag, kw, "film", differing(got, want))
+    assert same_bits_strict(gh, wh), (tag, kw, "history", differing(gh, wh))
+    assert same_bits_strict(gv, wv), (tag, kw, "variance", differing(gv, wv))
+    assert same_bits_strict(gf, wf), (tag, kw, "fast", differing(gf, wf))
     return wh, wf
 
 
@@ -93,13 +88,13 @@ def test_identities_on_the_device(gpu_lib, kz):
         want = kz.denoise_motion_films(*films, history=junk, **common)
         for f, more in ((fast, dict(fast_history=2, clamp_sigma=0.3, radius=1)), (None, dict())):
             got = kz.denoise_responsive_films(*films, history=junk, fast=f, clamp=False, **more, **common)
-            assert same_bits(got[0], want[0]) and same_bits(got[1], want[1]) and same_bits(got[3], want[2]), (kw, more)
+            assert same_bits_strict(got[0], want[0]) and same_bits_strict(got[1], want[1]) and same_bits_strict(got[3], want[2]), (kw, more)
         on = kz.denoise_responsive_films(*films, history=junk, fast=fast, fast_history=2, clamp_sigma=0.3, radius=1, **common)
-        assert not same_bits(on[1], want[1])                          # (the clamp matters)
+        assert not same_bits_strict(on[1], want[1])                          # (the clamp matters)
         want, wv = kz.denoise_variance_films(*films, border=b, samples=8, return_variance=True, **{k: v for k, v in kw.items() if "tolerance" not in k})
         got, hist, f1, gv = kz.denoise_responsive_films(*films, fast=fast, **dict(common, previous=None))
-        assert same_bits(got, want) and same_bits(gv, wv) and set(np.unique(hist[..., 8])) == {0.0, 1.0}
-        assert same_bits(f1, hist[..., :4])
+        assert same_bits_strict(got, want) and same_bits_strict(gv, wv) and set(np.unique(hist[..., 8])) == {0.0, 1.0}
+        assert same_bits_strict(f1, hist[..., :4])
 
 
 # ---------------------------------------------------------------- a replica
@@ -150,9 +145,9 @@ def test_replica_chain_equals_the_reference_chain(gpu_lib, kz, ref):
         bitten += int((off[..., 8] != history[..., 8]).sum())
         prev, prev_mats = view, mats.copy()
         got, gh, gf = sc.denoised_film(), sc.temporal_history(), sc.responsive_fast()
-        assert same_bits(got, want), (f, differing(got, want))
-        assert same_bits(gh, history), (f, differing(gh, history))
-        assert same_bits(gf, fast), (f, differing(gf, fast))
+        assert same_bits_strict(got, want), (f, differing(got, want))
+        assert same_bits_strict(gh, history), (f, differing(gh, history))
+        assert same_bits_strict(gf, fast), (f, differing(gf, fast))
         assert sc.temporal_info() == (2 * W * H * 36, f + 1)          # (f = 5: the light edit reset nothing)
         assert sc.responsive_info() == 2 * W * H * 16
     assert bitten > 0
@@ -183,9 +178,9 @@ def test_mixing_calls_on_one_history(gpu_lib, kz, ref):
     _, h0, f0, _ = ref_denoise_responsive(ref, kz, *frames[0], **ropts, **kw)
     _, h1, _ = ref_denoise_motion(ref, kz, *frames[1], previous=view, history=h0, **kw)
     want, h2, f2, _ = ref_denoise_responsive(ref, kz, *frames[2], previous=view, history=h1, fast=None, **ropts, **kw)
-    assert same_bits(sc.denoised_film(), want) and same_bits(sc.temporal_history(), h2) and same_bits(sc.responsive_fast(), f2)
+    assert same_bits_strict(sc.denoised_film(), want) and same_bits_strict(sc.temporal_history(), h2) and same_bits_strict(sc.responsive_fast(), f2)
     other = ref_denoise_responsive(ref, kz, *frames[2], previous=view, history=h1, fast=f0, **ropts, **kw)
-    assert not same_bits(other[2], f2)
+    assert not same_bits_strict(other[2], f2)
     assert sc.temporal_info() == (2 * W * H * 36, 3)
 
 

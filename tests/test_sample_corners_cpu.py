@@ -28,11 +28,11 @@ def _identity(kz, O, case, ks, ranges, tiles=None, w=SC.W, h=SC.H):
         x, y = pxy[~edge, 0], pxy[~edge, 1]
         want = np.concatenate([np.float32(0) + rows[:, 2:5], np.ones((len(rows), 1), np.float32)], 1)       # (0 + -0 = +0: the tap sum starts at +0)
         want[~ok] = 0                                                                                       # Color3f::isValid drops the sample and its weight
-        bad = SC.differing(film[y, x], want[~edge]).any(axis=1)
+        bad = SC.differing_words(film[y, x], want[~edge]).any(axis=1)
         assert not bad.any(), (case.id, k, int(bad.sum()), pxy[~edge][bad][:4].tolist())
         assert (film[y, x, 3] == ok[~edge]).all()
         if not edge.any():                                                                                  # nothing anywhere else (untouched tiles included)
-            assert not SC.differing(film, SC.film_of_samples([rows], pxy, w, h)).any(), (case.id, k)
+            assert not SC.differing_words(film, SC.film_of_samples([rows], pxy, w, h)).any(), (case.id, k)
     assert n_edge <= EDGE_SHARE * n_all, (case.id, n_edge, n_all)
     for b, e in ranges:
         per_sample = [SC.samples_of(ora, pxy, k) for k in range(b, e)]
@@ -45,7 +45,7 @@ def _identity(kz, O, case, ks, ranges, tiles=None, w=SC.W, h=SC.H):
         out = SC.edge_texels(per_sample, pxy, w, h)
         assert out.sum() <= 9 * n_range_edge and out.sum() <= EDGE_SHARE * 9 * out.size, (case.id, b, e, int(out.sum()))
         film = SC.range_film(ora, b, e, tiles=tiles)
-        bad = SC.differing(film, SC.film_of_samples(per_sample, pxy, w, h)).any(axis=2) & ~out
+        bad = SC.differing_words(film, SC.film_of_samples(per_sample, pxy, w, h)).any(axis=2) & ~out
         assert not bad.any(), (case.id, b, e, int(bad.sum()), np.argwhere(bad)[:4].tolist())
     return ora
 
@@ -112,7 +112,7 @@ def test_the_high_word_of_the_seed_reaches_every_case(kz, O, case):
     a = SC.samples_of(O.OracleScene(SC.scene_of(kz.scenes, case)), pxy, k)
     b = SC.samples_of(O.OracleScene(SC.with_seed(SC.scene_of(kz.scenes, case), case.seed ^ SC.HIGH_WORD)), pxy, k)
     assert (case.seed ^ SC.HIGH_WORD) & 0xffffffff == case.seed & 0xffffffff
-    changed = int(SC.differing(a, b).any(axis=1).sum())
+    changed = int(SC.differing_words(a, b).any(axis=1).sum())
     if case.sampler == "pmj02bn" and (case.count == 1 or case.setting == "sphere_env"):
         assert changed == 0
     else:

@@ -8,7 +8,7 @@ is that sample of every pixel, so a failure names the pixel, the sample index, t
 import pytest
 
 import sample_corners as SC
-from test_gpu_parity import same_bits
+from checks import same_bits
 
 pytestmark = pytest.mark.gpu
 PIPELINES = ((0, "kz_render pipeline 0 (wavefront)"), (1, "kz_render pipeline 1 (megakernel)"))

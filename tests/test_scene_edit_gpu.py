@@ -8,31 +8,12 @@ import time
 import numpy as np
 import pytest
 
+from checks import all_samples_equal_the_oracle, same_bits
+from film_cases import fresh_film
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 TABLES = range(7)           # KZ_TABLE_NODES .. KZ_TABLE_IL_TRIS
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
-
-
-def fresh_film(kz, desc, **kw):
-    sc = kz.Scene(desc, device=0)
-    sc.render(**kw)
-    f = sc.film()
-    sc.close()
-    return f
-
-
-def all_samples_equal_the_oracle(kz, O, sc, desc, stride=1):
-    w, h, n = desc.camera["width"], desc.camera["height"], sc.sample_count
-    yy, xx, ii = np.meshgrid(np.arange(0, h, stride), np.arange(0, w, stride), np.arange(n), indexing="ij")
-    pxy, idx = np.stack([xx.ravel(), yy.ravel()], 1).astype(np.int32), ii.ravel().astype(np.uint32)
-    g, c = sc.render_samples(pxy, idx), O.OracleScene(desc).render_samples(pxy, idx)
-    assert np.abs(c[:, 2:]).max() > 0
-    return same_bits(g, c), int((g.view(np.uint32) != c.view(np.uint32)).any(axis=1).sum())
 
 
 def camera_b(kz, d):

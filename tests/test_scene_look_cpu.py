@@ -22,7 +22,7 @@ def tables(sc, which=range(NTAB)):
     return {t: sc.table(t).copy() for t in which}
 
 
-def differing(a, b):
+def differing_tables(a, b):
     return [k for k in a if not np.array_equal(a[k], b[k])]
 
 
@@ -92,7 +92,7 @@ def _refused(sc, fn, typ, rows, code, name, before, info):
     assert _call(fn, sc, typ, rows) == code, (name, lib.kz_last_error())
     msg = lib.kz_last_error().decode()
     assert len(msg) >= 25 and fn.__name__ in msg, (name, msg)
-    assert differing(before, tables(sc)) == [] and bvh(sc) == info, name
+    assert differing_tables(before, tables(sc)) == [] and bvh(sc) == info, name
     return msg
 
 
@@ -143,7 +143,7 @@ def test_every_refusal_has_a_code_a_message_and_changes_nothing(kz):
     # the Python wrapper refuses what needs a new scene
     with pytest.raises(ValueError):
         sc.set_bsdfs({0: S.diffuse(S.constanttexture((0.1, 0.2, 0.3)))})          # a texture the scene does not have
-    assert differing(before, tables(sc)) == []
+    assert differing_tables(before, tables(sc)) == []
 
     # ---- lights and transforms: cornell (mesh 7 is its light)
     d = S.cornell_box(32, 32, 4)
@@ -186,12 +186,12 @@ def test_q1_all_22_parameter_sets_on_one_scene(kz):
         d.meshes[4]["bsdf"] = b
         fresh = tables(kz.Scene(d))
         now = tables(sc)
-        assert differing(fresh, now) == [], name
-        assert differing(start, now) in ([], [8]), name
+        assert differing_tables(fresh, now) == [], name
+        assert differing_tables(start, now) in ([], [8]), name
         seen.add(now[8].tobytes())
     assert len(seen) >= 20                                      # (the study's sets differ from one another)
     sc.set_bsdfs({4: default})
-    assert differing(start, tables(sc)) == []
+    assert differing_tables(start, tables(sc)) == []
 
 
 def test_bsdf_ext_transitions_and_row_swaps(kz):
@@ -204,12 +204,12 @@ def test_bsdf_ext_transitions_and_row_swaps(kz):
     old = sc.desc.meshes[wall]["bsdf"]
     sc.set_bsdfs({wall: S.mirror()})
     assert prm_i32(sc, P_BSDFEXT) == ext0 | 1 and ext0 & 1 == 0
-    assert differing(tables(kz.Scene(sc.desc)), tables(sc)) == []
+    assert differing_tables(tables(kz.Scene(sc.desc)), tables(sc)) == []
     sc.set_bsdfs({wall: old})
-    assert prm_i32(sc, P_BSDFEXT) == ext0 and differing(start, tables(sc)) == []
+    assert prm_i32(sc, P_BSDFEXT) == ext0 and differing_tables(start, tables(sc)) == []
     # rough models are resolved as at creation (alpha = max(0.001, x^2))
     sc.set_bsdfs({wall: S.roughconductor(0.3, "Cu")})
-    assert differing(tables(kz.Scene(sc.desc)), tables(sc)) == []
+    assert differing_tables(tables(kz.Scene(sc.desc)), tables(sc)) == []
     # rows swapped among a scene's existing textures / models
     for make in (lambda: S.textured_scene(32, 20, 4), lambda: S.materials_scene(32, 24, 4)):
         sc = kz.Scene(make())
@@ -218,8 +218,8 @@ def test_bsdf_ext_transitions_and_row_swaps(kz):
         t0 = tables(sc)
         sc.set_bsdfs(rolled)
         now = tables(sc)
-        assert differing(tables(kz.Scene(sc.desc)), now) == []
-        assert 8 in differing(t0, now) and [t for t in differing(t0, now) if t < 7] == []
+        assert differing_tables(tables(kz.Scene(sc.desc)), now) == []
+        assert 8 in differing_tables(t0, now) and [t for t in differing_tables(t0, now) if t < 7] == []
 
 
 def _big_light_scene(kz):
@@ -249,8 +249,8 @@ def test_lights_scale_and_visibility_toggles_equal_fresh_scenes(kz, name):
     def step(upd, what):
         sc.set_lights(upd)
         now, fresh = tables(sc), tables(kz.Scene(sc.desc))
-        assert differing(fresh, now) == [], (what, differing(fresh, now))
-        assert [t for t in differing(start, now) if t not in (5, 6, 7)] == [], what
+        assert differing_tables(fresh, now) == [], (what, differing_tables(fresh, now))
+        assert [t for t in differing_tables(start, now) if t not in (5, 6, 7)] == [], what
         return now
 
     original = {m: dict(d.meshes[m]["light"]) for m in lights}
@@ -264,7 +264,7 @@ def test_lights_scale_and_visibility_toggles_equal_fresh_scenes(kz, name):
         assert prm_i32(sc, P_SHADOWFAST) == 0 and prm_i32(sc, P_NIL) == 0 and sc.table(6).size == 0
     else:
         assert prm_i32(sc, P_SHADOWFAST) == 1 and prm_i32(sc, P_NIL) == sum(d.meshes[m]["F"].shape[0] for m in lights)
-    assert differing(start, step(original, "back")) == []
+    assert differing_tables(start, step(original, "back")) == []
 
 
 def _with_bare_triangle(kz):
@@ -310,7 +310,7 @@ def test_transforms_equal_set_vertices_of_the_numpy_arithmetic(kz):
         for b in batches[:i + 1]:
             state.update(b)
         twin.set_vertices({m: _arrays(kz, d0, m, M) for m, M in state.items()})
-        assert differing(tables(twin, range(8)), tables(sc, range(8))) == [], i
+        assert differing_tables(tables(twin, range(8)), tables(sc, range(8))) == [], i
         assert bvh(twin) == bvh(sc), i
         for m, M in state.items():
             want = _arrays(kz, d0, m, M)
@@ -320,7 +320,7 @@ def test_transforms_equal_set_vertices_of_the_numpy_arithmetic(kz):
     # the same batch again: idempotent
     t = tables(sc)
     sc.set_transforms(batches[-1])
-    assert differing(t, tables(sc)) == []
+    assert differing_tables(t, tables(sc)) == []
     # the singular matrix left the normals as they were (normalised); the projective one moved w
     V, N = kz.scenes.transform_vertices(singular, d0.meshes[6]["V"], d0.meshes[6]["N"])
     n0 = d0.meshes[6]["N"]
@@ -336,10 +336,10 @@ def test_transform_then_set_vertices_then_transform(kz):
     newV = {m: (d0.meshes[m]["V"] + np.float32(0.03), d0.meshes[m]["N"]) for m in (5, 7)}
     sc.set_vertices(newV)
     twin.set_vertices(newV)
-    assert differing(tables(twin), tables(sc)) == []
+    assert differing_tables(tables(twin), tables(sc)) == []
     sc.set_transforms({5: B, 7: B})
     twin.set_vertices({m: kz.scenes.transform_vertices(B, *newV[m]) for m in (5, 7)})
-    assert differing(tables(twin), tables(sc)) == []
+    assert differing_tables(tables(twin), tables(sc)) == []
     assert np.array_equal(sc.desc.meshes[5]["V"], kz.scenes.transform_vertices(B, *newV[5])[0])
 
 
@@ -362,7 +362,7 @@ def test_mini_xml_identity_load_plus_transform_equals_the_loaders_transform(kz):
     assert np.array_equal(sc.desc.meshes[1]["V"], loaded.meshes[1]["V"]) and np.array_equal(sc.desc.meshes[1]["N"], loaded.meshes[1]["N"])
     twin = kz.Scene(ident_copy(X, path, V, N))
     twin.set_vertices({1: (loaded.meshes[1]["V"], loaded.meshes[1]["N"])})
-    assert differing(tables(twin), tables(sc)) == []
+    assert differing_tables(tables(twin), tables(sc)) == []
     fresh = kz.Scene(loaded)
     assert all(np.array_equal(fresh.table(t), sc.table(t)) for t in (3, 4, 5, 6, 8))
 
@@ -388,4 +388,4 @@ def test_lazy_host_sync_equals_syncing_after_every_edit(kz):
         e(eager)
         tables(eager)
         eager.bvh_info()
-    assert differing(tables(eager), tables(lazy)) == [] and bvh(eager) == bvh(lazy)
+    assert differing_tables(tables(eager), tables(lazy)) == [] and bvh(eager) == bvh(lazy)

@@ -10,15 +10,13 @@ import time
 import numpy as np
 import pytest
 
+from checks import same_bits
+from film_cases import fresh_film
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 Q1 = os.path.join(HERE, "golden", "q1_default_m0_r0.5.npz")
 DEVICE_TABLES = (1, 2, 3, 4, 5, 6, 8)       # KZ_TABLE_NODES4 .. KZ_TABLE_IL_TRIS and KZ_TABLE_BSDFS (0, the BVH2, once a refit has made it resident; 7 is a host table)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
 
 
 def _grid(desc, S=None, stride=1):
@@ -26,14 +24,6 @@ def _grid(desc, S=None, stride=1):
     S = S or desc.sampler["sampleCount"]
     yy, xx, ii = np.meshgrid(np.arange(0, H, stride), np.arange(0, W, stride), np.arange(S), indexing="ij")
     return np.stack([xx.ravel(), yy.ravel()], 1).astype(np.int32), ii.ravel().astype(np.uint32)
-
-
-def fresh_film(kz, desc, **kw):
-    sc = kz.Scene(desc, device=0)
-    sc.render(**kw)
-    f = sc.film()
-    sc.close()
-    return f
 
 
 def samples_equal_the_oracle(O, sc, stride=1):

@@ -2,134 +2,39 @@
 oracle's camera rays and against itself, the refusals that need no device, the test-only CPU reference (tests/cpu_ref/kz_temporal_ref.cpp) the GPU tests compare
 against - checked here against the variance-guided reference where the two must agree to the bit, on a two-view case whose answer is known, and against a float64
 numpy restatement - and what the history is worth on the oracle's own films."""
-import copy
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_denoise_cpu import BAD_OPTS, GUIDES, frame_rgb, synthetic_films
-from test_variance_cpu import BAD_VOPTS, MomentRef, ref_denoise_variance, synthetic_moment, variance_ref_lib
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-REF_SRC = os.path.join(HERE, "cpu_ref", "kz_temporal_ref.cpp")
-
-# ---------------------------------------------------------------- the CPU reference (also imported by test_temporal_gpu.py)
-_ref = {}
-
-
-def temporal_ref_lib(tmpdir):
-    """Compiles the CPU reference with the oracle's flags into `tmpdir` once per process (beside variance_ref_lib: the same flags, the same entries and kzt_denoise)."""
-    if "lib" not in _ref:
-        out = os.path.join(str(tmpdir), "libkz_temporal_ref.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", out, REF_SRC])
-        L = C.CDLL(out)
-        import oracle
-        abi = oracle.abi
-        f32p = C.POINTER(C.c_float)
-        L.kzo_last_error.restype = C.c_char_p
-        L.kzo_scene_create.argtypes = [C.POINTER(abi.KzSceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.kzo_scene_destroy.argtypes = [C.c_void_p]
-        L.kzo_scene_destroy.restype = None
-        L.kzo_film_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.kzv_render_canonical.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, f32p]
-        L.kzi_render_canonical.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, f32p]
-        L.kzt_denoise.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, f32p, f32p]
-        _ref["lib"] = L
-    return _ref["lib"]
-
-
-def ref_denoise_temporal(L, kz, film, moment, albedo=None, normal=None, depth=None, border=0, samples=4, sigma_variance=0.0, current=None, previous=None, history=None,
-                         depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, **opts):
-    """The reference's (film, history (h, w, 12), v_last) of five films (albedo / normal may be None), the two views and a history (None: none); options as
-    kz.denoise_opts / kz.variance_opts / kz.temporal_opts take them."""
-    f32p = C.POINTER(C.c_float)
-    film = np.ascontiguousarray(film, np.float32)
-    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (moment, albedo, normal, depth)]
-    h, w = film.shape[0] - 2 * border, film.shape[1] - 2 * border
-    history = None if history is None else np.ascontiguousarray(history, np.float32).reshape(h, w, 12)
-    out, hist, var = np.full(film.shape, np.nan, np.float32), np.full((h, w, 12), np.nan, np.float32), np.full((h, w), np.nan, np.float32)
-    o, v, t = kz.denoise_opts(**opts), kz.variance_opts(sigma_variance, samples), kz.temporal_opts(depth_tolerance, normal_tolerance, max_history)
-    p = lambda a: None if a is None else a.ctypes.data_as(f32p)
-    rc = L.kzt_denoise(w, h, border, p(film), *[p(a) for a in g], C.byref(o), C.byref(v), C.byref(t), None if current is None else C.byref(current),
-                       None if previous is None else C.byref(previous), p(history), p(out), p(hist), p(var))
-    assert rc == 0, "the reference refused the options"
-    return out, hist, var
-
-
-def camera_of(kz, width, height, origin, target, up=(0, 1, 0), fov=40.0, **more):
-    """A SceneDescription.camera: a perspective look-at camera."""
-    cam = dict(kz.scenes.SceneDescription().camera)
-    cam.update(width=width, height=height, fov=fov, toWorld=kz.scenes.look_at(origin, target, up), **more)
-    return cam
-
-
-def view_arrays(view):
-    """(o, a, u, v, inv 3 x 3) of a KzTemporalView as float64 arrays of the fp32 words."""
-    f = lambda x: np.array(list(x), np.float32).astype(np.float64)
-    return f(view.o), f(view.a), f(view.u), f(view.v), f(view.inv).reshape(3, 3)
-
-
-def random_history(w, h, seed, holes=0.2):
-    """A history nobody rendered: lognormal colours and variances, unit normals, distances 1 .. 9, counts 1 .. 40, and `holes` of the pixels empty (N = 0, all zeros)."""
-    rng = np.random.default_rng(seed)
-    hist = np.zeros((h, w, 12), np.float32)
-    hist[..., :3] = rng.lognormal(-1.0, 1.0, (h, w, 3))
-    hist[..., 3] = rng.lognormal(-3.0, 2.0, (h, w))
-    n = rng.normal(size=(h, w, 3))
-    hist[..., 4:7] = n / np.linalg.norm(n, axis=2, keepdims=True)
-    hist[..., 7] = rng.uniform(1.0, 9.0, (h, w))
-    hist[..., 8] = rng.integers(1, 41, (h, w))
-    hist[rng.random((h, w)) < holes] = 0.0
-    return hist
+from checks import c_layout, header_surface, refused, same_bits_strict
+from cpu_refs import AovRef, MomentRef, lib, ref_denoise_temporal, ref_denoise_variance
+from film_cases import BAD_OPTS, BAD_TOPTS, BAD_VOPTS, GUIDES, _orbit, camera_of, frame_rgb, quality_inputs, random_history, synthetic_films, synthetic_moment, view_arrays
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return temporal_ref_lib(tmp_path_factory.mktemp("kzt"))
+    return lib("temporal", tmp_path_factory.mktemp("kzt"))
 
 
 @pytest.fixture(scope="module")
 def vref(tmp_path_factory):
-    return variance_ref_lib(tmp_path_factory.mktemp("kzv"))
+    return lib("variance", tmp_path_factory.mktemp("kzv"))
 
 
 # ---------------------------------------------------------------- 1. ABI
 def test_header_declarations_are_exported(kz):
     a = kz.abi
-    lib = a.load_library()
-    src = open(os.path.join(ROOT, "include", "kazen_mi355x_temporal.h")).read()
-    declared = set(re.findall(r"^(?:int|void|const char \*)\s*\*?(kz_[a-z0-9_]+)\s*\(", src, re.M))
-    assert declared == set(a.TEMPORAL_EXPORTS) and len(a.TEMPORAL_EXPORTS) == 6, declared ^ set(a.TEMPORAL_EXPORTS)
-    exported = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.LIB_PATH], text=True)))
-    assert declared <= exported, declared - exported
-    if os.path.exists(a.DEV_LIB_PATH):
-        dev = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.DEV_LIB_PATH], text=True)))
-        assert declared <= dev, declared - dev
-    for sym in declared:
-        assert getattr(lib, sym) is not None
     # a surface of its own: disjoint from every other list, and nothing added to the existing headers
-    for other in (a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS, a.VARIANCE_EXPORTS):
-        assert not (declared & set(other)), declared & set(other)
-    for name in ("kazen_mi355x.h", "kazen_mi355x_dev.h", "kazen_mi355x_edit.h", "kazen_mi355x_aov.h", "kazen_mi355x_denoise.h", "kazen_mi355x_variance.h"):
-        text = open(os.path.join(ROOT, "include", name)).read().lower()
-        for word in ("kz_temporal", "kz_denoise_temporal", "kztemporal"):
-            assert word not in text, (name, word)
-    assert lib.kz_abi_version() == a.KZ_ABI_VERSION == 6
+    header_surface(kz, "include/kazen_mi355x_temporal.h", a.TEMPORAL_EXPORTS, 6, [a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS, a.VARIANCE_EXPORTS],
+                   ["include/kazen_mi355x.h", "include/kazen_mi355x_dev.h", "include/kazen_mi355x_edit.h", "include/kazen_mi355x_aov.h", "include/kazen_mi355x_denoise.h",
+                    "include/kazen_mi355x_variance.h"], ["kz_temporal", "kz_denoise_temporal", "kztemporal"])
 
 
 def test_struct_sizes(kz, tmp_path):
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "kazen_mi355x_temporal.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", '
-                   'sizeof(KzTemporalView), offsetof(KzTemporalView, a), offsetof(KzTemporalView, inv), offsetof(KzTemporalView, reserved), sizeof(KzTemporalOpts), '
-                   'offsetof(KzTemporalOpts, normalTolerance), offsetof(KzTemporalOpts, maxHistory), offsetof(KzTemporalOpts, flags), offsetof(KzTemporalOpts, reserved));return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    assert subprocess.check_output([str(exe)], text=True).split() == ["96", "12", "48", "84", "32", "4", "8", "12", "16"]
+    assert c_layout(tmp_path, "kazen_mi355x_temporal.h", ["sizeof(KzTemporalView)", "offsetof(KzTemporalView, a)", "offsetof(KzTemporalView, inv)", "offsetof(KzTemporalView, reserved)",
+                                                          "sizeof(KzTemporalOpts)", "offsetof(KzTemporalOpts, normalTolerance)", "offsetof(KzTemporalOpts, maxHistory)",
+                                                          "offsetof(KzTemporalOpts, flags)", "offsetof(KzTemporalOpts, reserved)"]) == ["96", "12", "48", "84", "32", "4", "8", "12", "16"]
     v, o = kz.abi.KzTemporalView, kz.abi.KzTemporalOpts
     assert C.sizeof(v) == 96 and (v.o.offset, v.a.offset, v.u.offset, v.v.offset, v.inv.offset, v.reserved.offset) == (0, 12, 24, 36, 48, 84)
     assert C.sizeof(o) == 32 and (o.depthTolerance.offset, o.normalTolerance.offset, o.maxHistory.offset, o.flags.offset, o.reserved.offset) == (0, 4, 8, 12, 16)
@@ -196,19 +101,6 @@ def test_view_round_trip(kz):
 
 
 # ---------------------------------------------------------------- 4. refusals
-BAD_TOPTS = [{"depth_tolerance": -1.0}, {"depth_tolerance": float("nan")}, {"depth_tolerance": float("inf")}, {"normal_tolerance": -1e-30}, {"normal_tolerance": float("nan")},
-             {"normal_tolerance": float("-inf")}, {"max_history": 65536}, {"max_history": 1 << 31}, {"tflags": 1}, {"tflags": 1 << 31}, {"treserved": (1, 0, 0, 0)},
-             {"treserved": (0, 2, 0, 0)}, {"treserved": (0, 0, 3, 0)}, {"treserved": (0, 0, 0, 4)}]
-
-
-def _refused(kz, fn, code, *words):
-    with pytest.raises(kz.abi.KzError) as e:
-        fn()
-    assert e.value.code == code, str(e.value)
-    for w in words:
-        assert w in str(e.value), (w, str(e.value))
-
-
 def test_refusals_without_a_device(kz):
     a = kz.abi
     lib = a.load_library()
@@ -216,48 +108,48 @@ def test_refusals_without_a_device(kz):
     cam = camera_of(kz, 64, 48, (0, 0, 0), (0, 0, 1))
     flat = np.array(cam["toWorld"], np.float32).reshape(4, 4).copy()
     flat[:3, 0] = 0.0
-    _refused(kz, lambda: kz.temporal_view(dict(cam, toWorld=flat)), a.KZ_ERR_UNSUPPORTED, "kz_temporal_view", "singular")
+    refused(kz, lambda: kz.temporal_view(dict(cam, toWorld=flat)), a.KZ_ERR_UNSUPPORTED, "kz_temporal_view", "singular")
     persp = np.array(cam["toWorld"], np.float32).reshape(4, 4).copy()
     persp[3, 0] = 0.25
-    _refused(kz, lambda: kz.temporal_view(dict(cam, toWorld=persp)), a.KZ_ERR_UNSUPPORTED, "kz_temporal_view", "not affine")
-    _refused(kz, lambda: kz.temporal_view(dict(cam, type="orthographic")), a.KZ_ERR_UNSUPPORTED)
+    refused(kz, lambda: kz.temporal_view(dict(cam, toWorld=persp)), a.KZ_ERR_UNSUPPORTED, "kz_temporal_view", "not affine")
+    refused(kz, lambda: kz.temporal_view(dict(cam, type="orthographic")), a.KZ_ERR_UNSUPPORTED)
     assert lib.kz_temporal_view(None, None) == a.KZ_ERR_INVALID_ARG
     assert not any(kz.temporal_view(cam).reserved)
     # kz_denoise_temporal: bad options of each of the three structs first, then the state, all before a replica is looked for
     sc = kz.Scene(kz.scenes.cornell_box(16, 16, 2))
     assert lib.kz_denoise_temporal(None, -1, None, None, None) == a.KZ_ERR_INVALID_ARG
     for bad in BAD_OPTS + BAD_VOPTS + BAD_TOPTS:
-        _refused(kz, lambda: sc.denoise_temporal(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal")
+        refused(kz, lambda: sc.denoise_temporal(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal")
     for bad in BAD_TOPTS:
-        _refused(kz, lambda: sc.denoise_temporal(**bad), a.KZ_ERR_INVALID_ARG, "KzTemporalOpts")
-    _refused(kz, sc.denoise_temporal, a.KZ_ERR_STATE, "kz_denoise_temporal", "KZ_AOV_DEPTH", "mask 0")
+        refused(kz, lambda: sc.denoise_temporal(**bad), a.KZ_ERR_INVALID_ARG, "KzTemporalOpts")
+    refused(kz, sc.denoise_temporal, a.KZ_ERR_STATE, "kz_denoise_temporal", "KZ_AOV_DEPTH", "mask 0")
     sc.set_aovs(["albedo", "normal"])
-    _refused(kz, sc.denoise_temporal, a.KZ_ERR_STATE, "kz_denoise_temporal", "KZ_AOV_DEPTH", "mask 3")
+    refused(kz, sc.denoise_temporal, a.KZ_ERR_STATE, "kz_denoise_temporal", "KZ_AOV_DEPTH", "mask 3")
     sc.set_aovs(GUIDES)
-    _refused(kz, sc.denoise_temporal, a.KZ_ERR_STATE, "kz_denoise_temporal", "switched off")
-    _refused(kz, lambda: sc.denoise_temporal(guides=["albedo", "normal"]), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal", "KZ_AOV_DEPTH")
+    refused(kz, sc.denoise_temporal, a.KZ_ERR_STATE, "kz_denoise_temporal", "switched off")
+    refused(kz, lambda: sc.denoise_temporal(guides=["albedo", "normal"]), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal", "KZ_AOV_DEPTH")
     sc.set_variance(True)
     for bad in BAD_OPTS + BAD_VOPTS + BAD_TOPTS:
-        _refused(kz, lambda: sc.denoise_temporal(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal")
+        refused(kz, lambda: sc.denoise_temporal(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal")
     for good in ({}, {"samples": 4, "max_history": 65535, "depth_tolerance": 0.5, "normal_tolerance": 2.0, "iterations": 8}):
-        _refused(kz, lambda: sc.denoise_temporal(**good), a.KZ_ERR_STATE, "kz_scene_upload")      # the scene is on no device
+        refused(kz, lambda: sc.denoise_temporal(**good), a.KZ_ERR_STATE, "kz_scene_upload")      # the scene is on no device
     for fn in (sc.temporal_info, sc.temporal_reset, sc.temporal_history):
-        _refused(kz, fn, a.KZ_ERR_STATE, "kz_scene_upload")
+        refused(kz, fn, a.KZ_ERR_STATE, "kz_scene_upload")
     # the test surface checks its arguments and options first, then the sample count, then asks for the device
     film = np.ones((5, 7, 4), np.float32)
     view = kz.temporal_view(camera_of(kz, 7, 5, (0, 0, 0), (0, 0, 1)))
     ok = dict(depth=film, samples=4, current=view)
     for bad in BAD_OPTS + BAD_VOPTS + BAD_TOPTS:
-        _refused(kz, lambda: kz.denoise_temporal_films(film, film, **ok, **bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films")
-    _refused(kz, lambda: kz.denoise_temporal_films(film, film, samples=4, current=view), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films", "depth")
-    _refused(kz, lambda: kz.denoise_temporal_films(film, None, **ok), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films")
-    _refused(kz, lambda: kz.denoise_temporal_films(film, film, depth=film, samples=4), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films", "view")
-    _refused(kz, lambda: kz.denoise_temporal_films(film, film, **ok, history=np.zeros((5, 7, 12), np.float32)), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films", "view")
-    _refused(kz, lambda: kz.denoise_temporal_films(film, film, film, **ok, guides="albedo"), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films", "KZ_AOV_DEPTH")
-    _refused(kz, lambda: kz.denoise_temporal_films(film, film, **ok, border=3), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films")
-    _refused(kz, lambda: kz.denoise_temporal_films(film, film, depth=film, current=view), a.KZ_ERR_STATE, "kz_denoise_temporal_films", "samples = 0")
+        refused(kz, lambda: kz.denoise_temporal_films(film, film, **ok, **bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films")
+    refused(kz, lambda: kz.denoise_temporal_films(film, film, samples=4, current=view), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films", "depth")
+    refused(kz, lambda: kz.denoise_temporal_films(film, None, **ok), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films")
+    refused(kz, lambda: kz.denoise_temporal_films(film, film, depth=film, samples=4), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films", "view")
+    refused(kz, lambda: kz.denoise_temporal_films(film, film, **ok, history=np.zeros((5, 7, 12), np.float32)), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films", "view")
+    refused(kz, lambda: kz.denoise_temporal_films(film, film, film, **ok, guides="albedo"), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films", "KZ_AOV_DEPTH")
+    refused(kz, lambda: kz.denoise_temporal_films(film, film, **ok, border=3), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal_films")
+    refused(kz, lambda: kz.denoise_temporal_films(film, film, depth=film, current=view), a.KZ_ERR_STATE, "kz_denoise_temporal_films", "samples = 0")
     if lib.kz_device_count() == 0:
-        _refused(kz, lambda: kz.denoise_temporal_films(film, film, **ok), a.KZ_ERR_NO_DEVICE)
+        refused(kz, lambda: kz.denoise_temporal_films(film, film, **ok), a.KZ_ERR_NO_DEVICE)
 
 
 # ---------------------------------------------------------------- 5. identities
@@ -278,7 +170,6 @@ def test_identities(kz, ref, vref, frame, border):
     moment = synthetic_moment(colour, seed=w + 7 * h + b)
     view = kz.temporal_view(camera_of(kz, w, h, (0.3, -0.2, 1.0), (0.1, 0.4, 9.0), fov=47.0))
     other = kz.temporal_view(camera_of(kz, w, h, (0.35, -0.2, 1.0), (0.1, 0.4, 9.0), fov=47.0))
-    bits = lambda x: np.ascontiguousarray(x, np.float32).view(np.uint32)
     inner = (slice(b, b + h), slice(b, b + w))
     for al, no in _guide_subsets():
         given = [albedo if al else None, normal if no else None, depth]
@@ -286,17 +177,17 @@ def test_identities(kz, ref, vref, frame, border):
             kw = dict(border=b, samples=4, demodulate=demodulate, iterations=2)
             want, wv = ref_denoise_variance(vref, kz, colour, moment, *given, **kw)
             got, hist, gv = ref_denoise_temporal(ref, kz, colour, moment, *given, current=view, **kw)
-            assert np.array_equal(bits(got), bits(want)) and np.array_equal(bits(gv), bits(wv)), (frame, b, al, no, demodulate)
+            assert same_bits_strict(got, want) and same_bits_strict(gv, wv), (frame, b, al, no, demodulate)
             valid = colour[inner][..., 3] != 0
             assert np.array_equal(hist[..., 8], valid.astype(np.float32)) and not hist[..., 9:].any() and not hist[~valid].any()
             junk = random_history(w, h, seed=5)
             got, hist1, gv = ref_denoise_temporal(ref, kz, colour, moment, *given, current=view, previous=other, history=junk, max_history=1, **kw)
-            assert np.array_equal(bits(got), bits(want)) and np.array_equal(bits(gv), bits(wv)) and np.array_equal(bits(hist1), bits(hist))
+            assert same_bits_strict(got, want) and same_bits_strict(gv, wv) and same_bits_strict(hist1, hist)
             # the frame's own history, the same view
             _, hist2, _ = ref_denoise_temporal(ref, kz, colour, moment, *given, current=view, previous=view, history=hist, max_history=32, **kw)
             z = np.where(depth[inner][..., 3] != 0, depth[inner][..., 0] / np.where(depth[inner][..., 3] == 0, 1, depth[inner][..., 3]), 0)
             assert np.array_equal(hist2[..., 8], np.where(valid, np.where(z > 0, 2.0, 1.0), 0.0).astype(np.float32)), (frame, b, al, no, demodulate)
-            assert np.array_equal(bits(hist2[..., 4:8]), bits(hist[..., 4:8]))
+            assert same_bits_strict(hist2[..., 4:8], hist[..., 4:8])
 
 
 # ---------------------------------------------------------------- 6. two views of a plane
@@ -488,24 +379,9 @@ def test_reference_agrees_with_numpy(kz, ref, case):
 
 
 # ---------------------------------------------------------------- 7. what it is worth
-def _orbit(kz, desc, degrees):
-    """`desc` with its camera turned by `degrees` about the world's y axis through the point it looks at (taken 4 units along its axis)."""
-    d = copy.copy(desc)
-    m = np.array(desc.camera["toWorld"], np.float64).reshape(4, 4)
-    centre = m[:3, 3] + 4.0 * m[:3, 2]
-    t = np.radians(degrees)
-    R = np.array([[np.cos(t), 0, np.sin(t)], [0, 1, 0], [-np.sin(t), 0, np.cos(t)]])
-    out = m.copy()
-    out[:3, :3] = R @ m[:3, :3]
-    out[:3, 3] = centre + R @ (m[:3, 3] - centre)
-    d.camera = dict(desc.camera, toWorld=out.astype(np.float32))
-    return d
-
-
 def _sequence(kz, ref, aov_lib, make, frames, step_degrees):
     """The reference chain over `frames` frames of 4 spp from the sample ranges [4f, 4f + 4), the camera turned by step_degrees per frame. Returns the last
     frame's description, its temporal result, its variance-guided result on the frame alone, and its noisy film."""
-    from test_aov_cpu import AovRef
     history, prev, last = None, None, None
     for f in range(frames):
         d = _orbit(kz, make(96, 72, 4), f * step_degrees) if step_degrees else make(96, 72, 4)
@@ -527,11 +403,9 @@ def test_quality_on_the_oracles_films(kz, O, ref, vref, tmp_path_factory, scene)
     """The setting of test_variance_cpu.test_quality_on_the_oracles_films - 96 x 72, 4 spp frames against 1024 spp, default options - with eight frames folded into
     the history: the MSE of frame 8's result is strictly below that of the variance-guided filter on frame 8 alone (asserted on Cornell, static camera; printed for
     the other scenes and for a camera that orbits by 2 degrees per frame; recorded in DESIGN.md 4g)."""
-    from test_aov_cpu import aov_ref_lib
-    from test_variance_cpu import _quality_inputs
     make = {"cornell": kz.scenes.cornell_box, "materials": kz.scenes.materials_scene, "textured": kz.scenes.textured_scene}[scene]
-    aov_lib = aov_ref_lib(tmp_path_factory.mktemp("kza"))
-    clean, _ = _quality_inputs(kz, O, vref, tmp_path_factory, scene)      # (shared with test_variance_cpu when both run: the 1024 spp film is the expensive one)
+    aov_lib = lib("aov", tmp_path_factory.mktemp("kza"))
+    clean, _ = quality_inputs(kz, O, vref, tmp_path_factory, scene)      # (shared with test_variance_cpu when both run: the 1024 spp film is the expensive one)
     b = (clean.shape[0] - 72) // 2
     mse = lambda f, want: float(((frame_rgb(f, b).astype(np.float64) - want) ** 2).mean())
     want = frame_rgb(clean, b).astype(np.float64)

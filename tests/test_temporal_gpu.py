@@ -7,43 +7,29 @@ import copy
 import numpy as np
 import pytest
 
-from test_aov_cpu import H, SPP, W
-from test_aov_gpu import same_bits
-from test_denoise_cpu import GUIDES, synthetic_films
-from test_temporal_cpu import _orbit, camera_of, random_history, ref_denoise_temporal, temporal_ref_lib
-from test_variance_cpu import ref_denoise_variance, synthetic_moment, variance_ref_lib
-from test_variance_gpu import differing
+from checks import differing, same_bits_strict
+from cpu_refs import lib, ref_denoise_temporal, ref_denoise_variance
+from film_cases import GUIDES, H, SPP, W, _orbit, random_history, synthetic_films, synthetic_moment, view_pairs
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return temporal_ref_lib(tmp_path_factory.mktemp("kzt"))
+    return lib("temporal", tmp_path_factory.mktemp("kzt"))
 
 
 @pytest.fixture(scope="module")
 def vref(tmp_path_factory):
-    return variance_ref_lib(tmp_path_factory.mktemp("kzv"))
-
-
-def view_pairs(kz, w, h):
-    """(current, previous) over a frame whose synthetic depths are 1 .. 9: the same view; the camera moved by 0.3 of a pixel's footprint at distance 5; turned by the
-    angle of 40 pixels, so that part of a wide frame leaves (and all of a narrow one); turned round."""
-    at = lambda o, t: kz.temporal_view(camera_of(kz, w, h, o, t, fov=50.0))
-    base = at((0, 0, 0), (0, 0, 1))
-    pix = 2.0 * np.tan(np.radians(25.0)) / w
-    yaw = 40 * pix
-    return {"same": (base, base), "fraction": (at((1.5 * pix, -0.9 * pix, 0), (1.5 * pix, -0.9 * pix, 1)), base),
-            "forty": (at((0, 0, 0), (np.sin(yaw), 0, np.cos(yaw))), base), "round": (at((0, 0, 0), (0, 0, -1)), base)}
+    return lib("variance", tmp_path_factory.mktemp("kzv"))
 
 
 def check(kz, ref, films, b, cur, prev, history, tag, **kw):
     got, gh, gv = kz.denoise_temporal_films(*films, border=b, samples=4, current=cur, previous=prev, history=history, return_variance=True, **kw)
     want, wh, wv = ref_denoise_temporal(ref, kz, *films, border=b, samples=4, current=cur, previous=prev, history=history, **kw)
-    assert same_bits(got, want), (tag, kw, "film", differing(got, want))
-    assert same_bits(gh, wh), (tag, kw, "history", differing(gh, wh))
-    assert same_bits(gv, wv), (tag, kw, "variance", differing(gv, wv))
+    assert same_bits_strict(got, want), (tag, kw, "film", differing(got, want))
+    assert same_bits_strict(gh, wh), (tag, kw, "history", differing(gh, wh))
+    assert same_bits_strict(gv, wv), (tag, kw, "variance", differing(gv, wv))
     return wh
 
 
@@ -89,10 +75,10 @@ def test_identities_on_the_device(gpu_lib, kz):
     for kw in (dict(), dict(iterations=3, demodulate=False, sigma_variance=1.5)):
         want, wv = kz.denoise_variance_films(colour, moment, albedo, normal, depth, border=b, samples=8, return_variance=True, **kw)
         got, hist, gv = kz.denoise_temporal_films(colour, moment, albedo, normal, depth, border=b, samples=8, current=cur, return_variance=True, **kw)
-        assert same_bits(got, want) and same_bits(gv, wv)
+        assert same_bits_strict(got, want) and same_bits_strict(gv, wv)
         got, hist1, gv = kz.denoise_temporal_films(colour, moment, albedo, normal, depth, border=b, samples=8, current=cur, previous=prev, history=random_history(70, 45, 1),
                                                    max_history=1, return_variance=True, **kw)
-        assert same_bits(got, want) and same_bits(gv, wv) and same_bits(hist1, hist)
+        assert same_bits_strict(got, want) and same_bits_strict(gv, wv) and same_bits_strict(hist1, hist)
         assert set(np.unique(hist[..., 8])) == {0.0, 1.0}
 
 
@@ -122,11 +108,11 @@ def test_replica_chain_equals_the_reference_chain(gpu_lib, kz, ref, scene):
         want, history, _ = ref_denoise_temporal(ref, kz, *films, border=b, samples=SPP, current=view, previous=prev, history=history)
         prev = view
         got, gh = sc.denoised_film(), sc.temporal_history()
-        assert same_bits(got, want), (scene, f, differing(got, want))
-        assert same_bits(gh, history), (scene, f, differing(gh, history))
+        assert same_bits_strict(got, want), (scene, f, differing(got, want))
+        assert same_bits_strict(gh, history), (scene, f, differing(gh, history))
         assert sc.temporal_info() == (2 * W * H * 36, f + 1)
         for x, y in zip(films, _films(sc)):                           # the films do not notice
-            assert same_bits(x, y)
+            assert same_bits_strict(x, y)
         if f:                                                         # most of the frame found its history
             found = float((history[..., 8] > 1).mean())
             print("temporal chain %s frame %d: %.1f %% of the pixels found a history" % (scene, f + 1, 100 * found))
@@ -167,15 +153,15 @@ def test_lifecycle(gpu_lib, kz, ref, vref):
     sc.denoise_temporal()
     assert sc.denoise_info() == dn_bytes and sc.temporal_info() == (tp_bytes, 1)      # no buffer beyond kz_denoise's but the history
     first, _ = ref_denoise_variance(vref, kz, *films, border=b, samples=SPP)
-    assert same_bits(sc.denoised_film(), first)                      # no history yet: kz_denoise_variance's bits
+    assert same_bits_strict(sc.denoised_film(), first)                      # no history yet: kz_denoise_variance's bits
     sc.denoise_temporal()
     assert sc.temporal_info() == (tp_bytes, 2)
     _, h1, _ = ref_denoise_temporal(ref, kz, *films, border=b, samples=SPP, current=view)
     want2, h2, _ = ref_denoise_temporal(ref, kz, *films, border=b, samples=SPP, current=view, previous=view, history=h1)
-    assert same_bits(sc.denoised_film(), want2) and same_bits(sc.temporal_history(), h2) and not same_bits(want2, first)
+    assert same_bits_strict(sc.denoised_film(), want2) and same_bits_strict(sc.temporal_history(), h2) and not same_bits_strict(want2, first)
     # kz_denoise_release leaves the history; the next call finds it
     sc.denoise_release()
-    assert sc.denoise_info() == 0 and sc.temporal_info() == (tp_bytes, 2) and same_bits(sc.temporal_history(), h2)
+    assert sc.denoise_info() == 0 and sc.temporal_info() == (tp_bytes, 2) and same_bits_strict(sc.temporal_history(), h2)
     sc.denoise_temporal()
     assert sc.temporal_info() == (tp_bytes, 3) and sc.denoise_info() == dn_bytes
     # a material edit keeps it, an edit of the geometry - even one that moves nothing - makes it stale: the next call starts at 1 in the buffers it has
@@ -189,21 +175,21 @@ def test_lifecycle(gpu_lib, kz, ref, vref):
     assert sc.temporal_info() == (tp_bytes, 4)                       # (a host flag: nothing happens until the next call)
     sc.denoise_temporal()
     assert sc.temporal_info() == (tp_bytes, 1)
-    assert same_bits(sc.denoised_film(), first) and same_bits(sc.temporal_history(), h1)      # (the films are still the ones rendered above)
+    assert same_bits_strict(sc.denoised_film(), first) and same_bits_strict(sc.temporal_history(), h1)      # (the films are still the ones rendered above)
     # a call that demodulates differently from the history is refused and changes nothing
     refused(lambda: sc.denoise_temporal(demodulate=False), a.KZ_ERR_STATE, "kz_denoise_temporal", "kz_temporal_reset")
     refused(lambda: sc.denoise_temporal(guides=["normal", "depth"]), a.KZ_ERR_STATE, "kz_denoise_temporal", "kz_temporal_reset")
     refused(lambda: sc.denoise_temporal(guides=["albedo", "normal"]), a.KZ_ERR_INVALID_ARG, "kz_denoise_temporal", "KZ_AOV_DEPTH")
-    assert sc.temporal_info() == (tp_bytes, 1) and same_bits(sc.temporal_history(), h1)
+    assert sc.temporal_info() == (tp_bytes, 1) and same_bits_strict(sc.temporal_history(), h1)
     # kz_temporal_reset: the info is zero, the next result is kz_denoise_variance's, and the other demodulation is welcome
     sc.temporal_reset()
     assert sc.temporal_info() == (0, 0) and sc.denoise_info() == dn_bytes
     refused(sc.temporal_history, a.KZ_ERR_STATE, "kz_temporal_download")
     sc.denoise_temporal(demodulate=False)
     want, _ = ref_denoise_variance(vref, kz, *films, border=b, samples=SPP, demodulate=False)
-    assert same_bits(sc.denoised_film(), want) and sc.temporal_info() == (tp_bytes, 1)
+    assert same_bits_strict(sc.denoised_film(), want) and sc.temporal_info() == (tp_bytes, 1)
     sc.denoise_variance()
-    assert same_bits(sc.denoised_film(), first) and sc.temporal_info() == (tp_bytes, 1)      # the other calls leave the history alone
+    assert same_bits_strict(sc.denoised_film(), first) and sc.temporal_info() == (tp_bytes, 1)      # the other calls leave the history alone
     # the variance switch off: refused; the history stays until it is reset
     sc.set_variance(False)
     refused(sc.denoise_temporal, a.KZ_ERR_STATE, "kz_denoise_temporal", "switched off")

@@ -13,11 +13,11 @@ import numpy as np
 import pytest
 
 import trace_ray_sets as R
-from test_scene_edit_cpu import check_refit
+from scene_tables import check_refit
+from trace_ray_sets import LDS_ENTRIES, flattened_ties
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P_STACKBOUND4, P_SHADOWFAST = 292, 296        # offsets into KzParams (nano-kazen_amd/csrc/kz_internal.h), pinned by test_stack_bound_offset
-LDS_ENTRIES = 16                              # stack entries per lane the default launch keeps in LDS
 CASES = sorted(set(R.REFIT_CLOSEST) | set(R.REFIT_SHADOW))
 
 
@@ -150,7 +150,7 @@ def test_deformations_are_seeded_stay_in_the_room_and_name_each_mesh_once(kz, na
 
 @pytest.mark.parametrize("name,deform", CASES)
 def test_refit_is_conservative_and_keeps_the_stack_bound(kz, O, name, deform):
-    """check_refit of tests/test_scene_edit_cpu.py on the deformed host scene; the stack bound recomputed from the child words and empty-slot marks of
+    """check_refit of tests/scene_tables.py on the deformed host scene; the stack bound recomputed from the child words and empty-slot marks of
     KZ_TABLE_NODES4 equals KzParams.stackBound4, before and after the edit - the same number: the overflow area a launch owns covers the deformed tree."""
     fresh, case = fresh_case(kz, O, name), deformed_case(kz, O, name, deform)
     sc = case["scene"]
@@ -237,15 +237,6 @@ def test_stacked_copies_tie_four_ways_across_subtrees(kz, O):
     spread = sum(len(set(where[:, p])) >= 2 for p in range(625))
     print("soup/stacked: the four copies of %d of 625 triangles lie under two or more children of packet %d" % (spread, top))
     assert spread >= 313, spread
-
-
-def flattened_ties(kz, O, case):
-    """The rays of a flattened case whose closest hit lies on the squashed box's footprint with the floor's triangle and the box's triangle at the SAME t, bit for bit
-    (the floor alone and the box alone answer with the bits of the scene's closest hit): a tie between mesh 0 and mesh 5."""
-    floor = O.OracleScene(R.only_meshes(kz.scenes, case["desc"], [0]), brute=True).trace_rays(*case["rays"])
-    box = O.OracleScene(R.only_meshes(kz.scenes, case["desc"], [5]), brute=True).trace_rays(*case["rays"])
-    t = case["ref"]["t"].view(np.uint32)
-    return (floor["mesh"] >= 0) & (box["mesh"] >= 0) & (floor["t"].view(np.uint32) == t) & (box["t"].view(np.uint32) == t)
 
 
 def test_flattened_box_ties_with_the_floor_and_the_collapsed_box_is_never_hit(kz, O):

@@ -3,7 +3,7 @@
 A resident scene is deformed with Scene.set_vertices (tests/trace_ray_sets.py `deformation`: scatter, slivers, stacked, nested on the 5 000-triangle soup, flattened
 on the cornell box) and the kernels a render launches walk what kz_refit.hip and the host refit left: inner boxes about the size of the room, children that all
 contain the ray's origin (entry distances tie at tmin, overlaps tie at tmax - tmin), four coincident copies of 625 triangles in different subtrees, boxes
-that are nothing but the leaf pad, triangles without area, invisible lights that moved. The checks are those of tests/test_trace_wf_gpu.py - its helpers, imported - against the brute force of
+that are nothing but the leaf pad, triangles without area, invisible lights that moved. The checks are those of tests/test_trace_wf_gpu.py - the helpers of tests/trace_ray_sets.py - against the brute force of
 the DEFORMED description: mesh and prim equal, t / u / v the oracle's bits; shadow sums exact; every launch shape the bits of the default one.
 
 tests/test_trace_refit_cpu.py runs before these tests (no GPU) and establishes the stack bound first: the bound of the refit tree is the build's, so the overflow
@@ -13,10 +13,9 @@ import numpy as np
 import pytest
 
 import trace_ray_sets as R
-from test_gpu_parity import same_bits
-from test_scene_edit_gpu import all_samples_equal_the_oracle, fresh_film
-from test_trace_refit_cpu import LDS_ENTRIES, flattened_ties
-from test_trace_wf_gpu import KINDS, PACKET_SHAPES, SHAPES, check_closest, check_shadow, report, run, same_result, u32
+from checks import all_samples_equal_the_oracle, same_bits
+from film_cases import fresh_film
+from trace_ray_sets import KINDS, LDS_ENTRIES, PACKET_SHAPES, SHAPES, check_closest, check_shadow, flattened_ties, report, run, same_result, u32
 
 pytestmark = pytest.mark.gpu
 TABLES = range(7)           # KZ_TABLE_NODES .. KZ_TABLE_IL_TRIS
@@ -106,7 +105,7 @@ def test_overlapping_boxes_fill_the_stacks_and_stay_inside_the_overflow_area(gpu
 
 @pytest.mark.parametrize("kernel", [0, 1, 2])
 def test_launch_shapes_give_the_bits_of_the_default_launch_on_a_refit_tree(gpu_lib, kz, O, kernel):
-    """soup/scatter, a 4 113-entry permuted queue: every shape of SHAPES / PACKET_SHAPES (tests/test_trace_wf_gpu.py) gives the bits of the default launch - one
+    """soup/scatter, a 4 113-entry permuted queue: every shape of SHAPES / PACKET_SHAPES (tests/trace_ray_sets.py) gives the bits of the default launch - one
     workgroup whose lanes take ray after ray on stacks that reach the overflow area, 2 LDS entries, the thresholds, the counting instantiations - and the counting
     shapes agree on node visits and triangle tests. The deformed tree costs many times the node visits of the fresh one (printed)."""
     fresh, case = R.closest_case(kz, O, "soup", device=0), R.closest_case(kz, O, "soup", device=0, deform="scatter")

@@ -13,74 +13,10 @@ import numpy as np
 import pytest
 
 import trace_ray_sets as R
-from test_gpu_parity import same_bits
+from checks import same_bits
+from trace_ray_sets import KINDS, PACKET_SHAPES, SHAPES, check_closest, check_shadow, pending_of, report, run, same_result, sums_before, u32
 
 pytestmark = pytest.mark.gpu
-KINDS = {0: "per-lane", 1: "packet", 2: "walk-through"}
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def sentinel_hits(n):
-    """A hit record per slot that no kernel writes: t = 2^20 + slot, u, v, and a gid the scene does not have."""
-    h = np.zeros((n, 4), np.float32)
-    h[:, 0] = np.float32(1 << 20) + np.arange(n, dtype=np.float32)
-    h[:, 1], h[:, 2] = 0.125, 0.375
-    h[:, 3] = (np.uint32(0xF0000000) | np.arange(n, dtype=np.uint32)).view(np.float32)
-    return h
-
-
-def sums_before(n):
-    return ((np.arange(3 * n, dtype=np.float32) + 1) * np.float32(0.03125)).reshape(n, 3)
-
-
-def pending_of(n):
-    return ((np.arange(3 * n, dtype=np.float32) + 1) * np.float32(0.001)).reshape(n, 3)
-
-
-def run(case, kernel, queue=None, **opts):
-    o, d, tmin, tmax = case["rays"]
-    n = len(o)
-    return case["scene"].trace_rays_wf(o, d, tmin, tmax, kernel=kernel, queue=queue, hits=sentinel_hits(n), sums=sums_before(n), pending=pending_of(n), **opts)
-
-
-def report(case, bad, got, want, what):
-    o, d, tmin, tmax = case["rays"]
-    lines = ["%s: %d of %d rays differ; the first:" % (what, len(bad), len(o))]
-    for i in bad[:6]:
-        lines.append("  ray %d o=%r d=%r tmin=%r tmax=%r\n    kernel: %s\n    oracle: %s" % (i, o[i].tolist(), d[i].tolist(), float(tmin[i]), float(tmax[i]),
-                     {k: got[k][i].tolist() for k in ("t", "u", "v", "mesh", "prim")}, {k: want[k][i].tolist() for k in ("t", "u", "v", "mesh", "prim")}))
-    return "\n".join(lines)
-
-
-def check_closest(case, kernel, res, queue=None):
-    """`res` against the brute-force hits for the slots of `queue` (None: all), the sentinel for the others; the sums untouched everywhere."""
-    ref, n = case["ref"], len(case["rays"][0])
-    queued = np.ones(n, bool) if queue is None else np.isin(np.arange(n), queue)
-    sent = sentinel_hits(n)
-    hit = ref["mesh"] >= 0
-    want = {"t": np.where(hit, ref["t"], np.float32(np.inf)), "u": np.where(hit, ref["u"], np.float32(0)), "v": np.where(hit, ref["v"], np.float32(0)),
-            "mesh": ref["mesh"].copy(), "prim": ref["prim"].copy()}
-    if kernel == 2:                      # the walk-through ray keeps the slot's previous hit on a miss
-        for j, k in enumerate(("t", "u", "v")):
-            want[k] = np.where(hit, want[k], sent[:, j])
-    keep = ~queued | ((kernel == 2) & ~hit)
-    for j, k in enumerate(("t", "u", "v")):
-        want[k] = np.where(queued, want[k], sent[:, j]).astype(np.float32)
-    want["mesh"][keep], want["prim"][keep] = -1, -1
-    wrong = (res["mesh"] != want["mesh"]) | (res["prim"] != want["prim"])
-    for k in ("t", "u", "v"):
-        wrong |= u32(res[k]) != u32(want[k])
-    wrong |= keep & (res["gid"] != u32(sent[:, 3]))                 # what a kernel must not write keeps its gid too
-    wrong |= queued & ~hit & (kernel != 2) & (res["gid"] != 0)      # the miss record is (+inf, 0, 0, 0)
-    bad = np.flatnonzero(wrong)
-    assert len(bad) == 0, report(case, bad, res, want, "%s kernel" % KINDS[kernel])
-    assert same_bits(res["sums"], sums_before(n)), "a closest-hit launch wrote sample sums"
-    assert same_bits(res["t"][hit & queued], ref["t"][hit & queued])
-
-
 # ------------------------------------------------------------------------------------------------ closest-hit kinds
 @pytest.mark.parametrize("kernel", [0, 1, 2])
 @pytest.mark.parametrize("name", R.CLOSEST_SCENES)
@@ -123,16 +59,6 @@ def test_queues_of_every_length_write_their_slots_and_no_other(gpu_lib, kz, O, n
     for nq in (1, 63, 64, 65, 4113, n):
         q = perm[:nq]
         check_closest(case, kernel, run(case, kernel, queue=q), queue=q)
-
-
-SHAPES = [dict(grid_blocks=1, batch=64), dict(lds_stack=2), dict(refill=1), dict(refill=64), dict(postpone=1), dict(postpone=64), dict(stats=True),
-          dict(stats=True, grid_blocks=1, batch=64, lds_stack=2, refill=64, postpone=1)]
-PACKET_SHAPES = [dict(grid_blocks=1, packet_batch=1), dict(grid_blocks=2, packet_batch=3), dict(stats=True), dict(stats=True, grid_blocks=1, packet_batch=1)]
-OUT = ("t", "u", "v", "gid", "mesh", "prim", "sums")
-
-
-def same_result(a, b):
-    return all(np.array_equal(u32(a[k]) if a[k].dtype == np.float32 else a[k], u32(b[k]) if b[k].dtype == np.float32 else b[k]) for k in OUT)
 
 
 @pytest.mark.parametrize("kernel", [0, 1, 2])
@@ -199,29 +125,6 @@ def test_a_two_entry_lds_stack_spills_into_the_overflow_area_and_stays_inside_it
 
 
 # ------------------------------------------------------------------------------------------------ the shadow kind
-def check_shadow(case, res, queue=None, stats=False):
-    occluded, walks, crosses = case["ref"]
-    n = len(occluded)
-    queued = np.ones(n, bool) if queue is None else np.isin(np.arange(n), queue)
-    before, pend = sums_before(n), pending_of(n)
-    want = np.where((queued & ~occluded)[:, None], before + pend, before).astype(np.float32)
-    wrong = (u32(res["sums"]) != u32(want)).any(axis=1)
-    bad = np.flatnonzero(wrong)
-    o, d, tmin, tmax = case["rays"]
-    msg = "\n".join("  segment %d o=%r d=%r tmin=%r tmax=%r queued=%s reference: occluded=%s walk-throughs=%d crosses=%s\n    sums before %r pending %r after %r" %
-                    (i, o[i].tolist(), d[i].tolist(), float(tmin[i]), float(tmax[i]), queued[i], occluded[i], walks[i], crosses[i], before[i].tolist(), pend[i].tolist(), res["sums"][i].tolist()) for i in bad[:6])
-    assert len(bad) == 0, "shadow kernels: %d of %d segments differ; the first:\n%s" % (len(bad), n, msg)
-    sent = sentinel_hits(n)
-    assert all(same_bits(res[k], sent[:, j]) for j, k in enumerate(("t", "u", "v"))) and np.array_equal(res["gid"], u32(sent[:, 3])), "a shadow launch wrote hit records"
-    info = res["info"]
-    if info["shadowFast"]:
-        assert info["nQueueB"] == int((crosses & queued).sum()), (info, int((crosses & queued).sum()))
-    else:
-        assert info["nQueueB"] == 0
-    if stats:
-        assert info["rays"] == int(queued.sum()) + int(walks[queued].sum()), (info, int(queued.sum()), int(walks[queued].sum()))
-
-
 @pytest.mark.parametrize("name", R.SHADOW_SCENES)
 def test_shadow_kernels_add_each_pending_radiance_once_to_its_own_slot(gpu_lib, kz, O, name):
     """The shadow launches of a bounce on segments between random points, from surfaces to the lights and through the invisible lights, against the occlusion loop of

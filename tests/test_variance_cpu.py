@@ -2,109 +2,15 @@
 that need no device, the test-only CPU reference (tests/cpu_ref/kz_variance_ref.cpp) the GPU tests compare against - checked here against a float64 numpy
 restatement, against the existing denoiser's reference where the two must agree to the bit, and on inputs whose answer is known - and what the variance guidance is
 worth on the oracle's own films."""
-import copy
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_denoise_cpu import BAD_OPTS, GUIDES, denoise_ref_lib, frame_rgb, ref_denoise, synthetic_films
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-REF_SRC = os.path.join(HERE, "cpu_ref", "kz_variance_ref.cpp")
-INTEGRATOR_TAGS = {"path_mis": 0, "normals": 1, "ao": 2, "path_mats": 3}
-
-# ---------------------------------------------------------------- the CPU reference (also imported by test_variance_gpu.py)
-_ref = {}
-
-
-def variance_ref_lib(tmpdir):
-    """Compiles the CPU reference with the oracle's flags into `tmpdir` once per process."""
-    if "lib" not in _ref:
-        out = os.path.join(str(tmpdir), "libkz_variance_ref.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "include"), "-o", out, REF_SRC])
-        L = C.CDLL(out)
-        import oracle
-        abi = oracle.abi
-        f32p = C.POINTER(C.c_float)
-        L.kzo_last_error.restype = C.c_char_p
-        L.kzo_scene_create.argtypes = [C.POINTER(abi.KzSceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.kzo_scene_destroy.argtypes = [C.c_void_p]
-        L.kzo_scene_destroy.restype = None
-        L.kzo_film_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.kzv_render_canonical.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, f32p]
-        L.kzi_render_canonical.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, f32p]
-        L.kzv_denoise.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_void_p, C.c_void_p, f32p, f32p]
-        _ref["lib"] = L
-    return _ref["lib"]
-
-
-class MomentRef:
-    """A scene of the CPU reference (created with the path_mis tag, as the oracle demands; the integrator named in the description picks the Li): its canonical
-    second-moment film and, from the same translation unit, its canonical picture."""
-
-    def __init__(self, L, desc):
-        import oracle
-        self.L, self.abi = L, oracle.abi
-        self.tag = INTEGRATOR_TAGS[desc.integrator["type"]]
-        d = copy.copy(desc)
-        d.integrator = dict(desc.integrator, type="path_mis")
-        self._c = d.to_c()
-        h = C.c_void_p()
-        rc = L.kzo_scene_create(C.byref(self._c), 0, C.byref(h))
-        if rc != 0:
-            raise self.abi.KzError(rc, L.kzo_last_error().decode())
-        self.h = h
-        w, hh, b = C.c_int(), C.c_int(), C.c_int()
-        L.kzo_film_dims(self.h, C.byref(w), C.byref(hh), C.byref(b))
-        self.width, self.height, self.border = w.value, hh.value, b.value
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.kzo_scene_destroy(self.h)
-
-    def _render(self, fn, s0, s1, threads, grid):
-        film = np.zeros((self.height + 2 * self.border, self.width + 2 * self.border, 4), np.float32)
-        assert fn(self.h, self.tag, s0, s1, threads, grid, film.ctypes.data_as(self.abi.f32p)) == 0
-        return film
-
-    def moment_film(self, s0=0, s1=0, threads=16, grid=64):
-        return self._render(self.L.kzv_render_canonical, s0, s1, threads, grid)
-
-    def film(self, s0=0, s1=0, threads=16, grid=64):
-        return self._render(self.L.kzi_render_canonical, s0, s1, threads, grid)
-
-
-def ref_denoise_variance(L, kz, film, moment, albedo=None, normal=None, depth=None, border=0, samples=4, sigma_variance=0.0, **opts):
-    """The reference's (film, v_last) of five films (guides may be None); options as kz.denoise_opts / kz.variance_opts take them."""
-    f32p = C.POINTER(C.c_float)
-    film = np.ascontiguousarray(film, np.float32)
-    g = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (moment, albedo, normal, depth)]
-    out = np.full(film.shape, np.nan, np.float32)
-    var = np.full((film.shape[0] - 2 * border, film.shape[1] - 2 * border), np.nan, np.float32)
-    o, v = kz.denoise_opts(**opts), kz.variance_opts(sigma_variance, samples)
-    rc = L.kzv_denoise(film.shape[1] - 2 * border, film.shape[0] - 2 * border, border, film.ctypes.data_as(f32p),
-                       *[None if a is None else a.ctypes.data_as(f32p) for a in g], C.byref(o), C.byref(v), out.ctypes.data_as(f32p), var.ctypes.data_as(f32p))
-    assert rc == 0, "the reference refused the options"
-    return out, var
-
-
-def synthetic_moment(colour, seed, degenerate=False):
-    """A second-moment film for a synthetic picture: the picture's own weights (zeros included), values c^2 (1 + t) with t = lognormal(-3, 2) - 0.01 - relative variances
-    from 1e-3 to 10, so that the variance's tolerance is the tighter one in some pixels and iterations and the fixed one in others; a fifth of the channels below c^2,
-    where the variance clamps to 0 - and the apron left non-zero. degenerate: 1e30 x w in every channel, which takes the variance's tolerance out of the filter."""
-    rng = np.random.default_rng(seed)
-    w = colour[..., 3:]
-    c = np.where(w != 0, colour[..., :3] / np.where(w == 0, 1, w), 0)
-    s = np.full(c.shape, 1e30, np.float32) if degenerate else (c * c * (0.99 + rng.lognormal(-3.0, 2.0, c.shape))).astype(np.float32)
-    m = np.concatenate([s * w, w], axis=2).astype(np.float32)
-    dead = w[..., 0] == 0
-    m[dead, :3] = 5.0                                                 # (what a texel of weight 0 holds must not count)
-    return m
+from checks import c_layout, header_surface, refused
+from cpu_refs import MomentRef, lib, ref_denoise, ref_denoise_variance
+from film_cases import BAD_OPTS, BAD_VOPTS, frame_rgb, quality_inputs, synthetic_films, synthetic_moment
 
 
 def np_denoise_variance(film, moment, albedo=None, normal=None, depth=None, border=0, samples=4, sigma_variance=3.0, iterations=5, demodulate=True, use_guides=True,
@@ -184,62 +90,31 @@ def np_denoise_variance(film, moment, albedo=None, normal=None, depth=None, bord
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return variance_ref_lib(tmp_path_factory.mktemp("kzv"))
+    return lib("variance", tmp_path_factory.mktemp("kzv"))
 
 
 @pytest.fixture(scope="module")
 def dref(tmp_path_factory):
-    return denoise_ref_lib(tmp_path_factory.mktemp("kzd"))
+    return lib("denoise", tmp_path_factory.mktemp("kzd"))
 
 
 # ---------------------------------------------------------------- ABI
 def test_header_declarations_are_exported(kz):
     a = kz.abi
-    lib = a.load_library()
-    src = open(os.path.join(ROOT, "include", "kazen_mi355x_variance.h")).read()
-    declared = set(re.findall(r"^(?:int|void|const char \*)\s*\*?(kz_[a-z0-9_]+)\s*\(", src, re.M))
-    assert declared == set(a.VARIANCE_EXPORTS) and len(a.VARIANCE_EXPORTS) == 6, declared ^ set(a.VARIANCE_EXPORTS)
-    exported = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.LIB_PATH], text=True)))
-    assert declared <= exported, declared - exported
-    if os.path.exists(a.DEV_LIB_PATH):
-        dev = set(re.findall(r" T (kz_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", a.DEV_LIB_PATH], text=True)))
-        assert declared <= dev, declared - dev
-    for sym in declared:
-        assert getattr(lib, sym) is not None
     # a surface of its own: disjoint from the five other lists, and nothing added to the existing headers
-    for other in (a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS):
-        assert not (declared & set(other)), declared & set(other)
-    for name in ("kazen_mi355x.h", "kazen_mi355x_dev.h", "kazen_mi355x_edit.h", "kazen_mi355x_aov.h", "kazen_mi355x_denoise.h"):
-        text = open(os.path.join(ROOT, "include", name)).read().lower()
-        for word in ("kz_variance", "kz_denoise_variance", "kz_scene_set_variance", "kz_scene_variance", "kzvarianceopts"):
-            assert word not in text, (name, word)
-    assert lib.kz_abi_version() == a.KZ_ABI_VERSION == 6
+    _, src = header_surface(kz, "include/kazen_mi355x_variance.h", a.VARIANCE_EXPORTS, 6, [a.EXPORTS, a.PRODUCT_EXPORTS, a.EDIT_EXPORTS, a.AOV_EXPORTS, a.DENOISE_EXPORTS],
+                            ["include/kazen_mi355x.h", "include/kazen_mi355x_dev.h", "include/kazen_mi355x_edit.h", "include/kazen_mi355x_aov.h", "include/kazen_mi355x_denoise.h"],
+                            ["kz_variance", "kz_denoise_variance", "kz_scene_set_variance", "kz_scene_variance", "kzvarianceopts"])
     for n, v in (("KZ_VARIANCE_OFF", a.KZ_VARIANCE_OFF), ("KZ_VARIANCE_ON", a.KZ_VARIANCE_ON), ("KZ_VARIANCE_TWO_LAUNCHES", a.KZ_VARIANCE_TWO_LAUNCHES),
                  ("KZ_VARIANCE_ONE_PASS", a.KZ_VARIANCE_ONE_PASS)):
         assert int(re.search(r"#define %s\s+(\d+)" % n, src).group(1)) == v
 
 
 def test_opts_struct_is_16_bytes(kz, tmp_path):
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "kazen_mi355x_variance.h"\nint main(void){printf("%zu %zu %zu %zu\\n", sizeof(KzVarianceOpts), '
-                   'offsetof(KzVarianceOpts, samples), offsetof(KzVarianceOpts, flags), offsetof(KzVarianceOpts, reserved));return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    assert subprocess.check_output([str(exe)], text=True).split() == ["16", "4", "8", "12"]
+    assert c_layout(tmp_path, "kazen_mi355x_variance.h", ["sizeof(KzVarianceOpts)", "offsetof(KzVarianceOpts, samples)", "offsetof(KzVarianceOpts, flags)",
+                                                          "offsetof(KzVarianceOpts, reserved)"]) == ["16", "4", "8", "12"]
     o = kz.abi.KzVarianceOpts
     assert C.sizeof(o) == 16 and (o.sigmaVariance.offset, o.samples.offset, o.flags.offset, o.reserved.offset) == (0, 4, 8, 12)
-
-
-BAD_VOPTS = [{"sigma_variance": -1.0}, {"sigma_variance": float("nan")}, {"sigma_variance": float("inf")}, {"sigma_variance": -1e-30}, {"vflags": 1}, {"vflags": 1 << 31},
-             {"vreserved": 1}]
-
-
-def _refused(kz, fn, code, *words):
-    with pytest.raises(kz.abi.KzError) as e:
-        fn()
-    assert e.value.code == code, str(e.value)
-    for w in words:
-        assert w in str(e.value), (w, str(e.value))
 
 
 def test_refusals_without_a_device(kz):
@@ -248,55 +123,55 @@ def test_refusals_without_a_device(kz):
     sc = kz.Scene(kz.scenes.cornell_box(16, 16, 2))
     assert sc.variance() == 0
     for bad in (-1, 4, 1 << 20):
-        _refused(kz, lambda: sc.set_variance(bad), a.KZ_ERR_INVALID_ARG, "kz_scene_set_variance")
+        refused(kz, lambda: sc.set_variance(bad), a.KZ_ERR_INVALID_ARG, "kz_scene_set_variance")
     assert sc.variance() == 0
     assert lib.kz_scene_set_variance(None, 1) == a.KZ_ERR_INVALID_ARG and lib.kz_denoise_variance(None, -1, None, None) == a.KZ_ERR_INVALID_ARG
     # the switch off: bad options first, then the state - all before a replica is looked for
     for bad in BAD_OPTS:
-        _refused(kz, lambda: sc.denoise_variance(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance")
+        refused(kz, lambda: sc.denoise_variance(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance")
     for bad in BAD_VOPTS:
-        _refused(kz, lambda: sc.denoise_variance(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance", "KzVarianceOpts")
-    _refused(kz, lambda: sc.denoise_variance(guides="albedo"), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance", "guides")      # the scene's mask is 0
-    _refused(kz, sc.denoise_variance, a.KZ_ERR_STATE, "kz_denoise_variance", "switched off", "0")
-    _refused(kz, sc.moment_film, a.KZ_ERR_STATE, "kz_variance_download", "switched off")
-    _refused(kz, sc.variance_info, a.KZ_ERR_STATE)
+        refused(kz, lambda: sc.denoise_variance(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance", "KzVarianceOpts")
+    refused(kz, lambda: sc.denoise_variance(guides="albedo"), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance", "guides")      # the scene's mask is 0
+    refused(kz, sc.denoise_variance, a.KZ_ERR_STATE, "kz_denoise_variance", "switched off", "0")
+    refused(kz, sc.moment_film, a.KZ_ERR_STATE, "kz_variance_download", "switched off")
+    refused(kz, sc.variance_info, a.KZ_ERR_STATE)
     tiles = [(0, 0, 16, 16)]
     counter = np.zeros(2, np.uint32)
     for mode in (True, a.KZ_VARIANCE_TWO_LAUNCHES, a.KZ_VARIANCE_ONE_PASS):
         sc.set_variance(mode)                                         # (a scene on no device: the switch alone)
         assert sc.variance() == int(mode)
         # what AOVs refuse, naming the call
-        _refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_UNSUPPORTED, "kz_render", "pipeline = 1", "second-moment")
-        _refused(kz, lambda: sc.render_multi([0]), a.KZ_ERR_UNSUPPORTED, "kz_render_multi", "second-moment")
-        _refused(kz, lambda: sc.render_dealt(tiles, counter, device=0), a.KZ_ERR_UNSUPPORTED, "kz_render_tiles", "KzTileDealer")
-        _refused(kz, lambda: sc.render_tiles(tiles, device=0, packed=True), a.KZ_ERR_UNSUPPORTED, "kz_render_tiles", "packedOutput")
-        _refused(kz, lambda: sc.film_tiles(tiles, device=0), a.KZ_ERR_UNSUPPORTED, "kz_film_download_tiles", "second-moment")
+        refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_UNSUPPORTED, "kz_render", "pipeline = 1", "second-moment")
+        refused(kz, lambda: sc.render_multi([0]), a.KZ_ERR_UNSUPPORTED, "kz_render_multi", "second-moment")
+        refused(kz, lambda: sc.render_dealt(tiles, counter, device=0), a.KZ_ERR_UNSUPPORTED, "kz_render_tiles", "KzTileDealer")
+        refused(kz, lambda: sc.render_tiles(tiles, device=0, packed=True), a.KZ_ERR_UNSUPPORTED, "kz_render_tiles", "packedOutput")
+        refused(kz, lambda: sc.film_tiles(tiles, device=0), a.KZ_ERR_UNSUPPORTED, "kz_film_download_tiles", "second-moment")
         # bad options are still refused first; good ones get as far as the missing device
         for bad in BAD_OPTS + BAD_VOPTS:
-            _refused(kz, lambda: sc.denoise_variance(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance")
+            refused(kz, lambda: sc.denoise_variance(**bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance")
         for good in ({}, {"samples": 4, "sigma_variance": 2.0, "iterations": 8, "sigma_color": 1.0, "flags": 2}):
-            _refused(kz, lambda: sc.denoise_variance(**good), a.KZ_ERR_STATE, "kz_scene_upload")
-        _refused(kz, sc.moment_film, a.KZ_ERR_STATE, "kz_scene_upload")
+            refused(kz, lambda: sc.denoise_variance(**good), a.KZ_ERR_STATE, "kz_scene_upload")
+        refused(kz, sc.moment_film, a.KZ_ERR_STATE, "kz_scene_upload")
     # with AOVs on as well, the AOVs' refusal comes first, as before
     sc.set_aovs(["depth"])
-    _refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_UNSUPPORTED, "kz_render", "AOVs")
+    refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_UNSUPPORTED, "kz_render", "AOVs")
     sc.set_aovs(())
     # switched off, the same calls get as far as they got before: the scene is on no device
     sc.set_variance(False)
     assert sc.variance() == 0
-    _refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_STATE)
-    _refused(kz, lambda: sc.film_tiles(tiles, device=0), a.KZ_ERR_STATE)
-    _refused(kz, lambda: sc.render_tiles(tiles, device=0, packed=True), a.KZ_ERR_STATE)
+    refused(kz, lambda: sc.render(pipeline=1), a.KZ_ERR_STATE)
+    refused(kz, lambda: sc.film_tiles(tiles, device=0), a.KZ_ERR_STATE)
+    refused(kz, lambda: sc.render_tiles(tiles, device=0, packed=True), a.KZ_ERR_STATE)
     # the test surface checks its arguments and options first, then the sample count, then asks for the device
     film = np.ones((5, 7, 4), np.float32)
     for bad in BAD_OPTS + BAD_VOPTS:
-        _refused(kz, lambda: kz.denoise_variance_films(film, film, samples=4, **bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance_films")
-    _refused(kz, lambda: kz.denoise_variance_films(film, film, samples=4, guides="normal"), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance_films", "guides")
-    _refused(kz, lambda: kz.denoise_variance_films(film, film, samples=4, border=3), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance_films")
-    _refused(kz, lambda: kz.denoise_variance_films(film, None, samples=4), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance_films")
-    _refused(kz, lambda: kz.denoise_variance_films(film, film), a.KZ_ERR_STATE, "kz_denoise_variance_films", "samples = 0")
+        refused(kz, lambda: kz.denoise_variance_films(film, film, samples=4, **bad), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance_films")
+    refused(kz, lambda: kz.denoise_variance_films(film, film, samples=4, guides="normal"), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance_films", "guides")
+    refused(kz, lambda: kz.denoise_variance_films(film, film, samples=4, border=3), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance_films")
+    refused(kz, lambda: kz.denoise_variance_films(film, None, samples=4), a.KZ_ERR_INVALID_ARG, "kz_denoise_variance_films")
+    refused(kz, lambda: kz.denoise_variance_films(film, film), a.KZ_ERR_STATE, "kz_denoise_variance_films", "samples = 0")
     if lib.kz_device_count() == 0:
-        _refused(kz, lambda: kz.denoise_variance_films(film, film, samples=4), a.KZ_ERR_NO_DEVICE)
+        refused(kz, lambda: kz.denoise_variance_films(film, film, samples=4), a.KZ_ERR_NO_DEVICE)
 
 
 # ---------------------------------------------------------------- the reference itself
@@ -448,32 +323,13 @@ def test_moment_reference_sanity(kz, ref):
 
 
 # ---------------------------------------------------------------- what it is worth
-_quality = {}
-
-
-def _quality_inputs(kz, O, ref, tmp_path_factory, scene):
-    """The oracle's canonical films of `scene` at 96 x 72: 4 and 16 spp noisy, 1024 spp clean, the AOV reference's feature films and the new reference's moment film."""
-    if scene not in _quality:
-        from test_aov_cpu import AovRef, aov_ref_lib
-        make = {"cornell": kz.scenes.cornell_box, "materials": kz.scenes.materials_scene, "textured": kz.scenes.textured_scene}[scene]
-        clean = O.OracleScene(make(96, 72, 1024)).render_canonical(threads=0)
-        per = {}
-        for spp in (4, 16):
-            desc = make(96, 72, spp)
-            noisy = O.OracleScene(desc).render_canonical(threads=0)
-            aov = AovRef(aov_ref_lib(tmp_path_factory.mktemp("kza")), desc)
-            per[spp] = (noisy, MomentRef(ref, desc).moment_film(), [aov.film(a) for a in GUIDES])
-        _quality[scene] = (clean, per)
-    return _quality[scene]
-
-
 @pytest.mark.parametrize("scene", ["cornell", "materials", "textured"])
 def test_quality_on_the_oracles_films(kz, O, ref, dref, tmp_path_factory, scene):
     """The setting and the metric of test_denoise_cpu.test_quality_on_the_oracles_films - 4 spp against 1024 spp at 96 x 72, the oracle's canonical film, the AOV
     reference's feature films, MSE after the filter over MSE before it - with the second-moment film of tests/cpu_ref/kz_variance_ref.cpp and samples = 4. At default
     options (sigmaVariance 3, sigmaColor 2) the ratio is strictly below the existing filter's at its defaults on each scene; both are computed here. The relative-MSE
     pair (x - ref)^2 / (ref^2 + 0.01) and the 16-spp figures are printed, not asserted. Recorded in DESIGN.md 4f."""
-    clean, per = _quality_inputs(kz, O, ref, tmp_path_factory, scene)
+    clean, per = quality_inputs(kz, O, ref, tmp_path_factory, scene)
     b = (clean.shape[0] - 72) // 2
     want = frame_rgb(clean, b).astype(np.float64)
     mse = lambda f: float(((frame_rgb(f, b).astype(np.float64) - want) ** 2).mean())

@@ -5,10 +5,9 @@ films and on the films a render leaves on the device. Comparisons are same_bits 
 import numpy as np
 import pytest
 
-from test_aov_cpu import H, SPP, W, with_integrator
-from test_aov_gpu import FILTERS, SCHEDULES, _visible, _with_filter, same_bits
-from test_denoise_cpu import BAD_OPTS, GUIDES, denoise_ref_lib, ref_denoise, synthetic_films
-from test_variance_cpu import BAD_VOPTS, MomentRef, ref_denoise_variance, synthetic_moment, variance_ref_lib
+from checks import differing, same_bits_strict
+from cpu_refs import lib, ref_denoise, ref_denoise_variance, ref_moment
+from film_cases import BAD_OPTS, BAD_VOPTS, FILTERS, GUIDES, H, SCHEDULES, SPP, W, _visible, _with_filter, synthetic_films, synthetic_moment, with_integrator
 
 pytestmark = pytest.mark.gpu
 
@@ -17,36 +16,19 @@ TAPS = 5                                                              # gaussian
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return variance_ref_lib(tmp_path_factory.mktemp("kzv"))
+    return lib("variance", tmp_path_factory.mktemp("kzv"))
 
 
 @pytest.fixture(scope="module")
 def dref(tmp_path_factory):
-    return denoise_ref_lib(tmp_path_factory.mktemp("kzd"))
-
-
-_moments = {}
-
-
-def ref_moment(ref, key, desc, s0=0, s1=0):
-    """The reference's second-moment film of a description, computed once per (key, sample range) and shared."""
-    k = (key, s0, s1)
-    if k not in _moments:
-        _moments[k] = MomentRef(ref, desc).moment_film(s0, s1)
-        _moments[k].setflags(write=False)
-    return _moments[k]
-
-
-def differing(a, b):
-    bad = np.ascontiguousarray(a, np.float32).view(np.uint32) != np.ascontiguousarray(b, np.float32).view(np.uint32)
-    return int(bad.sum()), np.argwhere(bad)[:3].tolist()
+    return lib("denoise", tmp_path_factory.mktemp("kzd"))
 
 
 # ---------------------------------------------------------------- the film
 @pytest.mark.parametrize("scene", ["cornell", "textured"])
 @pytest.mark.parametrize("filt", list(FILTERS))
 def test_moment_film_equals_the_reference(gpu_lib, kz, ref, scene, filt):
-    """Every filter of test_aov_gpu (7 taps: the 4-group kernel, which the one-pass form leaves to two launches), and each way of feeding the film."""
+    """Every filter of film_cases.FILTERS, the feature films' (7 taps: the 4-group kernel, which the one-pass form leaves to two launches), and each way of feeding the film."""
     a = kz.abi
     base = kz.scenes.cornell_box(W, H, SPP) if scene == "cornell" else kz.scenes.textured_scene(W, H, SPP)
     d = _with_filter(base, FILTERS[filt])
@@ -57,7 +39,7 @@ def test_moment_film_equals_the_reference(gpu_lib, kz, ref, scene, filt):
         sc.render()
         m, f = sc.moment_film(), sc.film()
         assert np.array_equal(m, want), (mode, differing(m, want))
-        assert same_bits(m[..., 3], f[..., 3]), mode                  # the w channel is the picture's, bit for bit
+        assert same_bits_strict(m[..., 3], f[..., 3]), mode                  # the w channel is the picture's, bit for bit
         assert m[..., 3].max() > 0 and m[..., :3].max() > 0 and not np.array_equal(m[..., :3], f[..., :3])
     assert sc.variance_info()[1] == SPP
 
@@ -171,14 +153,14 @@ def test_lifecycle(gpu_lib, kz, ref, dref):
     sc.denoise_variance()
     assert sc.denoise_info() == 4 * W * H * 16 + (H + 2 * b) * (W + 2 * b) * 16
     want, _ = ref_denoise_variance(ref, kz, sc.film(), sc.moment_film(), border=b, samples=SPP)
-    assert same_bits(sc.denoised_film(), want)
+    assert same_bits_strict(sc.denoised_film(), want)
     sc.denoise_release()
     assert sc.denoise_info() == 0
     fresh = kz.Scene(d, device=0)
     fresh.set_variance(True)
     fresh.render()
     fresh.denoise_variance()                                          # allocated by the variance call's first call, counted from then on, freed by the release
-    assert fresh.denoise_info() == 4 * W * H * 16 + (H + 2 * b) * (W + 2 * b) * 16 and same_bits(fresh.denoised_film(), want)
+    assert fresh.denoise_info() == 4 * W * H * 16 + (H + 2 * b) * (W + 2 * b) * 16 and same_bits_strict(fresh.denoised_film(), want)
     fresh.denoise_release()
     assert fresh.denoise_info() == 0
 
@@ -194,14 +176,14 @@ def test_static_tiles_over_half_the_frame(gpu_lib, kz, ref):
     b = sc.border
     m, f = sc.moment_film(), sc.film()
     whole = ref_moment(ref, ("cornell", "gaussian r=2"), _with_filter(kz.scenes.cornell_box(W, H, SPP), FILTERS["gaussian r=2"]))
-    assert same_bits(m[..., 3], f[..., 3]) and sc.variance_info()[1] == SPP
+    assert same_bits_strict(m[..., 3], f[..., 3]) and sc.variance_info()[1] == SPP
     reach = W // 2 + b - 2                                            # the first film column a pixel of the right half reaches (5 taps: 2 to its left)
     assert np.array_equal(m[:, :reach], whole[:, :reach]) and not m[:, b + W // 2 + b:].any() and (m[b:b + H, b:b + W // 2, 3] > 0).all()
     films = [f, m] + [sc.aov_film(g) for g in GUIDES]
     sc.denoise_variance()
     got = sc.denoised_film()
     want, _ = ref_denoise_variance(ref, kz, *films, border=b, samples=SPP)
-    assert same_bits(got, want), differing(got, want)
+    assert same_bits_strict(got, want), differing(got, want)
     assert (got[b:b + H, b:b + W // 2, 3] == 1).all() and got[b:b + H, b:b + W // 2, :3].max() > 0.1 and not got[:, b + W // 2 + b:].any()
 
 
@@ -265,10 +247,10 @@ def test_films_entry_has_the_references_bits(gpu_lib, kz, ref, frame):
         for it in (1, 5, 8):
             got, gv = kz.denoise_variance_films(films[0], moment, *films[1:], border=b, iterations=it, samples=4, return_variance=True)
             want, wv = ref_denoise_variance(ref, kz, films[0], moment, *films[1:], border=b, iterations=it, samples=4)
-            assert same_bits(got, want), (frame, b, it, differing(got, want))
-            assert same_bits(gv, wv), (frame, b, it, differing(gv, wv))
+            assert same_bits_strict(got, want), (frame, b, it, differing(got, want))
+            assert same_bits_strict(gv, wv), (frame, b, it, differing(gv, wv))
             assert np.isfinite(got).all() and np.isfinite(gv).all() and (w * h < 20 or (0 < (got[..., 3] == 1).sum() < w * h))
-        assert same_bits(kz.denoise_variance_films(films[0], moment, *films[1:], border=b, samples=4),
+        assert same_bits_strict(kz.denoise_variance_films(films[0], moment, *films[1:], border=b, samples=4),
                          ref_denoise_variance(ref, kz, films[0], moment, *films[1:], border=b, iterations=5, samples=4)[0])      # the defaults; outVariance NULL
 
 
@@ -281,26 +263,26 @@ def test_every_guide_subset(gpu_lib, kz, ref, dref, subset, demodulate):
     given = [f if subset & (1 << k) else None for k, f in enumerate((albedo, normal, depth))]
     got, gv = kz.denoise_variance_films(colour, moment, *given, border=b, demodulate=demodulate, samples=8, return_variance=True)
     want, wv = ref_denoise_variance(ref, kz, colour, moment, *given, border=b, demodulate=demodulate, samples=8)
-    assert same_bits(got, want) and same_bits(gv, wv), (subset, demodulate, differing(got, want), differing(gv, wv))
+    assert same_bits_strict(got, want) and same_bits_strict(gv, wv), (subset, demodulate, differing(got, want), differing(gv, wv))
     if subset:
         # the same subset named by `guides` with every film given, and colour weights alone with the subset's demodulation
-        assert same_bits(kz.denoise_variance_films(colour, moment, albedo, normal, depth, border=b, demodulate=demodulate, guides=subset, samples=8), want)
+        assert same_bits_strict(kz.denoise_variance_films(colour, moment, albedo, normal, depth, border=b, demodulate=demodulate, guides=subset, samples=8), want)
         flat, fv = kz.denoise_variance_films(colour, moment, *given, border=b, demodulate=demodulate, use_guides=False, samples=8, return_variance=True)
         wflat, wfv = ref_denoise_variance(ref, kz, colour, moment, *given, border=b, demodulate=demodulate, use_guides=False, samples=8)
-        assert same_bits(flat, wflat) and same_bits(fv, wfv) and not same_bits(flat, want)
+        assert same_bits_strict(flat, wflat) and same_bits_strict(fv, wfv) and not same_bits_strict(flat, want)
     # other sigmas and sample counts than the defaults
     sig = dict(sigma_color=0.8, sigma_normal=0.7, sigma_depth=0.25, sigma_albedo=0.05, iterations=3, sigma_variance=1.5, samples=3)
     got, gv = kz.denoise_variance_films(colour, moment, *given, border=b, demodulate=demodulate, return_variance=True, **sig)
     want2, wv2 = ref_denoise_variance(ref, kz, colour, moment, *given, border=b, demodulate=demodulate, **sig)
-    assert same_bits(got, want2) and same_bits(gv, wv2)
+    assert same_bits_strict(got, want2) and same_bits_strict(gv, wv2)
     # the degenerate identity on the device: a moment film of 1e30 x w leaves kz_denoise_films' colours at the same KzDenoiseOpts, and the reference's
     huge = synthetic_moment(colour, 0, degenerate=True)
     for kw in (dict(sigma_color=2.0), dict(sigma_color=1.0, iterations=8)):
         deg = kz.denoise_variance_films(colour, huge, *given, border=b, demodulate=demodulate, samples=4, **kw)
         plain = kz.denoise_films(colour, *given, border=b, demodulate=demodulate, **kw)
-        assert same_bits(deg, plain), (subset, demodulate, kw, differing(deg, plain))
-        assert same_bits(plain, ref_denoise(dref, kz, colour, *given, border=b, demodulate=demodulate, **kw))
-    assert not same_bits(kz.denoise_films(colour, *given, border=b, demodulate=demodulate, sigma_color=2.0), want)      # the variance's tolerance did something
+        assert same_bits_strict(deg, plain), (subset, demodulate, kw, differing(deg, plain))
+        assert same_bits_strict(plain, ref_denoise(dref, kz, colour, *given, border=b, demodulate=demodulate, **kw))
+    assert not same_bits_strict(kz.denoise_films(colour, *given, border=b, demodulate=demodulate, sigma_color=2.0), want)      # the variance's tolerance did something
 
 
 # ---------------------------------------------------------------- a scene's own films
@@ -317,20 +299,20 @@ def test_scene_denoise_variance_equals_the_reference(gpu_lib, kz, ref, dref, sce
     sc.denoise_variance()
     got = sc.denoised_film()
     want, _ = ref_denoise_variance(ref, kz, *films, border=b, samples=SPP)
-    assert same_bits(got, want), (scene, filt, differing(got, want))
-    assert same_bits(kz.denoise_variance_films(*films, border=b, samples=SPP), want)
+    assert same_bits_strict(got, want), (scene, filt, differing(got, want))
+    assert same_bits_strict(kz.denoise_variance_films(*films, border=b, samples=SPP), want)
     inner = got[b:got.shape[0] - b, b:got.shape[1] - b] if b else got
     assert (inner[..., 3] == 1).all() and inner[..., :3].max() > 0.1 and np.isfinite(got).all()
     # the picture's film, the moment film and the AOV films do not notice
     for x, y in zip(films, [sc.film(), sc.moment_film()] + [sc.aov_film(g) for g in GUIDES]):
-        assert same_bits(x, y)
+        assert same_bits_strict(x, y)
     # the raster serves both calls
     assert sc.denoised_srgb8().shape == (H, W, 3)
     # a stated sample count, a subset of the mask, and options
     sc.denoise_variance(guides=["normal", "depth"], iterations=3, sigma_color=1.0, sigma_variance=2.0, samples=16)
     want2, _ = ref_denoise_variance(ref, kz, films[0], films[1], None, films[3], films[4], border=b, iterations=3, sigma_color=1.0, sigma_variance=2.0, samples=16)
-    assert same_bits(sc.denoised_film(), want2) and not same_bits(want2, want)
+    assert same_bits_strict(sc.denoised_film(), want2) and not same_bits_strict(want2, want)
     # afterwards kz_denoise on the same replica still gives its own reference's bits
     sc.denoise()
     plain = ref_denoise(dref, kz, films[0], *films[2:], border=b)
-    assert same_bits(sc.denoised_film(), plain) and not same_bits(plain, want)
+    assert same_bits_strict(sc.denoised_film(), plain) and not same_bits_strict(plain, want)

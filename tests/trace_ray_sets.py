@@ -8,8 +8,10 @@ lightPrimaryVisibility == false. test_trace_wf_cpu.py holds every set to what it
 
 With deform=..., a case is the scene AFTER an edit (Scene.set_vertices, `deformation` below): the build's topology under refit boxes that no longer form a good
 tree. Scene, oracle, ray sets and reference are then those of the deformed description, and two aimed sets (h), (i) follow the others
-(tests/test_trace_refit_cpu.py, tests/test_trace_refit_gpu.py)."""
+(tests/test_trace_refit_cpu.py, tests/test_trace_refit_gpu.py). Last: a launch of kz_trace_rays_wf on a case and the checks of its result, which the two GPU modules share."""
 import numpy as np
+
+from checks import same_bits
 
 NODE4 = np.dtype([("p", "<f4", 3), ("scaleX", "<f4"), ("qlo", "<u4", 3), ("qhi", "<u4", 3), ("scaleY", "<f4"), ("scaleZ", "<f4"), ("child", "<u4", 4)])
 EPS = np.float32(1e-3)                 # the scenes' traceBias (SceneDescription's default)
@@ -487,3 +489,112 @@ def shadow_case(kz, O, name, device=None, deform=None):
         rays, spans = concat(shadow_sets(kz.scenes, name, desc, ora))
         _cases[key] = {"desc": desc, "scene": sc, "ora": ora, "ora_il": ora_il, "rays": rays, "spans": spans, "ref": shadow_reference(ora, ora_il, desc, *rays)}
     return _cases[key]
+
+
+def flattened_ties(kz, O, case):
+    """The rays of a flattened case whose closest hit lies on the squashed box's footprint with the floor's triangle and the box's triangle at the SAME t, bit for bit
+    (the floor alone and the box alone answer with the bits of the scene's closest hit): a tie between mesh 0 and mesh 5."""
+    floor = O.OracleScene(only_meshes(kz.scenes, case["desc"], [0]), brute=True).trace_rays(*case["rays"])
+    box = O.OracleScene(only_meshes(kz.scenes, case["desc"], [5]), brute=True).trace_rays(*case["rays"])
+    t = case["ref"]["t"].view(np.uint32)
+    return (floor["mesh"] >= 0) & (box["mesh"] >= 0) & (floor["t"].view(np.uint32) == t) & (box["t"].view(np.uint32) == t)
+
+
+# ------------------------------------------------------------------------------------------------ a launch of kz_trace_rays_wf on a case, and its checks
+LDS_ENTRIES = 16                              # stack entries per lane the default launch keeps in LDS
+KINDS = {0: "per-lane", 1: "packet", 2: "walk-through"}
+
+
+def u32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def sentinel_hits(n):
+    """A hit record per slot that no kernel writes: t = 2^20 + slot, u, v, and a gid the scene does not have."""
+    h = np.zeros((n, 4), np.float32)
+    h[:, 0] = np.float32(1 << 20) + np.arange(n, dtype=np.float32)
+    h[:, 1], h[:, 2] = 0.125, 0.375
+    h[:, 3] = (np.uint32(0xF0000000) | np.arange(n, dtype=np.uint32)).view(np.float32)
+    return h
+
+
+def sums_before(n):
+    return ((np.arange(3 * n, dtype=np.float32) + 1) * np.float32(0.03125)).reshape(n, 3)
+
+
+def pending_of(n):
+    return ((np.arange(3 * n, dtype=np.float32) + 1) * np.float32(0.001)).reshape(n, 3)
+
+
+def run(case, kernel, queue=None, **opts):
+    o, d, tmin, tmax = case["rays"]
+    n = len(o)
+    return case["scene"].trace_rays_wf(o, d, tmin, tmax, kernel=kernel, queue=queue, hits=sentinel_hits(n), sums=sums_before(n), pending=pending_of(n), **opts)
+
+
+def report(case, bad, got, want, what):
+    o, d, tmin, tmax = case["rays"]
+    lines = ["%s: %d of %d rays differ; the first:" % (what, len(bad), len(o))]
+    for i in bad[:6]:
+        lines.append("  ray %d o=%r d=%r tmin=%r tmax=%r\n    kernel: %s\n    oracle: %s" % (i, o[i].tolist(), d[i].tolist(), float(tmin[i]), float(tmax[i]),
+                     {k: got[k][i].tolist() for k in ("t", "u", "v", "mesh", "prim")}, {k: want[k][i].tolist() for k in ("t", "u", "v", "mesh", "prim")}))
+    return "\n".join(lines)
+
+
+def check_closest(case, kernel, res, queue=None):
+    """`res` against the brute-force hits for the slots of `queue` (None: all), the sentinel for the others; the sums untouched everywhere."""
+    ref, n = case["ref"], len(case["rays"][0])
+    queued = np.ones(n, bool) if queue is None else np.isin(np.arange(n), queue)
+    sent = sentinel_hits(n)
+    hit = ref["mesh"] >= 0
+    want = {"t": np.where(hit, ref["t"], np.float32(np.inf)), "u": np.where(hit, ref["u"], np.float32(0)), "v": np.where(hit, ref["v"], np.float32(0)),
+            "mesh": ref["mesh"].copy(), "prim": ref["prim"].copy()}
+    if kernel == 2:                      # the walk-through ray keeps the slot's previous hit on a miss
+        for j, k in enumerate(("t", "u", "v")):
+            want[k] = np.where(hit, want[k], sent[:, j])
+    keep = ~queued | ((kernel == 2) & ~hit)
+    for j, k in enumerate(("t", "u", "v")):
+        want[k] = np.where(queued, want[k], sent[:, j]).astype(np.float32)
+    want["mesh"][keep], want["prim"][keep] = -1, -1
+    wrong = (res["mesh"] != want["mesh"]) | (res["prim"] != want["prim"])
+    for k in ("t", "u", "v"):
+        wrong |= u32(res[k]) != u32(want[k])
+    wrong |= keep & (res["gid"] != u32(sent[:, 3]))                 # what a kernel must not write keeps its gid too
+    wrong |= queued & ~hit & (kernel != 2) & (res["gid"] != 0)      # the miss record is (+inf, 0, 0, 0)
+    bad = np.flatnonzero(wrong)
+    assert len(bad) == 0, report(case, bad, res, want, "%s kernel" % KINDS[kernel])
+    assert same_bits(res["sums"], sums_before(n)), "a closest-hit launch wrote sample sums"
+    assert same_bits(res["t"][hit & queued], ref["t"][hit & queued])
+
+
+SHAPES = [dict(grid_blocks=1, batch=64), dict(lds_stack=2), dict(refill=1), dict(refill=64), dict(postpone=1), dict(postpone=64), dict(stats=True),
+          dict(stats=True, grid_blocks=1, batch=64, lds_stack=2, refill=64, postpone=1)]
+PACKET_SHAPES = [dict(grid_blocks=1, packet_batch=1), dict(grid_blocks=2, packet_batch=3), dict(stats=True), dict(stats=True, grid_blocks=1, packet_batch=1)]
+OUT = ("t", "u", "v", "gid", "mesh", "prim", "sums")
+
+
+def same_result(a, b):
+    return all(np.array_equal(u32(a[k]) if a[k].dtype == np.float32 else a[k], u32(b[k]) if b[k].dtype == np.float32 else b[k]) for k in OUT)
+
+
+def check_shadow(case, res, queue=None, stats=False):
+    occluded, walks, crosses = case["ref"]
+    n = len(occluded)
+    queued = np.ones(n, bool) if queue is None else np.isin(np.arange(n), queue)
+    before, pend = sums_before(n), pending_of(n)
+    want = np.where((queued & ~occluded)[:, None], before + pend, before).astype(np.float32)
+    wrong = (u32(res["sums"]) != u32(want)).any(axis=1)
+    bad = np.flatnonzero(wrong)
+    o, d, tmin, tmax = case["rays"]
+    msg = "\n".join("  segment %d o=%r d=%r tmin=%r tmax=%r queued=%s reference: occluded=%s walk-throughs=%d crosses=%s\n    sums before %r pending %r after %r" %
+                    (i, o[i].tolist(), d[i].tolist(), float(tmin[i]), float(tmax[i]), queued[i], occluded[i], walks[i], crosses[i], before[i].tolist(), pend[i].tolist(), res["sums"][i].tolist()) for i in bad[:6])
+    assert len(bad) == 0, "shadow kernels: %d of %d segments differ; the first:\n%s" % (len(bad), n, msg)
+    sent = sentinel_hits(n)
+    assert all(same_bits(res[k], sent[:, j]) for j, k in enumerate(("t", "u", "v"))) and np.array_equal(res["gid"], u32(sent[:, 3])), "a shadow launch wrote hit records"
+    info = res["info"]
+    if info["shadowFast"]:
+        assert info["nQueueB"] == int((crosses & queued).sum()), (info, int((crosses & queued).sum()))
+    else:
+        assert info["nQueueB"] == 0
+    if stats:
+        assert info["rays"] == int(queued.sum()) + int(walks[queued].sum()), (info, int(queued.sum()), int(walks[queued].sum()))

@@ -9,3 +9,4 @@ from .render import Scene, denoise_films, denoise_opts, denoise_variance_films, 
 from .render import denoise_temporal_films, temporal_opts, temporal_view      # noqa: F401
 from .render import denoise_motion_films, motion_rows      # noqa: F401
 from .render import denoise_responsive_films, responsive_opts      # noqa: F401
+from .render import adaptive_classify_films, adaptive_opts, adaptive_schedule, adaptive_tiles      # noqa: F401

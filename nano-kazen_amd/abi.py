@@ -248,6 +248,27 @@ class KzMatteTexel(C.Structure):
 MATTE_DTYPE = [("id", "<u4", (7,)), ("count", "<u4", (7,)), ("other", "<u4"), ("miss", "<u4")]
 
 
+class KzAdaptiveOpts(C.Structure):
+    # include_ext/kazen_mi355x_adaptive.h: 32 bytes; threshold has no default, a zero in any other field means its default
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("minSamples", C.c_uint32), ("maxSamples", C.c_uint32), ("step", C.c_uint32), ("block", C.c_uint32),
+                ("outlierPermille", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class KzAdaptiveBlock(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("noisy", C.c_uint32), ("valid", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class KzAdaptiveInfo(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("blocks", C.c_uint32), ("converged", C.c_uint32), ("atCap", C.c_uint32), ("samples", C.c_uint64), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the same 16 bytes as a numpy record: what Scene.adaptive_blocks() and adaptive_classify_films() hand back
+ADAPTIVE_BLOCK_DTYPE = [("samples", "<u4"), ("noisy", "<u4"), ("valid", "<u4"), ("flags", "<u4")]
+
+
 class KzBvhInfo(C.Structure):
     _fields_ = [("nNodes", C.c_uint32), ("nLeaves", C.c_uint32), ("nTris", C.c_uint32), ("maxDepth", C.c_uint32),
                 ("maxLeafSize", C.c_uint32), ("sahCost", C.c_float), ("buildSeconds", C.c_double)]
@@ -290,6 +311,10 @@ MATTE_EXPORTS = ["kz_scene_set_mattes", "kz_scene_mattes", "kz_matte_download", 
                  "kz_matte_accumulate_items"]
 KZ_MATTE_MESH, KZ_MATTE_BSDF, KZ_MATTE_ALL, KZ_MATTE_SLOTS, KZ_MATTE_NONE = 1, 2, 3, 7, 0xFFFFFFFF
 MATTE_BITS = {"mesh": KZ_MATTE_MESH, "bsdf": KZ_MATTE_BSDF}
+# what include_ext/kazen_mi355x_adaptive.h declares (checked by tests/test_adaptive_cpu.py): adaptive sampling - rounds over the blocks whose variance has not converged
+ADAPTIVE_EXPORTS = ["kz_render_adaptive", "kz_adaptive_blocks", "kz_adaptive_counts", "kz_adaptive_info", "kz_adaptive_classify_films", "kz_adaptive_schedule",
+                    "kz_adaptive_tiles", "kz_adaptive_stage_ms"]
+KZ_ADAPTIVE_CONVERGED, KZ_ADAPTIVE_AT_CAP = 1, 2
 KZ_TABLE_NODES, KZ_TABLE_NODES4, KZ_TABLE_TRIS, KZ_TABLE_SHADE, KZ_TABLE_CDF, KZ_TABLE_LIGHTS, KZ_TABLE_IL_TRIS, KZ_TABLE_PARAMS, KZ_TABLE_BSDFS, KZ_TABLE_EM_TRIS = range(10)
 # exported by DEVELOPMENT builds of the library only (-DKZ_EXPERIMENTS): the hooks that are process-global state. The product library must NOT export them.
 DEV_ONLY_EXPORTS = ["kz_debug_fail_alloc", "kz_debug_fail_device", "kz_debug_grow_delay", "kz_debug_trace", "kz_debug_alias_devices", "kz_debug_rr_ahead", "kz_debug_shadow_order", "kz_debug_compact_late"]
@@ -441,6 +466,15 @@ def load_library(path=None):
         lib.kz_matte_top.argtypes = [C.c_void_p, C.c_int, C.c_uint32, u32p, C.c_size_t]
         lib.kz_matte_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
         lib.kz_matte_accumulate_items.argtypes = [C.c_void_p, C.c_int, u32p, C.c_uint32, C.c_uint32, u32p, C.POINTER(KzMatteTexel), C.c_uint32]
+    if hasattr(lib, "kz_render_adaptive"):        # (absent only in a KZ_LIB_PATH development build of older sources)
+        lib.kz_render_adaptive.argtypes = [C.c_void_p, C.POINTER(KzRenderOpts), C.POINTER(KzAdaptiveOpts), C.POINTER(KzAdaptiveInfo)]
+        lib.kz_adaptive_blocks.argtypes = [C.c_void_p, C.c_int, C.POINTER(KzAdaptiveBlock), C.c_size_t]
+        lib.kz_adaptive_counts.argtypes = [C.c_void_p, C.c_int, u32p, C.c_size_t]
+        lib.kz_adaptive_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(KzAdaptiveInfo)]
+        lib.kz_adaptive_stage_ms.argtypes = [C.c_void_p, C.c_int, f32p]
+        lib.kz_adaptive_classify_films.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, u32p, C.POINTER(KzAdaptiveOpts), C.POINTER(KzAdaptiveBlock)]
+        lib.kz_adaptive_schedule.argtypes = [C.POINTER(KzAdaptiveOpts), C.c_uint32, u32p, C.c_uint32, u32p]
+        lib.kz_adaptive_tiles.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(KzTile), C.c_uint32, u32p]
     lib.kz_kat_pow4.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
     if hasattr(lib, "kz_kat_math"):
         lib.kz_kat_math.argtypes = [C.c_int, C.c_int, C.c_uint32, f32p, f32p, f32p]

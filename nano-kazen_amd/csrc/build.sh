@@ -16,9 +16,10 @@ DEV="--offload-arch=gfx950 -fgpu-flush-denormals-to-zero -fno-slp-vectorize ${KZ
 DEVICE_UNITS="kz_render kz_replica kz_film kz_film_moment kz_debug kz_motion kz_matte"
 # kz_refit.hip (the refit of an edited scene) keeps subnormals: its tables must equal the host's to the bit (kz_refit.h); so does kz_denoise.hip (the
 # a-trous denoiser, plain and variance-guided): its results must equal plain C++ restatements' to the bit, subnormal tap weights included (kz_denoise.h); and so
-# does kz_responsive.hip (the fast history and the clamp of kazen_mi355x_responsive.h), for the same reason
-IEEE_UNITS="kz_refit kz_denoise kz_responsive"
-HOST_UNITS="kz_multi kz_host kz_bvh kz_arena kz_plan kz_edit"
+# does kz_responsive.hip (the fast history and the clamp of kazen_mi355x_responsive.h), for the same reason; and kz_adaptive.hip (the pixel test of
+# kazen_mi355x_adaptive.h): a subnormal variance or bound must compare as it does on the host
+IEEE_UNITS="kz_refit kz_denoise kz_responsive kz_adaptive"
+HOST_UNITS="kz_multi kz_host kz_bvh kz_arena kz_plan kz_edit kz_adaptive_host"
 for u in $DEVICE_UNITS $IEEE_UNITS $HOST_UNITS; do rm -f "$OUT/$u.o"; done
 PIDS=""
 for u in $DEVICE_UNITS; do hipcc $FLAGS $DEV -c $u.hip -o "$OUT/$u.o" & PIDS="$PIDS $!"; done

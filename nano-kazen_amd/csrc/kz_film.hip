@@ -200,6 +200,7 @@ int kzFilmEnsure(KzScene *scene, KzFilm &film, size_t filmPixels, bool accumulat
 int kzFilmClear(KzDeviceState *ds, hipStream_t stream) {
     for (KzFilm &film : ds->films) if (const int rc = film.clear(stream)) return rc;      // the picture, then the feature films, then the second-moment film
     ds->pictureSamples = ds->momentSamples = 0;
+    ds->adValid = false;                                                 // (the block records of an adaptive call, kazen_mi355x_adaptive.h: they described the film that went)
     return kzMatteClear(ds, stream);                                     // (the ID-matte tables, kazen_mi355x_matte.h: nothing where there are none)
 }
 

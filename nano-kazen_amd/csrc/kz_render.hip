@@ -782,7 +782,7 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     // the ID-matte tables (kazen_mi355x_matte.h): outside the budget too, cleared unless the call accumulates
     if (scene->matteMask && (rc = kzMatteEnsure(scene, ds, opts->accumulate != 0, s1 - s0, stream))) return rc;
     // ... and the second-moment film's (kazen_mi355x_variance.h). What each of the two films has been given since it was last zeroed is counted per pixel.
-    if (!opts->accumulate) ds->pictureSamples = 0;
+    if (!opts->accumulate) { ds->pictureSamples = 0; ds->adValid = false; }      // (... and the block records of an adaptive call describe a film that is gone)
     if (scene->varianceMode) {
         if (!ds->moment().sums || !opts->accumulate) ds->momentSamples = 0;
         if ((rc = kzFilmEnsure(scene, ds->moment(), ds->filmPixels, opts->accumulate != 0, stream))) return rc;
@@ -854,19 +854,26 @@ static int renderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts)
     return KZ_OK;
 }
 
+// opts->device addresses a replica by HIP device index; a scene resident on ONE device is addressed by any zero-initialised opts
+int kzRenderReplica(KzScene *scene, const KzRenderOpts *opts, KzDeviceState **out) {
+    int rc;
+    if ((rc = findReplica(scene, opts->device, out))) {
+        KzReplicaSet *rs = scene ? replicaSet(scene) : nullptr;
+        bool single = false;
+        if (rs) { std::lock_guard<std::mutex> g(rs->m); single = rs->v.size() == 1 && opts->device == 0; }
+        if (!single || (rc = findReplica(scene, -1, out))) return rc;
+    }
+    return KZ_OK;
+}
+int kzRenderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts) { return renderOn(scene, ds, opts); }
+
 extern "C" {
 
 int kz_render(KzScene *scene, const KzRenderOpts *opts) {
     if (!opts) return kz_fail(KZ_ERR_INVALID_ARG, "null opts");
     KzDeviceState *ds; int rc;
     if ((rc = kzAovRefuse(scene, opts, "kz_render")) || (rc = kzVarianceRefuse(scene, opts, "kz_render")) || (rc = kzMatteRefuse(scene, opts, "kz_render"))) return rc;
-    // opts->device addresses a replica by HIP device index; a scene resident on ONE device is addressed by any zero-initialised opts
-    if ((rc = findReplica(scene, opts->device, &ds))) {
-        KzReplicaSet *rs = scene ? replicaSet(scene) : nullptr;
-        bool single = false;
-        if (rs) { std::lock_guard<std::mutex> g(rs->m); single = rs->v.size() == 1 && opts->device == 0; }
-        if (!single || (rc = findReplica(scene, -1, &ds))) return rc;
-    }
+    if ((rc = kzRenderReplica(scene, opts, &ds))) return rc;
     return renderOn(scene, ds, opts);
 }
 

@@ -10,6 +10,8 @@
 //                   replica's denoise buffers, kz_denoise* and kz_denoise_variance* entry points
 //   kz_motion.hip   include/kazen_mi355x_motion.h beyond the denoiser's unit: the id kernel (which mesh every frame pixel shows) and the host-only row table
 //   kz_matte.hip    include_ext/kazen_mi355x_matte.h: the ID-matte tables, the stage of a pass that feeds them (kernels: kz_matte.h), their readers and entry points
+//   kz_adaptive.hip the classification stage of include_ext/kazen_mi355x_adaptive.h (kernel: kz_adaptive.h), its launcher and the test surface kz_adaptive_classify_films;
+//                   kz_adaptive_host.cpp (host code only): the rule's options, schedule and tile lists, the driver kz_render_adaptive and the readers of its records
 //   kz_responsive.hip  the two kernels of include/kazen_mi355x_responsive.h (the fast history and the clamp) and their launcher; the entry points: kz_denoise.hip
 //   (kz_history.h   the history prepare stage of the temporal, motion and responsive calls, one body: its three kernels are instances in the two units above)
 //   kz_multi.cpp    tile dealing, host merge of tile rects, kz_render_multi (host code only)
@@ -22,6 +24,7 @@
 #include "kz_plan.h"
 #include "../../include/kazen_mi355x_motion.h"
 #include "../../include_ext/kazen_mi355x_matte.h"
+#include "../../include_ext/kazen_mi355x_adaptive.h"
 
 #include <atomic>
 #include <chrono>
@@ -267,6 +270,13 @@ struct KzDeviceState {
     // kz_scene_set_transforms: per mesh its base V (then N) on this replica, there from the replica's first transform of the mesh (kz_scene_set_vertices keeps it current);
     // the flag kz_edit_xform raises for a non-finite position. kz_scene_set_lights: T.ilTris re-allocated once to hold the 64 rows a visibility toggle may need.
     std::vector<DevBuf<float>> editBase; DevBuf<uint32_t> editFlag; bool ilTrisRoomy = false;
+    // Adaptive sampling (kazen_mi355x_adaptive.h; kz_adaptive_host.cpp): one record per block of the frame and the byte per block a round's test leaves for the host
+    // (read back through adActiveHost), there from the replica's first kz_render_adaptive, outside the budget. adValid: the records are those of a finished adaptive
+    // call and nothing has cleared the film since (renderOn without accumulate and kzFilmClear lower it); adBlock / adNbx: the block edge and blocks per row they were
+    // made with; adInfo: that call's summary.
+    DevBuf<KzAdaptiveBlock> adRec; DevBuf<uint8_t> adActive; PinnedBuf<uint8_t> adActiveHost; bool adValid = false; uint32_t adBlock = 0, adNbx = 0; KzAdaptiveInfo adInfo{};
+    Event adEv[4]; float adStageMs[3] = {};                          // the stage clock of a round (moment resolve | classification | read-back) and its sums over the last call's rounds
+    size_t adBytes() const { return adRec.bytes() + adActive.bytes(); }
     size_t editBytes() const {
         size_t b = editTriVtx.bytes() + editSlotSrc.bytes() + editPad.bytes() + editStage.bytes() + editFlag.bytes() + (ilTrisRoomy ? ilTris.bytes() : 0);
         for (const DevBuf<float> &e : editBase) b += e.bytes();
@@ -288,6 +298,16 @@ int kzMatteStage(KzScene *scene, KzDeviceState *ds, hipStream_t stream, const fl
 int kzEmitterUpload(KzScene *scene, KzDeviceState *ds);                                                   // the emitter triangles, their count and box (upload and every edit of a light)
 int prepareTiles(KzScene *scene, KzDeviceState *ds, const KzTile *tiles, uint32_t nTiles, hipStream_t stream);      // makes `tiles` the replica's tile set
 static inline int requireDevice(KzScene *scene, KzDeviceState **out) { return findReplica(scene, -1, out); }
+// kz_render.hip: the replica a render call's opts->device addresses (a scene resident on ONE device is addressed by any zero-initialised opts), and the render of one
+// call on it - kz_render is the two in a row; kz_render_adaptive (kz_adaptive_host.cpp) renders every round through the second
+int kzRenderReplica(KzScene *scene, const KzRenderOpts *opts, KzDeviceState **out);
+int kzRenderOn(KzScene *scene, KzDeviceState *ds, const KzRenderOpts *opts);
+// kz_adaptive_host.cpp: the rule's numbers from a caller's options, defaults filled in (sceneSamples 0: no scene - maxSamples stays as given, 0 = no cap known); a bad
+// field: KZ_ERR_INVALID_ARG under `call`'s name. kz_adaptive.hip: the test of one round on `stream` - film and moment resolved, rec and active one entry per block.
+struct KzAdaptiveRule { float threshold, thr2, floor; uint32_t minSamples, maxSamples, step, block, permille; };
+int kzAdaptiveResolve(const KzAdaptiveOpts *aopts, uint32_t sceneSamples, const char *call, KzAdaptiveRule *rule);
+int kzAdaptiveClassify(const float4 *film, const float4 *moment, int32_t width, int32_t height, int32_t border, const KzAdaptiveRule &rule, const uint32_t *blockSamples, uint32_t nAll,
+                       KzAdaptiveBlock *rec, uint8_t *active, hipStream_t stream);
 // kz_film.hip
 size_t packedFloats(const KzParams &P, const KzTile *tiles, uint32_t nTiles);
 int checkTiles(const KzParams &P, const KzTile *tiles, uint32_t nTiles);

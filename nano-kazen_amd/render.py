@@ -555,6 +555,40 @@ class Scene:
         o, v = denoise_opts(**opts), variance_opts(sigma_variance, samples, vflags, vreserved)
         abi.check(self.lib, self.lib.kz_denoise_variance(self.h, -1 if device is None else int(device), C.byref(o), C.byref(v)))
 
+    # ---- adaptive sampling (include_ext/kazen_mi355x_adaptive.h)
+    def render_adaptive(self, threshold, floor=0.0, min_samples=0, max_samples=0, step=0, block=0, outlier_permille=0, aflags=0, **kw):
+        """kz_render_adaptive: rounds of samples over the blocks whose relative standard error is still above `threshold` (set_variance(True) first). Blocks until the
+        last round is tested. Keywords beyond the rule's: render()'s. Returns the KzAdaptiveInfo as a dict (rounds, blocks, converged, atCap, samples, bytes)."""
+        o, keep = self._opts(**kw)
+        a = adaptive_opts(threshold, floor, min_samples, max_samples, step, block, outlier_permille, aflags)
+        info = abi.KzAdaptiveInfo()
+        abi.check(self.lib, self.lib.kz_render_adaptive(self.h, C.byref(o), C.byref(a), C.byref(info)))
+        return info.as_dict()
+
+    def adaptive_info(self, device=-1):
+        """kz_adaptive_info: the summary of the replica's last adaptive call, as a dict."""
+        info = abi.KzAdaptiveInfo()
+        abi.check(self.lib, self.lib.kz_adaptive_info(self.h, int(device), C.byref(info)))
+        return info.as_dict()
+
+    def adaptive_stage_ms(self, device=-1):
+        """kz_adaptive_stage_ms: device milliseconds of the last adaptive call's (moment resolve, classification, read-back), summed over its rounds."""
+        out = (C.c_float * 3)()
+        abi.check(self.lib, self.lib.kz_adaptive_stage_ms(self.h, int(device), out))
+        return [float(x) for x in out]
+
+    def adaptive_blocks(self, device=-1):
+        """kz_adaptive_blocks: the block records of the replica's last adaptive call, 1-D of abi.ADAPTIVE_BLOCK_DTYPE, the frame's blocks row-major."""
+        out = np.zeros(self.adaptive_info(device)["blocks"], abi.ADAPTIVE_BLOCK_DTYPE)
+        abi.check(self.lib, self.lib.kz_adaptive_blocks(self.h, int(device), out.ctypes.data_as(C.POINTER(abi.KzAdaptiveBlock)), out.size))
+        return out
+
+    def adaptive_counts(self, device=-1):
+        """kz_adaptive_counts: (h, w) uint32, the samples every frame pixel received in the replica's last adaptive call."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        abi.check(self.lib, self.lib.kz_adaptive_counts(self.h, int(device), out.ctypes.data_as(abi.u32p), out.size))
+        return out
+
     # ---- the denoiser's history across camera edits (include/kazen_mi355x_temporal.h)
     def _denoise_history(self, entry, device, opts, vargs, targs, rargs=None):
         """denoise_temporal, denoise_motion and (rargs: responsive_opts' arguments) denoise_responsive: the option structs and the call of `entry`."""
@@ -736,6 +770,51 @@ def denoise_variance_films(film, moment, albedo=None, normal=None, depth=None, b
     abi.check(lib, lib.kz_denoise_variance_films(int(device), *frame, film.ctypes.data_as(abi.f32p), *[None if a is None else a.ctypes.data_as(abi.f32p) for a in g],
                                                  C.byref(o), C.byref(v), out.ctypes.data_as(abi.f32p), None if var is None else var.ctypes.data_as(abi.f32p)))
     return (out, var) if return_variance else out
+
+
+def adaptive_opts(threshold, floor=0.0, min_samples=0, max_samples=0, step=0, block=0, outlier_permille=0, flags=0):
+    """A KzAdaptiveOpts (include_ext/kazen_mi355x_adaptive.h): threshold has no default; 0 elsewhere means the default (floor 0.01, min(16, max) samples before the
+    first test, the scene's sample count as the cap, doubling rounds, blocks of 16 pixels, no outliers)."""
+    return abi.KzAdaptiveOpts(float(threshold), float(floor), int(min_samples), int(max_samples), int(step), int(block), int(outlier_permille), int(flags))
+
+
+def adaptive_schedule(scene_samples, threshold=1.0, lib=None, **opts):
+    """kz_adaptive_schedule: the round ends n_0 < n_1 < ... = the cap of a call that converges nowhere, as a list."""
+    lib = lib or abi.load_library()
+    a, n = adaptive_opts(threshold, **opts), C.c_uint32()
+    abi.check(lib, lib.kz_adaptive_schedule(C.byref(a), int(scene_samples), None, 0, C.byref(n)))
+    out = (C.c_uint32 * max(1, n.value))()
+    abi.check(lib, lib.kz_adaptive_schedule(C.byref(a), int(scene_samples), out, n.value, C.byref(n)))
+    return [int(out[i]) for i in range(n.value)]
+
+
+def adaptive_tiles(width, height, block, active, lib=None):
+    """kz_adaptive_tiles: the tile list [(x0, y0, w, h)] of the blocks whose entry of `active` (block rows x block columns, row-major) is non-zero."""
+    lib = lib or abi.load_library()
+    act = np.ascontiguousarray(np.asarray(active).ravel() != 0, np.uint8)
+    if act.size != ((int(width) + int(block) - 1) // int(block)) * ((int(height) + int(block) - 1) // int(block)):
+        raise ValueError("active: one entry per block of the frame")
+    ptr, n = act.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint32()
+    abi.check(lib, lib.kz_adaptive_tiles(int(width), int(height), int(block), ptr, None, 0, C.byref(n)))
+    out = (abi.KzTile * max(1, n.value))()
+    abi.check(lib, lib.kz_adaptive_tiles(int(width), int(height), int(block), ptr, out, n.value, C.byref(n)))
+    return [(t.x0, t.y0, t.w, t.h) for t in out[:n.value]]
+
+
+def adaptive_classify_films(film, moment, block_samples, threshold, border=0, device=0, lib=None, **opts):
+    """kz_adaptive_classify_films, the test surface: the device's classification stage on host films (denoise_films' layout) with `block_samples` (one n per block,
+    row-major; 0 = skipped). Returns the records, 1-D of abi.ADAPTIVE_BLOCK_DTYPE. max_samples = 0 here: no cap is known."""
+    lib = lib or abi.load_library()
+    film, (moment,), frame = _host_films(film, (moment,), border, "the moment film has the picture's shape")
+    a = adaptive_opts(threshold, **opts)
+    e = a.block or 16
+    ns = np.ascontiguousarray(np.asarray(block_samples).ravel(), np.uint32)
+    if e in (8, 16, 32, 64) and ns.size != ((frame[0] + e - 1) // e) * ((frame[1] + e - 1) // e):      # (another edge: the library refuses it by name)
+        raise ValueError("block_samples: one entry per block of the frame")
+    out = np.zeros(ns.size, abi.ADAPTIVE_BLOCK_DTYPE)
+    abi.check(lib, lib.kz_adaptive_classify_films(int(device), *frame, film.ctypes.data_as(abi.f32p), moment.ctypes.data_as(abi.f32p), ns.ctypes.data_as(abi.u32p), C.byref(a),
+                                                  out.ctypes.data_as(C.POINTER(abi.KzAdaptiveBlock))))
+    return out
 
 
 def temporal_opts(depth_tolerance=0.0, normal_tolerance=0.0, max_history=0, flags=0, reserved=(0, 0, 0, 0)):

@@ -2,7 +2,7 @@
 # Did the compiled device code stay? Compiles the device side of the device units of the working tree and of another revision with build.sh's flags
 # (plain and -DKZ_EXPERIMENTS), disassembles the gfx950 code objects and compares them kernel by kernel. Needs no GPU. (kz_variance: a unit of the revisions
 # before the denoiser's two became one; its kernels and kz_denoise's are compared as one set, by name. kz_responsive: the unit of kazen_mi355x_responsive.h, compiled
-# like kz_denoise. kz_matte: the unit of kazen_mi355x_matte.h, compiled like the render units.)
+# like kz_denoise. kz_matte: the unit of kazen_mi355x_matte.h, compiled like the render units. kz_adaptive: the unit of kazen_mi355x_adaptive.h, compiled like kz_denoise.)
 #   scripts/device_code_diff.sh <git-rev>
 # Prints the kernels whose instructions differ - their own, or those of a device function they call (pathLi, matsLi, the texture filters ...) - with the
 # kernel_resources.sh row of both sides, and exits non-zero if there is one. Instructions are compared as text without their addresses and encodings; the
@@ -35,7 +35,7 @@ for build in plain exp; do
     for side in this rev; do
         [ $side = this ] && TREE=$ROOT || TREE=$WT
         for u in kz_render kz_replica kz_film kz_film_moment kz_debug kz_motion kz_matte; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fgpu-flush-denormals-to-zero -fno-slp-vectorize" & PIDS="$PIDS $!"; done
-        for u in kz_refit kz_denoise kz_variance kz_responsive; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fno-slp-vectorize" & PIDS="$PIDS $!"; done      # (build.sh's IEEE units: no flush to zero)
+        for u in kz_refit kz_denoise kz_variance kz_responsive kz_adaptive; do one $side "$TREE" $build $u "--offload-arch=gfx950 -fno-slp-vectorize" & PIDS="$PIDS $!"; done      # (build.sh's IEEE units: no flush to zero)
     done
 done
 FAILED=0
@@ -103,7 +103,7 @@ def side(which, build, units):          # functions, kernels and resource rows o
 
 differing = 0
 for build in ("plain", "exp"):
-    for unit in ("kz_render", "kz_replica", "kz_film", "kz_film_moment", "kz_debug", "kz_motion", "kz_matte", "kz_refit", "kz_denoise+kz_variance", "kz_responsive"):
+    for unit in ("kz_render", "kz_replica", "kz_film", "kz_film_moment", "kz_debug", "kz_motion", "kz_matte", "kz_refit", "kz_denoise+kz_variance", "kz_responsive", "kz_adaptive"):
         (fa, ka, ra), (fb, kb, rb) = side("this", build, unit), side("rev", build, unit)
         # kernels on one side only, paired by their demangled name without the parameter list: the other revision's takes this tree's mangled name
         lone = demangle((ka - kb) | (kb - ka))

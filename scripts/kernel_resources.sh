@@ -1,9 +1,9 @@
 #!/bin/sh
 # VGPRs / SGPRs / spills / scratch / LDS / occupancy of every kernel of the product library (hipcc -Rpass-analysis=kernel-resource-usage).
 cd "$(dirname "$0")/../nano-kazen_amd/csrc"
-# (kz_denoise.hip and kz_responsive.hip with the flags build.sh gives them: IEEE units, no flush to zero; the newer units last, so the rows above them keep their place)
-for u in kz_render kz_replica kz_film kz_debug kz_denoise kz_film_moment kz_motion kz_responsive kz_matte; do
-    [ $u = kz_denoise -o $u = kz_responsive ] && FTZ= || FTZ=-fgpu-flush-denormals-to-zero
+# (kz_denoise.hip, kz_responsive.hip and kz_adaptive.hip with the flags build.sh gives them: IEEE units, no flush to zero; the newer units last, so the rows above them keep their place)
+for u in kz_render kz_replica kz_film kz_debug kz_denoise kz_film_moment kz_motion kz_responsive kz_matte kz_adaptive; do
+    [ $u = kz_denoise -o $u = kz_responsive -o $u = kz_adaptive ] && FTZ= || FTZ=-fgpu-flush-denormals-to-zero
     hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 $FTZ -fno-slp-vectorize ${KZ_EXTRA_HIPFLAGS} -Rpass-analysis=kernel-resource-usage -c $u.hip -o /tmp/kz_res_$u.o 2>&1
 done |
 python3 -c '
